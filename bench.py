@@ -18,9 +18,13 @@ rank (the only exchange of the path); outputs are disjoint, no reduction.  That 
 the default: total work is fixed as N grows).  `--scaling weak` keeps a full C2-sized post slice per rank instead
 (1M pre x N·1M post: a different, N times larger problem — per-GPU work fixed).
 
-Prints ONE JSON line (rank 0).  With the default arguments on one GPU the line also carries `secondary`: the other
-single-GPU BASELINE.json configs (C3 JITC scatter, C4 FixedNumPerPre N = 10M K = 1000, C5 batched dense fp16), each with
-its own value / ms_per_step / kernel_ms / roofline, timed after the headline.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly --steps steps, writes --dump-outputs DIR if
+given (what the last timed step returned, DIR/<name>.npy) and prints the line: metric, value, unit, ms_per_step, dtype, ...
+`--full` adds everything else: the parity check of the last timed step, the instrumented passes (kernel_ms, step_ms, roofline
+with the read-only ceiling), the CPU baseline, a rank's step breakdown, the verbose line to --full-line-file, and with the
+default arguments on one GPU `secondary`: the other single-GPU BASELINE.json configs (C3 JITC scatter, C4 FixedNumPerPre
+N = 10M K = 1000, C5 batched dense fp16), each with its own value / ms_per_step / kernel_ms / roofline, timed after the headline
+(on N GPUs: the extra legs C4_strong / C2_weak).
 """
 import argparse
 import math
@@ -86,10 +90,38 @@ def parse(argv=None):
     ap.add_argument('--secondary-steps', type=int, default=60)
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
     ap.add_argument('--full-line', action='store_true', help='print the verbose line (every prose field per entry) instead of the compact '
-                    'one; the verbose line is always also written to --full-line-file')
+                    'one; with --full the verbose line is always also written to --full-line-file')
     ap.add_argument('--full-line-file', default=os.path.join('gpurun_out', 'bench_full_line.json'),
                     help="where rank 0 writes the verbose line ('' = nowhere)")
-    return ap.parse_args(argv)
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline figure: parity checks, the instrumented '
+                    'passes (kernel_ms, step_ms, roofline, read ceiling), the CPU baseline, the rank breakdown, the secondary configs, '
+                    'the extra legs of a multi-rank job and the verbose line.  Without it a run sets up, warms up, times --steps '
+                    'steps, writes --dump-outputs and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last timed step '
+                    'returned as DIR/<name>.npy (float32 / float64; a fixed, seeded sample where an output exceeds the 64 MB budget)')
+    args = ap.parse_args(argv)
+    if not args.full:           # a plain run: the headline figure alone
+        args.no_cpu = args.no_secondary = True
+    return args
+
+
+DUMP_BYTES = 64 << 20           # --dump-outputs: at most this much in all (over every rank)
+
+
+def dump_outputs(args, arrays, world=1):
+    """--dump-outputs DIR: each array of `arrays` ({name: tensor}) as DIR/<name>.npy in float32 (float64 stays float64).  An array
+    above its share of DUMP_BYTES is replaced by a fixed, seeded sample of its flattened elements (the same positions every run)."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_BYTES // (max(1, world) * max(1, len(arrays)))
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.numel() * t.element_size() > share:
+            pick = np.sort(np.random.default_rng(0).choice(t.numel(), share // t.element_size(), replace=False))
+            t = t.reshape(-1)[torch.from_numpy(pick).to(t.device)]
+        np.save(os.path.join(args.dump_outputs, name + '.npy'), t.cpu().numpy())
 
 
 # =====================================================================================================================
@@ -259,13 +291,15 @@ def cpu_baseline_dense(n, batch, fire, seconds):
 # =====================================================================================================================
 # timing
 # =====================================================================================================================
-def time_steps(step, steps, warmup, fence=None):
+def time_steps(step, steps, warmup, fence=None, instrument=True, after_timed=None):
     """W untimed steps, then exactly K steps bracketed by `fence` (synchronize [+ barrier]) on both sides — nothing else is
     issued inside that region: no profiling events, no per-step markers.  `value` / `ms_per_step` come from it.
-    A SECOND pass over the same K steps (same inputs, outside the timed region) then carries the instrumentation: the
-    in-library HIP events around each op's dominant kernel (on the op's own stream) and one HIP event between steps on the
-    stream the calls are issued on (whole step: compaction + kernels + reduce).
-    Returns (wall seconds of the K timed steps, per-step dominant-kernel ms, per-step whole-step ms, last output)."""
+    `after_timed(out)` then sees the last timed step's output (--dump-outputs).
+    With `instrument` (--full), a SECOND pass over the same K steps (same inputs, outside the timed region) then carries the
+    instrumentation: the in-library HIP events around each op's dominant kernel (on the op's own stream) and one HIP event between
+    steps on the stream the calls are issued on (whole step: compaction + kernels + reduce).
+    Returns (wall seconds of the K timed steps, per-step dominant-kernel ms, per-step whole-step ms, last output); without
+    `instrument` the two per-step arrays are None."""
     from brainevent_amd import _lib
     fence = fence or torch.cuda.synchronize
     out = None
@@ -277,6 +311,10 @@ def time_steps(step, steps, warmup, fence=None):
         out = step(warmup + i)
     fence()
     elapsed = time.perf_counter() - t0
+    if after_timed is not None:
+        after_timed(out)
+    if not instrument:
+        return elapsed, None, None, out
     # ---- instrumented passes (not part of `value`): each kind of event in a pass of its own, so that neither perturbs the other
     # (a marker per step costs ~7 us of step time on this runtime: 0.121 ms/step uninstrumented vs 0.128 with both kinds armed)
     prof_enable = _lib.fn('be_profile_enable', ctypes.c_int, [ctypes.c_int])
@@ -404,7 +442,8 @@ def run_jitc(args, dev, g):
     spikes = torch.rand((n_batch, n), device=dev, generator=g) < args.fire
     target = M.scatter_shard(args.jit_shard, 0) if args.jit_shard > 1 else M     # rank 0's walk classes of an N-way split
     step = lambda i: be.BinaryArray(spikes[i % n_batch]) @ target
-    elapsed, kern, step_ms, out = time_steps(step, args.steps, args.warmup)
+    elapsed, kern, step_ms, out = time_steps(step, args.steps, args.warmup, instrument=args.full,
+                                             after_timed=lambda o: dump_outputs(args, {'out': o}))
     kern_ms = float(np.mean(kern)) if kern is not None else None
     upd = float(out.double().sum().item())          # weight 1: the sum is the number of delivered edges
     value = upd * args.steps / elapsed / 1e9 if not args.jit_gather else n * n * prob * args.steps / elapsed / 1e9
@@ -446,7 +485,7 @@ def run_jitc(args, dev, g):
                     'basis': 'no SQ counter pass exists for this configuration (profiles/sq_counters.json covers C3 at its default size)',
                     'equivalent_stored_matrix_GBps': round(8 * upd / (kern_ms * 1e-3) / 1e9, 1)}
     line = _line(metric, value, args, elapsed, 'f32', cfg, roof, kern, step_ms)
-    if args.jit_shard <= 1:
+    if args.jit_shard <= 1 and args.full:
         try:
             line['parity_check'] = jitc_parity(M, spikes[(args.warmup + args.steps - 1) % n_batch], out, args.jit_gather)
         except Exception as e:
@@ -506,10 +545,11 @@ def run_fcn(args, dev, g):
     spikes = torch.rand((n_batch, n), device=dev, generator=g) < args.fire
     act = spikes.sum(dim=1).cpu().numpy()
     step = lambda i: be.BinaryArray(spikes[i % n_batch]) @ conn
-    elapsed, kern, step_ms, out = time_steps(step, args.steps, args.warmup)
+    elapsed, kern, step_ms, out = time_steps(step, args.steps, args.warmup, instrument=args.full,
+                                             after_timed=lambda o: dump_outputs(args, {'out': o}))
     kern_ms = float(np.mean(kern)) if kern is not None else None
     ws_chk = conn.buffers.get('scatter_plan')
-    if hasattr(ws_chk, 'check_status'):      # binned route: sticky give-up flag + conservation counters over every step above (raises)
+    if args.full and hasattr(ws_chk, 'check_status'):      # binned route: sticky give-up flag + conservation counters over every step above (raises)
         ws_chk.check_status()
     upd = sum(int(act[(args.warmup + i) % n_batch]) for i in range(args.steps)) * K
     value = upd / elapsed / 1e9
@@ -520,6 +560,9 @@ def run_fcn(args, dev, g):
            'route': (type(ws).__name__ + (' (32-bit fixed-point sums, BE_BINNED_ACC32)' if getattr(ws, 'acc32', False) else ''))
                     if ws is not None else 'direct (global atomics)',
            'setup_s': round(t_setup, 3)}
+    if not args.full:           # the roofline (instrumented passes) and the parity check are --full only
+        del conn, w, idx
+        return _line(metric, value, args, elapsed, 'f32', cfg, None, kern, step_ms)
     alg = (4 if args.homo else 8) * float(np.mean(act)) * K + n + 4 * n_post
     # the step is several kernels of similar weight on this route: the whole-step HIP-event time is the honest divisor
     whole = float(np.median(step_ms))
@@ -566,7 +609,8 @@ def run_dense(args, dev, g):
     W = torch.empty((n, n), dtype=torch.float16, device=dev).normal_(0, 1, generator=g)
     spikes = torch.rand((n_batch, args.batch, n), device=dev, generator=g) < args.fire
     step = lambda i: be.BinaryArray(spikes[i % n_batch]) @ W
-    elapsed, kern, step_ms, out = time_steps(step, args.steps, args.warmup)
+    elapsed, kern, step_ms, out = time_steps(step, args.steps, args.warmup, instrument=args.full,
+                                             after_timed=lambda o: dump_outputs(args, {'out': o}))
     kern_ms = float(np.mean(kern)) if kern is not None else None
     pairs = float(spikes.sum().item()) / n_batch
     value = pairs * n * args.steps / elapsed / 1e9
@@ -574,6 +618,9 @@ def run_dense(args, dev, g):
     union = float(spikes.any(dim=1).sum().item()) / n_batch
     cfg = {'workload': f'BinaryArray({args.fire:g}) [{args.batch},{n}] @ dense fp16 [{n},{n}]', 'union_rows': union,
            'active_pairs': pairs}
+    if not args.full:           # the roofline (instrumented passes) and the parity check are --full only
+        del W
+        return _line(metric, value, args, elapsed, 'f16', cfg, None, kern, step_ms)
     roof = hbm_roofline(union * n * 2 + args.batch * n * 2, kern_ms, kernel='k_densemm_mfma',
                         traffic=traffic_lookup('c5') if (n == 65536 and args.batch == 32 and args.fire == 0.01) else None) if kern_ms else None
     try:          # last timed step on 64 sampled output columns vs an f64 matmul of the same operands
@@ -619,11 +666,19 @@ def run_gather_mirror(args, dev, g):
     upd_per_vec = torch.stack([mr.counts[spikes[b]].sum() for b in range(n_batch)]).cpu().numpy()
     act = spikes.sum(dim=1).cpu().numpy()
     step = lambda i: csr @ be.BinaryArray(spikes[i % n_batch])
-    elapsed, kern, step_ms, out = time_steps(step, args.steps, args.warmup)
+    elapsed, kern, step_ms, out = time_steps(step, args.steps, args.warmup, instrument=args.full,
+                                             after_timed=lambda o: dump_outputs(args, {'out': o}))
     kern_ms = float(np.mean(kern)) if kern is not None else None
     timed = [(args.warmup + i) % n_batch for i in range(args.steps)]
     value = float(upd_per_vec[timed].sum()) / elapsed / 1e9
     last = timed[-1]
+    metric = 'synaptic updates/sec (Geff/s), CSR @ BinaryArray through the CSC mirror'
+    if not args.full:           # the gather-kernel checker, the roofline (instrumented passes) and the parity check are --full only
+        cfg = {'workload': f"CSR f32 {'homo' if args.homo else 'hetero'} @ BinaryArray({args.fire:g} fire), {n} x {n}, {n_conn} "
+                           f"synapses/row: the gather direction through the event-driven mirror (route={type(mr.plan).__name__})",
+               'mirror_build_s': round(t_setup, 2), 'mirror_GB': round(mr.nbytes() / 1e9, 2)}
+        del csr, mr, w, idx, ptr
+        return _line(metric, value, args, elapsed, 'f32', cfg, None, kern, step_ms)
     # the checker: the gather kernel over all stored entries (one pass of the matrix per call)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ref = be.binary_csrmv(w, idx, ptr, spikes[last], shape=(n, n), transpose=False)
@@ -719,7 +774,8 @@ def secondary_configs(base):
                             # gather walk _jit_scalar/binary.py:353-377): every edge of the matrix is regenerated per step
                             ('C3_gather', 'jitc', ['--jit-gather', '--no-cpu', '--steps', '12', '--warmup', '3']),
                             ('C4', 'fcn', []), ('C4_homo', 'fcn', ['--homo', '--cpu-seconds', '3']), ('C5', 'dense', [])):
-        a = parse(['--workload', wl, '--steps', str(base.secondary_steps), '--warmup', '10'] + extra + (['--no-cpu'] if base.no_cpu else []))
+        a = parse(['--full', '--workload', wl, '--steps', str(base.secondary_steps), '--warmup', '10'] + extra
+                  + (['--no-cpu'] if base.no_cpu else []))
         try:
             ln = secondary(a, wl)
             out[name] = {k: ln[k] for k in ('metric', 'value', 'unit', 'ms_per_step', 'steps', 'warmup', 'dtype', 'kernel_ms',
@@ -740,7 +796,7 @@ def secondary_configs(base):
     for name, extra in (('C2_homo', ['--homo', '--steps', '100', '--warmup', '20']),
                         ('ref_tuner_point', ['--n', '500000', '--conn', '0.004', '--fire', '0.004', '--homo', '--exact-active',
                                              '--steps', '200', '--warmup', '50'])):
-        a = parse(['--no-cpu', '--no-secondary'] + extra)
+        a = parse(['--full', '--no-cpu', '--no-secondary'] + extra)
         try:
             ln = run_scatter(a)
             out[name] = {k: ln[k] for k in ('metric', 'value', 'unit', 'ms_per_step', 'steps', 'warmup', 'step_ms_hip_events',
@@ -756,7 +812,7 @@ def secondary_configs(base):
     # what ONE rank of the 8-way strong split does per step, measured on this GPU (shard rank 0 of 8 of the same global matrix
     # + the exchange path on a one-rank RCCL group): the single-GPU evidence for the multi-GPU projection in DESIGN.md section 4
     for name, extra in (('C2_rank_of_8', []), ('C4_rank_of_8', ['--workload', 'fcn'])):
-        a = parse(['--emulate-world', '8', '--steps', '100', '--warmup', '20', '--no-cpu', '--no-secondary'] + extra)
+        a = parse(['--full', '--emulate-world', '8', '--steps', '100', '--warmup', '20', '--no-cpu', '--no-secondary'] + extra)
         try:
             ln = run_scatter(a)
             out[name] = {k: ln[k] for k in ('metric', 'value', 'unit', 'ms_per_step', 'steps', 'warmup', 'scaling', 'step_ms_hip_events',
@@ -1047,7 +1103,8 @@ def run_scatter(args):
     # measurements that follow the timed region.  (It does not change the number: at the driver's flags — W = 5, K = 20, a 2.5-ms timed
     # region — three A/B pairs read 776-810 Geff/s either way; 200-step runs read 850-870: the short region is simply colder.)
     last = (args.warmup + args.steps - 1) % n_batch
-    ref = reference_for_shard(weights, indices, indptr, full[last], n_post, args.homo)
+    ref = reference_for_shard(weights, indices, indptr, full[last], n_post, args.homo) if args.full else None
+    dump = lambda o: dump_outputs(args, {'out' if world == 1 else f'out_rank{rank}': o}, world)
     if mock:
         for i in range(args.warmup):
             out = step(i)
@@ -1057,8 +1114,9 @@ def run_scatter(args):
             out = step(args.warmup + i)
         fence()
         elapsed, kern, step_ms = time.perf_counter() - t0, None, np.zeros(0)
+        dump(out)
     else:
-        elapsed, kern, step_ms, out = time_steps(step, args.steps, args.warmup, fence)
+        elapsed, kern, step_ms, out = time_steps(step, args.steps, args.warmup, fence, instrument=args.full, after_timed=dump)
     if fast_ahead:
         rank_step.drain()
     elif ahead:      # the exchange posted by the last step (never consumed)
@@ -1071,13 +1129,13 @@ def run_scatter(args):
     #      multi-GPU node says whether a rank waits in the all-gather (exchange_us spread), in its scatter, or for the slowest rank.
     breakdown = None
     fast = use_dist and rank_step is not None and rank_step._fast is not None
-    if use_dist and not mock:
+    if use_dist and not mock and args.full:
         # the two host paths below issue different numbers of collectives: every rank must take the same one (a rank whose shard fell
         # back to the direct route has no fast path) — agreed with a MIN, like the native init result
         agree = torch.tensor([1.0 if fast else 0.0], dtype=torch.float64, device=dev)
         dist.all_reduce(agree, op=dist.ReduceOp.MIN)
         fast = bool(agree.item() >= 1.0)
-    if use_dist and not mock:
+    if use_dist and not mock and args.full:
         def timed(fn_i, prime=None, finish=None):
             if prime:
                 prime()
@@ -1145,10 +1203,12 @@ def run_scatter(args):
         if emulated is not None:
             breakdown['emulated'] = emulated
 
-    if hasattr(ws_obj, 'check_status'):       # binned route: sticky give-up flag + conservation counters over every step above (raises)
+    if args.full and hasattr(ws_obj, 'check_status'):       # binned route: sticky give-up flag + conservation counters over every step above (raises)
         ws_obj.check_status()
     # one-step parity check of what was timed (every rank checks its own slice; rank 0 reports the worst)
-    if args.homo:
+    if not args.full:
+        err = 0.0                   # (not checked: a plain run carries no parity_check)
+    elif args.homo:
         err = float((out.to(torch.float64) - ref.to(torch.float64) * float(weights[0])).abs().max().item())
     else:
         err = float(((out.double() - ref).abs() / ref.abs().clamp_min(1e-30)).max().item())
@@ -1165,7 +1225,7 @@ def run_scatter(args):
 
     read_gbps = None
     line = None
-    if rank == 0 and args.emulate_world <= 1 and not mock:
+    if rank == 0 and args.emulate_world <= 1 and not mock and args.full:
         read_gbps = read_ceiling_gbps(dev)
     if rank == 0:
         timed = [(args.warmup + i) % n_batch for i in range(args.steps)]
@@ -1227,6 +1287,9 @@ def run_scatter(args):
                              'expected_stored_synapses': float(n_pre) * n_conn_global if args.emulate_world <= 1 else None},
             'roofline': roof,
         }
+        if not args.full:           # a plain run: no parity check, no instrumented passes
+            for k in ('parity_check', 'roofline', 'step_ms_hip_events', 'timing'):
+                del line[k]
         if breakdown is not None:
             line['rank_breakdown'] = breakdown
         if _STATE.get('exchange_init_timed_out'):
@@ -1277,6 +1340,9 @@ LEGEND = {
              'CUBA_2005.py:96-123)',
     'full': 'verbose line (kernel names, bytes, samples): --full-line-file, default gpurun_out/bench_full_line.json',
 }
+
+LEGEND_PLAIN = ('value, ms_per_step: wall clock over exactly `steps` bare steps between synchronize(+barrier) fences, inputs in HBM.  A '
+                'plain run: no instrumented passes, checks, CPU baseline or secondary configs (--full adds them)')
 
 WORKLOADS = {
     'C2_gather_mirror': 'CSR @ spk via the CSC mirror, headline matrix', 'C3': 'spk @ JITCScalarR 4M^2 p=1e-3, scatter',
@@ -1371,9 +1437,10 @@ def _compact_entry(ln, read_ceiling=None, top=False):
     return e
 
 
-def compact_line(line):
+def compact_line(line, full=True):
     """The line as printed: the driver contract's keys in full on the headline, numbers only per secondary, every prose string once in
-    `legend` (LEGEND / WORKLOADS).  The verbose form (what run_* return) goes to --full-line-file."""
+    `legend` (LEGEND / WORKLOADS).  The verbose form (what run_* return) goes to --full-line-file.  `full=False` (a plain run): no
+    roofline, and the legend says what the plain timing is."""
     roof = line.get('roofline') or {}
     rc = roof.get('read_ceiling_GBps')
     out = {k: line.get(k) for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
@@ -1392,7 +1459,8 @@ def compact_line(line):
         for k in ('algorithmic_bytes_per_launch', 'traffic_GBps', 'read_ceiling_GBps', 'kernel_ms_median'):
             if roof.get(k) is not None:
                 r[k] = _sig(roof[k], 10 if k.startswith('alg') else 5)
-    out['roofline'] = r
+    if full:
+        out['roofline'] = r
     cb = line.get('cpu_baseline')
     if cb:
         c = {k: (_sig(cb[k]) if not isinstance(cb[k], str) else cb[k]) for k in ('value', 'unit', 'cores', 'kind', 'sample', 'host_cpus', 'error')
@@ -1422,14 +1490,16 @@ def compact_line(line):
         out['legend'].pop('rank_breakdown', None)
     if not (isinstance(sec, dict) and any(isinstance(v, dict) and 'sweep' in v for v in sec.values())):
         out['legend'].pop('sweep', None)
+    if not full:
+        out['legend'] = {'timing': LEGEND_PLAIN}
     return out
 
 
 def emit(line, args):
-    """Rank 0: the verbose line to --full-line-file, the compact one (or the verbose one with --full-line) on stdout."""
+    """Rank 0: with --full the verbose line to --full-line-file; the compact one (or the verbose one with --full-line) on stdout."""
     full = json.dumps(_finite(line), allow_nan=False)
     path = getattr(args, 'full_line_file', '')
-    if path:
+    if path and args.full:
         try:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             with open(path, 'w') as f:
@@ -1439,9 +1509,9 @@ def emit(line, args):
     if getattr(args, 'full_line', False):
         print(full, flush=True)
         return
-    txt = json.dumps(_finite(compact_line(line)), allow_nan=False, separators=(',', ':'))
+    txt = json.dumps(_finite(compact_line(line, args.full)), allow_nan=False, separators=(',', ':'))
     if len(txt) > LINE_BYTE_BOUND:          # never silently outgrow the driver's record: drop the legend's workload map, then say so
-        c = compact_line(line)
+        c = compact_line(line, args.full)
         c['legend'] = {'see': 'bench.py LEGEND / WORKLOADS', 'line_bytes_before_trim': len(txt)}
         txt = json.dumps(_finite(c), allow_nan=False, separators=(',', ':'))
     print(txt, flush=True)
@@ -1526,7 +1596,8 @@ def multi_rank_extras(args, line, world):
     legs = (('C4_strong', ['--workload', 'fcn', '--steps', '100', '--warmup', '20']),
             ('C2_weak', ['--scaling', 'weak', '--steps', '100', '--warmup', '20']))
     for i, (name, extra) in enumerate(legs):
-        a = parse(['--gpus', str(args.gpus), '--no-cpu', '--no-secondary', '--exchange', args.exchange, '--exchange-impl', args.exchange_impl]
+        a = parse(['--full', '--gpus', str(args.gpus), '--no-cpu', '--no-secondary', '--exchange', args.exchange, '--exchange-impl',
+                   args.exchange_impl]
                   + extra + os.environ.get('BENCH_EXTRAS_ARGS', '').split())        # (BENCH_EXTRAS_ARGS: smaller sizes for rehearsals)
         a.keep_group = True
         state['leg'] = name

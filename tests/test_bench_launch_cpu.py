@@ -16,7 +16,7 @@ def _run(extra, n):
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--neurons', '20000', '--steps', '3', '--warmup', '1',
-           '--no-cpu', '--no-secondary'] + extra
+           '--full', '--no-cpu', '--no-secondary', '--full-line-file', ''] + extra
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -48,7 +48,7 @@ def _run_extras(env_extra, n=2, expect_rc=0):
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--neurons', '20000', '--steps', '3', '--warmup', '1',
-           '--no-cpu', '--exchange', 'bytes', '--full-line-file', '']
+           '--full', '--no-cpu', '--exchange', 'bytes', '--full-line-file', '']
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert (r.returncode == 0) == (expect_rc == 0), (r.returncode, r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -81,3 +81,43 @@ def test_a_leg_that_raises_on_rank_zero_prints_the_headline_before_anything_else
     d = _run_extras({'BENCH_EXTRAS_FAIL': 'C2_weak:0', 'BENCH_EXTRAS_SECONDS': '120'}, expect_rc=1)
     assert d['value'] > 0 and 'C4_strong' in d['secondary'] and 'error' in d['secondary']['C2_weak']
     assert d['extras']['leg'] == 'C2_weak'
+
+
+def _run_plain(n, out_dir, cwd):
+    env = dict(os.environ, BENCH_MOCK_STEP='1', OMP_NUM_THREADS='2')
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--neurons', '20000', '--steps', '4', '--warmup', '2',
+           '--dump-outputs', str(out_dir)]
+    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=str(cwd))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_a_plain_run_prints_the_headline_alone_and_dumps_what_the_last_step_returned(tmp_path):
+    """Without --full: the line keeps the headline keys (metric / value / unit / higher_is_better / dtype / ms_per_step, `steps` as
+    asked) and nothing that needs a pass, a check or a configuration of its own; --dump-outputs writes the last timed step's output
+    (float32, one file per rank), the same numbers from run to run; nothing else is written."""
+    import numpy as np
+    for n in (1, 2):
+        outs = []
+        for rep in range(2):
+            work = tmp_path / f'w{n}_{rep}'
+            work.mkdir()
+            d = _run_plain(n, work / 'dump', work)
+            assert d['metric'] == 'synaptic updates/sec (Geff/s), BinaryArray @ CSR scatter' + (
+                '' if n == 1 else ' [strong scaling over 2 post slices]')
+            assert d['unit'] == 'Geff/s' and d['higher_is_better'] is True and d['dtype'] == 'f32' and d['mock_step'] is True
+            assert d['steps'] == 4 and d['warmup'] == 2 and d['n_gpus'] == n and d['value'] > 0 and d['ms_per_step'] > 0
+            for k in ('parity_check', 'roofline', 'cpu_baseline', 'secondary', 'rank_breakdown', 'step_ms'):
+                assert k not in d, k
+            names = ['out.npy'] if n == 1 else [f'out_rank{r}.npy' for r in range(n)]
+            assert sorted(os.listdir(work)) == ['dump'] and sorted(os.listdir(work / 'dump')) == names
+            arrs = [np.load(work / 'dump' / f) for f in names]
+            assert all(a.dtype == np.float32 for a in arrs) and sum(a.size for a in arrs) == 20000
+            cs = d['config']['checksum']          # (the sum of rank 0's output)
+            assert abs(float(arrs[0].astype(np.float64).sum()) - cs) <= 1e-6 * abs(cs)
+            outs.append(arrs)
+        assert all(np.array_equal(a, b) for a, b in zip(*outs))

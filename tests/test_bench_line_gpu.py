@@ -14,7 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _run(*args):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *args], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full-line-file', '', *args], capture_output=True, text=True,
+                       timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, f'bench.py must print ONE JSON line, got {len(lines)}'
@@ -25,7 +26,7 @@ def _run(*args):
 
 
 def test_the_line_keeps_the_driver_contract_on_a_small_problem():
-    d = _run('--n', '200000', '--steps', '8', '--warmup', '3', '--no-secondary', '--cpu-seconds', '1')
+    d = _run('--full', '--n', '200000', '--steps', '8', '--warmup', '3', '--no-secondary', '--cpu-seconds', '1')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
               'dtype', 'data', 'config', 'roofline', 'cpu_baseline', 'parity_check'):
         assert k in d, k
@@ -43,7 +44,7 @@ def test_the_line_keeps_the_driver_contract_on_a_small_problem():
 
 
 def test_one_rank_of_eight_reports_where_its_step_goes():
-    d = _run('--n', '200000', '--emulate-world', '8', '--steps', '8', '--warmup', '3', '--no-cpu', '--no-secondary')
+    d = _run('--full', '--n', '200000', '--emulate-world', '8', '--steps', '8', '--warmup', '3', '--no-cpu', '--no-secondary')
     assert d['parity_check']['ok'] is True and 'post-slice x8' in d['config']['parallelism']
     rb = d['rank_breakdown']          # compact form: [min, max] over the ranks per quantity (bench.py LEGEND['rank_breakdown'])
     assert rb['schedule'] == 'sequential' and rb['other_schedule'] == 'exchange_ahead_1'
@@ -51,15 +52,16 @@ def test_one_rank_of_eight_reports_where_its_step_goes():
     assert 'rank_breakdown' in d['legend']
     # both schedules once more against an exchange lengthened by 9 us (be_exchange_emulate_latency_us): [us, sequential, pipelined]
     assert rb['emul'][0] == 9 and rb['emul'][1] > 0 and rb['emul'][2] > 0        # (8 steps of a small problem: no ordering asserted)
-    d2 = _run('--n', '200000', '--emulate-world', '8', '--steps', '8', '--warmup', '3', '--no-cpu', '--no-secondary', '--exchange-ahead', '1')
+    d2 = _run('--full', '--n', '200000', '--emulate-world', '8', '--steps', '8', '--warmup', '3', '--no-cpu', '--no-secondary',
+               '--exchange-ahead', '1')
     assert d2['parity_check']['ok'] is True and d2['rank_breakdown']['schedule'] == 'exchange_ahead_1'
 
 
 def test_the_default_line_fits_the_drivers_record_and_every_entry_carries_its_own_check():
-    """The default command at the driver's flags: ONE line of at most 8000 bytes (the driver keeps an 8 KB tail of stdout), every
+    """The default command at the driver's flags with --full: ONE line of at most 8000 bytes (the driver keeps an 8 KB tail of stdout), every
     secondary present with a value, a roofline fraction where one applies and its own parity verdict; the headline's roofline carries
     the read-only ceiling measured in the same run.  (About a minute: the full-size configurations.)"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '20', '--warmup', '5', '--cpu-seconds', '2',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '20', '--warmup', '5', '--cpu-seconds', '2',
                         '--full-line-file', ''], capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -74,3 +76,21 @@ def test_the_default_line_fits_the_drivers_record_and_every_entry_carries_its_ow
         assert name in d['legend']['workloads']
     for name in ('C1_coba', 'C1_cuba'):
         assert [row[0] for row in sec[name]['sweep']] == [1, 10, 100]
+
+
+def test_a_plain_run_times_the_steps_alone_and_dumps_the_output_the_full_run_checks(tmp_path):
+    """Without --full the line carries the headline (`steps` timed steps as asked) and none of the checks or instrumented passes;
+    --dump-outputs writes what the last timed step returned.  The same arguments with --full compute the same output (same inputs)
+    and its parity check passes."""
+    import numpy as np
+    d = _run('--n', '200000', '--steps', '8', '--warmup', '3', '--dump-outputs', str(tmp_path / 'plain'))
+    assert d['metric'] == 'synaptic updates/sec (Geff/s), BinaryArray @ CSR scatter' and d['unit'] == 'Geff/s' and d['dtype'] == 'f32'
+    assert d['steps'] == 8 and d['warmup'] == 3 and d['higher_is_better'] is True and d['value'] > 0 and d['ms_per_step'] > 0
+    for k in ('parity_check', 'roofline', 'cpu_baseline', 'secondary', 'step_ms'):
+        assert k not in d, k
+    out = np.load(tmp_path / 'plain' / 'out.npy')
+    assert out.dtype == np.float32 and out.shape == (200000,)
+    assert abs(float(out.astype(np.float64).sum()) - d['config']['checksum']) <= 1e-6 * abs(d['config']['checksum'])
+    f = _run('--full', '--n', '200000', '--steps', '8', '--warmup', '3', '--no-cpu', '--dump-outputs', str(tmp_path / 'full'))
+    assert f['parity_check']['ok'] is True
+    np.testing.assert_allclose(np.load(tmp_path / 'full' / 'out.npy'), out, rtol=1e-5, atol=1e-5)

@@ -4,8 +4,8 @@ set -e
 export AB_FILE=brainevent_amd/csrc/be_dense.hip
 run() {
   for f in 0.01 0.5; do
-    timeout -k 10 300 python3 bench.py --workload dense --fire $f --no-cpu --no-secondary > gpurun_out/ab_dense.log 2>&1 || { tail -3 gpurun_out/ab_dense.log; return 1; }
-    echo "  C5 fire $f: $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/ab_dense.log | head -1) $(grep -o '"kernel_ms": [0-9.]*' gpurun_out/ab_dense.log | head -1)"
+    log=$(mktemp); timeout -k 10 300 python3 bench.py --full --workload dense --fire $f --no-cpu --no-secondary > $log 2>&1 || { tail -3 $log; return 1; }
+    echo "  C5 fire $f: $(grep -o '"ms_per_step": [0-9.]*' $log | head -1) $(grep -o '"kernel_ms": [0-9.]*' $log | head -1)"
   done
 }
 export -f run

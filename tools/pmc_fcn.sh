@@ -9,7 +9,7 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU" "SQ_INSTS
            "SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_WAIT_ANY SQ_IFETCH"; do
   d=$R/gpurun_out/pmc_fcn_${tag}_$i
   rm -rf $d
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $d -o p -- python3 $R/bench.py --workload fcn "$@" --steps 12 --warmup 3 --no-cpu > $d.log 2>&1
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $d -o p -- python3 $R/bench.py --full --workload fcn "$@" --steps 12 --warmup 3 --no-cpu > $d.log 2>&1
   python3 $R/tools/summarize_prof.py "$d/*counter_collection.csv" "$d/*/*counter_collection.csv" 2>/dev/null | grep "k_bin_"
   i=$((i+1))
 done

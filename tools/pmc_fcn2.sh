@@ -8,7 +8,7 @@ for set in "SQ_LDS_CMD_FIFO_FULL SQ_LDS_DATA_FIFO_FULL SQ_LDS_ADDR_CONFLICT SQ_L
            "SQ_INST_CYCLES_VMEM_WR SQ_INST_CYCLES_VMEM_RD SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_MISC" "SQ_INST_LEVEL_LDS SQ_INST_LEVEL_VMEM SQ_IFETCH_LEVEL SQ_LEVEL_WAVES"; do
   d=$R/gpurun_out/pmc2_fcn_${tag}_$i
   rm -rf $d
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $d -o p -- python3 $R/bench.py --workload fcn "$@" --steps 12 --warmup 3 --no-cpu > $d.log 2>&1
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $d -o p -- python3 $R/bench.py --full --workload fcn "$@" --steps 12 --warmup 3 --no-cpu > $d.log 2>&1
   python3 $R/tools/summarize_prof.py "$d/*counter_collection.csv" "$d/*/*counter_collection.csv" 2>/dev/null | grep "k_bin_stream\|k_bin_acc"
   i=$((i+1))
 done

@@ -12,7 +12,7 @@ PA="SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WA
 PB="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_LDS_ADDR_CONFLICT SQ_INSTS_SALU"
 for pass in A B; do
   eval "CN=\$P$pass"
-  timeout -k 10 300 rocprofv3 --pmc $CN --output-format csv -d $O/homo_$pass -o p -- python3 $R/bench.py --homo --steps 10 --warmup 3 --no-cpu --no-secondary > $O/homo_$pass.log 2>&1 || { echo "homo pass $pass failed"; tail -3 $O/homo_$pass.log; }
+  timeout -k 10 300 rocprofv3 --pmc $CN --output-format csv -d $O/homo_$pass -o p -- python3 $R/bench.py --full --homo --steps 10 --warmup 3 --no-cpu --no-secondary > $O/homo_$pass.log 2>&1 || { echo "homo pass $pass failed"; tail -3 $O/homo_$pass.log; }
   timeout -k 10 300 rocprofv3 --pmc $CN --output-format csv -d $O/shard_$pass -o p -- python3 $R/tools/rank_step_lab.py --schedule seq --steps 30 --warmup 5 > $O/shard_$pass.log 2>&1 || { echo "shard pass $pass failed"; tail -3 $O/shard_$pass.log; }
 done
 cd $R

@@ -6,7 +6,7 @@ O=$R/gpurun_out/final2
 mkdir -p $O
 run() {  # name, args...
   name=$1; shift
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$name -o p -- python3 $R/bench.py "$@" > $O/$name.log 2>&1
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$name -o p -- python3 $R/bench.py --full "$@" > $O/$name.log 2>&1
   echo "$name rc=$?"
 }
 run jitc --workload jitc --steps 50 --warmup 10

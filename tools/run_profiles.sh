@@ -31,7 +31,7 @@ PMC_ORDER=${ONLY:-"c2 c2_homo c2_gather_mirror c4 c4_homo c5 c2_rank_of_8 c4_ran
 if [[ $what == *stats* ]]; then
   for name in $ORDER; do
     rm -rf $O/s_$name
-    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s_$name -o p -- python3 $R/bench.py ${CFG[$name]} > $O/s_$name.log 2>&1
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s_$name -o p -- python3 $R/bench.py --full ${CFG[$name]} > $O/s_$name.log 2>&1
     echo "stats $name rc=$?"
     { echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py ${CFG[$name]}"
       echo "# med_timed = median over the last ${STEPS[$name]} launches of the kernel (the timed steps); avg_us = rocprofv3's average over all launches"
@@ -44,7 +44,7 @@ if [[ $what == *pmc* ]]; then
   for name in $PMC_ORDER; do
     for c in FETCH_SIZE WRITE_SIZE; do
       rm -rf $O/p_${name}_$c
-      timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/p_${name}_$c -o p -- python3 $R/bench.py ${CFG[$name]} --steps 12 --warmup 3 > $O/p_${name}_$c.log 2>&1
+      timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/p_${name}_$c -o p -- python3 $R/bench.py --full ${CFG[$name]} --steps 12 --warmup 3 > $O/p_${name}_$c.log 2>&1
       echo "pmc $name $c rc=$?"
     done
   done
@@ -61,7 +61,7 @@ if [[ $what == *sq* ]]; then
     for c in "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_WAVES GRBM_GUI_ACTIVE"; do
       t=$(echo $c | tr ' ' '_')
       rm -rf $O/q_${name}_$t
-      timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/q_${name}_$t -o p -- python3 $R/bench.py ${CFG[$name]} --steps 6 --warmup 2 > $O/q_${name}_$t.log 2>&1
+      timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/q_${name}_$t -o p -- python3 $R/bench.py --full ${CFG[$name]} --steps 6 --warmup 2 > $O/q_${name}_$t.log 2>&1
       echo "sq $name $t rc=$?"
     done
   done
@@ -73,7 +73,7 @@ if [[ $what == *sq* ]]; then
   python3 $R/tools/make_sq_json.py $O > $O/sq_counters.json
 fi
 if [[ $what == *bench* ]]; then
-  ( cd $R && timeout -k 10 900 python3 bench.py > $O/bench.log 2>&1 ); echo "bench rc=$?"
+  ( cd $R && timeout -k 10 900 python3 bench.py --full > $O/bench.log 2>&1 ); echo "bench rc=$?"
   grep '^{' $O/bench.log | tail -1 > $O/bench_line.json
 fi
 cat $O/*_kernel_stats.txt 2>/dev/null | cut -c1-170

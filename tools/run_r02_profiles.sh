@@ -7,16 +7,16 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r02_$tag
 rm -rf $O; mkdir -p $O
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- python3 $R/bench.py > $O/bench_profiled.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- python3 $R/bench.py --full > $O/bench_profiled.log 2>&1
 echo "stats rc=$?"
 python3 $R/tools/summarize_prof.py "$O/stats/p_kernel_stats.csv" | grep -v "at::native\|rocclr\|rocprim" > $O/kernel_stats.txt
-( cd $R && timeout -k 10 400 python3 bench.py > $O/bench.log 2>&1 ); echo "bench rc=$?"
+( cd $R && timeout -k 10 400 python3 bench.py --full > $O/bench.log 2>&1 ); echo "bench rc=$?"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/c2_$c -o p -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu --no-secondary > $O/c2_$c.log 2>&1
+  timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/c2_$c -o p -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu --no-secondary > $O/c2_$c.log 2>&1
   echo "c2 $c rc=$?"
-  timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/c4_$c -o p -- python3 $R/bench.py --workload fcn --steps 10 --warmup 3 > $O/c4_$c.log 2>&1
+  timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/c4_$c -o p -- python3 $R/bench.py --full --workload fcn --steps 10 --warmup 3 > $O/c4_$c.log 2>&1
   echo "c4 $c rc=$?"
-  timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/c4h_$c -o p -- python3 $R/bench.py --workload fcn --homo --steps 10 --warmup 3 > $O/c4h_$c.log 2>&1
+  timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/c4h_$c -o p -- python3 $R/bench.py --full --workload fcn --homo --steps 10 --warmup 3 > $O/c4h_$c.log 2>&1
   echo "c4 homo $c rc=$?"
 done
 # the K = 1000 planned regime: per-step times over N and the kernel stats at N = 1M weighted

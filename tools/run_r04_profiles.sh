@@ -26,7 +26,7 @@ PMC_ORDER=${ONLY:-"c2 c2_homo c2_gather_mirror c4 c4_homo c5 c2_rank_of_8 c4_ran
 if [[ $what == *stats* ]]; then
   for name in $ORDER; do
     rm -rf $O/s_$name
-    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s_$name -o p -- python3 $R/bench.py ${CFG[$name]} > $O/s_$name.log 2>&1
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/s_$name -o p -- python3 $R/bench.py --full ${CFG[$name]} > $O/s_$name.log 2>&1
     echo "stats $name rc=$?"
     { echo "# rocprofv3 --kernel-trace --stats -- python3 bench.py ${CFG[$name]}"; python3 $R/tools/summarize_prof.py "$O/s_$name/p_kernel_stats.csv" | grep -v "at::native\|rocclr\|rocprim" | head -14 | cut -c1-150;
       grep -o '"ms_per_step": [0-9.]*' $O/s_$name.log | head -1; } > $O/${name}_kernel_stats.txt
@@ -37,7 +37,7 @@ if [[ $what == *pmc* ]]; then
     [ "$name" = c3 ] && continue
     for c in FETCH_SIZE WRITE_SIZE; do
       rm -rf $O/p_${name}_$c
-      timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/p_${name}_$c -o p -- python3 $R/bench.py ${CFG[$name]} --steps 12 --warmup 3 > $O/p_${name}_$c.log 2>&1
+      timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d $O/p_${name}_$c -o p -- python3 $R/bench.py --full ${CFG[$name]} --steps 12 --warmup 3 > $O/p_${name}_$c.log 2>&1
       echo "pmc $name $c rc=$?"
     done
   done
@@ -51,7 +51,7 @@ if [[ $what == *pmc* ]]; then
   python3 $R/tools/make_traffic_json.py $O > $O/traffic.json
 fi
 if [[ $what == *bench* ]]; then
-  ( cd $R && timeout -k 10 900 python3 bench.py > $O/bench.log 2>&1 ); echo "bench rc=$?"
+  ( cd $R && timeout -k 10 900 python3 bench.py --full > $O/bench.log 2>&1 ); echo "bench rc=$?"
   grep '^{' $O/bench.log | tail -1 > $O/bench_line.json
 fi
 cat $O/*_kernel_stats.txt 2>/dev/null | cut -c1-150
