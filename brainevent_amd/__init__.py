@@ -2,7 +2,8 @@
 
 Only the spike-triggered SpMV/SpMM hot path of chaobrain/brainevent is provided:
 ``BinaryArray @ {CSR, CSC, dense, JITC{Scalar,Normal,Uniform}{R,C}, FixedNumPerPre/PerPost}`` and the
-functional ``binary_*`` operators, running hand-written HIP kernels (gfx950) through a C ABI.
+functional ``binary_*`` operators, running hand-written HIP kernels (gfx950) through a C ABI, and the spike-triggered
+plasticity updates (``update_*_on_binary_pre/post``, ``update_on_pre`` / ``update_on_post``).
 """
 from ._version import __version__
 __version_info__ = tuple(int(p) for p in __version__.split('.')[:3] if p.isdigit())
@@ -26,6 +27,9 @@ from ._graph import GraphedStep, capture_step
 from ._tuning import (ScatterTuning, DEFAULT_SCATTER_TUNING, get_scatter_tuning, save_scatter_tuning, apply_scatter_tuning,
                       tune_scatter_routes)
 from ._neuron import lif_coba_step, lif_cuba_step
+from ._plasticity import (update_csr_on_binary_pre, update_csr_on_binary_post, update_csc_on_binary_pre,
+                          update_csc_on_binary_post, update_dense_on_binary_pre, update_dense_on_binary_post,
+                          update_fixed_post_conn_on_binary_pre, update_fixed_pre_conn_on_binary_post)
 from ._op import OpKernel
 XLACustomKernel = OpKernel      # the operator object under the reference's name (no XLA underneath)
 from ._data import DataRepresentation

@@ -31,6 +31,7 @@ from ._event import BinaryArray, is_event, event_operand
 from ._lib import check, fn
 from ._misc import _as_indptr, _as_int32_indices, _check_compressed_structure
 from ._op import OpKernel
+from ._plasticity import PlasticityMixin
 
 __all__ = ['CSR', 'CSC', 'ScatterPlan', 'BinnedScatter', 'Mirror', 'binary_csrmv', 'binary_csrmm', 'binary_csrmv_p',
            'binary_csrmm_p', 'binary_csrmv_p_call', 'binary_csrmm_p_call', 'binary_csrmv_indexed', 'binary_csrmm_indexed',
@@ -1634,7 +1635,7 @@ def build_mirror_of(data, indices, indptr, row_len, m: int, k: int, *, keep_raw:
     return Mirror((k, m), t_data, t_idx, t_ptr, ws, perm, stamp, homo, b.counts)
 
 
-class CompressedSparseData(DataRepresentation):
+class CompressedSparseData(PlasticityMixin, DataRepresentation):
     """Common base of :class:`CSR` and :class:`CSC` (reference ``_csr/main.py:182-277``)."""
     _compressed_format = 'csr'
 
@@ -1770,7 +1771,9 @@ class CompressedSparseData(DataRepresentation):
     def refresh_weights(self):
         """Bring the cached workspaces up to date after ``self.data`` was modified in place.  The products check this by
         themselves on every call (``data._version``); call it explicitly between replays of a captured HIP graph, whose
-        launches cannot."""
+        launches cannot.  The same holds for ``update_on_pre`` / ``update_on_post(inplace=True)`` in a captured step: a replay
+        repeats the path chosen at capture time (with its clip certificate, ``brainevent_amd._plasticity``), so nothing else
+        may write ``data`` out of ``[w_min, w_max]`` between replays."""
         if 'scatter_plan' in self.buffers:
             self._scatter_workspace()
         if 'mirror' in self.buffers:

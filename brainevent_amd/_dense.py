@@ -20,6 +20,7 @@ from . import _array as A
 from ._data import DataRepresentation
 from ._lib import check, fn
 from ._op import OpKernel
+from ._plasticity import PlasticityMixin
 
 __all__ = ['Dense', 'binary_densemv', 'binary_densemm', 'binary_densemv_p', 'binary_densemm_p', 'binary_densemv_p_call',
            'binary_densemm_p_call']
@@ -127,9 +128,9 @@ def binary_densemm(weights, spikes, *, transpose, backend: Optional[str] = None)
     return A.to_result(binary_densemm_p_call(w, s, transpose=transpose, backend=backend)[0], as_np)
 
 
-class Dense(DataRepresentation):
+class Dense(PlasticityMixin, DataRepresentation):
     """Explicit dense matrix with the representation contract of the sparse families (reference
-    ``brainevent/_dense/main.py:60-490``, minus units, pytree plumbing and plasticity): ``data``, ``shape``,
+    ``brainevent/_dense/main.py:60-510``, minus units and pytree plumbing): ``data``, ``shape``,
     ``backend``, ``buffers``, ``with_data``, ``todense``, ``T`` / ``transpose`` and event-driven ``@``.
 
     ``Dense @ events`` -> ``binary_densemv/mm(transpose=False)``; ``events @ Dense`` -> ``transpose=True``

@@ -31,6 +31,7 @@ from ._event import BinaryArray, is_event, event_operand
 from ._lib import check, fn
 from ._misc import _as_int32_indices, check_fixed_conn_num_shape
 from ._op import OpKernel
+from ._plasticity import PlasticityMixin
 
 __all__ = ['FixedNumConn', 'FixedNumPerPre', 'FixedNumPerPost', 'binary_fcnmv', 'binary_fcnmm',
            'binary_fcnmv_p', 'binary_fcnmm_p', 'binary_fcnmv_p_call', 'binary_fcnmm_p_call']
@@ -173,7 +174,7 @@ def _contains_invalid_indices(indices, *, upper_bound: int):
                          f'But found indices with min {lo} and max {hi}.')
 
 
-class FixedNumConn(DataRepresentation):
+class FixedNumConn(PlasticityMixin, DataRepresentation):
     """Base of the two ELL containers (reference ``_fcn/main.py:199-460``)."""
 
     def __init__(self, data, indices=None, *, shape, backend: Optional[str] = None, buffers: Optional[Dict] = None,

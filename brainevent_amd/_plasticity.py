@@ -1,0 +1,459 @@
+"""Spike-triggered plasticity: the additive pair-based STDP updates of the reference
+(``brainevent/_csr/plasticity_binary.py``, ``brainevent/_dense/plasticity_binary.py``, ``brainevent/_fcn/plasticity_binary.py``)
+and the ``update_on_pre`` / ``update_on_post`` methods of ``CSR``, ``CSC``, ``Dense``, ``FixedNumPerPre`` and ``FixedNumPerPost``
+(``_csr/main.py:1389-1455``, ``:2290-2360``; ``_dense/main.py:477-510``; ``_fcn/main.py:627-680``, ``:987-1003``, ``:1256-1272``).
+
+Rule (the reference's order of operations):
+  pre : for every active pre neuron ``i`` and every stored synapse ``(i, j)``:  ``w += post_trace[j]``
+  post: for every active post neuron ``j`` and every stored synapse ``(i, j)``: ``w += pre_trace[i]``
+  then ``clip(w, w_min, w_max)`` over the WHOLE weight array (``min(max(w, w_min), w_max)``; ``None`` disables a bound).
+A spike is any nonzero value.  The trace is cast to the weight dtype first; f16 / bf16 add in f32 and round once.
+
+The hot path is ``csrc/be_plasticity.hip``: ``be_plasticity_rows`` (row-driven, or through a slot -> weight permutation for the
+unfavourable direction) and ``be_plasticity_dense``.  The functional API copies the weights, runs the kernel unclipped and clamps
+the whole copy.  The methods also take ``inplace=True``: the container's own ``data`` is updated and, once the container has
+established that every weight lies in ``[w_min, w_max]`` (a *clip certificate* kept in ``buffers``), the kernel clips the
+touched entries only, which gives the same result without a pass over the whole array.
+
+Captured graphs (``capture_step``): the calls never synchronise the host, but a replay repeats the path chosen at capture time
+(certified or not).  A step captured on the certified path assumes that nothing else writes ``data`` out of range between
+replays — the same contract as :meth:`CSR.refresh_weights`.
+"""
+import ctypes
+import numbers
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _array as A
+from ._event import is_event, event_operand
+from ._lib import check, fn
+
+__all__ = ['update_csr_on_binary_pre', 'update_csr_on_binary_post', 'update_csc_on_binary_pre', 'update_csc_on_binary_post',
+           'update_dense_on_binary_pre', 'update_dense_on_binary_post', 'update_fixed_post_conn_on_binary_pre',
+           'update_fixed_pre_conn_on_binary_post']
+
+c_i64, c_int, c_vp, c_dbl = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_double
+
+_HOMO_MSG = ("Plasticity updates require per-synapse (heterogeneous) weights, but received "
+             "a homogeneous (size-1) weight. Materialize per-synapse weights first "
+             "(e.g. broadcast to the connectivity shape) before applying a plasticity update.")
+
+CLIP_KEY = 'plasticity_clip'        # buffers: (weights_stamp(data), w_min, w_max) while every weight lies in the bounds
+INDEX_KEY = 'plasticity_index'      # buffers: (t_indptr, t_rows, perm) of the transposed structure (structure only)
+
+
+# =====================================================================================================
+# validation (host only: nothing here touches the device)
+# =====================================================================================================
+def _shape_of(x):
+    if is_event(x) or isinstance(x, (torch.Tensor, np.ndarray, A.PackedSpikes, A.ActiveIds)):
+        return tuple(int(s) for s in x.shape)
+    return tuple(np.shape(x))
+
+
+def _numel(x) -> int:
+    return int(np.prod(_shape_of(x), dtype=np.int64))
+
+
+def _check_vec(x, n: int, what: str) -> None:
+    s = _shape_of(x)
+    if len(s) != 1 or s[0] != n:
+        raise ValueError(f"{what} must have shape ({n},); got {s}.")
+
+
+def _check_weight(weight, n_syn: int) -> None:
+    if _numel(weight) == 1 and n_syn > 1:
+        raise ValueError(_HOMO_MSG)
+    dt = weight.dtype if isinstance(weight, (torch.Tensor, np.ndarray)) else np.asarray(weight).dtype
+    ok = dt.is_floating_point if isinstance(dt, torch.dtype) else np.issubdtype(dt, np.floating)
+    if not ok:
+        raise ValueError(f"weights must be a floating-point array; got {dt}.")
+
+
+def _bound(b, what: str):
+    """``None``, a float (host value) or a one-element device tensor."""
+    if b is None:
+        return None
+    if isinstance(b, bool) or not isinstance(b, (numbers.Number, np.generic, np.ndarray, torch.Tensor)):
+        raise ValueError(f"{what} must be None, a number or a one-element array; got {type(b).__name__}.")
+    if isinstance(b, (numbers.Number, np.generic)):
+        return float(b)
+    if b.size == 1 if isinstance(b, np.ndarray) else b.numel() == 1:
+        if isinstance(b, torch.Tensor) and b.is_cuda:
+            return b
+        return float(np.asarray(b.cpu() if isinstance(b, torch.Tensor) else b).reshape(()))
+    raise ValueError(f"{what} must be a scalar (one element); got shape {tuple(b.shape)}.")
+
+
+def _bounds(w_min, w_max):
+    return _bound(w_min, 'w_min'), _bound(w_max, 'w_max')
+
+
+# =====================================================================================================
+# device side
+# =====================================================================================================
+def _spikes(x):
+    """Event operand -> (buffer, spike code): ids / words / bytes / f32 (any nonzero value is a spike)."""
+    v = event_operand(x, scatter=True) if is_event(x) else x
+    if isinstance(v, A.ActiveIds):
+        return v, A.BE_SPIKE_IDS
+    if isinstance(v, A.PackedSpikes):
+        return A.to_device(v.bits), A.BE_SPIKE_BITS
+    t = A.to_device(v)
+    if t.dtype in (torch.bool, torch.uint8, torch.int8):
+        return t, A.BE_SPIKE_BOOL
+    if t.dtype == torch.float32:
+        return t, A.BE_SPIKE_FLOAT
+    return (t != 0), A.BE_SPIKE_BOOL
+
+
+def _rounded(b, dtype):
+    """A host bound as a value of the weight dtype (the kernel compares in that dtype)."""
+    return float(torch.tensor(b, dtype=torch.float64).to(dtype).to(torch.float64))
+
+
+def _clip_args(w: torch.Tensor, lo, hi):
+    if lo is None and hi is None:
+        return 0, 0.0, 0, 0.0
+    return int(lo is not None), (0.0 if lo is None else _rounded(lo, w.dtype)), int(hi is not None), \
+        (0.0 if hi is None else _rounded(hi, w.dtype))
+
+
+_ROWS_ARGS = [c_vp, c_int, c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_vp, c_int, c_i64, c_vp, c_int, c_dbl, c_int, c_dbl,
+              c_vp, c_i64, c_vp]
+_DENSE_ARGS = [c_int, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_vp, c_int, c_dbl, c_int, c_dbl, c_vp, c_i64, c_vp]
+
+
+def _workspace(n: int) -> torch.Tensor:
+    return A.workspace(fn('be_plasticity_workspace_bytes', c_i64, [c_i64])(int(n)))
+
+
+def _run_rows(w: torch.Tensor, col, indptr, row_len: int, perm, spikes, n_rows: int, trace, clip=(None, None)) -> None:
+    """``be_plasticity_rows`` on ``w`` in place (``clip``: bounds applied to the touched entries only)."""
+    sp, sd = _spikes(spikes)
+    tr = A.to_device(trace).to(w.dtype).contiguous()
+    ws = _workspace(n_rows)
+    f = fn('be_plasticity_rows', c_int, _ROWS_ARGS)
+    lo_on, lo, hi_on, hi = _clip_args(w, *clip)
+    check(f(A.ptr(w), A.wcode(w), A.ptr(col), A.ptr(indptr), int(indptr is not None and indptr.dtype == torch.int64),
+            int(row_len), int(col.numel()), A.ptr(perm), int(perm is not None and perm.dtype == torch.int64), A.ptr(sp), sd,
+            int(n_rows), A.ptr(tr), lo_on, lo, hi_on, hi, A.ptr(ws), ws.numel(), A.stream_ptr()), 'be_plasticity_rows')
+
+
+def _run_dense(w: torch.Tensor, pre: bool, spikes, trace, clip=(None, None)) -> None:
+    sp, sd = _spikes(spikes)
+    tr = A.to_device(trace).to(w.dtype).contiguous()
+    n_rows, n_cols = int(w.shape[0]), int(w.shape[1])
+    ws = _workspace(n_rows if pre else n_cols)
+    f = fn('be_plasticity_dense', c_int, _DENSE_ARGS)
+    lo_on, lo, hi_on, hi = _clip_args(w, *clip)
+    check(f(int(pre), A.ptr(w), A.wcode(w), n_rows, n_cols, A.ptr(sp), sd, A.ptr(tr), lo_on, lo, hi_on, hi, A.ptr(ws),
+            ws.numel(), A.stream_ptr()), 'be_plasticity_dense')
+
+
+def _clamp_(w: torch.Tensor, lo, hi) -> None:
+    """The reference's whole-array ``clip`` (torch.clamp: ``min(max(w, lo), hi)``, NaN kept)."""
+    if lo is None and hi is None:
+        return
+    as_arg = (lambda b: None if b is None else (b.to(device=w.device, dtype=w.dtype).reshape(()) if isinstance(b, torch.Tensor)
+                                                else _rounded(b, w.dtype)))
+    lo_t, hi_t = as_arg(lo), as_arg(hi)
+    if isinstance(lo_t, torch.Tensor) or isinstance(hi_t, torch.Tensor):
+        if lo_t is not None:
+            torch.maximum(w, lo_t if isinstance(lo_t, torch.Tensor) else torch.tensor(lo_t, dtype=w.dtype, device=w.device), out=w)
+        if hi_t is not None:
+            torch.minimum(w, hi_t if isinstance(hi_t, torch.Tensor) else torch.tensor(hi_t, dtype=w.dtype, device=w.device), out=w)
+        return
+    w.clamp_(min=lo_t, max=hi_t)
+
+
+def _functional(weight, run, lo, hi, *others):
+    """Copy, update without clipping, clamp the whole copy; numpy in -> numpy out."""
+    as_np = A.wants_numpy(weight, *others)
+    w = A.to_device(weight).clone()
+    run(w)
+    _clamp_(w, lo, hi)
+    return A.to_result(w, as_np)
+
+
+def _as_index(x):
+    return A.to_device(x)
+
+
+# =====================================================================================================
+# functional API (the reference's signatures)
+# =====================================================================================================
+def update_csr_on_binary_pre(weight, indices, indptr, pre_spike, post_trace, w_min=None, w_max=None, *, shape,
+                             backend: Optional[str] = None):
+    """``weight[e] += post_trace[indices[e]]`` for every entry ``e`` of every active row, then ``clip(weight, w_min, w_max)``
+    (reference ``brainevent/_csr/plasticity_binary.py:45-173``).  Returns a new weight array.
+
+    >>> update_csr_on_binary_pre(np.array([0.5, 0.3, 0.8, 0.2], np.float32), np.array([0, 1, 0, 2], np.int32),
+    ...                          np.array([0, 2, 4], np.int32), np.array([True, False]),
+    ...                          np.array([0.1, 0.2, 0.05], np.float32), shape=(2, 3))        # doctest: +SKIP
+    array([0.6, 0.5, 0.8, 0.2], dtype=float32)
+    """
+    m, k = int(shape[0]), int(shape[1])
+    nnz = _numel(indices)
+    _check_weight(weight, nnz)
+    if _numel(weight) != nnz:
+        raise ValueError(f"weight has {_numel(weight)} entries, indices {nnz}.")
+    _check_vec(indptr, m + 1, 'indptr')
+    _check_vec(pre_spike, m, 'pre_spike')
+    _check_vec(post_trace, k, 'post_trace')
+    lo, hi = _bounds(w_min, w_max)
+
+    def run(w):
+        _run_rows(w, A.to_device(indices).to(torch.int32), _as_index(indptr), -1, None, pre_spike, m, post_trace)
+    return _functional(weight, run, lo, hi, indices, indptr)
+
+
+def update_csr_on_binary_post(weight, indices, indptr, weight_indices, pre_trace, post_spike, w_min=None, w_max=None, *, shape,
+                              backend: Optional[str] = None):
+    """``weight[weight_indices[s]] += pre_trace[indices[s]]`` for every slot ``s`` of every active column, then the whole-array
+    clip; ``indices`` / ``indptr`` are the CSC arrays of the matrix and ``weight_indices`` the CSC -> CSR permutation (reference
+    ``brainevent/_csr/plasticity_binary.py:477-618``).  Returns a new weight array.
+
+    >>> update_csr_on_binary_post(np.array([1., 2., 3., 4.], np.float32), np.array([0, 1, 0, 1], np.int32),
+    ...                           np.array([0, 2, 4], np.int32), np.array([0, 2, 1, 3], np.int32),
+    ...                           np.array([0.5, 1.5], np.float32), np.array([False, True]), shape=(2, 2))  # doctest: +SKIP
+    array([1. , 2.5, 3. , 5.5], dtype=float32)
+    """
+    m, k = int(shape[0]), int(shape[1])
+    nnz = _numel(indices)
+    _check_weight(weight, nnz)
+    if not (_numel(weight) == nnz == _numel(weight_indices)):
+        raise ValueError(f"weight ({_numel(weight)}), weight_indices ({_numel(weight_indices)}) and indices ({nnz}) must have "
+                         "the same number of entries.")
+    _check_vec(indptr, k + 1, 'indptr')
+    _check_vec(post_spike, k, 'post_spike')
+    _check_vec(pre_trace, m, 'pre_trace')
+    lo, hi = _bounds(w_min, w_max)
+
+    def run(w):
+        p = A.to_device(weight_indices)
+        p = p if p.dtype in (torch.int32, torch.int64) else p.to(torch.int64)
+        _run_rows(w.reshape(-1), A.to_device(indices).to(torch.int32), _as_index(indptr), -1, p, post_spike, k, pre_trace)
+    return _functional(weight, run, lo, hi, indices, indptr)
+
+
+def update_csc_on_binary_pre(weight, indices, indptr, pre_spike, post_trace, w_min=None, w_max=None, *, shape,
+                             backend: Optional[str] = None):
+    """Pre-spike update of a CSC matrix ``(n_pre, n_post)`` (reference ``_csr/plasticity_binary.py:968-1063``): the
+    unfavourable direction, through the CSC -> CSR permutation built here (``csc_to_csr_index``)."""
+    from ._convert import csc_to_csr_index
+    m, k = int(shape[0]), int(shape[1])
+    _check_weight(weight, _numel(indices))
+    if _numel(weight) != _numel(indices):
+        raise ValueError(f"weight has {_numel(weight)} entries, indices {_numel(indices)}.")
+    _check_vec(indptr, k + 1, 'indptr')
+    _check_vec(pre_spike, m, 'pre_spike')
+    _check_vec(post_trace, k, 'post_trace')
+    _bounds(w_min, w_max)
+    csr_indptr, csr_indices, perm = csc_to_csr_index(A.to_device(indptr), A.to_device(indices), shape=(m, k))
+    out = update_csr_on_binary_post(A.to_device(weight), csr_indices, csr_indptr, perm, post_trace, pre_spike, w_min, w_max,
+                                    shape=(k, m), backend=backend)
+    return A.to_result(out, A.wants_numpy(weight, indices, indptr))
+
+
+def update_csc_on_binary_post(weight, indices, indptr, pre_trace, post_spike, w_min=None, w_max=None, *, shape,
+                              backend: Optional[str] = None):
+    """Post-spike update of a CSC matrix: the favourable, row-driven direction over the stored columns (reference
+    ``_csr/plasticity_binary.py:1066-1160``)."""
+    return update_csr_on_binary_pre(weight, indices, indptr, post_spike, pre_trace, w_min, w_max, shape=(int(shape[1]), int(shape[0])),
+                                    backend=backend)
+
+
+def update_dense_on_binary_pre(weight, pre_spike, post_trace, w_min=None, w_max=None, *, backend: Optional[str] = None):
+    """``W[i, :] += post_trace`` for every active pre neuron ``i``, then the whole-array clip (reference
+    ``brainevent/_dense/plasticity_binary.py:42-140``)."""
+    s = _shape_of(weight)
+    if len(s) != 2:
+        raise ValueError(f"weight must be 2-D; got shape {s}.")
+    _check_weight(weight, s[0] * s[1])
+    _check_vec(pre_spike, s[0], 'pre_spike')
+    _check_vec(post_trace, s[1], 'post_trace')
+    lo, hi = _bounds(w_min, w_max)
+    return _functional(weight, lambda w: _run_dense(w, True, pre_spike, post_trace), lo, hi)
+
+
+def update_dense_on_binary_post(weight, pre_trace, post_spike, w_min=None, w_max=None, *, backend: Optional[str] = None):
+    """``W[:, j] += pre_trace`` for every active post neuron ``j``, then the whole-array clip (reference
+    ``brainevent/_dense/plasticity_binary.py:360-458``)."""
+    s = _shape_of(weight)
+    if len(s) != 2:
+        raise ValueError(f"weight must be 2-D; got shape {s}.")
+    _check_weight(weight, s[0] * s[1])
+    _check_vec(pre_trace, s[0], 'pre_trace')
+    _check_vec(post_spike, s[1], 'post_spike')
+    lo, hi = _bounds(w_min, w_max)
+    return _functional(weight, lambda w: _run_dense(w, False, post_spike, pre_trace), lo, hi)
+
+
+def _check_fcn(data, indices, n_rows: int):
+    s = _shape_of(indices)
+    if len(s) != 2 or s[0] != n_rows:
+        raise ValueError(f"indices must have shape ({n_rows}, num_conn); got {s}.")
+    _check_weight(data, s[0] * s[1])
+    if _shape_of(data) != s:
+        raise ValueError(f"data shape {_shape_of(data)} must match indices shape {s}.")
+
+
+def update_fixed_post_conn_on_binary_pre(data, indices, pre_spike, post_trace, w_min=None, w_max=None, *, shape,
+                                         backend: Optional[str] = None):
+    """Pre-spike update of a ``FixedNumPerPre`` (``indices (num_pre, num_conn)`` = post ids): row-driven over the implicit
+    rows (reference ``brainevent/_fcn/plasticity_binary.py:207-266``)."""
+    n_pre, n_post = int(shape[0]), int(shape[1])
+    _check_fcn(data, indices, n_pre)
+    _check_vec(pre_spike, n_pre, 'pre_spike')
+    _check_vec(post_trace, n_post, 'post_trace')
+    lo, hi = _bounds(w_min, w_max)
+
+    def run(w):
+        idx = A.to_device(indices).to(torch.int32)
+        _run_rows(w, idx, None, int(idx.shape[1]), None, pre_spike, n_pre, post_trace)
+    return _functional(data, run, lo, hi, indices)
+
+
+def update_fixed_pre_conn_on_binary_post(data, indices, pre_trace, post_spike, w_min=None, w_max=None, *, shape,
+                                         backend: Optional[str] = None):
+    """Post-spike update of a ``FixedNumPerPost`` (``indices (num_post, num_conn)`` = pre ids): row-driven over the implicit
+    rows (reference ``brainevent/_fcn/plasticity_binary.py:269-300``)."""
+    n_pre, n_post = int(shape[0]), int(shape[1])
+    _check_fcn(data, indices, n_post)
+    _check_vec(pre_trace, n_pre, 'pre_trace')
+    _check_vec(post_spike, n_post, 'post_spike')
+    lo, hi = _bounds(w_min, w_max)
+
+    def run(w):
+        idx = A.to_device(indices).to(torch.int32)
+        _run_rows(w, idx, None, int(idx.shape[1]), None, post_spike, n_post, pre_trace)
+    return _functional(data, run, lo, hi, indices)
+
+
+# =====================================================================================================
+# container methods
+# =====================================================================================================
+def plasticity_index(M):
+    """``(t_indptr, t_rows, perm)`` of the transposed stored structure of a CSR / CSC / fixed-number container: for every
+    secondary id the stored rows that hold it, and the map of those slots to positions in ``data``.  Taken from the cached
+    :class:`~brainevent_amd.Mirror` when it kept its raw arrays and permutation, otherwise built once (device sort / the
+    column-block kernels) and cached in ``buffers`` — structure only, so it survives weight updates and travels with
+    ``update_on_*(inplace=False)``.  Memory: 4 (row id) + 4 bytes per entry (``perm`` int32), 4 + 8 above 2**31 entries
+    (``perm`` int64), plus the offsets."""
+    idx = M.buffers.get(INDEX_KEY)
+    if idx is not None:
+        return idx
+    mr = M.buffers.get('mirror')
+    if mr is not None and not mr.released and mr.perm is not None and mr.indices is not None and mr.indptr is not None:
+        return mr.indptr, mr.indices.to(torch.int32), mr.perm
+    from ._convert import csr_to_csc_index, fixed_conn_num_csc_structure
+    from ._fcn import FixedNumConn
+    if isinstance(M, FixedNumConn):
+        n_rows, n_cols = M._a_shape
+        ptr, rows, perm = fixed_conn_num_csc_structure(M.indices, shape=(n_rows, n_cols))
+    else:
+        m, k = M._plan_shape()
+        ptr, rows, perm = csr_to_csc_index(M.indptr, M.indices, shape=(m, k), include_perm=True)
+    nnz = int(rows.numel())
+    perm = perm.to(torch.int64 if nnz > np.iinfo(np.int32).max else torch.int32)
+    idx = M.buffers[INDEX_KEY] = (ptr, rows.to(torch.int32), perm)
+    return idx
+
+
+def _certified(M, lo, hi) -> bool:
+    from ._csr import weights_stamp
+    if isinstance(lo, torch.Tensor) or isinstance(hi, torch.Tensor) or (lo is None and hi is None):
+        return False
+    cert = M.buffers.get(CLIP_KEY)
+    return cert is not None and cert[0] == weights_stamp(M.data) and cert[1] == lo and cert[2] == hi
+
+
+def _certify(M, data, lo, hi) -> None:
+    from ._csr import weights_stamp
+    if isinstance(lo, torch.Tensor) or isinstance(hi, torch.Tensor) or (lo is None and hi is None):
+        M.buffers.pop(CLIP_KEY, None)
+    else:
+        M.buffers[CLIP_KEY] = (weights_stamp(data), lo, hi)
+
+
+def container_update(M, pre: bool, spikes, trace, w_min, w_max, inplace: bool):
+    """Shared body of the ``update_on_pre`` / ``update_on_post`` methods."""
+    from ._csr import CSR, CSC
+    from ._dense import Dense
+    from ._fcn import FixedNumPerPre, FixedNumPerPost
+    n_pre, n_post = int(M.shape[0]), int(M.shape[1])
+    n_spk, n_tr = (n_pre, n_post) if pre else (n_post, n_pre)
+    if isinstance(M, Dense):
+        n_syn = n_pre * n_post
+    else:
+        n_syn = int(M.indices.numel())
+    if M.data.numel() == 1 and n_syn > 1:
+        raise ValueError(_HOMO_MSG)
+    _check_vec(spikes, n_spk, 'pre_spike' if pre else 'post_spike')
+    _check_vec(trace, n_tr, 'post_trace' if pre else 'pre_trace')
+    lo, hi = _bounds(w_min, w_max)
+
+    # which kernel: row-driven over the stored rows, or permuted over the transposed structure
+    if isinstance(M, Dense):
+        rows = None
+    elif isinstance(M, (CSR, FixedNumPerPre)):
+        rows = pre
+    elif isinstance(M, (CSC, FixedNumPerPost)):
+        rows = not pre
+    else:
+        raise TypeError(f"plasticity updates are not defined for {type(M).__name__}")
+
+    def run(w, clip):
+        if rows is None:
+            _run_dense(w, pre, spikes, trace, clip)
+        elif rows:
+            fixed = M.indptr if not hasattr(M, 'num_conn') else None
+            _run_rows(w.reshape(-1), M.indices.reshape(-1), fixed, M.num_conn if fixed is None else -1, None, spikes, n_spk,
+                      trace, clip)
+        else:
+            t_ptr, t_rows, perm = plasticity_index(M)
+            _run_rows(w.reshape(-1), t_rows, t_ptr, -1, perm, spikes, n_spk, trace, clip)
+
+    if inplace:
+        if _certified(M, lo, hi):
+            run(M.data, (lo, hi))                         # untouched entries are already in range: clip the touched ones
+        else:
+            run(M.data, (None, None))
+            _clamp_(M.data, lo, hi)
+        # the kernel wrote through a raw pointer: move torch's version counter so that cached plans / mirrors see the change
+        torch.autograd.graph.increment_version(M.data)
+        _certify(M, M.data, lo, hi)
+        return M
+    w = M.data.clone()
+    run(w, (None, None))
+    _clamp_(w, lo, hi)
+    keep = {INDEX_KEY: M.buffers[INDEX_KEY]} if M.buffers.get(INDEX_KEY) is not None else {}
+    if isinstance(M, Dense):
+        out = Dense(w, shape=M.shape, backend=M.backend, buffers=keep)
+    elif isinstance(M, (CSR, CSC)):
+        out = type(M)._from_parts(w, M.indices, M.indptr, shape=M.shape, backend=M.backend, buffers=keep,
+                                  numpy_result=M._numpy_result)
+    else:
+        out = type(M)((w, M.indices), shape=M.shape, backend=M.backend, buffers=keep, check_indices=False)
+    out._numpy_result = M._numpy_result
+    _certify(out, w, lo, hi)
+    return out
+
+
+class PlasticityMixin:
+    """``update_on_pre`` / ``update_on_post`` of the weight containers (reference ``_csr/main.py:1389-1455``)."""
+
+    def update_on_pre(self, pre_spike, post_trace, w_min=None, w_max=None, *, inplace: bool = False):
+        """Pre-spike STDP update: every stored synapse ``(i, j)`` of an active pre neuron ``i`` gets ``+= post_trace[j]``, then
+        ``clip(W, w_min, w_max)`` over the whole array.  ``inplace=False`` (the reference's behaviour) returns a new container
+        sharing the structure; ``inplace=True`` updates ``self.data`` and returns ``self`` (cached plans and mirrors refresh
+        on the next product; see the module docstring for the clip certificate and captured graphs)."""
+        return container_update(self, True, pre_spike, post_trace, w_min, w_max, inplace)
+
+    def update_on_post(self, pre_trace, post_spike, w_min=None, w_max=None, *, inplace: bool = False):
+        """Post-spike STDP update: every stored synapse ``(i, j)`` of an active post neuron ``j`` gets ``+= pre_trace[i]``, then
+        the whole-array clip.  ``inplace`` as in :meth:`update_on_pre`."""
+        return container_update(self, False, post_spike, pre_trace, w_min, w_max, inplace)

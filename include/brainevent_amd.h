@@ -717,6 +717,36 @@ BE_FOR_JIT_VARIANTS(BE_DECL_JIT_VARIANT)
   int be_binary_densemm_transpose_##W##_##S(BE_DENSE_MM_ARGS);    \
   int be_binary_densemm_no_transpose_##W##_##S(BE_DENSE_MM_ARGS);
 
+/* ------------------------------------------------------------------------------------------------
+ * Spike-triggered plasticity (pair-based additive STDP).  Replaces the reference's update primitives:
+ *   update_csr_on_binary_pre  (brainevent/_csr/plasticity_binary.py:45-173, kernel plasticity_binary_on_pre.cu)
+ *   update_csr_on_binary_post (brainevent/_csr/plasticity_binary.py:477-618: CSC arrays + the CSC->CSR permutation)
+ *   update_csc_on_binary_pre / _post (brainevent/_csr/plasticity_binary.py:968-1160: the same two with the roles swapped)
+ *   update_fixed_post_conn_on_binary_pre / update_fixed_pre_conn_on_binary_post (brainevent/_fcn/plasticity_binary.py:207-300)
+ *   update_dense_on_binary_pre / _post (brainevent/_dense/plasticity_binary.py:42-140, :360-458)
+ * Rule: for every active row r (spike != 0; float spikes: any nonzero value) and every stored slot k of r:
+ *   w[perm ? perm[k] : k] = w[...] + trace[indices[k]]      one rounding to the weight dtype (f16 / bf16 add in f32);
+ * then, when clip_lo / clip_hi is set, min(max(w, w_lo), w_hi) on the TOUCHED entries (NaN stays NaN; w_lo > w_hi gives
+ * w_hi).  The reference clips the whole array: a caller that cannot certify the untouched entries calls with no bound and
+ * clamps the whole array itself.  trace has the weight dtype; w_lo / w_hi are values of the weight dtype.
+ * Row-driven (perm = NULL): CSR pre, CSC post, FixedNumPerPre pre / FixedNumPerPost post (indptr = NULL, row_len = num_conn).
+ * Permuted (perm = int32 / int64 map of the transposed structure's slots to weight positions, each position listed once):
+ * CSR post, CSC pre, FixedNumPerPre post, FixedNumPerPost pre, with indptr / indices = the transposed structure.
+ * spike_dtype: BE_SPIKE_BOOL, BE_SPIKE_FLOAT, BE_SPIKE_BITS, BE_SPIKE_IDS.  nnz = number of slots (sizes the grid).
+ * No atomics: every weight is written by one lane.  The host is never synchronised (graph-capturable).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t be_plasticity_workspace_bytes(int64_t n_rows);
+int be_plasticity_rows(void* weights, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64,
+                       int64_t row_len, int64_t nnz, const void* perm, int perm_is_i64, const void* spikes, int spike_dtype,
+                       int64_t n_rows, const void* trace, int clip_lo, double w_lo, int clip_hi, double w_hi,
+                       void* workspace, int64_t workspace_bytes, be_stream_t stream);
+/* Dense row-major weights [n_rows, n_cols].  pre = 1: spikes [n_rows], trace [n_cols], active row i gets += trace.
+ * pre = 0: spikes [n_cols], trace [n_rows], w[i, j] += trace[i] for each active column j.  Workspace: n = n_rows (pre)
+ * or n_cols (post). */
+int be_plasticity_dense(int pre, void* weights, int wdtype, int64_t n_rows, int64_t n_cols, const void* spikes,
+                        int spike_dtype, const void* trace, int clip_lo, double w_lo, int clip_hi, double w_hi,
+                        void* workspace, int64_t workspace_bytes, be_stream_t stream);
+
 #define BE_FOR_ALL_VARIANTS(X) \
   X(f32, BE_F32, bool, BE_SPIKE_BOOL)   X(f32, BE_F32, float, BE_SPIKE_FLOAT)   \
   X(f64, BE_F64, bool, BE_SPIKE_BOOL)   X(f64, BE_F64, float, BE_SPIKE_FLOAT)   \
