@@ -3,7 +3,8 @@
 Only the spike-triggered SpMV/SpMM hot path of chaobrain/brainevent is provided:
 ``BinaryArray @ {CSR, CSC, dense, JITC{Scalar,Normal,Uniform}{R,C}, FixedNumPerPre/PerPost}`` and the
 functional ``binary_*`` operators, running hand-written HIP kernels (gfx950) through a C ABI, and the spike-triggered
-plasticity updates (``update_*_on_binary_pre/post``, ``update_on_pre`` / ``update_on_post``).
+plasticity updates (``update_*_on_binary_pre/post``, ``update_on_pre`` / ``update_on_post``).  The products are
+differentiable under ``torch.autograd`` (weights and float spikes; ``brainevent_amd._autograd``).
 """
 from ._version import __version__
 __version_info__ = tuple(int(p) for p in __version__.split('.')[:3] if p.isdigit())

@@ -1,0 +1,291 @@
+"""``torch.autograd`` through the event-driven products: ``loss.backward()`` works through ``BinaryArray(s) @ csr``.
+
+The reference defines JVP / transpose rules for every binary product (``brainevent/_csr/binary.py:656-715``, ``:1303-1360``;
+``brainevent/_dense/binary.py:290-330``; ``brainevent/_fcn/binary.py:317-``); the torch counterpart is one
+``torch.autograd.Function`` per family here: :class:`RowsProduct` (CSR, CSC, ``FixedNumPerPre`` / ``FixedNumPerPost``) and
+:class:`DenseProduct`.  With ``a = active(s)`` (the forward kernels' rule: ``!= 0`` for bool / integer spikes, ``> 0`` for float
+spikes), ``g`` the incoming gradient and ``r(j)`` / ``c(j)`` the row / column of stored entry ``j`` in the CSR reading of the
+arrays:
+
+  ``s @ A``  ->  ``dw[j] = sum_b a[b, r(j)] * g[b, c(j)]``,  ``ds = A @ g``
+  ``A @ s``  ->  ``dw[j] = sum_b g[b, r(j)] * a[b, c(j)]``,  ``ds = A.T @ g``
+  one shared weight: the scalar sum over ``j``;  dense: ``dW = a.T @ g`` / ``g.T @ a`` (masked outer products).
+
+* Weight gradients use ``a``, not the spike values: the product is exactly linear in the weights, so this is the exact
+  derivative (the reference's ``_csrmv_jvp_weights``).  The reference's transpose rule multiplies by the raw float values
+  instead; the two agree for 0/1 spikes and differ for other float values (a spike of 0.5 counts as 1 here, as it does in the
+  forward product).
+* Spike gradients are straight-through: the gradient of the linear product (the reference's ``_csrmv_jvp_v``); a surrogate
+  function upstream supplies d(spike)/dV.  Only float spike tensors can receive one; bool / integer spikes and the bit-packed
+  and compacted containers get weight gradients only.
+* Weight gradients run on ``csrc/be_grad.hip``: per entry, f32 (f64) accumulation in ascending batch order, one rounding, every
+  entry written once, no atomics (bit-reproducible).  Spike gradients reuse the float-operand kernels (``_float``; through the
+  container's mirror when the direction is a scatter and a mirror exists); dense spike gradients are plain GEMMs
+  (``torch.matmul``: there is no event structure in them).
+* Wrapping happens only when grad mode is on and an operand requires grad; otherwise the existing path runs untouched.  The
+  forward pass of the Function IS the existing path (same route, same kernels, same bits).  Higher-order gradients are not
+  supported (``once_differentiable``).
+"""
+import ctypes
+from typing import Callable, Optional
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _array as A
+from ._error import UnsupportedOperationError
+from ._lib import check, fn
+
+__all__ = ['RowsProduct', 'DenseProduct', 'needed']
+
+c_i64, c_int, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
+_ROWS_ARGS = [c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]
+_DENSE_ARGS = [c_int, c_vp, c_int, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp]
+
+
+def _value(x):
+    from ._event import BinaryArray
+    return x.value if isinstance(x, BinaryArray) else x
+
+
+def _requires(x) -> bool:
+    x = _value(x)
+    return isinstance(x, torch.Tensor) and x.requires_grad
+
+
+def needed(*xs) -> bool:
+    """Grad mode is on and one of the operands (a tensor, or the value of a ``BinaryArray``) requires grad."""
+    return torch.is_grad_enabled() and any(_requires(x) for x in xs)
+
+
+def diff_spikes(x) -> Optional[torch.Tensor]:
+    """The spike tensor that receives a gradient: a float tensor that requires grad, given as is or as a ``BinaryArray``."""
+    v = _value(x)
+    if isinstance(v, torch.Tensor) and v.requires_grad and v.dtype.is_floating_point:
+        return v
+    return None
+
+
+# =====================================================================================================
+# device calls
+# =====================================================================================================
+def activity(operand, layout: str):
+    """The activity of a product's spike operand (as the kernels receive it: tensor, ``PackedSpikes`` or ``ActiveIds``) as the
+    per-neuron bit mask ``int32 [n, ceil(nb / 32)]`` of ``be_grad_pack_activity``.  ``layout``: ``'vec'`` (``[n]``), ``'nm'``
+    (``[n, nb]``) or ``'bm'`` (``[nb, n]``).  Returns ``(mask, nb)``."""
+    if layout == 'nm':
+        sp, sd = A.spikes_batch_major(operand)
+    else:
+        sp, sd = A.spikes_to_device(operand)
+    if layout == 'vec':
+        n, nb = int(operand.shape[0]), 1
+    else:
+        nb, n = (int(s) for s in (sp.shape if sd != A.BE_SPIKE_BITS else (sp.shape[0], operand.shape[-1])))
+    if sd not in (A.BE_SPIKE_BITS, A.BE_SPIKE_IDS):
+        sp = sp.contiguous()
+    mask = torch.empty(max(fn('be_grad_mask_bytes', c_i64, [c_i64, c_i64])(n, nb), 4) // 4, dtype=torch.int32, device=A.device())
+    f = fn('be_grad_pack_activity', c_int, [c_vp, c_int, c_i64, c_i64, c_vp, c_vp])
+    check(f(A.ptr(sp), sd, n, nb, A.ptr(mask), A.stream_ptr()), 'be_grad_pack_activity')
+    return mask, nb
+
+
+def rows_weight_grad(w_meta, indices, indptr, row_len: int, n_rows: int, transpose: bool, mask, nb: int, g_nm) -> torch.Tensor:
+    """``be_grad_rows``: the gradient of the weights (``w_meta``: a tensor or ``(shape, dtype)``; one value per stored entry, or
+    the scalar of a shared weight).  ``g_nm``: the output gradient neuron-major ``[out_len, nb]``."""
+    shape, dtype = (tuple(w_meta.shape), w_meta.dtype) if isinstance(w_meta, torch.Tensor) else w_meta
+    homo = _numel(shape) == 1
+    nse = int(indices.numel())
+    dw = torch.empty(1 if homo else nse, dtype=dtype, device=A.device())
+    g = g_nm.to(dtype).contiguous()
+    ws = A.workspace(fn('be_grad_rows_workspace_bytes', c_i64, [c_i64])(nse)) if homo else None
+    is64 = int(indptr is not None and indptr.dtype == torch.int64)
+    f = fn('be_grad_rows', c_int, _ROWS_ARGS)
+    check(f(int(transpose), A.ptr(dw), int(homo), A.wcode(dw), A.ptr(indices), A.ptr(indptr), is64, int(row_len), int(n_rows),
+            nse, A.ptr(mask), int(nb), A.ptr(g), int(nb), 1, A.ptr(ws), 0 if ws is None else ws.numel(), A.stream_ptr()),
+          'be_grad_rows')
+    return dw.reshape(shape)
+
+
+def _numel(shape) -> int:
+    n = 1
+    for d in shape:
+        n *= int(d)
+    return n
+
+
+def dense_weight_grad(w_meta, transpose: bool, mask, nb: int, g_nm) -> torch.Tensor:
+    """``be_grad_dense``: ``dW [R, C]`` (``w_meta``: a tensor or ``(shape, dtype)``).  ``g_nm``: the output gradient
+    ``[out_len, nb]``."""
+    shape, dtype = (tuple(w_meta.shape), w_meta.dtype) if isinstance(w_meta, torch.Tensor) else w_meta
+    n_rows, n_cols = int(shape[0]), int(shape[1])
+    dw = torch.empty((n_rows, n_cols), dtype=dtype, device=A.device())
+    if transpose:     # lanes run over the columns = output neurons: batch-major g keeps the loads contiguous
+        g = g_nm.to(dtype).T.contiguous()
+        g_sn, g_sb = 1, n_cols
+    else:             # one output neuron per row: neuron-major g, a broadcast per row
+        g = g_nm.to(dtype).contiguous()
+        g_sn, g_sb = nb, 1
+    f = fn('be_grad_dense', c_int, _DENSE_ARGS)
+    check(f(int(transpose), A.ptr(dw), A.wcode(dw), n_rows, n_cols, A.ptr(mask), int(nb), A.ptr(g), g_sn, g_sb,
+            A.stream_ptr()), 'be_grad_dense')
+    return dw
+
+
+def _to_nm(g: torch.Tensor, layout: str) -> torch.Tensor:
+    return g.reshape(-1, 1) if layout == 'vec' else (g.T if layout == 'bm' else g)
+
+
+def _from_nm(d: torch.Tensor, layout: str, shape, dtype) -> torch.Tensor:
+    d = d.reshape(-1) if layout == 'vec' else (d.T if layout == 'bm' else d)
+    return d.to(dtype).reshape(shape)
+
+
+# =====================================================================================================
+# the Functions
+# =====================================================================================================
+class RowsSpec:
+    """What the backward pass of a row-stored product needs: the stored structure (``indices`` flat or ``[rows, n_conn]``,
+    ``indptr`` or ``None`` with ``row_len``), its shape ``(m, k)``, the direction (``transpose``: ``s @ A`` in the CSR reading),
+    the operand / output layout, the packed activity and, for the scatter-direction spike gradient, an optional mirror source."""
+    __slots__ = ('run', 'indices', 'indptr', 'row_len', 'm', 'k', 'transpose', 'layout', 'mirror', 'mask', 'nb', 'w_meta',
+                 's_meta')
+
+    def __init__(self, run, indices, indptr, row_len, m, k, transpose, layout, mirror=None):
+        self.run, self.indices, self.indptr, self.row_len = run, indices, indptr, int(row_len)
+        self.m, self.k, self.transpose, self.layout, self.mirror = int(m), int(k), bool(transpose), layout, mirror
+        self.mask, self.nb, self.w_meta, self.s_meta = None, 1, None, None
+
+
+class RowsProduct(torch.autograd.Function):
+    """CSR / CSC / fixed-number products.  Saved: the structure, the packed activity (not the spikes) and — when the spikes
+    need a gradient — the weights."""
+
+    @staticmethod
+    def forward(ctx, weights, spikes, spec: RowsSpec):
+        out = spec.run()
+        ctx.spec = spec
+        if spikes is not None:
+            ctx.save_for_backward(weights)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        spec = ctx.spec
+        g_nm = _to_nm(g, spec.layout)
+        dw = ds = None
+        if ctx.needs_input_grad[0]:
+            n_rows = spec.m if spec.indptr is not None else int(spec.indices.shape[0])
+            dw = rows_weight_grad(spec.w_meta, spec.indices, spec.indptr, spec.row_len, n_rows, spec.transpose, spec.mask, spec.nb,
+                                  g_nm)
+        if ctx.needs_input_grad[1]:
+            ds = _from_nm(_rows_spike_grad(ctx.saved_tensors[0], spec, g_nm), spec.layout, *spec.s_meta)
+        return dw, ds, None
+
+
+def _rows_spike_grad(weights, spec: RowsSpec, g_nm) -> torch.Tensor:
+    from ._float import _float_csr
+    if spec.transpose:            # s @ A: ds = A @ g (gather over the stored rows)
+        return _float_csr(weights, spec.indices, spec.indptr, spec.row_len, g_nm, m=spec.m, k=spec.k, transpose=False)
+    mr = spec.mirror() if spec.mirror is not None else None
+    if mr is not None:            # A @ s: ds = A.T @ g — a scatter; the mirror turns it into a gather
+        return _float_csr(mr.data.detach(), mr.indices, mr.indptr, -1, g_nm, m=int(mr.shape[0]), k=int(mr.shape[1]), transpose=False)
+    return _float_csr(weights, spec.indices, spec.indptr, spec.row_len, g_nm, m=spec.m, k=spec.k, transpose=True)
+
+
+def rows_product(run: Callable, weights, spikes_arg, operand, layout: str, *, indices, indptr, row_len: int, m: int, k: int,
+                 transpose: bool, mirror=None):
+    """Run ``run()`` (the existing forward path) as a :class:`RowsProduct`.  ``spikes_arg``: what the caller got (tensor or
+    event container), ``operand``: what the kernels receive."""
+    spec = RowsSpec(run, indices, indptr, row_len, m, k, transpose, layout, mirror)
+    spec.w_meta = (tuple(weights.shape), weights.dtype)
+    s = diff_spikes(spikes_arg)
+    if s is not None:
+        spec.s_meta = (s.shape, s.dtype)
+    if weights.requires_grad:
+        spec.mask, spec.nb = activity(operand, layout)
+    return RowsProduct.apply(weights, s, spec)
+
+
+class DenseSpec:
+    __slots__ = ('run', 'transpose', 'layout', 'mask', 'nb', 's_meta')
+
+    def __init__(self, run, transpose, layout):
+        self.run, self.transpose, self.layout = run, bool(transpose), layout
+        self.mask, self.nb, self.s_meta = None, 1, None
+
+
+class DenseProduct(torch.autograd.Function):
+    """``binary_densemv/mm``.  ``transpose=True``: ``s @ W``; ``False``: ``W @ s``.  Spike gradients are plain GEMMs."""
+
+    @staticmethod
+    def forward(ctx, weights, spikes, spec: DenseSpec):
+        out = spec.run()
+        ctx.spec = spec
+        ctx.save_for_backward(weights if spikes is not None else None)
+        ctx.w_meta = (tuple(weights.shape), weights.dtype)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        spec = ctx.spec
+        g_nm = _to_nm(g, spec.layout)
+        dw = ds = None
+        if ctx.needs_input_grad[0]:
+            dw = dense_weight_grad(ctx.w_meta, spec.transpose, spec.mask, spec.nb, g_nm)
+        if ctx.needs_input_grad[1]:
+            w = ctx.saved_tensors[0]
+            gw = g_nm.to(w.dtype)
+            d = torch.matmul(w, gw) if spec.transpose else torch.matmul(w.T, gw)
+            ds = _from_nm(d, spec.layout, *spec.s_meta)
+        return dw, ds, None
+
+
+def dense_product(run: Callable, weights, spikes_arg, operand, layout: str, *, transpose: bool):
+    spec = DenseSpec(run, transpose, layout)
+    s = diff_spikes(spikes_arg)
+    if s is not None:
+        spec.s_meta = (s.shape, s.dtype)
+    if weights.requires_grad:
+        spec.mask, spec.nb = activity(operand, layout)
+    return DenseProduct.apply(weights, s, spec)
+
+
+def refuse_planned() -> None:
+    raise UnsupportedOperationError(
+        "PlannedMatrix holds no raw structure to differentiate against: a gradient through it cannot be computed. Keep the "
+        "container (prepare(release_raw=False)) or run the product under torch.no_grad().")
+
+
+def _live_mirror(M):
+    """The container's mirror when it exists and still holds its raw arrays (a gather for the scatter-direction spike
+    gradient), else ``None``; never builds one."""
+    if M.buffers.get('mirror') is None:
+        return None
+    mr = M._fresh_mirror(auto=False)
+    if mr is None or mr.released or mr.indices is None or mr.indptr is None:
+        return None
+    return mr
+
+
+def container_product(M, other, left: bool, run: Callable):
+    """``other @ M`` (``left``) or ``M @ other`` of a CSR / CSC / fixed-number container with an event operand, as a
+    :class:`RowsProduct` over the container's own arrays (whichever route — direct, plan, binned, mirror — ``run`` takes).
+    A numpy operand gives a numpy result, without autograd."""
+    from ._csr import CSR
+    from ._event import event_operand
+    from ._fcn import FixedNumConn
+    operand = event_operand(other, scatter=True)
+    if A.wants_numpy(operand):
+        with torch.no_grad():
+            return run()
+    if isinstance(M, FixedNumConn):
+        (m, k), indices, indptr, row_len = M._a_shape, M.indices, None, int(M.indices.shape[1])
+        t = M._ell_transpose(left)
+    else:
+        (m, k), indices, indptr, row_len = M._plan_shape(), M.indices, M.indptr, -1
+        t = left if isinstance(M, CSR) else not left
+    layout = 'vec' if operand.ndim == 1 else ('bm' if left else 'nm')
+    return rows_product(run, M.data, other, operand, layout, indices=indices, indptr=indptr, row_len=row_len, m=m, k=k,
+                        transpose=t, mirror=None if t else (lambda: _live_mirror(M)))

@@ -32,6 +32,7 @@ from ._lib import check, fn
 from ._misc import _as_indptr, _as_int32_indices, _check_compressed_structure
 from ._op import OpKernel
 from ._plasticity import PlasticityMixin
+from . import _autograd as _ag
 
 __all__ = ['CSR', 'CSC', 'ScatterPlan', 'BinnedScatter', 'Mirror', 'binary_csrmv', 'binary_csrmm', 'binary_csrmv_p',
            'binary_csrmm_p', 'binary_csrmv_p_call', 'binary_csrmm_p_call', 'binary_csrmv_indexed', 'binary_csrmm_indexed',
@@ -1061,6 +1062,8 @@ class PlannedMatrix:
     def __rmatmul__(self, other):
         if not is_event(other):
             raise NotImplementedError("only event operands (BinaryArray, BitPackedBinary, CompactBinary) are served.")
+        if _ag.needed(self.weight, other):
+            _ag.refuse_planned()
         v = _event_value(other, scatter=True)
         if v.ndim not in (1, 2):
             raise NotImplementedError(f"matmul with object of shape {v.shape}")
@@ -1162,6 +1165,13 @@ def binary_csrmv_p_call(weights, indices, indptr, vector, workspace=None, *, sha
     if weights.ndim == 0:
         weights = weights.reshape(1)
     native = _resolve_workspace(workspace, weights, indices, indptr, shape, transpose)
+    if _ag.needed(weights, vector):
+        def run():
+            return binary_csrmv_p(weights, indices, indptr, vector, shape=shape, transpose=transpose, workspace=native,
+                                  backend=backend)
+        out = _ag.rows_product(run, weights, vector, vector, 'vec', indices=indices, indptr=indptr, row_len=-1, m=shape[0],
+                               k=shape[1], transpose=transpose)
+        return (out,) + _task_operands(workspace)
     return (binary_csrmv_p(weights, indices, indptr, vector, shape=shape, transpose=transpose, workspace=native,
                            backend=backend),) + _task_operands(workspace)
 
@@ -1244,6 +1254,13 @@ def binary_csrmm_p_call(weights, indices, indptr, B, workspace=None, *, shape, t
     if weights.ndim == 0:
         weights = weights.reshape(1)
     native = _resolve_workspace(workspace, weights, indices, indptr, shape, transpose)
+    if _ag.needed(weights, B):
+        def run():
+            return binary_csrmm_p(weights, indices, indptr, B, shape=shape, transpose=transpose, workspace=native,
+                                  backend=backend)
+        out = _ag.rows_product(run, weights, B, B, 'nm', indices=indices, indptr=indptr, row_len=-1, m=shape[0], k=shape[1],
+                               transpose=transpose)
+        return (out,) + _task_operands(workspace)
     return (binary_csrmm_p(weights, indices, indptr, B, shape=shape, transpose=transpose, workspace=native,
                            backend=backend),) + _task_operands(workspace)
 
@@ -1867,6 +1884,8 @@ class CSR(CompressedSparseData):
     _compressed_format = 'csr'
 
     def __matmul__(self, other):      # csr @ other
+        if is_event(other) and _ag.needed(self.data, other):
+            return _ag.container_product(self, other, False, lambda: CSR.__matmul__(self, other))
         if is_event(other):
             v = _event_value(other)
             r = None
@@ -1888,6 +1907,8 @@ class CSR(CompressedSparseData):
         return _dense_product(self, other, shape=self.shape, transpose=False, operand_on_left=False)      # csr @ x
 
     def __rmatmul__(self, other):     # other @ csr
+        if is_event(other) and _ag.needed(self.data, other):
+            return _ag.container_product(self, other, True, lambda: CSR.__rmatmul__(self, other))
         if is_event(other):
             v = _event_value(other, scatter=True)
             ws = self._scatter_workspace()
@@ -1930,6 +1951,8 @@ class CSC(CompressedSparseData):
     _compressed_format = 'csc'
 
     def __matmul__(self, other):      # csc @ other : scatter over the active columns
+        if is_event(other) and _ag.needed(self.data, other):
+            return _ag.container_product(self, other, False, lambda: CSC.__matmul__(self, other))
         if is_event(other):
             v = _event_value(other, scatter=True)
             ws = self._scatter_workspace()
@@ -1945,6 +1968,8 @@ class CSC(CompressedSparseData):
         return _dense_product(self, other, shape=self.shape[::-1], transpose=True, operand_on_left=False)  # csc @ x = A'.T @ x
 
     def __rmatmul__(self, other):     # other @ csc : gather
+        if is_event(other) and _ag.needed(self.data, other):
+            return _ag.container_product(self, other, True, lambda: CSC.__rmatmul__(self, other))
         if is_event(other):
             v = _event_value(other)
             r = None

@@ -21,6 +21,7 @@ from ._data import DataRepresentation
 from ._lib import check, fn
 from ._op import OpKernel
 from ._plasticity import PlasticityMixin
+from . import _autograd as _ag
 
 __all__ = ['Dense', 'binary_densemv', 'binary_densemm', 'binary_densemv_p', 'binary_densemm_p', 'binary_densemv_p_call',
            'binary_densemm_p_call']
@@ -80,6 +81,9 @@ def binary_densemv_p_call(weights, spikes, *, transpose, backend=None):
     else:
         assert spikes.shape[0] == weights.shape[1], (
             f"spikes shape {tuple(spikes.shape)} and weights shape {tuple(weights.shape)} are not compatible")
+    if _ag.needed(weights, spikes):
+        return [_ag.dense_product(lambda: binary_densemv_p(weights, spikes, transpose=transpose, backend=backend), weights, spikes,
+                                  spikes, 'vec', transpose=transpose)]
     return [binary_densemv_p(weights, spikes, transpose=transpose, backend=backend)]
 
 
@@ -96,6 +100,9 @@ def binary_densemm_p_call(weights, spikes, *, transpose, backend=None):
         assert weights.shape[1] == spikes.shape[0], (
             f"weights.shape[1] ({weights.shape[1]}) != spikes.shape[0] ({spikes.shape[0]}), "
             f"weights: {tuple(weights.shape)}, spikes: {tuple(spikes.shape)}")
+    if _ag.needed(weights, spikes):
+        return [_ag.dense_product(lambda: binary_densemm_p(weights, spikes, transpose=transpose, backend=backend), weights, spikes,
+                                  spikes, 'nm', transpose=transpose)]
     return [binary_densemm_p(weights, spikes, transpose=transpose, backend=backend)]
 
 

@@ -32,6 +32,7 @@ from ._lib import check, fn
 from ._misc import _as_int32_indices, check_fixed_conn_num_shape
 from ._op import OpKernel
 from ._plasticity import PlasticityMixin
+from . import _autograd as _ag
 
 __all__ = ['FixedNumConn', 'FixedNumPerPre', 'FixedNumPerPost', 'binary_fcnmv', 'binary_fcnmm',
            'binary_fcnmv_p', 'binary_fcnmm_p', 'binary_fcnmv_p_call', 'binary_fcnmm_p_call']
@@ -101,6 +102,11 @@ def binary_fcnmv_p_call(weights, indices, spikes, *, shape, transpose, backend=N
     check_fixed_conn_num_shape(weights, indices, spikes, shape, transpose)
     assert weights.dtype.is_floating_point, 'Weights must be a floating-point type.'
     weights = weights.reshape(1) if weights.numel() == 1 else weights
+    if _ag.needed(weights, spikes):
+        def run():
+            return binary_fcnmv_p(weights, indices, spikes, shape=shape, transpose=transpose, workspace=workspace, backend=backend)
+        return (_ag.rows_product(run, weights, spikes, spikes, 'vec', indices=indices, indptr=None, row_len=int(indices.shape[1]),
+                                 m=shape[0], k=shape[1], transpose=transpose),)
     return (binary_fcnmv_p(weights, indices, spikes, shape=shape, transpose=transpose, workspace=workspace,
                            backend=backend),)
 
@@ -114,6 +120,11 @@ def binary_fcnmm_p_call(weights, indices, matrix, *, shape, transpose, backend=N
     check_fixed_conn_num_shape(weights, indices, matrix, shape, transpose)
     assert weights.dtype.is_floating_point, 'Weights must be a floating-point type.'
     weights = weights.reshape(1) if weights.numel() == 1 else weights
+    if _ag.needed(weights, matrix):
+        def run():
+            return binary_fcnmm_p(weights, indices, matrix, shape=shape, transpose=transpose, workspace=workspace, backend=backend)
+        return (_ag.rows_product(run, weights, matrix, matrix, 'nm', indices=indices, indptr=None, row_len=int(indices.shape[1]),
+                                 m=shape[0], k=shape[1], transpose=transpose),)
     return (binary_fcnmm_p(weights, indices, matrix, shape=shape, transpose=transpose, workspace=workspace,
                            backend=backend),)
 
@@ -305,6 +316,8 @@ class FixedNumConn(PlasticityMixin, DataRepresentation):
                                    backend=self.backend, workspace=ws)[0]
 
     def _dispatch(self, other, transpose_W: bool):
+        if is_event(other) and _ag.needed(self.data, other):
+            return _ag.container_product(self, other, transpose_W, lambda: self._dispatch(other, transpose_W))
         ell_t = self._ell_transpose(transpose_W)
         if not is_event(other):     # a dense operand: the float twins (reference ``_fcn/main.py:308-460`` dispatches them alike)
             from ._float import fcnmv_p_call, fcnmm_p_call

@@ -747,6 +747,36 @@ int be_plasticity_dense(int pre, void* weights, int wdtype, int64_t n_rows, int6
                         int spike_dtype, const void* trace, int clip_lo, double w_lo, int clip_hi, double w_hi,
                         void* workspace, int64_t workspace_bytes, be_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Weight gradients of the event-driven products (the backward pass of brainevent_amd/_autograd.py).  The reference's
+ * derivative rules: brainevent/_csr/binary.py:656-715 (mv), :1303-1360 (mm, SDDMM), brainevent/_dense/binary.py:290-330,
+ * brainevent/_fcn/binary.py:317-.  a = active(spike) (the forward kernels' rule: != 0 for bytes, > 0 for f32), g = the
+ * incoming gradient of the output, r(j) / c(j) = row / column of stored entry j:
+ *   transpose = 1 (s @ A):  dw[j] = sum_b a[b, r(j)] * g[b, c(j)]      transpose = 0 (A @ s):  dw[j] = sum_b g[b, r(j)] * a[b, c(j)]
+ *   homo = 1: the scalar sum over j of the same (dw has one element).
+ * Sums run over the active b only, in ascending b, in f32 (f64 for f64 weights), rounded once to the weight dtype.  Every
+ * entry is written once (zeros for an inactive row, without reading its indices); no atomics; the homogeneous sum is a
+ * fixed-order two-pass reduction (deterministic).  Never synchronises the host (graph-capturable).
+ *
+ * be_grad_pack_activity: the activity of a batch-major spike buffer [n_batch, n] (BE_SPIKE_BOOL / BE_SPIKE_FLOAT; BE_SPIKE_BITS:
+ * [n_batch, ceil(n/32)] words; BE_SPIKE_IDS: one vector) as the per-neuron bit mask mask[n][ceil(n_batch/32)] (bit b % 32 of
+ * word b / 32), be_grad_mask_bytes(n, n_batch) bytes.
+ * be_grad_rows: CSR rows (indptr int32 / int64) or fixed-length rows (indptr = NULL, row_len = num_conn, nse = n_rows *
+ * row_len).  mask has one row per stored row (transpose = 1) or per column id (transpose = 0).  g is the weight dtype; its
+ * element (batch b, neuron x) is g[x * g_sn + b * g_sb], x a column id (transpose = 1) or a row (transpose = 0).
+ * be_grad_dense: W [n_rows, n_cols] row-major.  transpose = 1 (events @ W): dW[i, j] = sum_{b: a[b, i]} g(b, j), mask over
+ * the rows; transpose = 0 (W @ events): dW[i, j] = sum_{b: a[b, j]} g(b, i), mask over the columns.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t be_grad_mask_bytes(int64_t n, int64_t n_batch);
+int be_grad_pack_activity(const void* spikes, int spike_dtype, int64_t n, int64_t n_batch, uint32_t* mask, be_stream_t stream);
+int64_t be_grad_rows_workspace_bytes(int64_t nse);
+int be_grad_rows(int transpose, void* dw, int homo, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64,
+                 int64_t row_len, int64_t n_rows, int64_t nse, const uint32_t* mask, int64_t n_batch, const void* g,
+                 int64_t g_sn, int64_t g_sb, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+int64_t be_grad_dense_workspace_bytes(int64_t n_rows, int64_t n_cols);
+int be_grad_dense(int transpose, void* dw, int wdtype, int64_t n_rows, int64_t n_cols, const uint32_t* mask, int64_t n_batch,
+                  const void* g, int64_t g_sn, int64_t g_sb, be_stream_t stream);
+
 #define BE_FOR_ALL_VARIANTS(X) \
   X(f32, BE_F32, bool, BE_SPIKE_BOOL)   X(f32, BE_F32, float, BE_SPIKE_FLOAT)   \
   X(f64, BE_F64, bool, BE_SPIKE_BOOL)   X(f64, BE_F64, float, BE_SPIKE_FLOAT)   \
