@@ -1,6 +1,7 @@
 """torch.autograd through the event-driven products on the device: weight gradients bit-exact against the host model of
 tests/test_autograd_cpu.py, spike and shared-weight gradients against an f64 dense reference, the forward pass unchanged,
-routes, determinism, training and graph capture."""
+routes, determinism, training and graph capture.
+The sizes past one pass of every loop of the kernels are in tests/test_update_kernels_at_scale_gpu.py."""
 import numpy as np
 import pytest
 import torch

@@ -1,6 +1,7 @@
 """Spike-triggered plasticity on the MI355X: every container x both directions x the four weight dtypes x the spike encodings
 x the bounds, bit-exact against the host model of tests/test_plasticity_cpu.py; the whole-array clip, the clip certificate,
-cached workspaces after an in-place update, graph capture, and a structure above 2**31 entries."""
+cached workspaces after an in-place update, graph capture, and a structure above 2**31 entries.
+The sizes past one pass of every loop of the kernels are in tests/test_update_kernels_at_scale_gpu.py."""
 import numpy as np
 import pytest
 import torch
