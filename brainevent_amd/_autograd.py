@@ -144,15 +144,13 @@ def _from_nm(d: torch.Tensor, layout: str, shape, dtype) -> torch.Tensor:
 # the Functions
 # =====================================================================================================
 class RowsSpec:
-    """What the backward pass of a row-stored product needs: the stored structure (``indices`` flat or ``[rows, n_conn]``,
-    ``indptr`` or ``None`` with ``row_len``), its shape ``(m, k)``, the direction (``transpose``: ``s @ A`` in the CSR reading),
-    the operand / output layout, the packed activity and, for the scatter-direction spike gradient, an optional mirror source."""
-    __slots__ = ('run', 'indices', 'indptr', 'row_len', 'm', 'k', 'transpose', 'layout', 'mirror', 'mask', 'nb', 'w_meta',
-                 's_meta')
+    """What the backward pass of a row-stored product needs: the stored structure (``rows``: a ``_csr.StoredRows``), the
+    direction (``transpose``: the scatter over the stored rows), the operand / output layout, the packed activity and, for the
+    scatter-direction spike gradient, an optional mirror source."""
+    __slots__ = ('run', 'rows', 'transpose', 'layout', 'mirror', 'mask', 'nb', 'w_meta', 's_meta')
 
-    def __init__(self, run, indices, indptr, row_len, m, k, transpose, layout, mirror=None):
-        self.run, self.indices, self.indptr, self.row_len = run, indices, indptr, int(row_len)
-        self.m, self.k, self.transpose, self.layout, self.mirror = int(m), int(k), bool(transpose), layout, mirror
+    def __init__(self, run, rows, transpose, layout, mirror=None):
+        self.run, self.rows, self.transpose, self.layout, self.mirror = run, rows, bool(transpose), layout, mirror
         self.mask, self.nb, self.w_meta, self.s_meta = None, 1, None, None
 
 
@@ -172,12 +170,11 @@ class RowsProduct(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         spec = ctx.spec
+        r = spec.rows
         g_nm = _to_nm(g, spec.layout)
         dw = ds = None
         if ctx.needs_input_grad[0]:
-            n_rows = spec.m if spec.indptr is not None else int(spec.indices.shape[0])
-            dw = rows_weight_grad(spec.w_meta, spec.indices, spec.indptr, spec.row_len, n_rows, spec.transpose, spec.mask, spec.nb,
-                                  g_nm)
+            dw = rows_weight_grad(spec.w_meta, r.indices, r.indptr, r.row_len, r.m, spec.transpose, spec.mask, spec.nb, g_nm)
         if ctx.needs_input_grad[1]:
             ds = _from_nm(_rows_spike_grad(ctx.saved_tensors[0], spec, g_nm), spec.layout, *spec.s_meta)
         return dw, ds, None
@@ -185,19 +182,19 @@ class RowsProduct(torch.autograd.Function):
 
 def _rows_spike_grad(weights, spec: RowsSpec, g_nm) -> torch.Tensor:
     from ._float import _float_csr
+    r = spec.rows
     if spec.transpose:            # s @ A: ds = A @ g (gather over the stored rows)
-        return _float_csr(weights, spec.indices, spec.indptr, spec.row_len, g_nm, m=spec.m, k=spec.k, transpose=False)
+        return _float_csr(weights, r.indices, r.indptr, r.row_len, g_nm, m=r.m, k=r.k, transpose=False)
     mr = spec.mirror() if spec.mirror is not None else None
     if mr is not None:            # A @ s: ds = A.T @ g — a scatter; the mirror turns it into a gather
         return _float_csr(mr.data.detach(), mr.indices, mr.indptr, -1, g_nm, m=int(mr.shape[0]), k=int(mr.shape[1]), transpose=False)
-    return _float_csr(weights, spec.indices, spec.indptr, spec.row_len, g_nm, m=spec.m, k=spec.k, transpose=True)
+    return _float_csr(weights, r.indices, r.indptr, r.row_len, g_nm, m=r.m, k=r.k, transpose=True)
 
 
-def rows_product(run: Callable, weights, spikes_arg, operand, layout: str, *, indices, indptr, row_len: int, m: int, k: int,
-                 transpose: bool, mirror=None):
-    """Run ``run()`` (the existing forward path) as a :class:`RowsProduct`.  ``spikes_arg``: what the caller got (tensor or
-    event container), ``operand``: what the kernels receive."""
-    spec = RowsSpec(run, indices, indptr, row_len, m, k, transpose, layout, mirror)
+def rows_product(run: Callable, weights, spikes_arg, operand, layout: str, rows, transpose: bool, mirror=None):
+    """Run ``run()`` (the existing forward path) as a :class:`RowsProduct` over the stored ``rows``.  ``spikes_arg``: what the
+    caller got (tensor or event container), ``operand``: what the kernels receive."""
+    spec = RowsSpec(run, rows, transpose, layout, mirror)
     spec.w_meta = (tuple(weights.shape), weights.dtype)
     s = diff_spikes(spikes_arg)
     if s is not None:
@@ -273,19 +270,12 @@ def container_product(M, other, left: bool, run: Callable):
     """``other @ M`` (``left``) or ``M @ other`` of a CSR / CSC / fixed-number container with an event operand, as a
     :class:`RowsProduct` over the container's own arrays (whichever route — direct, plan, binned, mirror — ``run`` takes).
     A numpy operand gives a numpy result, without autograd."""
-    from ._csr import CSR
     from ._event import event_operand
-    from ._fcn import FixedNumConn
     operand = event_operand(other, scatter=True)
     if A.wants_numpy(operand):
         with torch.no_grad():
             return run()
-    if isinstance(M, FixedNumConn):
-        (m, k), indices, indptr, row_len = M._a_shape, M.indices, None, int(M.indices.shape[1])
-        t = M._ell_transpose(left)
-    else:
-        (m, k), indices, indptr, row_len = M._plan_shape(), M.indices, M.indptr, -1
-        t = left if isinstance(M, CSR) else not left
+    t = M._scatter_side(left)
     layout = 'vec' if operand.ndim == 1 else ('bm' if left else 'nm')
-    return rows_product(run, M.data, other, operand, layout, indices=indices, indptr=indptr, row_len=row_len, m=m, k=k,
-                        transpose=t, mirror=None if t else (lambda: _live_mirror(M)))
+    return rows_product(run, M.data, other, operand, layout, M._stored_rows(), t,
+                        mirror=None if t else (lambda: _live_mirror(M)))

@@ -19,7 +19,7 @@ scatter kernel (see ``csrc/be_csr_plan.hip``; the binned route is ``csrc/be_csr_
 import ctypes
 import os
 import math
-from typing import Callable, Dict, Optional, Sequence, Tuple
+from typing import Callable, Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -1071,78 +1071,110 @@ class PlannedMatrix:
             raise MathError(f"shapes {tuple(v.shape)} and {self.shape} not aligned.")
         sp, sd = A.spikes_to_device(v)
         spikes_bm = sp.reshape(1, -1) if v.ndim == 1 else sp.contiguous()          # batch-major [n_batch, m] (packed: words)
-        out = torch.empty((1 if v.ndim == 1 else int(v.shape[0]), self.plan.k), dtype=self.plan.weight_dtype, device=A.device())
         w = self.weight if self.plan.homo else torch.empty(0, dtype=self.plan.weight_dtype, device=A.device())
-        _plan_call(self.plan, w, spikes_bm, sd, out)
+        out = rows_step(w, None, None, -1, spikes_bm, sd, m=self.plan.m, k=self.plan.k, transpose=True, workspace=self.plan)
         r = out[0] if v.ndim == 1 else out
         return r.cpu().numpy() if A.wants_numpy(v) else r
 
 
-def _variant(homo: bool, w: torch.Tensor, sd: int) -> str:
-    return f"{'homo' if homo else 'hetero'}_{A.wsuffix(w)}_{'bool' if sd == A.BE_SPIKE_BOOL else 'float'}"
-
-
-_CSRMM_ARGS = [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]
+class StoredRows(NamedTuple):
+    """The rows a container stores, as every kernel takes them: ``indices`` (flat, or ``[m, row_len]`` for fixed-length rows),
+    ``indptr`` — or ``None`` when every row has ``row_len`` entries (``row_len = -1`` beside an ``indptr``) — and the shape
+    ``(m, k)`` of the *stored* structure: ``m`` rows over ``k`` secondary ids.  CSC and ``FixedNumPerPost`` store the transpose
+    of the matrix they stand for; which operand side of ``@`` is the scatter over these rows is the container's
+    ``_scatter_side``."""
+    indices: torch.Tensor
+    indptr: Optional[torch.Tensor]
+    row_len: int
+    m: int
+    k: int
 
 
 _CSRMM_GENERIC_ARGS = [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]
+_CSRMM_INDEXED_ARGS = _CSRMM_GENERIC_ARGS[:7] + [c_vp, c_int] + _CSRMM_GENERIC_ARGS[7:]
 
 
-def _csrmm_generic(weights, indices, indptr, row_len, spikes_bm, sd, out, m, k, nb, ws, transpose) -> None:
-    """``be_binary_csrmm_{t,nt}`` with explicit dtype codes (any spike encoding; ``indptr=None`` = fixed row length)."""
-    name = 'be_binary_csrmm_t' if transpose else 'be_binary_csrmm_nt'
-    f = fn(name, c_int, _CSRMM_GENERIC_ARGS)
+def _csrmm_direct(weights, indices, indptr, row_len, perm, spikes_bm, sd, out, m, k, nb, transpose) -> None:
+    """``be_binary_csrmm_t`` (global atomics) / ``be_binary_csrmm_nt`` (gather) with explicit dtype codes: any spike encoding;
+    ``indptr=None`` = rows of ``row_len`` entries.  With ``perm`` the ``_indexed`` twins: slot ``j`` reads ``weights[perm[j]]``."""
+    if transpose:
+        ws = A.workspace(fn('be_binary_csrmm_t_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int])(m, k, nb, A.wcode(weights)))
+        name = 'be_binary_csrmm_t'
+    else:
+        ws = A.workspace(fn('be_binary_csrmm_nt_workspace_bytes', c_i64, [c_i64, c_i64, c_i64])(m, k, nb))
+        name = 'be_binary_csrmm_nt'
     is64 = int(indptr is not None and indptr.dtype == torch.int64)
-    check(f(A.ptr(weights), int(weights.numel() == 1), A.wcode(weights), A.ptr(indices), A.ptr(indptr), is64, row_len,
-            A.ptr(spikes_bm), sd, A.ptr(out), m, k, nb, A.ptr(ws), ws.numel(), A.stream_ptr()), name)
+    head = (A.ptr(weights), int(weights.numel() == 1), A.wcode(weights), A.ptr(indices), A.ptr(indptr), is64, row_len)
+    tail = (A.ptr(spikes_bm), sd, A.ptr(out), m, k, nb, A.ptr(ws), ws.numel(), A.stream_ptr())
+    if perm is None:
+        check(fn(name, c_int, _CSRMM_GENERIC_ARGS)(*head, *tail), name)
+    else:
+        name += '_indexed'
+        check(fn(name, c_int, _CSRMM_INDEXED_ARGS)(*head, A.ptr(perm), int(perm.dtype == torch.int64), *tail), name)
 
 
-def _csr_batched(weights, indices, indptr, spikes_bm, sd, *, shape, transpose, workspace=None):
-    """Run the CSR kernels on a batch-major spike matrix ``[n_batch, len]`` -> ``[n_batch, out_len]``."""
-    m, k = int(shape[0]), int(shape[1])
+def rows_step(weights, indices, indptr, row_len, spikes_bm, sd, *, m, k, transpose, workspace=None, perm=None):
+    """The event-driven product over stored rows (:class:`StoredRows`), for every container and functional op: batch-major
+    spikes ``[n_batch, m]`` -> ``[n_batch, k]`` (``transpose``: the scatter over the active rows) or ``[n_batch, k]`` ->
+    ``[n_batch, m]`` (the gather).  The scatter takes the matrix's ``workspace``: a :class:`ScatterPlan` — which needs only the
+    plan, the one shared weight and the spikes, so ``indices`` / ``indptr`` may be ``None`` (:class:`PlannedMatrix`, a released
+    :class:`Mirror`) — a :class:`BinnedScatter`, or ``None`` = the direct kernel.  ``perm``: the product over ``weights[perm]``
+    without a per-call gather pass (one shared weight ignores it, as in the reference)."""
+    m, k = int(m), int(k)
     nb = int(spikes_bm.shape[0])
-    homo = weights.numel() == 1
     out_len = k if transpose else m
     out = torch.empty((nb, out_len), dtype=weights.dtype, device=weights.device)
     if out_len == 0 or nb == 0:
         return out
-    if m == 0 or k == 0 or indices.numel() == 0:
+    if m == 0 or k == 0 or (indices is not None and indices.numel() == 0):
         return out.zero_()
-    is64 = int(indptr.dtype == torch.int64)
-    if transpose:
-        if isinstance(workspace, ScatterPlan):
-            assert workspace.m == m and workspace.k == k, "workspace was built for another matrix shape"
-            _plan_call(workspace, weights, spikes_bm, sd, out)
+    if weights.numel() == 1:
+        perm = None
+    elif perm is not None:
+        perm = _perm_of(perm, int(indices.numel()))
+    if transpose and isinstance(workspace, (ScatterPlan, BinnedScatter)):
+        assert workspace.m == m and workspace.k == k, "workspace was built for another matrix shape"
+        try:
+            # (a workspace of weights[perm] embeds or caches the permuted weights: brought up to date, never gathered per call)
+            w_step = weights if perm is None else _fresh_indexed_workspace(workspace, weights.reshape(-1), indices, indptr, perm)
+        except MathError:
+            pass                      # the new weights do not qualify for fixed point: the perm-fused direct kernel
+        else:
+            if isinstance(workspace, ScatterPlan):
+                _plan_call(workspace, w_step, spikes_bm, sd, out)
+            else:
+                binned_batch(workspace, w_step, indices, indptr, row_len, spikes_bm, sd, out)
             return out
-        if isinstance(workspace, BinnedScatter):
-            assert workspace.m == m and workspace.k == k, "workspace was built for another matrix shape"
-            binned_batch(workspace, weights, indices, indptr, -1, spikes_bm, sd, out)
-            return out
-        f_ws = fn('be_binary_csrmm_t_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int])
-        ws = A.workspace(f_ws(m, k, nb, A.wcode(weights)))
-        f = None if sd >= A.BE_SPIKE_BITS else fn('be_binary_csrmm_t_' + _variant(homo, weights, sd), c_int, _CSRMM_ARGS)
-    else:
-        f_ws = fn('be_binary_csrmm_nt_workspace_bytes', c_i64, [c_i64, c_i64, c_i64])
-        ws = A.workspace(f_ws(m, k, nb))
-        f = None    # generic entry point: it takes the average row length as a hint for the kernel choice
-    if f is None:     # (also: bit-packed events / id lists — the per-variant names cover bool / float only)
-        hint = -1 if transpose else int(indices.numel() // max(m, 1))
-        _csrmm_generic(weights, indices, indptr, hint, spikes_bm, sd, out, m, k, nb, ws, transpose)
-        return out
-    check(f(A.ptr(weights), A.ptr(indices), A.ptr(indptr), is64, A.ptr(spikes_bm), A.ptr(out), m, k, nb, A.ptr(ws),
-            ws.numel(), A.stream_ptr()), f.__name__)
+    # the plain gather kernel picks its lanes per row from the row length: the average one stands in where an indptr holds it
+    hint = row_len if transpose or indptr is None or perm is not None else int(indices.numel() // max(m, 1))
+    _csrmm_direct(weights, indices, indptr, hint, perm, spikes_bm, sd, out, m, k, nb, transpose)
     return out
 
 
-def _binary_csrmv_hip(weights, indices, indptr, vector, *, shape, transpose, workspace=None):
-    spikes, sd = A.spikes_to_device(vector)
-    return _csr_batched(weights, indices, indptr, spikes.reshape(1, -1), sd, shape=shape, transpose=transpose,
-                        workspace=workspace)[0]
+def _step_operand(operand):
+    """``(spikes_bm, sd)`` of an event vector ``[n]`` (one batch row) or a matrix operand ``[n, n_batch]``."""
+    if operand.ndim == 1:
+        spikes, sd = A.spikes_to_device(operand)
+        return spikes.reshape(1, -1), sd
+    # one launch per stage for the whole batch (gridDim.y = columns of B); the kernels take the spike
+    # matrix batch-major and emit a batch-major result, transposed back exactly like the reference
+    # does around its SRAW kernels (brainevent/_csr/binary.py:1263-1286).
+    return A.spikes_batch_major(operand)
+
+
+def _binary_csr_hip(weights, indices, indptr, operand, *, shape, transpose, workspace=None, perm=None):
+    spikes_bm, sd = _step_operand(operand)
+    out_bm = rows_step(weights, indices, indptr, -1, spikes_bm, sd, m=shape[0], k=shape[1], transpose=transpose,
+                       workspace=workspace, perm=perm)
+    return out_bm[0] if operand.ndim == 1 else out_bm.T
 
 
 binary_csrmv_p = OpKernel('binary_csrmv')
-binary_csrmv_p.def_kernel('hip', 'gpu', _binary_csrmv_hip, asdefault=True)
+binary_csrmv_p.def_kernel('hip', 'gpu', _binary_csr_hip, asdefault=True)
 binary_csrmv_p.def_tags('csr', 'binary')
+binary_csrmm_p = OpKernel('binary_csrmm')
+binary_csrmm_p.def_kernel('hip', 'gpu', _binary_csr_hip, asdefault=True)
+binary_csrmm_p.def_tags('csr', 'binary')
 
 
 def _check_csr_structure_dtypes(indices, indptr):
@@ -1150,33 +1182,45 @@ def _check_csr_structure_dtypes(indices, indptr):
     assert indptr.dtype in (torch.int32, torch.int64), f"indptr must be int32 or int64; got {indptr.dtype}."
 
 
-def binary_csrmv_p_call(weights, indices, indptr, vector, workspace=None, *, shape, transpose, backend=None):
-    """Validate, then dispatch (reference ``brainevent/_csr/binary.py:827-987``).  Returns the reference's 4-tuple
-    ``(y, task_begin, task_end, status)``: the three task arrays are those of a reference-style ``workspace`` handle
-    (:class:`_BinaryCsrmvTaskWorkspace`), else ``None`` — the kernels here do not produce them."""
+def _csr_p_call(op, weights, indices, indptr, operand, workspace, shape, transpose, backend):
+    """Validation and dispatch shared by ``binary_csrmv_p_call`` / ``binary_csrmm_p_call`` (``op``: the operator object)."""
     assert indptr.ndim == 1, "Indptr must be 1D."
     assert indices.ndim == 1, "Indices must be 1D."
     _check_csr_structure_dtypes(indices, indptr)
+    if op is binary_csrmm_p:
+        assert operand.ndim == 2, "B must be 2D."
     if transpose:
-        assert shape[0] == vector.shape[0], "Shape mismatch for transpose operation."
+        assert shape[0] == operand.shape[0], "Shape mismatch for transpose operation."
     else:
-        assert shape[1] == vector.shape[0], "Shape mismatch for non-transpose operation."
+        assert shape[1] == operand.shape[0], "Shape mismatch for non-transpose operation."
     assert weights.dtype.is_floating_point, 'Weights must be a floating-point type.'
     if weights.ndim == 0:
         weights = weights.reshape(1)
     native = _resolve_workspace(workspace, weights, indices, indptr, shape, transpose)
-    if _ag.needed(weights, vector):
+    if _ag.needed(weights, operand):
         def run():
-            return binary_csrmv_p(weights, indices, indptr, vector, shape=shape, transpose=transpose, workspace=native,
-                                  backend=backend)
-        out = _ag.rows_product(run, weights, vector, vector, 'vec', indices=indices, indptr=indptr, row_len=-1, m=shape[0],
-                               k=shape[1], transpose=transpose)
-        return (out,) + _task_operands(workspace)
-    return (binary_csrmv_p(weights, indices, indptr, vector, shape=shape, transpose=transpose, workspace=native,
-                           backend=backend),) + _task_operands(workspace)
+            return op(weights, indices, indptr, operand, shape=shape, transpose=transpose, workspace=native, backend=backend)
+        out = _ag.rows_product(run, weights, operand, operand, 'nm' if op is binary_csrmm_p else 'vec',
+                               StoredRows(indices, indptr, -1, int(shape[0]), int(shape[1])), transpose)
+    else:
+        out = op(weights, indices, indptr, operand, shape=shape, transpose=transpose, workspace=native, backend=backend)
+    return (out,) + _task_operands(workspace)
+
+
+def binary_csrmv_p_call(weights, indices, indptr, vector, workspace=None, *, shape, transpose, backend=None):
+    """Validate, then dispatch (reference ``brainevent/_csr/binary.py:827-987``).  Returns the reference's 4-tuple
+    ``(y, task_begin, task_end, status)``: the three task arrays are those of a reference-style ``workspace`` handle
+    (:class:`_BinaryCsrmvTaskWorkspace`), else ``None`` — the kernels here do not produce them."""
+    return _csr_p_call(binary_csrmv_p, weights, indices, indptr, vector, workspace, shape, transpose, backend)
+
+
+def binary_csrmm_p_call(weights, indices, indptr, B, workspace=None, *, shape, transpose, backend=None):
+    """Validation of the matrix-operand op (reference ``brainevent/_csr/binary.py:1452-1607``)."""
+    return _csr_p_call(binary_csrmm_p, weights, indices, indptr, B, workspace, shape, transpose, backend)
 
 
 binary_csrmv_p.def_call(binary_csrmv_p_call)
+binary_csrmm_p.def_call(binary_csrmm_p_call)
 
 
 def _binary_csrmv_benchmark_data(*, platform):
@@ -1204,6 +1248,16 @@ def _binary_csrmv_benchmark_data(*, platform):
 binary_csrmv_p.def_benchmark_data(_binary_csrmv_benchmark_data)
 
 
+def _csr_operands(data, indices, indptr, context):
+    """The three arrays of a functional op on the device, in the index dtypes the kernels take."""
+    w, idx, ptr_ = A.to_device(data), A.to_device(indices), A.to_device(indptr)
+    if idx.dtype != torch.int32:
+        idx = _as_int32_indices(idx, None, context, check_values=False)
+    if ptr_.dtype not in (torch.int32, torch.int64):
+        ptr_ = _as_indptr(ptr_, idx.shape[0], 'auto', context)
+    return w, idx, ptr_
+
+
 def binary_csrmv(data, indices, indptr, v, *, shape, workspace=None, transpose: bool = False,
                  backend: Optional[str] = None):
     """Event-driven ``A @ v`` (``transpose=False``) or ``A.T @ v`` (``transpose=True``) for CSR ``A``.
@@ -1213,59 +1267,10 @@ def binary_csrmv(data, indices, indptr, v, *, shape, workspace=None, transpose: 
     Output dtype = ``data`` dtype; output length ``shape[1]`` if ``transpose`` else ``shape[0]``.
     """
     as_np = A.wants_numpy(data, indices, indptr, v)
-    w = A.to_device(data)
-    idx = A.to_device(indices)
-    ptr_ = A.to_device(indptr)
-    if idx.dtype != torch.int32:
-        idx = _as_int32_indices(idx, None, 'binary_csrmv', check_values=False)
-    if ptr_.dtype not in (torch.int32, torch.int64):
-        ptr_ = _as_indptr(ptr_, idx.shape[0], 'auto', 'binary_csrmv')
+    w, idx, ptr_ = _csr_operands(data, indices, indptr, 'binary_csrmv')
     vec = v if isinstance(v, torch.Tensor) else np.asarray(v)
     res = binary_csrmv_p_call(w, idx, ptr_, vec, workspace, shape=tuple(shape), transpose=transpose, backend=backend)[0]
     return A.to_result(res, as_np)
-
-
-def _binary_csrmm_hip(weights, indices, indptr, B, *, shape, transpose, workspace=None):
-    # one launch per stage for the whole batch (gridDim.y = columns of B); the kernels take the spike
-    # matrix batch-major and emit a batch-major result, transposed back here exactly like the reference
-    # does around its SRAW kernels (brainevent/_csr/binary.py:1263-1286).
-    spikes_bm, sd = A.spikes_batch_major(B)
-    out_bm = _csr_batched(weights, indices, indptr, spikes_bm, sd, shape=shape, transpose=transpose,
-                          workspace=workspace)
-    return out_bm.T
-
-
-binary_csrmm_p = OpKernel('binary_csrmm')
-binary_csrmm_p.def_kernel('hip', 'gpu', _binary_csrmm_hip, asdefault=True)
-binary_csrmm_p.def_tags('csr', 'binary')
-
-
-def binary_csrmm_p_call(weights, indices, indptr, B, workspace=None, *, shape, transpose, backend=None):
-    """Validation of the matrix-operand op (reference ``brainevent/_csr/binary.py:1452-1607``)."""
-    assert indptr.ndim == 1, "Indptr must be 1D."
-    assert indices.ndim == 1, "Indices must be 1D."
-    _check_csr_structure_dtypes(indices, indptr)
-    assert B.ndim == 2, "B must be 2D."
-    if transpose:
-        assert shape[0] == B.shape[0], "Shape mismatch for transpose operation."
-    else:
-        assert shape[1] == B.shape[0], "Shape mismatch for non-transpose operation."
-    assert weights.dtype.is_floating_point, 'Weights must be a floating-point type.'
-    if weights.ndim == 0:
-        weights = weights.reshape(1)
-    native = _resolve_workspace(workspace, weights, indices, indptr, shape, transpose)
-    if _ag.needed(weights, B):
-        def run():
-            return binary_csrmm_p(weights, indices, indptr, B, shape=shape, transpose=transpose, workspace=native,
-                                  backend=backend)
-        out = _ag.rows_product(run, weights, B, B, 'nm', indices=indices, indptr=indptr, row_len=-1, m=shape[0], k=shape[1],
-                               transpose=transpose)
-        return (out,) + _task_operands(workspace)
-    return (binary_csrmm_p(weights, indices, indptr, B, shape=shape, transpose=transpose, workspace=native,
-                           backend=backend),) + _task_operands(workspace)
-
-
-binary_csrmm_p.def_call(binary_csrmm_p_call)
 
 
 def binary_csrmm(data, indices, indptr, B, *, shape, workspace=None, transpose: bool = False,
@@ -1273,13 +1278,7 @@ def binary_csrmm(data, indices, indptr, B, *, shape, workspace=None, transpose: 
     """Event-driven ``A @ B`` / ``A.T @ B`` with a binary matrix ``B[rows, cols]``
     (reference ``brainevent/_csr/binary.py:264-384``): ``C[j, l] = sum_i A[i, j] * e(B[i, l])``."""
     as_np = A.wants_numpy(data, indices, indptr, B)
-    w = A.to_device(data)
-    idx = A.to_device(indices)
-    ptr_ = A.to_device(indptr)
-    if idx.dtype != torch.int32:
-        idx = _as_int32_indices(idx, None, 'binary_csrmm', check_values=False)
-    if ptr_.dtype not in (torch.int32, torch.int64):
-        ptr_ = _as_indptr(ptr_, idx.shape[0], 'auto', 'binary_csrmm')
+    w, idx, ptr_ = _csr_operands(data, indices, indptr, 'binary_csrmm')
     Bm = B if isinstance(B, torch.Tensor) else np.asarray(B)
     res = binary_csrmm_p_call(w, idx, ptr_, Bm, workspace, shape=tuple(shape), transpose=transpose, backend=backend)[0]
     return A.to_result(res, as_np)
@@ -1332,65 +1331,23 @@ def _fresh_indexed_workspace(ws, w, idx, ptr_, p):
     return ws.indexed_data if isinstance(ws, BinnedScatter) else w
 
 
-def _csr_batched_indexed(weights, indices, indptr, perm, spikes_bm, sd, *, shape, transpose, workspace=None):
-    """``_csr_batched`` over ``weights[perm]`` without a per-call gather pass."""
-    if weights.numel() == 1 or perm is None:             # one shared weight ignores perm, as in the reference
-        return _csr_batched(weights, indices, indptr, spikes_bm, sd, shape=shape, transpose=transpose, workspace=workspace)
-    m, k = int(shape[0]), int(shape[1])
-    nb = int(spikes_bm.shape[0])
-    out_len = k if transpose else m
-    out = torch.empty((nb, out_len), dtype=weights.dtype, device=weights.device)
-    if out_len == 0 or nb == 0:
-        return out
-    if m == 0 or k == 0 or indices.numel() == 0:
-        return out.zero_()
-    p = _perm_of(perm, int(indices.numel()))
-    if transpose and isinstance(workspace, (ScatterPlan, BinnedScatter)):
-        assert workspace.m == m and workspace.k == k, "workspace was built for another matrix shape"
-        try:
-            w_step = _fresh_indexed_workspace(workspace, weights.reshape(-1), indices, indptr, p)
-        except MathError:
-            workspace = None          # the new weights do not qualify for fixed point: the perm-fused direct kernel
-        else:
-            if isinstance(workspace, ScatterPlan):
-                _plan_call(workspace, w_step, spikes_bm, sd, out)
-            else:
-                binned_batch(workspace, w_step, indices, indptr, -1, spikes_bm, sd, out)
-            return out
-    if transpose:
-        ws = A.workspace(fn('be_binary_csrmm_t_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int])(m, k, nb, A.wcode(weights)))
-        name = 'be_binary_csrmm_t_indexed'
-    else:
-        ws = A.workspace(fn('be_binary_csrmm_nt_workspace_bytes', c_i64, [c_i64, c_i64, c_i64])(m, k, nb))
-        name = 'be_binary_csrmm_nt_indexed'
-    f = fn(name, c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_vp,
-                         c_i64, c_vp])
-    check(f(A.ptr(weights), 0, A.wcode(weights), A.ptr(indices), A.ptr(indptr), int(indptr.dtype == torch.int64), -1, A.ptr(p),
-            int(p.dtype == torch.int64), A.ptr(spikes_bm), sd, A.ptr(out), m, k, nb, A.ptr(ws), ws.numel(), A.stream_ptr()), name)
-    return out
+def _binary_csr_indexed_hip(data, indices, indptr, perm, operand, *, shape, transpose, workspace=None):
+    return _binary_csr_hip(data, indices, indptr, operand, shape=shape, transpose=transpose, workspace=workspace, perm=perm)
 
 
-def _binary_csrmv_indexed_hip(data, indices, indptr, perm, vector, *, shape, transpose, workspace=None):
-    spikes, sd = A.spikes_to_device(vector)
-    return _csr_batched_indexed(data, indices, indptr, perm, spikes.reshape(1, -1), sd, shape=shape, transpose=transpose,
-                                workspace=workspace)[0]
-
-
-def _binary_csrmm_indexed_hip(data, indices, indptr, perm, B, *, shape, transpose, workspace=None):
-    spikes_bm, sd = A.spikes_batch_major(B)
-    return _csr_batched_indexed(data, indices, indptr, perm, spikes_bm, sd, shape=shape, transpose=transpose,
-                                workspace=workspace).T
-
-
-def _indexed_operands(data, indices, indptr, context):
-    w, idx, ptr_ = A.to_device(data), A.to_device(indices), A.to_device(indptr)
-    if idx.dtype != torch.int32:
-        idx = _as_int32_indices(idx, None, context, check_values=False)
-    if ptr_.dtype not in (torch.int32, torch.int64):
-        ptr_ = _as_indptr(ptr_, idx.shape[0], 'auto', context)
+def _indexed_call(op, context, data, indices, indptr, perm, operand, shape, workspace, transpose, backend):
+    as_np = A.wants_numpy(data, indices, indptr, perm, operand)
+    w, idx, ptr_ = _csr_operands(data, indices, indptr, context)
     assert indptr.ndim == 1 and indices.ndim == 1, "indices and indptr must be 1D."
     assert w.dtype.is_floating_point, 'Weights must be a floating-point type.'
-    return (w.reshape(1) if w.ndim == 0 else w), idx, ptr_
+    w = w.reshape(1) if w.ndim == 0 else w
+    x = operand if isinstance(operand, torch.Tensor) else np.asarray(operand)
+    if op is binary_csrmm_indexed_p:
+        assert x.ndim == 2, "B must be 2D."
+    assert (shape[0] if transpose else shape[1]) == x.shape[0], "Shape mismatch between the events and the structure."
+    res = op(w, idx, ptr_, None if w.numel() == 1 else A.to_device(perm), x, shape=tuple(shape), transpose=transpose,
+             workspace=workspace, backend=backend)
+    return A.to_result(res, as_np)
 
 
 def binary_csrmv_indexed(data, indices, indptr, perm, v, *, shape, workspace=None, transpose: bool = False,
@@ -1402,34 +1359,23 @@ def binary_csrmv_indexed(data, indices, indptr, perm, v, *, shape, workspace=Non
     direct kernels (``be_binary_csrmm_{t,nt}_indexed`` — only the weights of active rows are read); a workspace from
     :func:`indexed_workspace` embeds (plan) or caches (binned) the permuted weights, keyed on ``(data, perm)``, and is
     re-derived only when ``data`` was modified in place.  One shared weight ignores ``perm``."""
-    as_np = A.wants_numpy(data, indices, indptr, perm, v)
-    w, idx, ptr_ = _indexed_operands(data, indices, indptr, 'binary_csrmv_indexed')
-    vec = v if isinstance(v, torch.Tensor) else np.asarray(v)
-    assert (shape[0] if transpose else shape[1]) == vec.shape[0], "Shape mismatch between the events and the structure."
-    res = binary_csrmv_indexed_p(w, idx, ptr_, None if w.numel() == 1 else A.to_device(perm), vec, shape=tuple(shape),
-                                 transpose=transpose, workspace=workspace, backend=backend)
-    return A.to_result(res, as_np)
+    return _indexed_call(binary_csrmv_indexed_p, 'binary_csrmv_indexed', data, indices, indptr, perm, v, shape, workspace,
+                         transpose, backend)
 
 
 def binary_csrmm_indexed(data, indices, indptr, perm, B, *, shape, workspace=None, transpose: bool = False,
                          backend: Optional[str] = None):
     """Matrix-operand twin of :func:`binary_csrmv_indexed` (reference ``_csr/binary_indexed.py:615``)."""
-    as_np = A.wants_numpy(data, indices, indptr, perm, B)
-    w, idx, ptr_ = _indexed_operands(data, indices, indptr, 'binary_csrmm_indexed')
-    Bm = B if isinstance(B, torch.Tensor) else np.asarray(B)
-    assert Bm.ndim == 2, "B must be 2D."
-    assert (shape[0] if transpose else shape[1]) == Bm.shape[0], "Shape mismatch between the events and the structure."
-    res = binary_csrmm_indexed_p(w, idx, ptr_, None if w.numel() == 1 else A.to_device(perm), Bm, shape=tuple(shape),
-                                 transpose=transpose, workspace=workspace, backend=backend)
-    return A.to_result(res, as_np)
+    return _indexed_call(binary_csrmm_indexed_p, 'binary_csrmm_indexed', data, indices, indptr, perm, B, shape, workspace,
+                         transpose, backend)
 
 
 #: operator objects of the indexed products (reference ``_csr/binary_indexed.py``: ``binary_csrmv_indexed_p`` / ``binary_csrmm_indexed_p``)
 binary_csrmv_indexed_p = OpKernel('binary_csrmv_indexed')
-binary_csrmv_indexed_p.def_kernel('hip', 'gpu', _binary_csrmv_indexed_hip, asdefault=True)
+binary_csrmv_indexed_p.def_kernel('hip', 'gpu', _binary_csr_indexed_hip, asdefault=True)
 binary_csrmv_indexed_p.def_tags('csr', 'binary', 'indexed')
 binary_csrmm_indexed_p = OpKernel('binary_csrmm_indexed')
-binary_csrmm_indexed_p.def_kernel('hip', 'gpu', _binary_csrmm_indexed_hip, asdefault=True)
+binary_csrmm_indexed_p.def_kernel('hip', 'gpu', _binary_csr_indexed_hip, asdefault=True)
 binary_csrmm_indexed_p.def_tags('csr', 'binary', 'indexed')
 
 
@@ -1562,15 +1508,11 @@ class Mirror:
 
     def _apply(self, v, backend=None):
         if not self.released:
-            call = binary_csrmv_p_call if v.ndim == 1 else binary_csrmm_p_call
-            return call(self.data, self.indices, self.indptr, v, self.plan, shape=self.shape, transpose=True, backend=backend)[0]
-        if v.ndim == 1:
-            sp, sd = A.spikes_to_device(v)
-            spikes_bm = sp.reshape(1, -1)
-        else:
-            spikes_bm, sd = A.spikes_batch_major(v)
-        out = torch.empty((int(spikes_bm.shape[0]), self.shape[1]), dtype=self.plan.weight_dtype, device=A.device())
-        _plan_call(self.plan, self.data, spikes_bm, sd, out)
+            return _csr_p_call(binary_csrmv_p if v.ndim == 1 else binary_csrmm_p, self.data, self.indices, self.indptr, v, self.plan,
+                               self.shape, True, backend)[0]
+        spikes_bm, sd = _step_operand(v)
+        out = rows_step(self.data, None, None, -1, spikes_bm, sd, m=self.shape[0], k=self.shape[1], transpose=True,
+                        workspace=self.plan)
         return out[0] if v.ndim == 1 else out.T
 
 
@@ -1652,7 +1594,99 @@ def build_mirror_of(data, indices, indptr, row_len, m: int, k: int, *, keep_raw:
     return Mirror((k, m), t_data, t_idx, t_ptr, ws, perm, stamp, homo, b.counts)
 
 
-class CompressedSparseData(PlasticityMixin, DataRepresentation):
+class StoredRowsData(PlasticityMixin, DataRepresentation):
+    """Common base of the four containers that hold a matrix as stored rows — :class:`CSR` / :class:`CSC` and
+    ``FixedNumPerPre`` / ``FixedNumPerPost``: each says what it stores (:meth:`_stored_rows`, ``_stored_transposed``); the life
+    cycle of the two per-matrix workspaces in ``buffers`` — ``'scatter_plan'`` and ``'mirror'`` — is written once over that."""
+    #: the stored rows are the columns of the matrix the container stands for (CSC, ``FixedNumPerPost``)
+    _stored_transposed = False
+
+    def _stored_rows(self) -> StoredRows:
+        raise NotImplementedError
+
+    def _scatter_side(self, left: bool) -> bool:
+        """Whether ``other @ self`` (``left``) / ``self @ other`` is the scatter over the stored rows (else: the gather)."""
+        return bool(left) != self._stored_transposed
+
+    def _scatter_workspace(self):
+        """Workspace of the scatter direction (plan / binned / ``None`` = direct), built on first use and cached in
+        ``buffers`` (reference ``_ensure_binary_workspace_and_get``, ``_csr/main.py:148-161``); re-derived when ``self.data``
+        was modified in place since."""
+        ws = self.buffers.get('scatter_plan', False)          # (a cached None is an answer: the direct route)
+        if ws is None or (ws is not False and not ws.is_stale(self.data)):
+            return ws
+        rows = self._stored_rows()
+        if ws is False:
+            ws = make_scatter_workspace(choose_scatter_route(self.nse, rows.m, rows.k, self.data), self.data, rows.indices,
+                                        rows.indptr, rows.m, rows.k, self.nse, row_len=rows.row_len)
+        else:
+            ws = fresh_scatter_workspace(ws, self.data, rows.indices, rows.indptr)
+        self.buffers['scatter_plan'] = ws
+        return ws
+
+    def prepare(self, mirror: bool = False):
+        """Build the scatter workspace now (otherwise it is built by the first product of the scatter side).
+        ``mirror=True`` also builds the transposed mirror so that the *gather* side runs event-driven too."""
+        self._scatter_workspace()
+        if mirror:
+            self.build_mirror()
+        return self
+
+    def refresh_weights(self):
+        """Bring the cached workspaces up to date after ``self.data`` was modified in place.  The products check this by
+        themselves on every call (``data._version``); call it explicitly between replays of a captured HIP graph, whose
+        launches cannot.  The same holds for ``update_on_pre`` / ``update_on_post(inplace=True)`` in a captured step: a replay
+        repeats the path chosen at capture time (with its clip certificate, ``brainevent_amd._plasticity``), so nothing else
+        may write ``data`` out of ``[w_min, w_max]`` between replays."""
+        if 'scatter_plan' in self.buffers:
+            self._scatter_workspace()
+        self._fresh_mirror()
+        return self
+
+    # -- transposed mirror: makes the unfavourable (gather) side event-driven -----------------------------------
+    def build_mirror(self, *, keep_raw: Optional[bool] = None, keep_perm: Optional[bool] = None):
+        """Materialise the transposed structure once, with the weights moved along (the reference's ``_weight_indices`` /
+        ``csr_to_csc_index`` route, ``brainevent/_csr/main.py:1321-1357``, ``_fcn/main.py:280-300``) and give it a scatter
+        workspace of its own: afterwards the gather side scatters over the *active columns* instead of reading every stored row
+        (:class:`Mirror`, :func:`build_mirror_of`: the library's column-block count / scan / fill kernels, any entry count)."""
+        if self.buffers.get('mirror') is None:
+            rows = self._stored_rows()
+            self.buffers['mirror'] = build_mirror_of(self.data, rows.indices, rows.indptr, rows.row_len, rows.m, rows.k,
+                                                     keep_raw=keep_raw, keep_perm=keep_perm)
+        return self.buffers['mirror']
+
+    def _fresh_mirror(self, auto: bool = False):
+        """The cached mirror, brought up to date with ``self.data`` (it holds a permuted copy of the weights); with ``auto``
+        a matrix large enough for the event-driven route to pay gets its mirror on first use, like the reference builds
+        its CSC triple on the first ``CSR @ events`` (``_csr/main.py:1321-1357``)."""
+        mr = self.buffers.get('mirror')
+        if mr is None:
+            if not auto or 'mirror' in self.buffers:      # (a cached None: the automatic build was refused once)
+                return None
+            rows = self._stored_rows()
+            if not auto_mirror_wanted(self.nse, rows.m, rows.k, self.data):
+                self.buffers['mirror'] = None
+                return None
+            mr = self.build_mirror()
+            owner = weakref.ref(self)            # (no cycle container -> mirror -> closure -> container: 80-GB arrays must not wait for the GC)
+
+            def gather(v):      # the streaming gather over the stored rows: the mirror's one-off cross-check
+                c = owner()
+                r = c._stored_rows()
+                spikes, sd = A.spikes_to_device(v)
+                ref = rows_step(c.data, r.indices, r.indptr, r.row_len, spikes.reshape(1, -1), sd, m=r.m, k=r.k, transpose=False)[0]
+                return ref, lambda: c.buffers.__setitem__('mirror', None)
+            mr.check = gather
+        elif mr.is_stale(self.data):
+            rows = self._stored_rows()
+            mr = self.buffers['mirror'] = mr.refreshed(self.data, rows.indices, rows.indptr, rows.row_len, rows.m, rows.k)
+        return mr
+
+    def _res(self, t):
+        return A.to_result(t, self._numpy_result)
+
+
+class CompressedSparseData(StoredRowsData):
     """Common base of :class:`CSR` and :class:`CSC` (reference ``_csr/main.py:182-277``)."""
     _compressed_format = 'csr'
 
@@ -1739,24 +1773,9 @@ class CompressedSparseData(PlasticityMixin, DataRepresentation):
         return out
 
     # -- per-matrix workspace ----------------------------------------------------------------------
-    def _plan_shape(self) -> Tuple[int, int]:
-        """(rows, cols) of the stored compressed structure (CSC stores the transpose)."""
-        return self.shape if type(self)._compressed_format == 'csr' else self.shape[::-1]
-
-    def _scatter_workspace(self) -> Optional[ScatterPlan]:
-        """Plan for the scatter direction, built on first use and cached in ``buffers``
-        (reference ``_ensure_binary_workspace_and_get``, ``_csr/main.py:148-161``)."""
-        if 'scatter_plan' in self.buffers:
-            plan = self.buffers['scatter_plan'] = fresh_scatter_workspace(self.buffers['scatter_plan'], self.data, self.indices,
-                                                                          self.indptr)
-            return plan
-        m, k = self._plan_shape()
-        plan = None
-        if self.nse >= PLAN_MIN_NNZ and m > 0 and k > 0:
-            plan = make_scatter_workspace(choose_scatter_route(self.nse, m, k, self.data), self.data, self.indices, self.indptr,
-                                          m, k, self.nse)
-        self.buffers['scatter_plan'] = plan
-        return plan
+    def _stored_rows(self) -> StoredRows:
+        m, k = self.shape[::-1] if self._stored_transposed else self.shape          # (CSC stores the transpose)
+        return StoredRows(self.indices, self.indptr, -1, m, k)
 
     def prepare(self, mirror: bool = False, keep_order: Optional[bool] = None, release_raw: bool = False):
         """Build the scatter workspace now (otherwise it is built by the first ``spk @ matrix``).
@@ -1780,73 +1799,43 @@ class CompressedSparseData(PlasticityMixin, DataRepresentation):
                 self._scatter_workspace()
             finally:
                 PLAN_KEEP_ORDER = saved
-        self._scatter_workspace()
-        if mirror:
-            self.build_mirror()
-        return self
+        return super().prepare(mirror)
 
-    def refresh_weights(self):
-        """Bring the cached workspaces up to date after ``self.data`` was modified in place.  The products check this by
-        themselves on every call (``data._version``); call it explicitly between replays of a captured HIP graph, whose
-        launches cannot.  The same holds for ``update_on_pre`` / ``update_on_post(inplace=True)`` in a captured step: a replay
-        repeats the path chosen at capture time (with its clip certificate, ``brainevent_amd._plasticity``), so nothing else
-        may write ``data`` out of ``[w_min, w_max]`` between replays."""
-        if 'scatter_plan' in self.buffers:
-            self._scatter_workspace()
-        if 'mirror' in self.buffers:
-            self._fresh_mirror()
-        return self
+    # -- products ------------------------------------------------------------------------------------
+    def _event_product(self, other, left: bool):
+        """``other @ self`` (``left``) or ``self @ other``.  Scatter side: the matrix's workspace + the step; gather side: the
+        mirror when it exists (or this matrix is large enough to get one on first use), else the gather step; a dense operand:
+        the float twins.  ``events @ M`` hands the ops a matrix operand transposed, ``[in_len, n_batch]`` as the reference's ops
+        take it, and transposes the result back."""
+        if not is_event(other):
+            return _dense_product(self, other, left)
+        if _ag.needed(self.data, other):
+            return _ag.container_product(self, other, left, lambda: self._event_product(other, left))
+        scatter = left != self._stored_transposed
+        # scatter kernels take a compacted id list as it is (no compaction launch): the scatter side, and the other one once
+        # its mirror exists
+        v = _event_value(other, scatter=scatter)
+        if v.ndim not in (1, 2):
+            raise NotImplementedError(f"matmul with object of shape {v.shape}")
+        mr = None if scatter else self._fresh_mirror(auto=True)
+        if mr is not None and v.ndim == 1:
+            v = _event_value(other, scatter=True)
+        flip = left and v.ndim == 2
+        x = v.T if flip else v
+        if mr is not None:
+            r = mr.apply(x, backend=self.backend)
+        else:
+            rows = self._stored_rows()
+            r = _csr_p_call(binary_csrmv_p if v.ndim == 1 else binary_csrmm_p, self.data, rows.indices, rows.indptr, x,
+                            self._scatter_workspace() if scatter else None, (rows.m, rows.k), scatter, self.backend)[0]
+        r = r.T if flip else r
+        return self._res(r) if A.wants_numpy(v) else r
 
-    # -- transposed mirror: makes the unfavourable (gather) direction event-driven -----------------------------
-    def build_mirror(self, *, keep_raw: Optional[bool] = None, keep_perm: Optional[bool] = None):
-        """Materialise the transposed structure once (the reference's ``_weight_indices`` / ``csr_to_csc_index`` route,
-        ``brainevent/_csr/main.py:1321-1357``, ``brainevent/_misc.py:1516``) and give it a scatter workspace: afterwards
-        ``CSR @ spk`` / ``spk @ CSC`` scatter over the *active columns* instead of reading the whole matrix
-        (:class:`Mirror`, :func:`build_mirror_of`: the library's column-block count / scan / fill kernels, any entry count)."""
-        if 'mirror' in self.buffers:
-            return self.buffers['mirror']
-        m, k = self._plan_shape()                      # stored structure: m rows, k secondary ids
-        self.buffers['mirror'] = build_mirror_of(self.data, self.indices, self.indptr, -1, m, k, keep_raw=keep_raw,
-                                                 keep_perm=keep_perm)
-        return self.buffers['mirror']
+    def __matmul__(self, other):
+        return self._event_product(other, False)
 
-    def _fresh_mirror(self, auto: bool = False):
-        """The cached mirror, brought up to date with ``self.data`` (it holds a permuted copy of the weights); with ``auto``
-        a matrix large enough for the event-driven route to pay gets its mirror on first use, like the reference builds
-        its CSC triple on the first ``CSR @ events`` (``_csr/main.py:1321-1357``)."""
-        mr = self.buffers.get('mirror')
-        if mr is None:
-            if not auto or 'mirror' in self.buffers:      # (a cached None: the automatic build was refused once)
-                return None
-            m, k = self._plan_shape()
-            if not auto_mirror_wanted(self.nse, m, k, self.data):
-                self.buffers['mirror'] = None
-                return None
-            mr = self.build_mirror()
-
-            owner = weakref.ref(self)            # (no cycle container -> mirror -> closure -> container: 80-GB arrays must not wait for the GC)
-
-            def gather(v, _shape=(m, k)):
-                c = owner()
-                ref = binary_csrmv_p_call(c.data, c.indices, c.indptr, v, None, shape=_shape, transpose=False, backend=c.backend)[0]
-                return ref, lambda: c.buffers.__setitem__('mirror', None)
-            mr.check = gather
-            return mr
-        if mr.is_stale(self.data):
-            m, k = self._plan_shape()
-            mr = self.buffers['mirror'] = mr.refreshed(self.data, self.indices, self.indptr, -1, m, k)
-        return mr
-
-    def _gather_via_mirror(self, v):
-        """Event-driven evaluation of the gather direction through the mirror, or ``None`` if there is no mirror.  ``v``:
-        the event vector ``[k]`` or a matrix operand ``[k, n]`` (result ``[m, n]``)."""
-        mr = self._fresh_mirror(auto=True)
-        if mr is None:
-            return None
-        return mr.apply(v, backend=self.backend)
-
-    def _res(self, t):
-        return A.to_result(t, self._numpy_result)
+    def __rmatmul__(self, other):
+        return self._event_product(other, True)
 
 
 def _event_value(other, scatter: bool = False):
@@ -1855,14 +1844,15 @@ def _event_value(other, scatter: bool = False):
     return event_operand(other, scatter=scatter)
 
 
-def _dense_product(M, other, *, shape, transpose: bool, operand_on_left: bool):
-    """A dense (non-event) operand against the stored arrays of a CSR / CSC container: ``op(A) @ x`` or ``x @ op(A)`` with
-    ``op(A) = A.T if transpose else A`` and ``A`` the CSR reading of the arrays (``shape``).  Float-operand twins
-    (``_float.csrmv`` / ``csrmm``; reference ``_csr/main.py:1595-1697``, ``:1699-1776``): ``x @ op(A) = (op(A).T @ x.T).T``."""
+def _dense_product(M, other, left: bool):
+    """A dense (non-event) operand against a CSR / CSC container: ``x @ M`` (``left``) or ``M @ x`` over the stored rows
+    ``A`` — ``A.T @ x`` on the scatter side, ``A @ x`` on the gather side.  Float-operand twins (``_float.csrmv`` / ``csrmm``;
+    reference ``_csr/main.py:1595-1697``, ``:1699-1776``); ``x @ op(A) = (op(A).T @ x.T).T``."""
     from ._float import csrmv_p_call, csrmm_p_call
     x = other if isinstance(other, torch.Tensor) else np.asarray(other)
-    t = (not transpose) if operand_on_left else transpose
-    data, indices, indptr = M.data, M.indices, M.indptr
+    rows = M._stored_rows()
+    t = M._scatter_side(left)
+    data, indices, indptr, shape = M.data, rows.indices, rows.indptr, (rows.m, rows.k)
     if t:       # the scatter direction runs on float atomics (~21 G/s); the mirror turns it into a gather — an existing one, or
         #             the one a large matrix gets on first use as for event operands (auto_mirror_wanted) — but only while a
         #             mirror of that size keeps its raw arrays: a plan-only mirror cannot serve a dense operand
@@ -1872,8 +1862,8 @@ def _dense_product(M, other, *, shape, transpose: bool, operand_on_left: bool):
     if x.ndim == 1:
         r = csrmv_p_call(data, indices, indptr, x, shape=shape, transpose=t, backend=M.backend)[0]
     elif x.ndim == 2:
-        r = csrmm_p_call(data, indices, indptr, x.T if operand_on_left else x, shape=shape, transpose=t, backend=M.backend)[0]
-        r = r.T if operand_on_left else r
+        r = csrmm_p_call(data, indices, indptr, x.T if left else x, shape=shape, transpose=t, backend=M.backend)[0]
+        r = r.T if left else r
     else:
         raise NotImplementedError(f"matmul with object of shape {tuple(x.shape)}")
     return M._res(r) if A.wants_numpy(x) else r
@@ -1882,46 +1872,6 @@ def _dense_product(M, other, *, shape, transpose: bool, operand_on_left: bool):
 class CSR(CompressedSparseData):
     """Compressed sparse row matrix with event-driven products (reference ``_csr/main.py:977``)."""
     _compressed_format = 'csr'
-
-    def __matmul__(self, other):      # csr @ other
-        if is_event(other) and _ag.needed(self.data, other):
-            return _ag.container_product(self, other, False, lambda: CSR.__matmul__(self, other))
-        if is_event(other):
-            v = _event_value(other)
-            r = None
-            if v.ndim in (1, 2) and self._fresh_mirror(auto=True) is not None:
-                # the mirror turns this product into a scatter: a compacted container hands its id list over (no compaction launch)
-                v = _event_value(other, scatter=True)
-                r = self._gather_via_mirror(v)
-            if r is not None:
-                pass
-            elif v.ndim == 1:
-                r = binary_csrmv_p_call(self.data, self.indices, self.indptr, v, None, shape=self.shape,
-                                        transpose=False, backend=self.backend)[0]
-            elif v.ndim == 2:
-                r = binary_csrmm_p_call(self.data, self.indices, self.indptr, v, None, shape=self.shape,
-                                        transpose=False, backend=self.backend)[0]
-            else:
-                raise NotImplementedError(f"matmul with object of shape {v.shape}")
-            return self._res(r) if A.wants_numpy(v) else r
-        return _dense_product(self, other, shape=self.shape, transpose=False, operand_on_left=False)      # csr @ x
-
-    def __rmatmul__(self, other):     # other @ csr
-        if is_event(other) and _ag.needed(self.data, other):
-            return _ag.container_product(self, other, True, lambda: CSR.__rmatmul__(self, other))
-        if is_event(other):
-            v = _event_value(other, scatter=True)
-            ws = self._scatter_workspace()
-            if v.ndim == 1:
-                r = binary_csrmv_p_call(self.data, self.indices, self.indptr, v, ws, shape=self.shape, transpose=True,
-                                        backend=self.backend)[0]
-            elif v.ndim == 2:
-                r = binary_csrmm_p_call(self.data, self.indices, self.indptr, v.T, ws, shape=self.shape,
-                                        transpose=True, backend=self.backend)[0].T
-            else:
-                raise NotImplementedError(f"matmul with object of shape {v.shape}")
-            return self._res(r) if A.wants_numpy(v) else r
-        return _dense_product(self, other, shape=self.shape, transpose=False, operand_on_left=True)       # x @ csr
 
     def transpose(self, axes=None):
         assert axes is None, "transpose does not support axes argument."
@@ -1949,49 +1899,7 @@ class CSC(CompressedSparseData):
     """Compressed sparse column matrix (reference ``_csr/main.py:1890``): ``indices`` are row ids,
     ``indptr`` has ``shape[1] + 1`` entries — i.e. the CSR arrays of the transpose."""
     _compressed_format = 'csc'
-
-    def __matmul__(self, other):      # csc @ other : scatter over the active columns
-        if is_event(other) and _ag.needed(self.data, other):
-            return _ag.container_product(self, other, False, lambda: CSC.__matmul__(self, other))
-        if is_event(other):
-            v = _event_value(other, scatter=True)
-            ws = self._scatter_workspace()
-            if v.ndim == 1:
-                r = binary_csrmv_p_call(self.data, self.indices, self.indptr, v, ws, shape=self.shape[::-1],
-                                        transpose=True, backend=self.backend)[0]
-            elif v.ndim == 2:
-                r = binary_csrmm_p_call(self.data, self.indices, self.indptr, v, ws, shape=self.shape[::-1],
-                                        transpose=True, backend=self.backend)[0]
-            else:
-                raise NotImplementedError(f"matmul with object of shape {v.shape}")
-            return self._res(r) if A.wants_numpy(v) else r
-        return _dense_product(self, other, shape=self.shape[::-1], transpose=True, operand_on_left=False)  # csc @ x = A'.T @ x
-
-    def __rmatmul__(self, other):     # other @ csc : gather
-        if is_event(other) and _ag.needed(self.data, other):
-            return _ag.container_product(self, other, True, lambda: CSC.__rmatmul__(self, other))
-        if is_event(other):
-            v = _event_value(other)
-            r = None
-            if v.ndim == 1:
-                if self._fresh_mirror(auto=True) is not None:
-                    v = _event_value(other, scatter=True)      # (the mirror scatters: id lists are taken as they are)
-                r = self._gather_via_mirror(v)
-            elif v.ndim == 2:
-                r = self._gather_via_mirror(v.T)
-                r = None if r is None else r.T
-            if r is not None:
-                pass
-            elif v.ndim == 1:
-                r = binary_csrmv_p_call(self.data, self.indices, self.indptr, v, None, shape=self.shape[::-1],
-                                        transpose=False, backend=self.backend)[0]
-            elif v.ndim == 2:
-                r = binary_csrmm_p_call(self.data, self.indices, self.indptr, v.T, None, shape=self.shape[::-1],
-                                        transpose=False, backend=self.backend)[0].T
-            else:
-                raise NotImplementedError(f"matmul with object of shape {v.shape}")
-            return self._res(r) if A.wants_numpy(v) else r
-        return _dense_product(self, other, shape=self.shape[::-1], transpose=True, operand_on_left=True)   # x @ csc = x @ A'.T
+    _stored_transposed = True
 
     def transpose(self, axes=None):
         assert axes is None, "transpose does not support axes argument."

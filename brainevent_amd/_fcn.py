@@ -10,134 +10,84 @@ Semantics for ``indices[n_rows, n_conn]`` and ``shape = (n_rows, n_cols)`` as th
   transpose=False (gather) : ``out[i] = sum_c w[i, c] * e(s[indices[i, c]])``              -> ``out[n_rows]``
 
 An ELL matrix is a CSR matrix with an implicit ``indptr`` (``row r = [r*n_conn, (r+1)*n_conn)``), so the
-kernels are the CSR ones (``csrc/be_csr.hip``) reached through the ``be_binary_fcn*`` symbols.  The
+kernels are the CSR ones (``csrc/be_csr.hip``), reached through the stored-rows step (``_csr.rows_step``) with
+``indptr = None`` and ``row_len = n_conn``.  The
 unfavourable direction (``FixedNumPerPre @ spk``, ``spk @ FixedNumPerPost``) runs event-driven through the CSC
 mirror (reference ``_fcn/main.py:280-326``: ``_weight_indices`` + the perm-fused CSR kernel) — here a
 :class:`brainevent_amd._csr.Mirror` built by the column-block kernels with the weights moved along, on first use for
 matrices large enough for it to pay (``_csr.AUTO_MIRROR_MIN_NNZ``) or by ``prepare(mirror=True)`` — and the gather
 kernel otherwise.
 """
-import ctypes
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
 from . import _array as A
-from ._data import DataRepresentation
-from ._csr import ScatterPlan, BinnedScatter, _plan_call, binned_batch, _csrmm_generic
+from ._csr import StoredRows, StoredRowsData, rows_step, _step_operand
 from . import _csr as _csr_mod
-from ._event import BinaryArray, is_event, event_operand
-from ._lib import check, fn
+from ._event import is_event, event_operand
 from ._misc import _as_int32_indices, check_fixed_conn_num_shape
 from ._op import OpKernel
-from ._plasticity import PlasticityMixin
 from . import _autograd as _ag
 
 __all__ = ['FixedNumConn', 'FixedNumPerPre', 'FixedNumPerPost', 'binary_fcnmv', 'binary_fcnmm',
            'binary_fcnmv_p', 'binary_fcnmm_p', 'binary_fcnmv_p_call', 'binary_fcnmm_p_call']
 
-c_i64, c_int, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
-_FCN_MM_ARGS = [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]
 
-
-def _variant(homo: bool, w: torch.Tensor, sd: int) -> str:
-    return f"{'homo' if homo else 'hetero'}_{A.wsuffix(w)}_{'bool' if sd == A.BE_SPIKE_BOOL else 'float'}"
-
-
-def _fcn_batched(weights, indices, spikes_bm, sd, *, shape, transpose, workspace=None):
-    """``spikes_bm [n_batch, len]`` -> ``[n_batch, out_len]`` through the ``be_binary_fcnmm_*`` symbols."""
-    n_rows, n_conn = int(indices.shape[0]), int(indices.shape[1])
-    n_cols = int(shape[1])
-    nb = int(spikes_bm.shape[0])
-    homo = weights.numel() == 1
-    out_len = n_cols if transpose else n_rows
-    out = torch.empty((nb, out_len), dtype=weights.dtype, device=weights.device)
-    if out_len == 0 or nb == 0:
-        return out
-    if n_rows == 0 or n_cols == 0 or n_conn == 0:
-        return out.zero_()
-    if transpose:
-        if isinstance(workspace, ScatterPlan):
-            _plan_call(workspace, weights, spikes_bm, sd, out)
-            return out
-        if isinstance(workspace, BinnedScatter):
-            binned_batch(workspace, weights, indices, None, n_conn, spikes_bm, sd, out)
-            return out
-        f_ws = fn('be_binary_csrmm_t_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int])
-        ws = A.workspace(f_ws(n_rows, n_cols, nb, A.wcode(weights)))
-        f = fn('be_binary_fcnmm_scatter_' + _variant(homo, weights, sd), c_int, _FCN_MM_ARGS)
-    else:
-        f_ws = fn('be_binary_csrmm_nt_workspace_bytes', c_i64, [c_i64, c_i64, c_i64])
-        ws = A.workspace(f_ws(n_rows, n_cols, nb))
-        f = fn('be_binary_fcnmm_gather_' + _variant(homo, weights, sd), c_int, _FCN_MM_ARGS)
-    if sd >= A.BE_SPIKE_BITS:
-        _csrmm_generic(weights, indices, None, n_conn, spikes_bm, sd, out, n_rows, n_cols, nb, ws, transpose)
-        return out
-    check(f(A.ptr(weights), A.ptr(indices), A.ptr(spikes_bm), A.ptr(out), n_rows, n_cols, n_conn, nb, A.ptr(ws),
-            ws.numel(), A.stream_ptr()), f.__name__)
-    return out
-
-
-def _binary_fcnmv_hip(weights, indices, spikes, *, shape, transpose, workspace=None):
-    s, sd = A.spikes_to_device(spikes)
-    return _fcn_batched(weights, indices, s.reshape(1, -1), sd, shape=shape, transpose=transpose, workspace=workspace)[0]
-
-
-def _binary_fcnmm_hip(weights, indices, matrix, *, shape, transpose, workspace=None):
-    spikes_bm, sd = A.spikes_batch_major(matrix)
-    return _fcn_batched(weights, indices, spikes_bm, sd, shape=shape, transpose=transpose, workspace=workspace).T
+def _binary_fcn_hip(weights, indices, operand, *, shape, transpose, workspace=None):
+    """An event vector ``[len]`` or a matrix operand ``[len, n_batch]`` through the stored-rows step: rows of ``n_conn`` entries
+    each, no ``indptr``."""
+    spikes_bm, sd = _step_operand(operand)
+    out_bm = rows_step(weights, indices, None, int(indices.shape[1]), spikes_bm, sd, m=indices.shape[0], k=shape[1],
+                       transpose=transpose, workspace=workspace)
+    return out_bm[0] if operand.ndim == 1 else out_bm.T
 
 
 binary_fcnmv_p = OpKernel('binary_fcnmv')
-binary_fcnmv_p.def_kernel('hip', 'gpu', _binary_fcnmv_hip, asdefault=True)
+binary_fcnmv_p.def_kernel('hip', 'gpu', _binary_fcn_hip, asdefault=True)
 binary_fcnmv_p.def_tags('fcn', 'binary')
 binary_fcnmm_p = OpKernel('binary_fcnmm')
-binary_fcnmm_p.def_kernel('hip', 'gpu', _binary_fcnmm_hip, asdefault=True)
+binary_fcnmm_p.def_kernel('hip', 'gpu', _binary_fcn_hip, asdefault=True)
 binary_fcnmm_p.def_tags('fcn', 'binary')
+
+
+def _fcn_p_call(op, weights, indices, operand, shape, transpose, backend, workspace):
+    """Validation and dispatch shared by ``binary_fcnmv_p_call`` / ``binary_fcnmm_p_call`` (``op``: the operator object)."""
+    if op is binary_fcnmm_p:
+        assert operand.ndim == 2, "matrix must be 2D."
+    check_fixed_conn_num_shape(weights, indices, operand, shape, transpose)
+    assert weights.dtype.is_floating_point, 'Weights must be a floating-point type.'
+    weights = weights.reshape(1) if weights.numel() == 1 else weights
+    if _ag.needed(weights, operand):
+        def run():
+            return op(weights, indices, operand, shape=shape, transpose=transpose, workspace=workspace, backend=backend)
+        rows = StoredRows(indices, None, int(indices.shape[1]), int(shape[0]), int(shape[1]))
+        return (_ag.rows_product(run, weights, operand, operand, 'nm' if op is binary_fcnmm_p else 'vec', rows, transpose),)
+    return (op(weights, indices, operand, shape=shape, transpose=transpose, workspace=workspace, backend=backend),)
 
 
 def binary_fcnmv_p_call(weights, indices, spikes, *, shape, transpose, backend=None, workspace=None):
     """Validation + dispatch (reference ``brainevent/_fcn/binary.py:450-509``).  Returns a 1-tuple."""
-    check_fixed_conn_num_shape(weights, indices, spikes, shape, transpose)
-    assert weights.dtype.is_floating_point, 'Weights must be a floating-point type.'
-    weights = weights.reshape(1) if weights.numel() == 1 else weights
-    if _ag.needed(weights, spikes):
-        def run():
-            return binary_fcnmv_p(weights, indices, spikes, shape=shape, transpose=transpose, workspace=workspace, backend=backend)
-        return (_ag.rows_product(run, weights, spikes, spikes, 'vec', indices=indices, indptr=None, row_len=int(indices.shape[1]),
-                                 m=shape[0], k=shape[1], transpose=transpose),)
-    return (binary_fcnmv_p(weights, indices, spikes, shape=shape, transpose=transpose, workspace=workspace,
-                           backend=backend),)
-
-
-binary_fcnmv_p.def_call(binary_fcnmv_p_call)
+    return _fcn_p_call(binary_fcnmv_p, weights, indices, spikes, shape, transpose, backend, workspace)
 
 
 def binary_fcnmm_p_call(weights, indices, matrix, *, shape, transpose, backend=None, workspace=None):
     """Validation + dispatch of the matrix op (reference ``brainevent/_fcn/binary.py:1077-1137``)."""
-    assert matrix.ndim == 2, "matrix must be 2D."
-    check_fixed_conn_num_shape(weights, indices, matrix, shape, transpose)
-    assert weights.dtype.is_floating_point, 'Weights must be a floating-point type.'
-    weights = weights.reshape(1) if weights.numel() == 1 else weights
-    if _ag.needed(weights, matrix):
-        def run():
-            return binary_fcnmm_p(weights, indices, matrix, shape=shape, transpose=transpose, workspace=workspace, backend=backend)
-        return (_ag.rows_product(run, weights, matrix, matrix, 'nm', indices=indices, indptr=None, row_len=int(indices.shape[1]),
-                                 m=shape[0], k=shape[1], transpose=transpose),)
-    return (binary_fcnmm_p(weights, indices, matrix, shape=shape, transpose=transpose, workspace=workspace,
-                           backend=backend),)
+    return _fcn_p_call(binary_fcnmm_p, weights, indices, matrix, shape, transpose, backend, workspace)
 
 
+binary_fcnmv_p.def_call(binary_fcnmv_p_call)
 binary_fcnmm_p.def_call(binary_fcnmm_p_call)
 
 
-def _prep(weights, indices):
-    w = A.to_device(weights)
-    idx = A.to_device(indices)
+def _fcn_op(p_call, weights, indices, operand, shape, transpose, backend):
+    as_np = A.wants_numpy(weights, indices, operand)
+    w, idx = A.to_device(weights), A.to_device(indices)
     if idx.dtype != torch.int32:
         idx = _as_int32_indices(idx, None, 'binary_fcn', check_values=False)
-    return w, idx
+    x = operand if isinstance(operand, torch.Tensor) else np.asarray(operand)
+    return A.to_result(p_call(w, idx, x, shape=tuple(shape), transpose=transpose, backend=backend)[0], as_np)
 
 
 def binary_fcnmv(weights, indices, spikes, *, shape, transpose: bool = False, backend: Optional[str] = None):
@@ -146,21 +96,13 @@ def binary_fcnmv(weights, indices, spikes, *, shape, transpose: bool = False, ba
     ``transpose=False``: ``y[i] = sum_c w[i,c] * e(s[indices[i,c]])`` (``y`` has ``shape[0]`` entries);
     ``transpose=True`` : ``y[indices[i,c]] += w[i,c]`` for active ``s[i]`` (``y`` has ``shape[1]`` entries).
     """
-    as_np = A.wants_numpy(weights, indices, spikes)
-    w, idx = _prep(weights, indices)
-    s = spikes if isinstance(spikes, torch.Tensor) else np.asarray(spikes)
-    r = binary_fcnmv_p_call(w, idx, s, shape=tuple(shape), transpose=transpose, backend=backend)[0]
-    return A.to_result(r, as_np)
+    return _fcn_op(binary_fcnmv_p_call, weights, indices, spikes, shape, transpose, backend)
 
 
 def binary_fcnmm(weights, indices, matrix, *, shape, transpose: bool = False, backend: Optional[str] = None):
     """Matrix-operand version (reference ``_fcn/binary.py:564-675``): ``matrix`` is ``(shape[1], n)`` for
     ``transpose=False`` -> ``(shape[0], n)``; ``(shape[0], n)`` for ``transpose=True`` -> ``(shape[1], n)``."""
-    as_np = A.wants_numpy(weights, indices, matrix)
-    w, idx = _prep(weights, indices)
-    M = matrix if isinstance(matrix, torch.Tensor) else np.asarray(matrix)
-    r = binary_fcnmm_p_call(w, idx, M, shape=tuple(shape), transpose=transpose, backend=backend)[0]
-    return A.to_result(r, as_np)
+    return _fcn_op(binary_fcnmm_p_call, weights, indices, matrix, shape, transpose, backend)
 
 
 # =====================================================================================================
@@ -185,7 +127,7 @@ def _contains_invalid_indices(indices, *, upper_bound: int):
                          f'But found indices with min {lo} and max {hi}.')
 
 
-class FixedNumConn(PlasticityMixin, DataRepresentation):
+class FixedNumConn(StoredRowsData):
     """Base of the two ELL containers (reference ``_fcn/main.py:199-460``)."""
 
     def __init__(self, data, indices=None, *, shape, backend: Optional[str] = None, buffers: Optional[Dict] = None,
@@ -196,7 +138,7 @@ class FixedNumConn(PlasticityMixin, DataRepresentation):
         self.data = A.to_device(args[0])
         idx = A.to_device(args[1])
         self.shape = (int(shape[0]), int(shape[1]))
-        rows, upper = self._rows_and_upper()
+        rows, upper = self.shape[::-1] if self._stored_transposed else self.shape
         _validate_fixed_conn_indices(idx, expected_rows=rows, kind=self._kind)
         self.indices = _as_int32_indices(idx, upper, f'{type(self).__name__} indices', check_values=False)
         if self.data.numel() != 1 and tuple(self.data.shape) != tuple(self.indices.shape):
@@ -207,18 +149,7 @@ class FixedNumConn(PlasticityMixin, DataRepresentation):
         if check_indices:
             _contains_invalid_indices(self.indices, upper_bound=upper)
 
-    # -- subclass hooks ---------------------------------------------------------------------------
     _kind = 'Connection'
-
-    def _rows_and_upper(self):
-        raise NotImplementedError
-
-    @property
-    def _a_shape(self):
-        raise NotImplementedError
-
-    def _ell_transpose(self, transpose_W: bool) -> bool:
-        raise NotImplementedError
 
     # -- properties -------------------------------------------------------------------------------
     num_conn = property(lambda self: int(self.indices.shape[1]))
@@ -226,108 +157,45 @@ class FixedNumConn(PlasticityMixin, DataRepresentation):
     dtype = property(lambda self: self.data.dtype)
     ndim = property(lambda self: 2)
 
-    # -- per-matrix workspace -----------------------------------------------------------------------
-    def _scatter_workspace(self):
-        if 'scatter_plan' in self.buffers:     # re-derived when ``self.data`` was modified in place since
-            plan = self.buffers['scatter_plan'] = _csr_mod.fresh_scatter_workspace(self.buffers['scatter_plan'], self.data,
-                                                                                   self.indices, None)
-            return plan
-        n_rows, n_cols = self._a_shape
-        plan = None
-        plan = _csr_mod.make_scatter_workspace(_csr_mod.choose_scatter_route(self.nse, n_rows, n_cols, self.data), self.data,
-                                               self.indices, None, n_rows, n_cols, self.nse, row_len=self.num_conn)
-        self.buffers['scatter_plan'] = plan
-        return plan
-
-    def prepare(self, mirror: bool = False):
-        """Build the scatter workspace now; ``mirror=True`` also the CSC mirror of the unfavourable direction."""
-        self._scatter_workspace()
-        if mirror:
-            self.build_mirror()
-        return self
-
-    def refresh_weights(self):
-        """Bring the cached workspace up to date after ``self.data`` was modified in place (the products check it on every
-        call; needed explicitly only between replays of a captured HIP graph)."""
-        if 'scatter_plan' in self.buffers:
-            self._scatter_workspace()
-        if self.buffers.get('mirror') is not None:
-            self._fresh_mirror()
-        return self
-
-    # -- CSC mirror of the unfavourable direction (reference ``_weight_indices``, ``_fcn/main.py:280-300``) ---------------
-    def build_mirror(self, *, keep_raw: Optional[bool] = None, keep_perm: Optional[bool] = None):
-        """The transposed structure with the weights moved along and a scatter workspace of its own
-        (:func:`brainevent_amd._csr.build_mirror_of` over the implicit ``indptr``): afterwards ``FixedNumPerPre @ spk`` /
-        ``spk @ FixedNumPerPost`` scatter over the active entries of ``spk`` instead of reading every stored row."""
-        if self.buffers.get('mirror') is not None:
-            return self.buffers['mirror']
-        n_rows, n_cols = self._a_shape
-        self.buffers['mirror'] = _csr_mod.build_mirror_of(self.data, self.indices, None, self.num_conn, n_rows, n_cols,
-                                                          keep_raw=keep_raw, keep_perm=keep_perm)
-        return self.buffers['mirror']
-
-    def _fresh_mirror(self, auto: bool = False):
-        mr = self.buffers.get('mirror')
-        n_rows, n_cols = self._a_shape
-        if mr is None:
-            if not auto or 'mirror' in self.buffers:
-                return None
-            if not _csr_mod.auto_mirror_wanted(self.nse, n_rows, n_cols, self.data):
-                self.buffers['mirror'] = None
-                return None
-            mr = self.build_mirror()
-
-            import weakref
-            owner = weakref.ref(self)
-
-            def gather(s):      # the streaming gather over the fixed-length rows: the mirror's one-off cross-check
-                c = owner()
-                ref = binary_fcnmv_p_call(c.data, c.indices, s, shape=c._a_shape, transpose=False, backend=c.backend)[0]
-                return ref, lambda: c.buffers.__setitem__('mirror', None)
-            mr.check = gather
-            return mr
-        if mr.is_stale(self.data):
-            mr = self.buffers['mirror'] = mr.refreshed(self.data, self.indices, None, self.num_conn, n_rows, n_cols)
-        return mr
+    def _stored_rows(self) -> StoredRows:
+        m, k = self.shape[::-1] if self._stored_transposed else self.shape      # (FixedNumPerPost stores the transpose)
+        return StoredRows(self.indices, None, int(self.indices.shape[1]), m, k)
 
     # -- dispatch (reference ``_binary_matvec`` / ``_binary_matmat`` / ``_dispatch``) -----------------
-    def _binary_matvec(self, s, transpose_W: bool):
-        ell_t = self._ell_transpose(transpose_W)
-        if not ell_t:
+    def _binary_product(self, op, x, transpose_W: bool):
+        rows = self._stored_rows()
+        shape = (rows.m, rows.k)
+        scatter = transpose_W != self._stored_transposed
+        if not scatter:
             mr = self._fresh_mirror(auto=True)
             if mr is not None:           # unfavourable direction, event-driven (reference ``_fcn/main.py:317-326``)
-                check_fixed_conn_num_shape(self.data, self.indices, s, self._a_shape, False)
-                return mr.apply(s, backend=self.backend)
-        ws = self._scatter_workspace() if ell_t else None
-        return binary_fcnmv_p_call(self.data, self.indices, s, shape=self._a_shape, transpose=ell_t,
-                                   backend=self.backend, workspace=ws)[0]
+                if op is binary_fcnmm_p:
+                    assert x.ndim == 2, "matrix must be 2D."
+                check_fixed_conn_num_shape(self.data, self.indices, x, shape, False)
+                return mr.apply(x, backend=self.backend)
+        return _fcn_p_call(op, self.data, self.indices, x, shape, scatter, self.backend,
+                           self._scatter_workspace() if scatter else None)[0]
+
+    def _binary_matvec(self, s, transpose_W: bool):
+        return self._binary_product(binary_fcnmv_p, s, transpose_W)
 
     def _binary_matmat(self, matrix, transpose_W: bool):
-        ell_t = self._ell_transpose(transpose_W)
-        if not ell_t:
-            mr = self._fresh_mirror(auto=True)
-            if mr is not None:
-                assert matrix.ndim == 2, "matrix must be 2D."
-                check_fixed_conn_num_shape(self.data, self.indices, matrix, self._a_shape, False)
-                return mr.apply(matrix, backend=self.backend)
-        ws = self._scatter_workspace() if ell_t else None
-        return binary_fcnmm_p_call(self.data, self.indices, matrix, shape=self._a_shape, transpose=ell_t,
-                                   backend=self.backend, workspace=ws)[0]
+        return self._binary_product(binary_fcnmm_p, matrix, transpose_W)
 
     def _dispatch(self, other, transpose_W: bool):
         if is_event(other) and _ag.needed(self.data, other):
             return _ag.container_product(self, other, transpose_W, lambda: self._dispatch(other, transpose_W))
-        ell_t = self._ell_transpose(transpose_W)
+        scatter = transpose_W != self._stored_transposed
         if not is_event(other):     # a dense operand: the float twins (reference ``_fcn/main.py:308-460`` dispatches them alike)
             from ._float import fcnmv_p_call, fcnmm_p_call
             x = other if isinstance(other, torch.Tensor) else np.asarray(other)
             # scatter direction: a gather over the mirror beats float atomics (built on first use only while it keeps its raw arrays)
-            mr = self._fresh_mirror(auto=self.nse <= _csr_mod.MIRROR_KEEP_RAW_MAX_NNZ) if ell_t else None
+            mr = self._fresh_mirror(auto=self.nse <= _csr_mod.MIRROR_KEEP_RAW_MAX_NNZ) if scatter else None
             if mr is not None and (mr.released or mr.indices is None):
                 mr = None
             if x.ndim not in (1, 2):
                 raise NotImplementedError(f"matmul with object of shape {tuple(x.shape)}")
+            rows = self._stored_rows()
             if mr is not None:
                 from ._float import csrmv_p_call, csrmm_p_call
                 if x.ndim == 1:
@@ -337,34 +205,32 @@ class FixedNumConn(PlasticityMixin, DataRepresentation):
                                      backend=self.backend)[0]
                     r = r.T if transpose_W else r
             elif x.ndim == 1:
-                r = fcnmv_p_call(self.data, self.indices, x, shape=self._a_shape, transpose=ell_t, backend=self.backend)[0]
-            elif x.ndim == 2:
-                r = fcnmm_p_call(self.data, self.indices, x.T if transpose_W else x, shape=self._a_shape, transpose=ell_t,
+                r = fcnmv_p_call(self.data, self.indices, x, shape=(rows.m, rows.k), transpose=scatter, backend=self.backend)[0]
+            else:
+                r = fcnmm_p_call(self.data, self.indices, x.T if transpose_W else x, shape=(rows.m, rows.k), transpose=scatter,
                                  backend=self.backend)[0]
                 r = r.T if transpose_W else r
-            else:
-                raise NotImplementedError(f"matmul with object of shape {tuple(x.shape)}")
-            return A.to_result(r, self._numpy_result) if A.wants_numpy(x) else r
+            return self._res(r) if A.wants_numpy(x) else r
         # scatter kernels take compacted id lists as they are — the favourable direction, and the other one once its mirror exists
-        scatter = other.ndim == 1 and (ell_t or self._fresh_mirror(auto=True) is not None)
-        value = event_operand(other, scatter=scatter)
+        ids = other.ndim == 1 and (scatter or self._fresh_mirror(auto=True) is not None)
+        value = event_operand(other, scatter=ids)
         if value.ndim == 1:
-            r = self._binary_matvec(value, transpose_W)
+            r = self._binary_product(binary_fcnmv_p, value, transpose_W)
         elif value.ndim == 2:
             # binary_fcnmm returns (out_len, n) for an operand (in_len, n): ``events @ M`` hands it the transposed events and
             # transposes the result back.  (The orientation is fixed here, not guessed from the shapes: a square result —
             # batch size equal to the output length — would make such a guess ambiguous.)
             if transpose_W:
                 expected = (value.shape[0], self.shape[1])
-                r = self._binary_matmat(value.T, transpose_W).T
+                r = self._binary_product(binary_fcnmm_p, value.T, transpose_W).T
             else:
                 expected = (self.shape[0], value.shape[1])
-                r = self._binary_matmat(value, transpose_W)
+                r = self._binary_product(binary_fcnmm_p, value, transpose_W)
             if tuple(r.shape) != tuple(expected):
                 raise ValueError(f'binary matmat output shape mismatch: got {tuple(r.shape)}, expected {expected}.')
         else:
             raise NotImplementedError(f"matmul with object of shape {value.shape}")
-        return A.to_result(r, self._numpy_result) if A.wants_numpy(value) else r
+        return self._res(r) if A.wants_numpy(value) else r
 
     def __matmul__(self, other):
         return self._dispatch(other, transpose_W=False)
@@ -381,7 +247,7 @@ class FixedNumConn(PlasticityMixin, DataRepresentation):
         dense = mat.cpu().numpy() if isinstance(mat, torch.Tensor) else np.asarray(mat)
         if dense.ndim != 2:
             raise ValueError(f"{cls.__name__}.fromdense expects a 2-D matrix; got {dense.ndim}-D.")
-        view = dense if cls is FixedNumPerPre or issubclass(cls, FixedNumPerPre) else dense.T
+        view = dense.T if cls._stored_transposed else dense
         mask = view != 0
         nnz = mask.sum(axis=1)
         if num_conn is None:
@@ -419,7 +285,7 @@ class FixedNumConn(PlasticityMixin, DataRepresentation):
         """The same matrix as a :class:`CSR` (``FixedNumPerPre`` rows are CSR rows; ``FixedNumPerPost`` is re-encoded)."""
         from ._csr import CSR, CSC
         data, idx, ptr = self._as_compressed()
-        native = (CSR if isinstance(self, FixedNumPerPre) else CSC)._from_parts(data, idx, ptr, shape=self.shape, backend=self.backend,
+        native = (CSC if self._stored_transposed else CSR)._from_parts(data, idx, ptr, shape=self.shape, backend=self.backend,
                                                                              numpy_result=self._numpy_result)
         return native.tocsr()
 
@@ -427,19 +293,25 @@ class FixedNumConn(PlasticityMixin, DataRepresentation):
         """The same matrix as a :class:`CSC`."""
         from ._csr import CSR, CSC
         data, idx, ptr = self._as_compressed()
-        native = (CSR if isinstance(self, FixedNumPerPre) else CSC)._from_parts(data, idx, ptr, shape=self.shape, backend=self.backend,
+        native = (CSC if self._stored_transposed else CSR)._from_parts(data, idx, ptr, shape=self.shape, backend=self.backend,
                                                                              numpy_result=self._numpy_result)
         return native.tocsc()
+
+    def with_data(self, data):
+        data = A.to_device(data)
+        assert data.shape == self.data.shape and data.dtype == self.data.dtype
+        obj = type(self)((data, self.indices), shape=self.shape, backend=self.backend, check_indices=False)
+        obj._numpy_result = self._numpy_result
+        return obj
 
     def todense(self):
         idx = self.indices.cpu().numpy()
         w = (self.data.float() if self.data.dtype == torch.bfloat16 else self.data).cpu().numpy()
         vals = np.broadcast_to(w.reshape(-1), (idx.size,)) if w.size == 1 else w.reshape(-1)
         rows = np.repeat(np.arange(idx.shape[0]), idx.shape[1])
-        n_rows, n_cols = self._a_shape
-        dense = np.zeros((n_rows, n_cols), dtype=vals.dtype)
+        dense = np.zeros(self.shape[::-1] if self._stored_transposed else self.shape, dtype=vals.dtype)
         np.add.at(dense, (rows, idx.reshape(-1)), vals)
-        return dense if tuple(self._a_shape) == tuple(self.shape) else dense.T
+        return dense.T if self._stored_transposed else dense
 
 
 class FixedNumPerPre(FixedNumConn):
@@ -447,25 +319,8 @@ class FixedNumPerPre(FixedNumConn):
     (reference ``_fcn/main.py:781-854``).  ``spk @ M`` is the favourable (scatter) direction."""
     _kind = 'Post-synaptic'
 
-    def _rows_and_upper(self):
-        return self.shape[0], self.shape[1]
-
     num_pre = property(lambda self: int(self.indices.shape[0]))
     num_post = property(lambda self: int(self.shape[1]))
-
-    @property
-    def _a_shape(self):
-        return tuple(self.shape)
-
-    def _ell_transpose(self, transpose_W: bool) -> bool:
-        return bool(transpose_W)
-
-    def with_data(self, data):
-        data = A.to_device(data)
-        assert data.shape == self.data.shape and data.dtype == self.data.dtype
-        obj = FixedNumPerPre((data, self.indices), shape=self.shape, backend=self.backend, check_indices=False)
-        obj._numpy_result = self._numpy_result
-        return obj
 
     def transpose(self, axes=None):
         assert axes is None, "transpose does not support axes argument."
@@ -480,26 +335,10 @@ class FixedNumPerPost(FixedNumConn):
     """Each post-synaptic neuron has ``n_conn`` pre sources: ``indices (n_post, n_conn)`` hold pre ids
     (reference ``_fcn/main.py:1042-1115``).  ``M @ spk`` is the favourable (scatter) direction."""
     _kind = 'Pre-synaptic'
-
-    def _rows_and_upper(self):
-        return self.shape[1], self.shape[0]
+    _stored_transposed = True
 
     num_post = property(lambda self: int(self.indices.shape[0]))
     num_pre = property(lambda self: int(self.shape[0]))
-
-    @property
-    def _a_shape(self):
-        return tuple(self.shape)[::-1]
-
-    def _ell_transpose(self, transpose_W: bool) -> bool:
-        return not bool(transpose_W)
-
-    def with_data(self, data):
-        data = A.to_device(data)
-        assert data.shape == self.data.shape and data.dtype == self.data.dtype
-        obj = FixedNumPerPost((data, self.indices), shape=self.shape, backend=self.backend, check_indices=False)
-        obj._numpy_result = self._numpy_result
-        return obj
 
     def transpose(self, axes=None):
         assert axes is None, "transpose does not support axes argument."

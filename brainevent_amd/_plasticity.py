@@ -350,13 +350,11 @@ def plasticity_index(M):
     if mr is not None and not mr.released and mr.perm is not None and mr.indices is not None and mr.indptr is not None:
         return mr.indptr, mr.indices.to(torch.int32), mr.perm
     from ._convert import csr_to_csc_index, fixed_conn_num_csc_structure
-    from ._fcn import FixedNumConn
-    if isinstance(M, FixedNumConn):
-        n_rows, n_cols = M._a_shape
-        ptr, rows, perm = fixed_conn_num_csc_structure(M.indices, shape=(n_rows, n_cols))
+    r = M._stored_rows()
+    if r.indptr is None:
+        ptr, rows, perm = fixed_conn_num_csc_structure(r.indices, shape=(r.m, r.k))
     else:
-        m, k = M._plan_shape()
-        ptr, rows, perm = csr_to_csc_index(M.indptr, M.indices, shape=(m, k), include_perm=True)
+        ptr, rows, perm = csr_to_csc_index(r.indptr, r.indices, shape=(r.m, r.k), include_perm=True)
     nnz = int(rows.numel())
     perm = perm.to(torch.int64 if nnz > np.iinfo(np.int32).max else torch.int32)
     idx = M.buffers[INDEX_KEY] = (ptr, rows.to(torch.int32), perm)
@@ -381,9 +379,7 @@ def _certify(M, data, lo, hi) -> None:
 
 def container_update(M, pre: bool, spikes, trace, w_min, w_max, inplace: bool):
     """Shared body of the ``update_on_pre`` / ``update_on_post`` methods."""
-    from ._csr import CSR, CSC
     from ._dense import Dense
-    from ._fcn import FixedNumPerPre, FixedNumPerPost
     n_pre, n_post = int(M.shape[0]), int(M.shape[1])
     n_spk, n_tr = (n_pre, n_post) if pre else (n_post, n_pre)
     if isinstance(M, Dense):
@@ -396,23 +392,15 @@ def container_update(M, pre: bool, spikes, trace, w_min, w_max, inplace: bool):
     _check_vec(trace, n_tr, 'post_trace' if pre else 'pre_trace')
     lo, hi = _bounds(w_min, w_max)
 
-    # which kernel: row-driven over the stored rows, or permuted over the transposed structure
-    if isinstance(M, Dense):
-        rows = None
-    elif isinstance(M, (CSR, FixedNumPerPre)):
-        rows = pre
-    elif isinstance(M, (CSC, FixedNumPerPost)):
-        rows = not pre
-    else:
-        raise TypeError(f"plasticity updates are not defined for {type(M).__name__}")
+    # which kernel: row-driven over the stored rows (the spikes are on the scatter side: pre spikes are the left operand of
+    # ``spk @ M``), or permuted over the transposed structure
+    rows = None if isinstance(M, Dense) else M._stored_rows()
 
     def run(w, clip):
         if rows is None:
             _run_dense(w, pre, spikes, trace, clip)
-        elif rows:
-            fixed = M.indptr if not hasattr(M, 'num_conn') else None
-            _run_rows(w.reshape(-1), M.indices.reshape(-1), fixed, M.num_conn if fixed is None else -1, None, spikes, n_spk,
-                      trace, clip)
+        elif M._scatter_side(pre):
+            _run_rows(w.reshape(-1), rows.indices.reshape(-1), rows.indptr, rows.row_len, None, spikes, n_spk, trace, clip)
         else:
             t_ptr, t_rows, perm = plasticity_index(M)
             _run_rows(w.reshape(-1), t_rows, t_ptr, -1, perm, spikes, n_spk, trace, clip)
@@ -433,11 +421,9 @@ def container_update(M, pre: bool, spikes, trace, w_min, w_max, inplace: bool):
     keep = {INDEX_KEY: M.buffers[INDEX_KEY]} if M.buffers.get(INDEX_KEY) is not None else {}
     if isinstance(M, Dense):
         out = Dense(w, shape=M.shape, backend=M.backend, buffers=keep)
-    elif isinstance(M, (CSR, CSC)):
-        out = type(M)._from_parts(w, M.indices, M.indptr, shape=M.shape, backend=M.backend, buffers=keep,
-                                  numpy_result=M._numpy_result)
     else:
-        out = type(M)((w, M.indices), shape=M.shape, backend=M.backend, buffers=keep, check_indices=False)
+        out = M.with_data(w)
+        out.buffers.update(keep)
     out._numpy_result = M._numpy_result
     _certify(out, w, lo, hi)
     return out

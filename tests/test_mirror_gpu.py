@@ -236,6 +236,30 @@ def test_mirror_is_built_on_first_use_when_it_pays(be, oracle, monkeypatch):
     np.testing.assert_allclose(tight @ be.BinaryArray(v), ref, rtol=RTOL, atol=ATOL)      # refused once, not asked again
 
 
+def test_build_mirror_builds_after_a_refused_automatic_build(be, oracle, monkeypatch):
+    """A refused automatic build is cached as ``None`` and its warning names ``build_mirror()`` as the way to force the build:
+    the explicit call has to return a mirror (as it does for the fixed-number containers), not the cached refusal."""
+    import brainevent_amd._csr as C
+    monkeypatch.setattr(C, 'PLAN_MIN_NNZ', 1000)
+    monkeypatch.setattr(C, 'AUTO_MIRROR_MIN_NNZ', 1000)
+    rng = np.random.default_rng(25)
+    m, k = 800, 900
+    w, idx, ptr = rand_csr(rng, m, k, rng.integers(50, 100, m))
+    v = rng.random(k) < 0.1
+    ref = oracle.binary_csrmv(w.astype(np.float64), idx, ptr, v, (m, k), False)
+    csr = be.CSR((w, idx, ptr), shape=(m, k))
+    real = C._free_device_bytes
+    monkeypatch.setattr(C, '_free_device_bytes', lambda: 1 << 16)
+    with pytest.warns(UserWarning, match='build_mirror'):
+        np.testing.assert_allclose(csr @ be.BinaryArray(v), ref, rtol=RTOL, atol=ATOL)
+    assert 'mirror' in csr.buffers and csr.buffers['mirror'] is None
+    monkeypatch.setattr(C, '_free_device_bytes', real)
+    mr = csr.build_mirror()
+    assert isinstance(mr, C.Mirror) and csr.buffers['mirror'] is mr
+    np.testing.assert_allclose(csr @ be.BinaryArray(v), ref, rtol=RTOL, atol=ATOL)
+    assert csr.buffers['mirror'] is mr
+
+
 @pytest.mark.parametrize('dtype', [np.float32, np.float64, np.float16])
 @pytest.mark.parametrize('kind', ['bool', 'float'])
 def test_perm_fused_direct_products(be, oracle, dtype, kind):

@@ -123,6 +123,37 @@ def test_tuner_measures_and_the_library_takes_the_task_size(tuning_env):
     np.testing.assert_allclose(outs[0].cpu().numpy(), ref, rtol=1e-5, atol=1e-5)
 
 
+@pytest.mark.gpu
+def test_the_first_csr_product_is_routed_by_the_persisted_thresholds(tuning_env):
+    """The per-device store is resolved at the first route choice (`ensure_resolved`), so nothing may test a threshold in front
+    of `choose_scatter_route`: the first CSR matrix of a process, with fewer entries than the built-in `plan_min_nnz` and more
+    than the persisted one, gets its workspace.  200 x 200 with 100 entries per row: one slice, 100 entries per block."""
+    T, path = tuning_env
+    import numpy as np
+    import brainevent_amd as be
+    import brainevent_amd._csr as C
+    from oracle import oracle_np as O
+    m = k = 200
+    row = 100
+    default = T.DEFAULT_SCATTER_TUNING.plan_min_nnz
+    assert 1000 < m * row < default
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text(json.dumps({'gfx950': {'plan_min_nnz': 1000}}))
+    T.get_scatter_tuning.cache_clear()
+    T.apply_scatter_tuning(T.DEFAULT_SCATTER_TUNING, _resolved_key=('import', None))      # what the import leaves: the defaults
+    assert C.PLAN_MIN_NNZ == default
+    rng = np.random.default_rng(5)
+    idx = rng.integers(0, k, m * row).astype(np.int32)
+    w = rng.uniform(0.1, 1.0, m * row).astype(np.float32)
+    ptr = np.arange(0, m * row + 1, row, dtype=np.int32)
+    v = rng.random(m) < 0.2
+    csr = be.CSR((torch.tensor(w, device='cuda'), torch.tensor(idx, device='cuda'), torch.tensor(ptr, device='cuda')), shape=(m, k))
+    out = be.BinaryArray(torch.tensor(v, device='cuda')) @ csr
+    assert C.PLAN_MIN_NNZ == 1000                                       # resolved by that product
+    assert isinstance(csr.buffers['scatter_plan'], C.ScatterPlan)
+    np.testing.assert_allclose(out.cpu().numpy(), O.binary_csrmv(w.astype(np.float64), idx, ptr, v, (m, k), True), rtol=1e-5, atol=1e-5)
+
+
 def test_import_with_a_store_present_does_not_touch_the_gpu(tmp_path):
     """importing the package must not initialise the GPU even when a tuning store exists (torchrun ranks import
     before set_device; fork-after-import; exec-before-GPU re-launches).  The per-device entry is resolved at the first route
