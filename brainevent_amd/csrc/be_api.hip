@@ -96,6 +96,28 @@ int be_static_lds_bytes(const void* kernel) {
   return (int)fa.sharedSizeBytes;
 }
 
+// largest gridDim.y the current device launches (hipDeviceProp_t::maxGridSize[1]); the JIT kernels put a chunk index there
+int64_t be_max_grid_y(void) {
+  static std::mutex mu;
+  static std::vector<std::pair<int, int64_t>> seen;      // (device, limit)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return -1;
+  std::lock_guard<std::mutex> lock(mu);
+  for (auto& d : seen)
+    if (d.first == dev) return d.second;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
+  seen.emplace_back(dev, (int64_t)prop.maxGridSize[1]);
+  return (int64_t)prop.maxGridSize[1];
+}
+
+extern "C" int64_t be_device_max_grid_y(void) {
+  const int64_t y = be_max_grid_y();
+  if (y > 0) return y;
+  be_set_error("be_device_max_grid_y: cannot read the device's maxGridSize");
+  return BE_ERR_HIP;
+}
+
 hipError_t be_fill_async(void* p, int byte_value, size_t bytes, hipStream_t st) {
   if (bytes == 0) return hipSuccess;
   size_t blocks = (bytes / 16 + 255) / 256;

@@ -25,6 +25,8 @@ hipError_t be_fill_async(void* p, int byte_value, size_t bytes, hipStream_t st);
 hipError_t be_allow_lds(const void* kernel, int bytes);
 // static LDS bytes of a kernel, cached per kernel (-1: the query failed)
 int be_static_lds_bytes(const void* kernel);
+// hipDeviceProp_t::maxGridSize[1] of the current device, cached per device (-1: the query failed)
+int64_t be_max_grid_y(void);
 // optional HIP-event timing of an op's dominant kernel (be_api.hip); slot -1 = profiling off
 int be_prof_begin(hipStream_t st);
 void be_prof_end(int slot, hipStream_t st);

@@ -717,6 +717,7 @@ static int jitmv_impl(int mode, double w0, double w1, int wdtype, int64_t clen, 
              "scale_exp out of range");
   JitP p = make_params(shape1, gather ? in_len : out_len, seed, clen, 32, w0, w1);
   p.row0 = (uint32_t)row_begin;
+  BE_REQUIRE_CHUNK_GRID(p);
   if (class_count >= 0) {      // sharded scatter: only the classes [class_begin, class_begin + class_count)
     BE_REQUIRE(class_begin + class_count <= p.cls_count, BE_ERR_RANGE, "class range exceeds be_jit_scatter_classes()");
     p.cls_begin = class_begin;
@@ -763,6 +764,7 @@ int be_binary_jitmm(int mode, double w0, double w1, int wdtype, int64_t clen, ui
   if (!gather) {
     // scatter: the batched residue-class kernel of the mv path with lane stride 4 (gridDim.y = batch column)
     const JitP ps = make_params(shape1, out_len, seed, clen, 4, w0, w1);
+    BE_REQUIRE_CHUNK_GRID(ps);
     const int se = jit_scale_exp(mode, w0, w1, in_len);
 #define BE_JITMM_SC(MODE_)                                                                                              \
     switch (wdtype) {                                                                                                   \

@@ -291,6 +291,7 @@ int be_jitmm_float_scatter(int mode, double w0, double w1, int wdtype, int64_t c
   BE_REQUIRE(workspace != nullptr && workspace_bytes >= be_jitmm_float_scatter_workspace_bytes(shape1, out_len, n, stride),
              BE_ERR_WORKSPACE, "workspace too small");
   const JitP p = make_params(shape1, out_len, seed, clen, stride, w0, w1);
+  BE_REQUIRE_CHUNK_GRID(p);
 #define BE_JFS(MODE_)                                                                                                            \
   switch (wdtype) {                                                                                                             \
     case BE_F32: return run_jit_float_scatter_lds<MODE_, float>(p, X_bm, out_bm, in_len, n, scale_exp, workspace, st);          \
@@ -334,6 +335,7 @@ int be_jitmm_float(int mode, double w0, double w1, int wdtype, int64_t clen, uin
   BE_REQUIRE(workspace != nullptr && workspace_bytes >= be_jitmm_float_workspace_bytes(shape1, in_len, out_len, n, gather, wdtype),
              BE_ERR_WORKSPACE, "workspace too small");
   const JitP p = make_params(shape1, gather ? in_len : out_len, seed, clen, stride, w0, w1);
+  if (gather) BE_REQUIRE_CHUNK_GRID(p);      // (the atomic scatter walks its chunks in a flat task loop)
   switch (mode) {
     case MODE_SCALAR: return dispatch_jit_float<MODE_SCALAR>(p, wdtype, X, out, in_len, out_len, n, gather, workspace, st);
     case MODE_UNIFORM: return dispatch_jit_float<MODE_UNIFORM>(p, wdtype, X, out, in_len, out_len, n, gather, workspace, st);

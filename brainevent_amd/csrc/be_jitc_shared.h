@@ -119,6 +119,18 @@ inline JitP make_params(int64_t shape1, int64_t walk_len, uint32_t seed, int64_t
   return p;
 }
 
+// The gather kernels and the scatter's reduce launch with gridDim.y = n_chunks: a shape walked over its long side (chunks are
+// a quarter of shape[1] wide, the walk may run over shape[0]) can ask for more than the device launches.  Refused by the entry
+// points before anything is launched.
+#define BE_REQUIRE_CHUNK_GRID(p_)                                                                                           \
+  do {                                                                                                                      \
+    const int64_t lim__ = be_max_grid_y();                                                                                  \
+    BE_REQUIRE(lim__ > 0, BE_ERR_HIP, "cannot read the device's maxGridSize");                                              \
+    BE_REQUIRE((int64_t)(p_).n_chunks <= lim__, BE_ERR_RANGE,                                                               \
+               "the walk takes " + std::to_string((p_).n_chunks) + " chunks of " + std::to_string((p_).chunk_size) +        \
+                   " (a quarter of shape[1]) but the device launches at most " + std::to_string(lim__) +                    \
+                   " in gridDim.y: walk the matrix over its other side (transpose / corder)");                            \
+  } while (0)
 
 // ------------------------------------------------------------------------------------------------ scatter by residue class
 // (shared by the event-driven scatter of be_jitc.hip and the float-operand scatter of be_jitc_float.hip)

@@ -67,6 +67,8 @@ typedef void* be_stream_t; /* hipStream_t */
 int be_version(void);                 /* 10000*major + 100*minor + patch */
 const char* be_last_error(void);      /* thread-local, valid until the next failing call on this thread */
 int be_device_count(void);            /* number of visible HIP devices, or a negative BE_ERR_* */
+int64_t be_device_max_grid_y(void);   /* hipDeviceProp_t::maxGridSize[1] of the current device (the JIT products refuse a shape
+                                         whose walk takes more chunks than this), or a negative BE_ERR_* */
 const char* be_build_arch(void);      /* "gfx950" */
 /* HIP-event timing of each op's dominant kernel, recorded on the op's own stream.
  * enable(n) arms n record slots (0 disarms); read() synchronises and returns the number of

@@ -182,3 +182,48 @@ void oracle_jitmv(int mode, float w0, float w1, int64_t clen, uint32_t seed, con
     if (gather) out[row] = acc;
   }
 }
+
+/* ---- JITC float-operand twins (stride 32 / 4) -------------------------------------------------------------
+ * brainevent/_jit_scalar/float.py:838-905 (jitsmv), :1331-1420 (jitsmm) and the uniform / normal files: the walk of
+ * oracle_jitmv above against the VALUES of a dense operand.  Edge weights are formed in f32; the operand and every sum
+ * are double.  gather: out[row, :] = sum over the edges (row, j) of w * X[j, :];  scatter: out[j, :] += w * X[row, :] for
+ * every edge of every row whose operand row is not all zero (:886-887).  One shared weight (mode 0) multiplies once:
+ * the finished sum in gather (:870), the operand row in scatter.
+ * X: double [in_len, n];  out: double [out_len, n], both row-major. */
+void oracle_jit_float(int mode, float w0, float w1, int64_t clen, uint32_t seed, const double* X, int64_t n, int64_t shape1,
+                      int64_t in_len, int64_t out_len, int gather, int stride, double* out) {
+  for (int64_t i = 0; i < out_len * n; ++i) out[i] = 0.0;
+  if (clen <= 0) return;
+  const uint32_t cl = (uint32_t)(clen < 2 ? 2 : clen);
+  int64_t chunk = (shape1 + 3) / 4; if (chunk < 1) chunk = 1;
+  const int64_t n_rows = gather ? out_len : in_len, walk = gather ? in_len : out_len;
+  const int64_t n_chunks = (walk + chunk - 1) / chunk;
+  for (int64_t row = 0; row < n_rows; ++row) {
+    const double* xr = X + row * n;      /* scatter: this row's operand values */
+    if (!gather) {
+      int any = 0;
+      for (int64_t c = 0; c < n; ++c) any |= xr[c] != 0.0;
+      if (!any) continue;
+    }
+    double* acc = out + row * n;         /* gather: this row's sums */
+    for (int64_t ch = 0; ch < n_chunks; ++ch) {
+      const int64_t cs = ch * chunk, ce = cs + chunk < walk ? cs + chunk : walk, width = ce - cs;
+      for (int lane = 0; lane < stride; ++lane) {
+        uint32_t state = lr_init(seed, (uint32_t)row, (uint32_t)ch, (uint32_t)lane);
+        uint32_t q = lr_initial_q(&state, cl);
+        int64_t lj = lane + (int64_t)stride * q;
+        while (lj < width) {
+          const int64_t j = cs + lj;
+          const double w = mode == 0 ? 1.0 : (double)jit_weight(mode, w0, w1, seed, (uint32_t)row, (uint32_t)j);
+          if (gather) { const double* xj = X + j * n; for (int64_t c = 0; c < n; ++c) acc[c] += w * xj[c]; }
+          else if (mode == 0) { double* oj = out + j * n; for (int64_t c = 0; c < n; ++c) oj[c] += (double)w0 * xr[c]; }
+          else { double* oj = out + j * n; for (int64_t c = 0; c < n; ++c) oj[c] += w * xr[c]; }
+          state = lr_next(state);
+          q = q + 1u + lr_bounded(state, cl - 1u);
+          lj = lane + (int64_t)stride * q;
+        }
+      }
+    }
+    if (gather && mode == 0) for (int64_t c = 0; c < n; ++c) acc[c] *= (double)w0;
+  }
+}

@@ -96,3 +96,26 @@ def jitmv(mode, w0, w1, prob, vector, seed, *, shape, transpose, corder, stride=
     f.restype = None
     f(m, a, b, clen, int(seed) & 0xFFFFFFFF, _p(act), int(shape[1]), in_len, out_len, int(bool(corder)), int(stride), _p(out))
     return out
+
+
+def jit_float(mode, w0, w1, prob, X, seed, *, shape, transpose, corder, stride):
+    """jit{s,u,n}mv / mm with a dense operand in C: ``X [in_len]`` or ``[in_len, n]`` (taken as double) -> double
+    ``[out_len]`` / ``[out_len, n]``; mode and weight parameters as :func:`jitmv`, stride 32 (the mv matrix) or 4 (mm)."""
+    import math
+    X = np.asarray(X, dtype=np.float64)
+    vec = X.ndim == 1
+    X2 = np.ascontiguousarray(X.reshape(-1, 1) if vec else X)
+    in_len = shape[0] if transpose else shape[1]
+    out_len = shape[1] if transpose else shape[0]
+    assert X2.shape[0] == in_len, (X2.shape, in_len)
+    n = X2.shape[1]
+    clen = 0 if float(prob) == 0.0 else max(2, int(math.ceil(2.0 / float(prob))))
+    m = {'s': 0, 'u': 1, 'n': 2}[mode]
+    a = np.float32(w0)
+    b = np.float32(np.float32(w1) - np.float32(w0)) if mode == 'u' else np.float32(w1)
+    out = np.empty((out_len, n), dtype=np.float64)
+    f = lib().oracle_jit_float
+    f.argtypes = [_int, ctypes.c_float, ctypes.c_float, _i64, ctypes.c_uint32, _vp, _i64, _i64, _i64, _i64, _int, _int, _vp]
+    f.restype = None
+    f(m, a, b, clen, int(seed) & 0xFFFFFFFF, _p(X2), n, int(shape[1]), in_len, out_len, int(bool(corder)), int(stride), _p(out))
+    return out[:, 0] if vec else out

@@ -263,7 +263,7 @@ def test_jit_float_twins_agree_with_the_event_driven_products_on_0_1_operands(be
             np.testing.assert_array_equal(am, bm)
 
 
-def test_jit_containers_take_dense_operands(be):
+def test_jit_containers_take_dense_operands(be, oracle):
     rng = np.random.default_rng(33)
     for cls, params in ((be.JITCScalarR, (np.float32(0.7),)), (be.JITCUniformC, (np.float32(-1.0), np.float32(1.0))),
                         (be.JITCNormalR, (np.float32(0.1), np.float32(0.5)))):
@@ -278,7 +278,13 @@ def test_jit_containers_take_dense_operands(be):
             np.testing.assert_allclose(M @ X90, Dm @ X90, **tol)
             np.testing.assert_allclose(X60 @ M, X60 @ Dm, **tol)
     # half-precision weights and the prob = 0 convention (zeros, like the event-driven twins)
-    h = be.jitsmv(np.float16(0.5), 0.1, rng.normal(0, 1, 90).astype(np.float16), 3, shape=(60, 90))
+    x16 = rng.normal(0, 1, 90).astype(np.float16)
+    h = be.jitsmv(np.float16(0.5), 0.1, x16, 3, shape=(60, 90))
     assert h.dtype == np.float16 and h.shape == (60,)
+    # values too: the gather sums the f16 operand in double, then rounds to f32 and to f16 — the f64 oracle's sum to half an ulp
+    # of each (2^-24 + 2^-11 relative; 2^-24, half the smallest subnormal step, below f16's normal range)
+    ref = oracle.jitmv('s', 0.5, 0.0, 0.1, x16.astype(np.float64), 3, shape=(60, 90), transpose=False, corder=True)
+    assert np.count_nonzero(ref) > 30
+    np.testing.assert_allclose(h.astype(np.float64), ref, rtol=2.0 ** -11 + 2.0 ** -24, atol=2.0 ** -24)
     z = be.jitsmv(np.float32(0.5), 0.0, np.ones(90, np.float32), 3, shape=(60, 90))
     np.testing.assert_array_equal(z, np.zeros(60, np.float32))

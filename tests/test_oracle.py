@@ -173,6 +173,44 @@ def test_c_oracle_jit_and_dense_match_numpy_oracle():
         np.testing.assert_allclose(oracle_c.densemv_f32(W, s, transpose), O.binary_densemv(W, s, transpose), rtol=1e-6, atol=1e-6)
 
 
+def test_c_oracle_jit_float_matches_numpy_oracle():
+    """``oracle_c.jit_float`` (the fast reference of the at-scale float-twin tests) == ``oracle_np.jitmv`` / ``jitmm``, themselves
+    pinned bit for bit by the golden vectors.  Operand values are quarters of small integers and the scalar weight a power of
+    two, so every product and every double sum is exact in any order: scalar and uniform agree exactly whatever order numpy's
+    matrix product takes (and whether the shared weight multiplies each addend or the finished sum); normal differs by the
+    ULPs of libm's logf against numpy's log, as in the pin above.  Shapes: the usual one, one walked over its long side
+    (19 chunks of 2) and one whose walk (3) is shorter than one chunk (10) and than both lane strides."""
+    rng = np.random.default_rng(6)
+    checked = 0
+    for shape in ((19, 37), (37, 5), (3, 40)):
+        for mode, (w0, w1) in {'s': (0.5, 0.0), 'u': (0.1, 0.9), 'n': (0.2, 1.3)}.items():
+            for transpose in (False, True):
+                for corder in (False, True):
+                    for stride in (32, 4):
+                        for n in (1, 3):
+                            prob, seed = 0.25, 11
+                            in_len = shape[0] if transpose else shape[1]
+                            X = rng.integers(-8, 9, (in_len, n)).astype(np.float64) / 4
+                            X[rng.random(in_len) < 0.3] = 0          # whole zero rows: the scatter skips them
+                            kw = dict(shape=shape, transpose=transpose, corder=corder)
+                            a = oracle_c.jit_float(mode, w0, w1, prob, X, seed, stride=stride, **kw)
+                            # the numpy oracle picks its stride by entry point: jitmv walks stride 32, jitmm stride 4
+                            if stride == 32:
+                                b = np.stack([O.jitmv(mode, np.float32(w0), np.float32(w1), prob, X[:, c], seed, **kw)
+                                              for c in range(n)], axis=1)
+                            else:
+                                b = O.jitmm(mode, np.float32(w0), np.float32(w1), prob, X, seed, **kw)
+                            assert a.shape == b.shape == (shape[1] if transpose else shape[0], n)
+                            tol = 1e-5 if mode == 'n' else 0.0
+                            np.testing.assert_allclose(a, b, rtol=tol, atol=tol, err_msg=str((shape, mode, kw, stride, n)))
+                            if n == 1:      # a 1-D operand gives a 1-D result with the same numbers
+                                np.testing.assert_array_equal(oracle_c.jit_float(mode, w0, w1, prob, X[:, 0], seed, stride=stride, **kw),
+                                                              a[:, 0])
+                            checked += int(np.count_nonzero(b))
+    assert checked > 2000, 'the pin must compare edges, not zeros'
+    assert not oracle_c.jit_float('u', 0.1, 0.9, 0.0, np.ones(37), 1, shape=(19, 37), transpose=False, corder=True, stride=32).any()
+
+
 def test_c_oracle_parallel_variant_equals_serial():
     """The OpenMP + atomics variant timed by bench.py's cpu_baseline (not the reference's algorithm) adds the same numbers."""
     from oracle import oracle_c
