@@ -80,6 +80,7 @@ class ScatterPlan:
         self.row_len = -1                 # fixed row length when the plan was built without an indptr
         self.split_f64 = False            # per-entry f64 weights stored as two f32 entries each
         self.stamp = None                 # weights_stamp() of the weights the blocks were filled from
+        self.slot = None                  # plastic plans: uint16 position of every raw entry inside its block (2 B per entry)
         self.block_hint_override: Optional[int] = None
         self.items_hint: Optional[int] = None      # d8: average stored items (entries + escapes) per block, from the table
         self._ws: Dict = {}
@@ -220,7 +221,8 @@ class ScatterPlan:
 
     def nbytes(self) -> int:
         order = getattr(self, 'order', None)
-        return self.seg.numel() * 4 + self.blob.numel() + (order.numel() * 2 if order is not None else 0)
+        return self.seg.numel() * 4 + self.blob.numel() + (order.numel() * 2 if order is not None else 0) + \
+            (self.slot.numel() * 2 if self.slot is not None else 0)
 
     def workspace(self, parts: int, n_batch: int = 1) -> torch.Tensor:
         # with room for the pre-gathered segment table only when this plan's blocks are short enough for the step to use it
@@ -437,6 +439,7 @@ class ScatterPlan:
         segment table — block starts and lengths — depends on the structure only, so the same call refreshes the weights of
         an existing plan (:meth:`refresh_weights`)."""
         is64 = int(indptr is not None and indptr.dtype == torch.int64)
+        self.slot = None        # block positions belong to the pass that drew them (u16: an LDS counter): a fill voids the table
         maxabs = torch.zeros(2, dtype=torch.int32, device=self.seg.device)   # f32 bits of max |w| / smallest non-zero |w|
         name = 'be_scatter_plan_refresh_weights_ordered' if keep_exp else 'be_scatter_plan_fill_ordered'
         f_fill = fn(name, c_int,
@@ -1624,13 +1627,39 @@ class StoredRowsData(PlasticityMixin, DataRepresentation):
         self.buffers['scatter_plan'] = ws
         return ws
 
-    def prepare(self, mirror: bool = False):
+    def prepare(self, mirror: bool = False, plastic=None):
         """Build the scatter workspace now (otherwise it is built by the first product of the scatter side).
-        ``mirror=True`` also builds the transposed mirror so that the *gather* side runs event-driven too."""
-        self._scatter_workspace()
+        ``mirror=True`` also builds the transposed mirror so that the *gather* side runs event-driven too.
+
+        ``plastic=(w_min, w_max)`` arms *plastic mode* for learning with ``update_on_pre`` / ``update_on_post(inplace=True)`` under
+        exactly these bounds: every such update then brings the cached scatter workspace up to date itself — a plan's blocks of
+        the active rows are refilled, or the touched entries patched in; the binned and the direct route read the raw arrays
+        anyway — with launches on the current stream and work proportional to the touched entries, so the next scatter-side
+        product launches nothing extra and a whole learning step captures with ``capture_step``.  The fixed-point exponent is
+        lowered once to one that no weight inside the bounds can overflow (:func:`~brainevent_amd._plasticity.
+        plastic_exponent_bound`) and no longer follows the weights: every output then carries an absolute error below
+        ``n_j * 2^-exponent`` before its one rounding.  Needs per-entry f32 / f16 / bf16 weights that already lie in the bounds
+        (``ValueError``; weights are never modified here) and finite host bounds; ``MathError`` when the bound itself keeps fewer
+        than ``ScatterPlan.MIN_WEIGHT_BITS`` bits at that exponent.  A fresh cached workspace is used as it is; a plan built here
+        keeps its rows' column order.  An update with other bounds, or a foreign write to ``data``, disarms the container: it
+        then behaves as without this argument (full refresh on the next product).  A cached :class:`Mirror` is not covered: it
+        still refreshes in full on its next gather-side product.  :attr:`plastic_state` reports the armed state."""
+        if plastic is not None:
+            from ._plasticity import arm_plastic
+            arm_plastic(self, plastic)
+        else:
+            self._scatter_workspace()
         if mirror:
             self.build_mirror()
         return self
+
+    @property
+    def plastic_state(self):
+        """``None`` unless :meth:`prepare` armed plastic mode (and nothing disarmed it since); else a dict: ``route``
+        (``'plan-d8'``, ``'plan-u16'``, ``'binned'``, ``'direct'``), ``w_min``, ``w_max``, ``exponent`` (the fixed-point exponent of
+        the steps; ``None`` on the direct route) and ``cmax`` (the most stored entries on one output column)."""
+        from ._plasticity import plastic_state
+        return plastic_state(self)
 
     def refresh_weights(self):
         """Bring the cached workspaces up to date after ``self.data`` was modified in place.  The products check this by
@@ -1777,14 +1806,18 @@ class CompressedSparseData(StoredRowsData):
         m, k = self.shape[::-1] if self._stored_transposed else self.shape          # (CSC stores the transpose)
         return StoredRows(self.indices, self.indptr, -1, m, k)
 
-    def prepare(self, mirror: bool = False, keep_order: Optional[bool] = None, release_raw: bool = False):
+    def prepare(self, mirror: bool = False, keep_order: Optional[bool] = None, release_raw: bool = False, plastic=None):
         """Build the scatter workspace now (otherwise it is built by the first ``spk @ matrix``).
         ``mirror=True`` also builds the transposed mirror so that the *gather* direction runs event-driven too.
         ``keep_order=True``: a sorted-layout plan keeps its rows' column order (2 bytes per entry), which turns the refresh
         after an in-place weight update from a re-sort into a gather-copy (``ScatterPlan.build``).
         ``release_raw=True``: return a :class:`PlannedMatrix` that serves ``events @ M`` from the plan alone — the caller drops
         this container and with it the raw arrays (C2: 58 GB resident instead of 138 GB).  Needs a planned route (``MathError``
-        / ``ValueError`` otherwise: the binned and the direct route read the raw arrays on every step)."""
+        / ``ValueError`` otherwise: the binned and the direct route read the raw arrays on every step).
+        ``plastic=(w_min, w_max)``: plastic mode, see :meth:`StoredRowsData.prepare` (not together with ``release_raw``: the
+        updates need the raw arrays)."""
+        if plastic is not None and release_raw:
+            raise ValueError("prepare(plastic=...) keeps the workspace current from the raw arrays: not with release_raw=True.")
         if release_raw:
             plan = self._scatter_workspace() if keep_order is None else self.prepare(keep_order=keep_order)._scatter_workspace()
             if not isinstance(plan, ScatterPlan):
@@ -1799,7 +1832,7 @@ class CompressedSparseData(StoredRowsData):
                 self._scatter_workspace()
             finally:
                 PLAN_KEEP_ORDER = saved
-        return super().prepare(mirror)
+        return super().prepare(mirror, plastic=plastic)
 
     # -- products ------------------------------------------------------------------------------------
     def _event_product(self, other, left: bool):

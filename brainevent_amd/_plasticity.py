@@ -20,6 +20,7 @@ Captured graphs (``capture_step``): the calls never synchronise the host, but a 
 replays — the same contract as :meth:`CSR.refresh_weights`.
 """
 import ctypes
+import math
 import numbers
 from typing import Optional
 
@@ -42,6 +43,7 @@ _HOMO_MSG = ("Plasticity updates require per-synapse (heterogeneous) weights, bu
 
 CLIP_KEY = 'plasticity_clip'        # buffers: (weights_stamp(data), w_min, w_max) while every weight lies in the bounds
 INDEX_KEY = 'plasticity_index'      # buffers: (t_indptr, t_rows, perm) of the transposed structure (structure only)
+PLASTIC_KEY = 'plastic'             # buffers: the state of prepare(plastic=...) while the container is armed (arm_plastic)
 
 
 # =====================================================================================================
@@ -95,7 +97,10 @@ def _bounds(w_min, w_max):
 # device side
 # =====================================================================================================
 def _spikes(x):
-    """Event operand -> (buffer, spike code): ids / words / bytes / f32 (any nonzero value is a spike)."""
+    """Event operand -> (buffer, spike code): ids / words / bytes / f32 (any nonzero value is a spike).  A pair that this
+    function returned passes through (one conversion for the update and the plan's upkeep)."""
+    if isinstance(x, tuple):
+        return x
     v = event_operand(x, scatter=True) if is_event(x) else x
     if isinstance(v, A.ActiveIds):
         return v, A.BE_SPIKE_IDS
@@ -377,6 +382,204 @@ def _certify(M, data, lo, hi) -> None:
         M.buffers[CLIP_KEY] = (weights_stamp(data), lo, hi)
 
 
+# =====================================================================================================
+# plastic mode: prepare(plastic=(w_min, w_max)) — the cached scatter workspace follows in-place updates by itself
+# =====================================================================================================
+EXP_MIN, EXP_MAX = -90, 150          # the range of a fixed-point exponent (2^(e - 32) has to be a normal f32)
+SLOT_MAX_U16_ROW = 65536             # longest stored row whose block positions fit the uint16 slot table of a u16 plan
+
+
+def plastic_exponent_bound(cmax: int, bound: float) -> int:
+    """The fixed-point exponent no weight in ``[-bound, bound]`` can overflow: ``62 - ceil(log2(cmax * bound))`` with ``cmax`` the
+    most stored entries on one output column (duplicates counted) — every column sum then stays below ``2^62`` whatever the
+    weights become.  Written like ``BinnedScatter._exponent_by_steps``: ``62 - frexp(cmax * bound * 1.001)[1]`` (the factor
+    covers the roundings of the addends; a product that is an exact power of two ``2^p`` gives ``61 - p``, one below the formula:
+    its sum could reach ``2^62`` itself), clamped to the range of an exponent.  ``bound == 0`` or an empty structure: nothing
+    can overflow, the largest exponent.  Pure host arithmetic."""
+    cmax, bound = int(cmax), abs(float(bound))
+    if not math.isfinite(bound):
+        raise ValueError(f"the weight bound must be finite; got {bound}.")
+    if cmax <= 0 or bound == 0.0:
+        return EXP_MAX
+    return max(EXP_MIN, min(EXP_MAX, 62 - math.frexp(cmax * bound * 1.001)[1]))
+
+
+def plastic_bounds(bounds):
+    """``(w_min, w_max)`` of ``prepare(plastic=...)`` as two finite host floats with ``w_min <= w_max`` (``ValueError`` otherwise:
+    a missing bound, a bound on a device — the clip certificate refuses those too —, inf / nan, a reversed pair)."""
+    if not isinstance(bounds, (tuple, list)) or len(bounds) != 2:
+        raise ValueError(f"plastic must be a pair (w_min, w_max); got {bounds!r}.")
+    for b in bounds:
+        if isinstance(b, torch.Tensor) and b.device.type != 'cpu':
+            raise ValueError("plastic=(w_min, w_max) takes host numbers: bounds held in device tensors cannot be certified.")
+    lo, hi = _bounds(*bounds)
+    if lo is None or hi is None:
+        raise ValueError("plastic=(w_min, w_max) needs both bounds: an open side lets the weights outgrow any exponent.")
+    if not (math.isfinite(lo) and math.isfinite(hi)) or lo > hi:
+        raise ValueError(f"plastic=(w_min, w_max) needs finite bounds with w_min <= w_max; got ({lo}, {hi}).")
+    return lo, hi
+
+
+def _column_count_max(M, rows) -> int:
+    """The most stored entries on one secondary id (duplicates counted): from the cached transposed structure when there is
+    one, else one counted pass over the indices.  Synchronises (arming only)."""
+    if rows.k <= 0 or rows.indices.numel() == 0:
+        return 0
+    idx = M.buffers.get(INDEX_KEY)
+    mr = M.buffers.get('mirror')
+    ptr = idx[0] if idx is not None else (mr.indptr if mr is not None and not mr.released and mr.indptr is not None else None)
+    if ptr is not None:
+        return int((ptr[1:] - ptr[:-1]).max())
+    flat = rows.indices.reshape(-1)
+    counts = torch.zeros(rows.k, dtype=torch.int64, device=flat.device)
+    for a in range(0, int(flat.numel()), 1 << 27):
+        counts += torch.bincount(flat[a:a + (1 << 27)], minlength=rows.k)
+    return int(counts.max())
+
+
+def arm_plastic(M, bounds) -> None:
+    """``M.prepare(plastic=bounds)``: see :meth:`StoredRowsData.prepare`."""
+    from . import _csr as C
+    from ._error import MathError
+    lo, hi = plastic_bounds(bounds)
+    rows = M._stored_rows()
+    nse = int(rows.indices.numel())
+    w = M.data
+    if w.numel() == 1 and nse > 1:
+        raise ValueError(_HOMO_MSG)
+    if w.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"prepare(plastic=...) serves per-entry f32 / f16 / bf16 weights; got {w.dtype} (f64 entries are stored "
+                         "as two f32 entries each, which the touched-entries upkeep does not follow).")
+    lo_r, hi_r = _rounded(lo, w.dtype), _rounded(hi, w.dtype)          # what the update kernel clips to
+    if nse:
+        mn, mx = torch.aminmax(w)                                      # one pass; NaN fails both comparisons
+        if not (float(mn) >= lo_r and float(mx) <= hi_r):
+            raise ValueError(f"prepare(plastic=({lo}, {hi})): the weights span [{float(mn)}, {float(mx)}]; clamp them into the "
+                             "bounds first (arming never modifies weights).")
+    bound = max(abs(lo_r), abs(hi_r))
+    cmax = _column_count_max(M, rows)
+    e_bound = plastic_exponent_bound(cmax, bound)
+
+    ws = M.buffers.get('scatter_plan', False)
+    if ws is False or (ws is not None and ws.is_stale(w)):
+        saved, C.PLAN_KEEP_ORDER = C.PLAN_KEEP_ORDER, True             # (a plan built here keeps its rows' column order)
+        try:
+            ws = M._scatter_workspace()
+        finally:
+            C.PLAN_KEEP_ORDER = saved
+    if ws is not None and bound < math.ldexp(1.0, C.ScatterPlan.MIN_WEIGHT_BITS - e_bound):
+        raise MathError(f"prepare(plastic=({lo}, {hi})): at the exponent {e_bound} that {cmax} entries per column of that size "
+                        f"cannot overflow, the bound itself keeps fewer than {C.ScatterPlan.MIN_WEIGHT_BITS} bits.")
+    max_row = None
+    if isinstance(ws, C.ScatterPlan):
+        assert not ws.homo and not ws.split_f64 and ws.layout in (ws.LAYOUT_U16, ws.LAYOUT_D8)
+        route = 'plan-d8' if ws.layout == ws.LAYOUT_D8 else 'plan-u16'
+        if ws.layout == ws.LAYOUT_U16:
+            max_row = rows.row_len if rows.indptr is None else int((rows.indptr[1:] - rows.indptr[:-1]).max())
+    elif isinstance(ws, C.BinnedScatter):
+        route = 'binned'
+        if ws.acc32:            # the 32-bit sums' gate depends on the smallest weight, which learning moves: 64-bit bins
+            ws.scale_exp += 32
+            ws.acc32 = False
+            ws._set_geometry()
+            ws._ws = {}
+            ws.ws = ws.workspace(1)
+    else:
+        route = 'direct'
+    if ws is not None:
+        ws.scale_exp = min(ws.scale_exp, e_bound)       # a launch argument of every step: from here on independent of the weights
+    _certify(M, w, lo, hi)
+    M.buffers[PLASTIC_KEY] = {'route': route, 'w_min': lo, 'w_max': hi, 'cmax': cmax, 'e_bound': e_bound, 'ws': ws,
+                              'max_row': max_row}
+
+
+def plastic_state(M):
+    st = M.buffers.get(PLASTIC_KEY)
+    if st is None:
+        return None
+    ws = st['ws']
+    return {'route': st['route'], 'w_min': st['w_min'], 'w_max': st['w_max'], 'exponent': None if ws is None else ws.scale_exp,
+            'cmax': st['cmax']}
+
+
+def _disarm(M) -> None:
+    """Leave plastic mode: the state goes, and with it the plan's slot table (2 bytes per entry that only the entry patch reads)."""
+    st = M.buffers.pop(PLASTIC_KEY, None)
+    if st is not None and st['route'].startswith('plan'):
+        st['ws'].slot = None
+
+
+def _plastic_ready(M, lo, hi):
+    """The armed state when this in-place update may keep the workspace current itself — same bounds, valid certificate, the
+    armed workspace still cached and fresh — else ``None``, and the container is disarmed (the next product refreshes in full)."""
+    from ._csr import weights_stamp
+    st = M.buffers.get(PLASTIC_KEY)
+    if st is None:
+        return None
+    ws = M.buffers.get('scatter_plan', False)
+    if (ws is st['ws'] and isinstance(lo, float) and isinstance(hi, float) and st['w_min'] == lo and st['w_max'] == hi
+            and _certified(M, lo, hi) and (ws is None or ws.stamp == weights_stamp(M.data))):
+        return st
+    _disarm(M)
+    return None
+
+
+_PLAN_GEOM = [c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp]        # m, k, slice_shift, slice_width, layout, seg, blob
+_ROWS_HEAD = [c_vp, c_int, c_vp, c_vp, c_int, c_i64]                 # weights, wdtype, indices, indptr, is64, row_len
+
+
+def _geom(plan):
+    return plan.m, plan.k, plan.slice_shift, plan.slice_width, plan.layout, A.ptr(plan.seg), A.ptr(plan.blob)
+
+
+def _rows_head(w, rows):
+    return (A.ptr(w), A.wcode(w), A.ptr(rows.indices), A.ptr(rows.indptr),
+            int(rows.indptr is not None and rows.indptr.dtype == torch.int64), int(rows.row_len))
+
+
+def _refresh_workspace(n: int) -> torch.Tensor:
+    return A.workspace(fn('be_scatter_plan_refresh_workspace_bytes', c_i64, [c_i64])(int(n)))
+
+
+def _plan_slots(plan, st, w, rows) -> bool:
+    """The plan's slot table (built on first use of the permuted side, kept like ``order``); ``False`` — with the reason as a
+    warning — when block positions do not fit its uint16 entries."""
+    if plan.slot is not None:
+        return True
+    if plan.layout == plan.LAYOUT_U16 and st['max_row'] > SLOT_MAX_U16_ROW:
+        import warnings
+        warnings.warn(f"brainevent_amd: the permuted side of this plastic container is not kept current: a stored row of "
+                      f"{st['max_row']} entries exceeds the {SLOT_MAX_U16_ROW} block positions of the u16 plan's slot table; "
+                      "the container is disarmed and refreshes in full.", stacklevel=4)
+        return False
+    plan.slot = torch.empty(int(rows.indices.numel()), dtype=torch.int16, device=plan.blob.device)
+    f = fn('be_scatter_plan_slots', c_int, _ROWS_HEAD + _PLAN_GEOM + [c_vp, c_vp, c_vp])
+    check(f(*_rows_head(w, rows), *_geom(plan), A.ptr(getattr(plan, 'order', None)), A.ptr(plan.slot), A.stream_ptr()),
+          'be_scatter_plan_slots')
+    return True
+
+
+def _plan_refresh_rows(plan, w, rows, sp, sd) -> None:
+    """``be_scatter_plan_refresh_rows``: the blocks of the active stored rows rewritten from ``w``."""
+    ws = _refresh_workspace(plan.m)
+    f = fn('be_scatter_plan_refresh_rows', c_int, _ROWS_HEAD + _PLAN_GEOM + [c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp])
+    # (d8 positions follow from the structure alone: only a u16 refresh, which draws them anew, has slots to rewrite)
+    slot = plan.slot if plan.layout == plan.LAYOUT_U16 else None
+    check(f(*_rows_head(w, rows), *_geom(plan), A.ptr(getattr(plan, 'order', None)), A.ptr(slot), A.ptr(sp), sd,
+            A.ptr(ws), ws.numel(), A.stream_ptr()), 'be_scatter_plan_refresh_rows')
+
+
+def _plan_patch_entries(plan, w, index, sp, sd) -> None:
+    """``be_scatter_plan_patch_entries``: the entries on the active secondary ids stored into their blocks."""
+    t_ptr, t_rows, perm = index
+    ws = _refresh_workspace(plan.k)
+    f = fn('be_scatter_plan_patch_entries', c_int,
+           [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_i64, c_vp] + _PLAN_GEOM + [c_vp, c_int, c_vp, c_i64, c_vp])
+    check(f(A.ptr(w), A.wcode(w), A.ptr(t_ptr), int(t_ptr.dtype == torch.int64), A.ptr(t_rows), A.ptr(perm),
+            int(perm.dtype == torch.int64), int(t_rows.numel()), A.ptr(plan.slot), *_geom(plan), A.ptr(sp), sd, A.ptr(ws),
+            ws.numel(), A.stream_ptr()), 'be_scatter_plan_patch_entries')
+
+
 def container_update(M, pre: bool, spikes, trace, w_min, w_max, inplace: bool):
     """Shared body of the ``update_on_pre`` / ``update_on_post`` methods."""
     from ._dense import Dense
@@ -406,14 +609,32 @@ def container_update(M, pre: bool, spikes, trace, w_min, w_max, inplace: bool):
             _run_rows(w.reshape(-1), t_rows, t_ptr, -1, perm, spikes, n_spk, trace, clip)
 
     if inplace:
+        # plastic mode (prepare(plastic=...)): the cached scatter workspace is kept current by launches of its own after the
+        # update kernel — the active rows' blocks refilled, or the touched entries patched in — and never refreshed in full
+        st = None if rows is None else _plastic_ready(M, lo, hi)
+        plan = None
+        if st is not None and st['route'].startswith('plan'):
+            plan = st['ws']
+            spikes = _spikes(spikes)                      # (one conversion for the update and the plan's upkeep)
+            if not M._scatter_side(pre) and not _plan_slots(plan, st, M.data.reshape(-1), rows):
+                _disarm(M)
+                st = plan = None
         if _certified(M, lo, hi):
             run(M.data, (lo, hi))                         # untouched entries are already in range: clip the touched ones
         else:
             run(M.data, (None, None))
             _clamp_(M.data, lo, hi)
+        if plan is not None:
+            if M._scatter_side(pre):
+                _plan_refresh_rows(plan, M.data.reshape(-1), rows, *spikes)
+            else:
+                _plan_patch_entries(plan, M.data.reshape(-1), plasticity_index(M), *spikes)
         # the kernel wrote through a raw pointer: move torch's version counter so that cached plans / mirrors see the change
         torch.autograd.graph.increment_version(M.data)
         _certify(M, M.data, lo, hi)
+        if st is not None and st['ws'] is not None:
+            from ._csr import weights_stamp
+            st['ws'].stamp = weights_stamp(M.data)        # (binned: the bins are refilled from the raw arrays every step)
         return M
     w = M.data.clone()
     run(w, (None, None))

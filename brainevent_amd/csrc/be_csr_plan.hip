@@ -131,6 +131,7 @@ __global__ void __launch_bounds__(256) k_scan_apply(uint2* __restrict__ a, int64
 }
 
 // one workgroup per row (grid-stride): place every entry of the row into its block, then write the pads
+// (k_plan_refresh_rows below is this kernel over a list of rows: a fix here belongs there too)
 template <typename W, bool HOMO>
 __global__ void __launch_bounds__(256) k_plan_fill(const W* __restrict__ weights, const int32_t* __restrict__ indices, RowPtr rp,
                                                    int64_t m, int slice_shift, uint32_t slice_width, int n_slices,
@@ -1002,6 +1003,7 @@ __global__ void __launch_bounds__(1024) k_plan_d8_count(const int32_t* __restric
   }
 }
 
+// (k_plan_d8_refresh_rows below is this kernel over a list of rows: a fix here belongs there too)
 template <typename W>
 __global__ void __launch_bounds__(1024) k_plan_d8_fill(const W* __restrict__ weights, const int32_t* __restrict__ indices,
                                                        RowPtr rp, int64_t m, uint32_t slice_width, int n_slices,
@@ -1830,6 +1832,223 @@ __global__ void __launch_bounds__(1024) k_plan_colstats(const unsigned char* __r
   }
 }
 
+// =================================================================================================
+// plastic plans: keeping the blocks current under in-place weight updates (be_plasticity_rows), with work proportional to
+// the entries an update touched instead of a fill of the whole plan.
+//   * row refresh  — the update was row-driven: the blocks of the ACTIVE rows are rewritten exactly as the fill writes them
+//     (k_plan_d8_fill / k_plan_fill driven by a list of rows, no weight statistics: the exponent of a plastic plan is
+//     bound-certified and does not follow the weights);
+//   * entry patch  — the update went through the transposed structure (active COLUMNS, entries in every row): each touched
+//     entry's f32 weight is stored at its place in its block, found through `slot` — the position of raw entry j inside its
+//     block (d8: `pos` of the fill; u16: the `rank` drawn from the LDS counter, which is why a u16 refresh rewrites the slot
+//     entries of its rows).
+// slot is uint16: a d8 block holds at most kD8MaxRow entries + slice_width / 255 escapes; a u16 block at most the row's
+// entries, which the caller bounds by kSlotMaxU16Row.
+// =================================================================================================
+constexpr int kSlotMaxU16Row = 65536;
+static_assert(kD8MaxRow + 20000 / 255 + 1 <= 65536, "a d8 block position must fit the uint16 slot table");
+
+// rows of the list: the active ones, or every row (active == nullptr: the pass that builds the slot table)
+__device__ __forceinline__ int64_t listed_rows(const uint32_t* __restrict__ n_active_p, int64_t m) {
+  return n_active_p != nullptr ? (int64_t)*n_active_p : m;
+}
+
+// k_plan_d8_fill over a list of rows
+template <typename W>
+__global__ void __launch_bounds__(1024) k_plan_d8_refresh_rows(const W* __restrict__ weights, const int32_t* __restrict__ indices,
+                                                               RowPtr rp, int64_t m, uint32_t slice_width, int n_slices,
+                                                               const uint2* __restrict__ seg, unsigned char* __restrict__ blob,
+                                                               const uint16_t* __restrict__ order,
+                                                               const uint32_t* __restrict__ active,
+                                                               const uint32_t* __restrict__ n_active_p,
+                                                               uint16_t* __restrict__ slot) {
+  const uint32_t wmagic = d8_magic(slice_width);
+  extern __shared__ unsigned long long d8_keys[];
+  __shared__ uint32_t first_idx[kD8MaxSlices], e_first[kD8MaxSlices], seg_start[kD8MaxSlices], seg_ng[kD8MaxSlices],
+      tot[kD8MaxSlices];
+  __shared__ uint32_t wtot[16];
+  const int64_t n_list = listed_rows(n_active_p, m);
+  for (int64_t a = blockIdx.x; a < n_list; a += gridDim.x) {
+    const int64_t r = active != nullptr ? (int64_t)active[a] : a;
+    if (r >= m) continue;                                       // (uniform: an id past the matrix is skipped, not written)
+    for (int s = threadIdx.x; s < n_slices; s += blockDim.x) {
+      const uint2 sg = seg[r * n_slices + s];
+      seg_start[s] = sg.x;
+      seg_ng[s] = sg.y & 0xffffu;
+      tot[s] = 0;
+    }
+    const int64_t rb = rp.at(r);
+    const int len = d8_sort_row(d8_keys, indices, rb, rp.at(r + 1), order, nullptr, slice_width * (uint32_t)n_slices);
+    const int per = (len + 1023) >> 10;
+    const int i0 = threadIdx.x * per, i1 = (i0 + per < len) ? i0 + per : len;
+    uint32_t mine = 0;
+    for (int i = i0; i < i1; ++i) mine += d8_item(d8_keys, i, slice_width, wmagic).esc;
+    const uint32_t excl = block_scan_1024(mine, wtot) - mine;
+    uint32_t run = excl;
+    for (int i = i0; i < i1; ++i) {
+      const D8Item it = d8_item(d8_keys, i, slice_width, wmagic);
+      run += it.esc;
+      if (it.first) { first_idx[it.s] = (uint32_t)i; e_first[it.s] = run; }
+    }
+    __syncthreads();
+    // the thread's weights first, all in flight together (clamped positions instead of a branch per load)
+    constexpr int kOwn = kD8MaxRow / 1024;
+    float wown[kOwn];
+    if (len > 0) {
+#pragma unroll
+      for (int t = 0; t < kOwn; ++t) {
+        const int i = i0 + t < i1 ? i0 + t : (i1 > i0 ? i1 - 1 : len - 1);
+        wown[t] = (float)WTraits<W>::load(weights, rb + (int64_t)(d8_keys[i] & 0xffffull));
+      }
+    }
+    run = excl;
+#pragma unroll
+    for (int t = 0; t < kOwn; ++t) {
+      const int i = i0 + t;
+      if (i >= i1) break;
+      const D8Item it = d8_item(d8_keys, i, slice_width, wmagic);
+      run += it.esc;
+      const uint32_t pos = ((uint32_t)i - first_idx[it.s]) + (run - e_first[it.s]);
+      unsigned char* blk = blob + ((int64_t)seg_start[it.s] << 7);
+      float* wp = reinterpret_cast<float*>(blk);
+      unsigned char* dp = blk + (size_t)seg_ng[it.s] * 16;
+      for (uint32_t q = pos - it.esc; q < pos; ++q) { wp[q] = 0.f; dp[q] = 255; }
+      wp[pos] = wown[t];
+      dp[pos] = (unsigned char)it.rem;
+      if (slot != nullptr) slot[rb + (int64_t)(d8_keys[i] & 0xffffull)] = (uint16_t)pos;
+      atomicMax(&tot[it.s], pos + 1u);
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < n_slices; s += blockDim.x) {   // tail pads
+      unsigned char* blk = blob + ((int64_t)seg_start[s] << 7);
+      for (uint32_t q = tot[s]; q < seg_ng[s] * 4u; ++q) {
+        reinterpret_cast<float*>(blk)[q] = 0.f;
+        (blk + (size_t)seg_ng[s] * 16)[q] = 0;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// k_plan_fill (per-entry weights) over a list of rows
+template <typename W>
+__global__ void __launch_bounds__(256) k_plan_refresh_rows(const W* __restrict__ weights, const int32_t* __restrict__ indices,
+                                                           RowPtr rp, int64_t m, int slice_shift, uint32_t slice_width,
+                                                           int n_slices, const uint2* __restrict__ seg,
+                                                           unsigned char* __restrict__ blob,
+                                                           const uint32_t* __restrict__ active,
+                                                           const uint32_t* __restrict__ n_active_p,
+                                                           uint16_t* __restrict__ slot) {
+  __shared__ uint32_t cur[kMaxSlices];
+  __shared__ uint32_t seg_start[kMaxSlices];
+  __shared__ uint32_t seg_n4[kMaxSlices];
+  const int64_t n_list = listed_rows(n_active_p, m);
+  for (int64_t a = blockIdx.x; a < n_list; a += gridDim.x) {
+    const int64_t r = active != nullptr ? (int64_t)active[a] : a;
+    if (r >= m) continue;
+    for (int s = threadIdx.x; s < n_slices; s += blockDim.x) {
+      const uint2 sg = seg[r * n_slices + s];
+      cur[s] = 0;
+      seg_start[s] = sg.x;
+      seg_n4[s] = sg.y;
+    }
+    __syncthreads();
+    const int64_t b = rp.at(r), e = rp.at(r + 1);
+    for (int64_t j = b + threadIdx.x; j < e; j += blockDim.x) {
+      const uint32_t c = (uint32_t)indices[j];
+      const uint32_t s = c / slice_width;
+      const uint32_t loc = c - s * slice_width;
+      const uint32_t rank = atomicAdd(&cur[s], 1u);
+      unsigned char* blk = blob + ((int64_t)seg_start[s] << 7);
+      reinterpret_cast<float*>(blk)[rank] = (float)WTraits<W>::load(weights, j);
+      reinterpret_cast<uint16_t*>(blk + (size_t)seg_n4[s] * 16)[rank] = (uint16_t)loc;
+      if (slot != nullptr) slot[j] = (uint16_t)rank;
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < n_slices; s += blockDim.x) {   // pads: dummy slot, zero weight
+      unsigned char* blk = blob + ((int64_t)seg_start[s] << 7);
+      const uint32_t n = seg_n4[s] * 4u;
+      for (uint32_t i = cur[s]; i < n; ++i) {
+        reinterpret_cast<float*>(blk)[i] = 0.f;
+        reinterpret_cast<uint16_t*>(blk + (size_t)seg_n4[s] * 16)[i] = (uint16_t)(1u << slice_shift);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Entry patch: the k_plast_rows walk (entry-balanced tiles over the virtual concatenation of the active rows of the transposed
+// structure; a thread binary-searches the row of its first entry; 64-bit entry offsets).  Entry e of active column c lies in
+// stored row t_rows[e]; its weight is raw entry perm[e].  Per entry: one 8-byte gather from the segment table, the weight,
+// the slot, and one 4-byte store into the block.  The three rounds of loads of a thread's kPatchPer entries are each issued
+// together (clamped indices instead of a branch per load).
+constexpr int kPatchThreads = 256, kPatchPer = 8, kPatchTile = kPatchThreads * kPatchPer;
+
+template <typename W, typename PT>
+__global__ void __launch_bounds__(kPatchThreads) k_plan_patch(const W* __restrict__ weights, const int32_t* __restrict__ t_rows,
+                                                              RowPtr tp, const PT* __restrict__ perm,
+                                                              const uint16_t* __restrict__ slot, const uint2* __restrict__ seg,
+                                                              unsigned char* __restrict__ blob, uint32_t slice_width,
+                                                              int n_slices, const uint32_t* __restrict__ active,
+                                                              const uint32_t* __restrict__ n_active_p,
+                                                              const int64_t* __restrict__ offs) {
+  const int64_t n_active = *n_active_p;
+  const int64_t total = offs[n_active];
+  for (int64_t tile = (int64_t)blockIdx.x * kPatchTile; tile < total; tile += (int64_t)gridDim.x * kPatchTile) {
+    int64_t p = tile + threadIdx.x;
+    if (p >= total) break;
+    int64_t lo = 0, hi = n_active - 1;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) >> 1;
+      if (offs[mid] <= p) lo = mid; else hi = mid - 1;
+    }
+    int64_t a = lo;
+    int64_t a_end = offs[a + 1];
+    uint32_t c = active[a];
+    int64_t row_start = tp.at(c) - offs[a];       // entry index = row_start + p
+    uint32_t s = c / slice_width;
+    int64_t ent[kPatchPer];
+    uint32_t sl[kPatchPer];
+    int nv = 0;
+    int64_t last = 0;
+#pragma unroll
+    for (int u = 0; u < kPatchPer; ++u, p += kPatchThreads) {
+      if (p < total) {
+        while (p >= a_end) {        // columns shorter than the stride (or empty) are stepped over
+          ++a;
+          a_end = offs[a + 1];
+          c = active[a];
+          row_start = tp.at(c) - offs[a];
+          s = c / slice_width;
+        }
+        nv = u + 1;
+        last = row_start + p;
+      }
+      ent[u] = last;                // (past the end: the thread's last valid entry again — loaded, not stored)
+      sl[u] = s;
+    }
+    int32_t rr[kPatchPer];
+    int64_t jj[kPatchPer];
+#pragma unroll
+    for (int u = 0; u < kPatchPer; ++u) {
+      rr[u] = __builtin_nontemporal_load(t_rows + ent[u]);
+      jj[u] = (int64_t)__builtin_nontemporal_load(perm + ent[u]);
+    }
+    uint2 sg[kPatchPer];
+    float wv[kPatchPer];
+    uint32_t ps[kPatchPer];
+#pragma unroll
+    for (int u = 0; u < kPatchPer; ++u) {
+      sg[u] = seg[(int64_t)rr[u] * n_slices + sl[u]];
+      wv[u] = (float)WTraits<W>::load(weights, jj[u]);
+      ps[u] = slot[jj[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < kPatchPer; ++u)
+      if (u < nv) reinterpret_cast<float*>(blob + ((int64_t)sg[u].x << 7))[ps[u]] = wv[u];
+  }
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -2083,6 +2302,125 @@ int be_scatter_plan_refresh_weights(const void* weights, int homo, int wdtype, c
                                     be_stream_t stream) {
   return be_scatter_plan_refresh_weights_ordered(weights, homo, wdtype, indices, indptr, indptr_is_i64, row_len, m, k, slice_shift,
                                                  slice_width, layout, seg, blob, maxabs_bits, nullptr, stream);
+}
+
+// ---- plastic plans: the blocks follow in-place weight updates with work proportional to the touched entries.  No call here
+//      reads anything back or takes an exponent; all of them are launches on `stream`.
+static int launch_refresh_rows(const void* weights, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64,
+                               int64_t row_len, int64_t m, int64_t k, int slice_shift, int slice_width, int layout,
+                               const void* seg, void* blob, const uint16_t* order, uint16_t* slot, const uint32_t* active,
+                               const uint32_t* n_active, hipStream_t st) {
+  BE_REQUIRE(m > 0 && k > 0, BE_ERR_INVALID, "empty matrix has no plan");
+  BE_REQUIRE(slice_shift >= 4 && slice_shift <= 15, BE_ERR_INVALID, "slice_shift must be in [4, 15]");
+  BE_REQUIRE(layout == BE_PLAN_U16 || layout == BE_PLAN_D8, BE_ERR_UNSUPPORTED,
+             "only plans of per-entry weights (u16 / d8) are refreshed by rows");
+  BE_REQUIRE(width_ok(slice_shift, slice_width, layout), BE_ERR_INVALID, "slice_width out of range for this layout");
+  BE_REQUIRE(check_rows(indptr, row_len), BE_ERR_INVALID, "indptr is NULL and row_len < 0");
+  BE_REQUIRE(weights && indices && seg && blob, BE_ERR_INVALID, "null pointer");
+  BE_REQUIRE(wdtype == BE_F32 || wdtype == BE_F16 || wdtype == BE_BF16, BE_ERR_UNSUPPORTED, "f32 / f16 / bf16 weights");
+  const int n_slices = n_slices_of(k, slice_shift, slice_width);
+  const uint32_t wdt = (uint32_t)width_of(slice_shift, slice_width);
+  const RowPtr rp{indptr, indptr_is_i64, row_len};
+  if (layout == BE_PLAN_D8) {
+    BE_REQUIRE(n_slices <= kD8MaxSlices, BE_ERR_INVALID, "d8 layout: <= 1024 slices");
+    BE_REQUIRE(indptr != nullptr || row_len <= kD8MaxRow, BE_ERR_RANGE, "d8 layout: rows of at most 16384 entries");
+    const int g8 = grid_for(m, 1, 256 * 8);
+#define BE_D8_ROWS(WT)                                                                                                        \
+    {                                                                                                                         \
+      auto kern = k_plan_d8_refresh_rows<WT>;                                                                                 \
+      BE_HIP(be_allow_lds(reinterpret_cast<const void*>(kern), kD8MaxRow * 8));                                               \
+      hipLaunchKernelGGL(kern, dim3(g8), dim3(1024), kD8MaxRow * 8, st, static_cast<const WT*>(weights), indices, rp, m, wdt, \
+                         n_slices, static_cast<const uint2*>(seg), static_cast<unsigned char*>(blob), order, active,         \
+                         n_active, slot);                                                                                     \
+    }
+    switch (wdtype) {
+      case BE_F32: BE_D8_ROWS(float) break;
+      case BE_F16: BE_D8_ROWS(__half) break;
+      default: BE_D8_ROWS(__hip_bfloat16) break;
+    }
+#undef BE_D8_ROWS
+  } else {
+    BE_REQUIRE(n_slices <= kMaxSlices, BE_ERR_RANGE, "too many slices for the plan kernels");
+    const int grid = grid_for(m, 1, 256 * 16);
+#define BE_U16_ROWS(WT)                                                                                                       \
+    hipLaunchKernelGGL((k_plan_refresh_rows<WT>), dim3(grid), dim3(256), 0, st, static_cast<const WT*>(weights), indices, rp, \
+                       m, slice_shift, wdt, n_slices, static_cast<const uint2*>(seg), static_cast<unsigned char*>(blob),     \
+                       active, n_active, slot);
+    switch (wdtype) {
+      case BE_F32: BE_U16_ROWS(float) break;
+      case BE_F16: BE_U16_ROWS(__half) break;
+      default: BE_U16_ROWS(__hip_bfloat16) break;
+    }
+#undef BE_U16_ROWS
+  }
+  BE_LAUNCH_CHECK();
+  return BE_OK;
+}
+
+int64_t be_scatter_plan_refresh_workspace_bytes(int64_t n) { return n < 0 ? (int64_t)BE_ERR_INVALID : be_plast_active_bytes(n); }
+
+int be_scatter_plan_refresh_rows(const void* weights, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64,
+                                 int64_t row_len, int64_t m, int64_t k, int slice_shift, int slice_width, int layout,
+                                 const void* seg, void* blob, const uint16_t* order, uint16_t* slot, const void* spikes,
+                                 int spike_dtype, void* workspace, int64_t workspace_bytes, be_stream_t stream) {
+  BE_REQUIRE(m > 0 && m <= 0xffffffffll, BE_ERR_INVALID, "m out of range");
+  BE_REQUIRE(workspace != nullptr && workspace_bytes >= be_plast_active_bytes(m), BE_ERR_WORKSPACE, "workspace too small");
+  BE_REQUIRE(spikes, BE_ERR_INVALID, "null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ActiveList al;
+  int rc = be_plast_active_offsets(spikes, spike_dtype, m, nullptr, workspace, st, &al, nullptr);
+  if (rc != BE_OK) return rc;
+  return launch_refresh_rows(weights, wdtype, indices, indptr, indptr_is_i64, row_len, m, k, slice_shift, slice_width, layout, seg,
+                             blob, order, slot, al.ids, al.count, st);
+}
+
+int be_scatter_plan_slots(const void* weights, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64,
+                          int64_t row_len, int64_t m, int64_t k, int slice_shift, int slice_width, int layout, const void* seg,
+                          void* blob, const uint16_t* order, uint16_t* slot, be_stream_t stream) {
+  BE_REQUIRE(slot, BE_ERR_INVALID, "null pointer");
+  BE_REQUIRE(layout != BE_PLAN_U16 || indptr != nullptr || row_len <= kSlotMaxU16Row, BE_ERR_RANGE,
+             "u16 layout: the slot table holds rows of at most 65536 entries");
+  return launch_refresh_rows(weights, wdtype, indices, indptr, indptr_is_i64, row_len, m, k, slice_shift, slice_width, layout, seg,
+                             blob, order, slot, nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int be_scatter_plan_patch_entries(const void* weights, int wdtype, const void* t_indptr, int t_indptr_is_i64,
+                                  const int32_t* t_rows, const void* perm, int perm_is_i64, int64_t nnz, const uint16_t* slot,
+                                  int64_t m, int64_t k, int slice_shift, int slice_width, int layout, const void* seg, void* blob,
+                                  const void* spikes, int spike_dtype, void* workspace, int64_t workspace_bytes,
+                                  be_stream_t stream) {
+  BE_REQUIRE(m > 0 && k > 0 && k <= 0xffffffffll && nnz >= 0, BE_ERR_INVALID, "shape out of range");
+  BE_REQUIRE(slice_shift >= 4 && slice_shift <= 15, BE_ERR_INVALID, "slice_shift must be in [4, 15]");
+  BE_REQUIRE(layout == BE_PLAN_U16 || layout == BE_PLAN_D8, BE_ERR_UNSUPPORTED,
+             "only plans of per-entry weights (u16 / d8) are patched");
+  BE_REQUIRE(width_ok(slice_shift, slice_width, layout), BE_ERR_INVALID, "slice_width out of range for this layout");
+  BE_REQUIRE(wdtype == BE_F32 || wdtype == BE_F16 || wdtype == BE_BF16, BE_ERR_UNSUPPORTED, "f32 / f16 / bf16 weights");
+  BE_REQUIRE(workspace != nullptr && workspace_bytes >= be_plast_active_bytes(k), BE_ERR_WORKSPACE, "workspace too small");
+  if (nnz == 0) return BE_OK;
+  BE_REQUIRE(weights && t_indptr && t_rows && perm && slot && seg && blob && spikes, BE_ERR_INVALID, "null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ActiveList al;
+  const int64_t* offs = nullptr;
+  const RowPtr tp{t_indptr, t_indptr_is_i64, -1};
+  int rc = be_plast_active_offsets(spikes, spike_dtype, k, &tp, workspace, st, &al, &offs);
+  if (rc != BE_OK) return rc;
+  const int n_slices = n_slices_of(k, slice_shift, slice_width);
+  const uint32_t wdt = (uint32_t)width_of(slice_shift, slice_width);
+  const int grid = grid_for(nnz, kPatchTile, 4096);
+#define BE_PATCH(WT, PT)                                                                                                     \
+  hipLaunchKernelGGL((k_plan_patch<WT, PT>), dim3(grid), dim3(kPatchThreads), 0, st, static_cast<const WT*>(weights), t_rows, \
+                     tp, static_cast<const PT*>(perm), slot, static_cast<const uint2*>(seg),                                 \
+                     static_cast<unsigned char*>(blob), wdt, n_slices, al.ids, al.count, offs);
+#define BE_PATCH_W(WT) { if (perm_is_i64) { BE_PATCH(WT, int64_t) } else { BE_PATCH(WT, int32_t) } }
+  switch (wdtype) {
+    case BE_F32: BE_PATCH_W(float) break;
+    case BE_F16: BE_PATCH_W(__half) break;
+    default: BE_PATCH_W(__hip_bfloat16) break;
+  }
+#undef BE_PATCH_W
+#undef BE_PATCH
+  BE_LAUNCH_CHECK();
+  return BE_OK;
 }
 
 // The fixed-point exponent of a weighted plan from the plan itself (k_plan_colstats): same bound, same gate and same keep_exp rule

@@ -47,6 +47,13 @@ struct ActiveList {
 int be_resolve_active(const void* spikes, int sd, int64_t n, int64_t nb, uint32_t* ws_active, int64_t astride,
                       uint32_t* ws_count, hipStream_t st, bool zero_first, ActiveList* al);
 
+// Plasticity's view of a spike vector (be_plasticity.hip; a spike is any NONZERO value, all four spike codes): the active ids
+// as a device list in `workspace` (>= be_plast_active_bytes(n) bytes) and, with `rp`, the 64-bit exclusive offsets of their
+// rows' entries (offs[n_active] = total) — what be_plasticity_rows walks, for the plan upkeep that follows it.
+int64_t be_plast_active_bytes(int64_t n);
+int be_plast_active_offsets(const void* spikes, int sd, int64_t n, const RowPtr* rp, void* workspace, hipStream_t st,
+                            ActiveList* al, const int64_t** offs);
+
 // ---------------------------------------------------------------- device helpers
 // block-wide inclusive scan over 1024 threads (wave shuffles + one LDS hop): 2 barriers instead of 20
 __device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t* wave_tot /* [16] in LDS */) {

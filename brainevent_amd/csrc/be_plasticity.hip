@@ -297,6 +297,23 @@ int plast_dense_t(bool pre, void* weights, int64_t n_rows, int64_t n_cols, const
 
 }  // namespace
 
+// the active list (and, with `rp`, the entry offsets) of a spike vector for the plan upkeep of be_csr_plan.hip (declared in
+// be_csr_shared.h): the same workspace layout, compaction and offsets scan as be_plasticity_rows
+int64_t be_plast_active_bytes(int64_t n) { return plast_ws_bytes(n); }
+
+int be_plast_active_offsets(const void* spikes, int sd, int64_t n, const RowPtr* rp, void* workspace, hipStream_t st,
+                            ActiveList* al, const int64_t** offs) {
+  const PlastWs ws = plast_ws(workspace, n);
+  int rc = plast_active(spikes, sd, n, ws, st, al);
+  if (rc != BE_OK) return rc;
+  if (rp != nullptr) {
+    hipLaunchKernelGGL(k_plast_offsets, dim3(1), dim3(kScanThreads), 0, st, *rp, al->ids, al->count, ws.offs);
+    BE_LAUNCH_CHECK();
+    *offs = ws.offs;
+  }
+  return BE_OK;
+}
+
 extern "C" {
 
 int64_t be_plasticity_workspace_bytes(int64_t n_rows) { return n_rows < 0 ? (int64_t)BE_ERR_INVALID : plast_ws_bytes(n_rows); }

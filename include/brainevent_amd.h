@@ -327,6 +327,42 @@ int be_scatter_plan_refresh_weights_ordered(const void* weights, int homo, int w
                                             int slice_width, int layout, const void* seg, void* blob, uint32_t* maxabs_bits,
                                             const uint16_t* order, be_stream_t stream);
 
+/* Plastic plans: a plan of per-entry f32 / f16 / bf16 weights (BE_PLAN_U16 / BE_PLAN_D8) kept current under in-place weight
+ * updates (be_plasticity_rows) with work proportional to the entries the update touched.  None of these calls computes weight
+ * statistics, takes an exponent or synchronises: the caller runs its steps at a scale_exp that the weights cannot outgrow
+ * (bounds [w_min, w_max] that the update clips to: scale_exp <= 62 - ceil(log2(cmax * max(|w_min|, |w_max|))), cmax = the most
+ * stored entries on one output column).  All launches go to `stream`, so a captured step replays them.
+ *
+ * be_scatter_plan_refresh_rows : the update was row-driven (perm == NULL there).  The blocks — entries, escapes, tail pads — of
+ *   every ACTIVE stored row are rewritten exactly as be_scatter_plan_fill_ordered writes them; `order` (or NULL: the rows are
+ *   sorted again) as there.  spikes / spike_dtype: any encoding be_plasticity_rows takes (a spike is any nonzero value), over
+ *   the m stored rows; an id list (BE_SPIKE_IDS) holds ids below m, each at most once — the contract of be_plasticity_rows,
+ *   whose list this is; the same holds for the ids below k of be_scatter_plan_patch_entries (they index t_indptr).  slot: NULL, or the table below — the refreshed rows' entries are
+ *   rewritten (BE_PLAN_U16 draws block positions from a counter, so a refresh moves them).
+ *   workspace >= be_scatter_plan_refresh_workspace_bytes(m).
+ * be_scatter_plan_slots : builds slot[nnz] (uint16): the position of raw entry j inside its (row, slice) block.  It rewrites
+ *   every block from `weights` on the way (for BE_PLAN_U16 positions and columns are only consistent with the pass that drew
+ *   them).  Fits uint16 by the layouts' limits: a d8 block holds at most 16384 entries + slice_width / 255 escapes; for
+ *   BE_PLAN_U16 the caller guarantees rows of at most 65536 entries (checked where row_len says so: BE_ERR_RANGE).
+ * be_scatter_plan_patch_entries : the update went through the transposed structure (t_indptr[k + 1], t_rows[nnz], perm[nnz]:
+ *   for every secondary id the stored rows holding it and the raw positions of those entries).  For every entry e of every
+ *   ACTIVE secondary id c it stores (float)weights[perm[e]] at
+ *   blob + (seg[t_rows[e] * n_slices + c / slice_width].start << 7) + 4 * slot[perm[e]].  spikes: over the k secondary ids.
+ *   workspace >= be_scatter_plan_refresh_workspace_bytes(k). */
+int64_t be_scatter_plan_refresh_workspace_bytes(int64_t n);
+int be_scatter_plan_refresh_rows(const void* weights, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64,
+                                 int64_t row_len, int64_t m, int64_t k, int slice_shift, int slice_width, int layout,
+                                 const void* seg, void* blob, const uint16_t* order, uint16_t* slot, const void* spikes,
+                                 int spike_dtype, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+int be_scatter_plan_slots(const void* weights, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64,
+                          int64_t row_len, int64_t m, int64_t k, int slice_shift, int slice_width, int layout, const void* seg,
+                          void* blob, const uint16_t* order, uint16_t* slot, be_stream_t stream);
+int be_scatter_plan_patch_entries(const void* weights, int wdtype, const void* t_indptr, int t_indptr_is_i64,
+                                  const int32_t* t_rows, const void* perm, int perm_is_i64, int64_t nnz, const uint16_t* slot,
+                                  int64_t m, int64_t k, int slice_shift, int slice_width, int layout, const void* seg, void* blob,
+                                  const void* spikes, int spike_dtype, void* workspace, int64_t workspace_bytes,
+                                  be_stream_t stream);
+
 /* Fixed-point exponent of a weight array — the `scale_exp` of the planned and the binned step — chosen by the library:
  *   overflow bound : the largest e with (largest column sum of |w|) * 2^e < 2^62 (every row active; a row may list a column
  *                    several times, so "rows x max|w|" is NOT a bound).  indices == NULL: all the weights bound a column.

@@ -8,9 +8,13 @@ refresh measurement fit one card together; C2 itself holds 1e4 per row):
     ``keep_order`` (the product after an update minus the same product on unchanged weights);
   * ref_point_ms: the reference's one published point (5000 x 5000, 10 % spikes, 2.30 ms on its GPU,
     ``_csr/plasticity_binary_on_pre.cu:37-38``), here at 10 % connectivity.
+  * ``--plastic``: only the learning step ``update_on_pre`` + ``update_on_post`` + ``spk @ M`` (all in place, bounds (0, 1)):
+    ``step_ms_refresh`` — the product re-derives the plan after the updates (``keep_order=True``) — and ``step_ms_plastic`` — the
+    container armed with ``prepare(plastic=(0, 1))``, where the updates keep the plan current themselves —, the latter also
+    replayed from one captured graph (``step_ms_plastic_graph``).  A build without plastic mode reports the first figure only.
 Times are HIP-event means over ``--reps`` calls after a warm-up.  Under rocprofv3 use ``--reps 5``.
 
-    python tools/exp_plasticity.py [--rows 1000000] [--conn 2000] [--reps 20]
+    python tools/exp_plasticity.py [--rows 1000000] [--conn 2000] [--reps 20] [--plastic]
 """
 import argparse
 import json
@@ -46,12 +50,52 @@ def make(n, conn, dev, g):
     return be.CSR((w, idx, ptr), shape=(n, n), check_structure=False)
 
 
+def step_legs(M, spk, tr, reps):
+    """The learning step on the refresh path and in plastic mode (see the module docstring)."""
+    x = be.BinaryArray(spk)
+    res = {}
+
+    def step():
+        M.update_on_pre(spk, tr, 0.0, 1.0, inplace=True)
+        M.update_on_post(tr, spk, 0.0, 1.0, inplace=True)
+        return x @ M
+
+    M.prepare(keep_order=True)
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    res['step_ms_refresh'] = timed(step, reps)
+    res['route'] = type(M.buffers.get('scatter_plan')).__name__
+    try:
+        M.prepare(plastic=(0.0, 1.0))
+    except TypeError:                       # a build without plastic mode
+        res['step_ms_plastic'] = None
+        return res
+    res['plastic_state'] = M.plastic_state
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    assert M.plastic_state is not None
+    res['step_ms_plastic'] = timed(step, reps)
+    res['pre_ms_plastic'] = timed(lambda: M.update_on_pre(spk, tr, 0.0, 1.0, inplace=True), reps)
+    res['post_ms_plastic'] = timed(lambda: M.update_on_post(tr, spk, 0.0, 1.0, inplace=True), reps)
+    res['product_ms_plastic'] = timed(lambda: x @ M, reps)
+    graphed = be.capture_step(step)
+    torch.cuda.synchronize()
+    res['step_ms_plastic_graph'] = timed(graphed, reps)
+    ws = M.buffers.get('scatter_plan')
+    res['plan_bytes'] = ws.nbytes() if hasattr(ws, 'nbytes') else None
+    assert M.plastic_state is not None
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, default=1_000_000)
     ap.add_argument('--conn', type=int, default=2000)
     ap.add_argument('--rate', type=float, default=0.01)
     ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--plastic', action='store_true', help='measure the learning step only: refresh path vs plastic mode')
     a = ap.parse_args()
     dev = torch.device('cuda')
     g = torch.Generator(device=dev).manual_seed(0)
@@ -62,6 +106,10 @@ def main():
     n_act = int(spk.sum())
     upd = n_act * a.conn
     out = {'tool': 'exp_plasticity', 'shape': [n, n], 'nnz': n * a.conn, 'active_rows': n_act, 'updated_synapses_pre': upd}
+    if a.plastic:
+        out.update(step_legs(M, spk, tr, a.reps))
+        print(json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in out.items()}))
+        return
     # warm-up: builds the plasticity index (once, structure only) and the clip certificate
     M.update_on_pre(spk, tr, 0.0, 1.0, inplace=True)
     M.update_on_post(tr, spk, 0.0, 1.0, inplace=True)
