@@ -1079,6 +1079,11 @@ class PlannedMatrix:
         r = out[0] if v.ndim == 1 else out
         return r.cpu().numpy() if A.wants_numpy(v) else r
 
+    def dt2t(self, y_dim_arr, w_dim_arr):
+        raise NotImplementedError("PlannedMatrix holds no raw structure: the per-synapse products need the stored rows.")
+
+    dt2t_transposed = dt2t
+
 
 class StoredRows(NamedTuple):
     """The rows a container stores, as every kernel takes them: ``indices`` (flat, or ``[m, row_len]`` for fixed-length rows),
@@ -1713,6 +1718,19 @@ class StoredRowsData(PlasticityMixin, DataRepresentation):
 
     def _res(self, t):
         return A.to_result(t, self._numpy_result)
+
+    # -- per-synapse products (reference ``_csr/main.py:1816-1886``, ``:2736-2809``, ``_fcn/main.py:359-418``) -------------
+    def dt2t(self, y_dim_arr, w_dim_arr, *, out=None):
+        """``w * y[pre]`` for every stored entry, in storage order: ``y_dim_arr`` has ``shape[0]`` elements and is indexed by
+        the row of this matrix whatever the storage axis; ``w_dim_arr`` is shaped like ``data`` (for the fixed-number
+        containers, or one shared value).  ``out=``: a device tensor to write — ``w_dim_arr`` itself updates a trace in place."""
+        from ._dt2t import container_dt2t
+        return container_dt2t(self, y_dim_arr, w_dim_arr, True, out)
+
+    def dt2t_transposed(self, y_dim_arr, w_dim_arr, *, out=None):
+        """``w * y[post]`` for every stored entry: ``y_dim_arr`` has ``shape[1]`` elements and is indexed by the column."""
+        from ._dt2t import container_dt2t
+        return container_dt2t(self, y_dim_arr, w_dim_arr, False, out)
 
 
 class CompressedSparseData(StoredRowsData):

@@ -56,3 +56,12 @@ class DataRepresentation:
 
     def transpose(self, axes=None):
         raise NotImplementedError(f"{type(self).__name__}.transpose")
+
+    def dt2t(self, y_dim_arr, w_dim_arr):
+        """Per-synapse ``w * y`` with ``y`` indexed by the row (pre axis) of the matrix (reference ``_data.py``, the ``dt2t``
+        protocol; ``brainevent_amd._dt2t``)."""
+        raise NotImplementedError(f"{type(self).__name__}.dt2t")
+
+    def dt2t_transposed(self, y_dim_arr, w_dim_arr):
+        """Per-synapse ``w * y`` with ``y`` indexed by the column (post axis) of the matrix."""
+        raise NotImplementedError(f"{type(self).__name__}.dt2t_transposed")

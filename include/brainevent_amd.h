@@ -564,6 +564,25 @@ int be_csrmv(const void* weights, int homo, int wdtype, const int32_t* indices, 
              int64_t row_len, const void* v, void* out, int64_t m, int64_t k, int64_t nnz_hint, int transpose, void* workspace,
              int64_t workspace_bytes, be_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * per-synapse products ("dt2t"): one output per stored entry, the entry's value times a per-neuron factor — the D^t e^{t-1}
+ * term of an eligibility-trace update, or any per-synapse state scaled per neuron.
+ * replaces: csrmv_dt2t / csrmm_dt2t / cscmv_dt2t / cscmm_dt2t (brainevent/_csr/dt2t.py:42-234, :545-760; _csr/dt2t.cu)
+ *           and fcnmv_dt2t / fcnmm_dt2t (brainevent/_fcn/dt2t.py:33-345) — indptr NULL + row_len = n_conn.
+ *   by_col = 0:  out[b, j] = w[b, j] * y[b, row(j)]        y [n_batch, n_rows]
+ *   by_col = 1:  out[b, j] = w[b, j] * y[b, indices[j]]    y [n_batch, n_cols]
+ * w, out [n_batch, nnz] and y share wdtype (f32 / f64 / f16 / bf16); the product is formed in f32 (f64 for f64) and rounded
+ * once.  homo != 0: w is one shared value w[0] for every batch row.  out is written in full; out == w (in place) is allowed.
+ * indptr (by_col = 0 only; ignored otherwise) must ascend from 0 to nnz over n_rows + 1 entries; indptr NULL: row r holds
+ * entries [r * row_len, (r + 1) * row_len).  indices is read only when by_col != 0 (may be NULL otherwise).  No pointer needs
+ * more than its element's alignment: the runs that hang over a 16-byte boundary are handled in the kernel.  No workspace,
+ * nothing allocated, no host synchronisation: capturable in a HIP graph.  nnz = 0 or n_batch = 0 returns without a launch;
+ * n_batch <= 65535.  Entry offsets are 64-bit throughout.
+ * ---------------------------------------------------------------------------------------------- */
+int be_dt2t(const void* w, int homo, int wdtype, const void* y, const int32_t* indices, const void* indptr, int indptr_is_i64,
+            int64_t row_len, void* out, int64_t n_rows, int64_t n_cols, int64_t n_batch, int64_t nnz, int by_col,
+            be_stream_t stream);
+
 /* JIT connectivity against a dense operand: the same on-the-fly matrices as be_binary_jitmv / be_binary_jitmm (same walks, same
  * per-edge weight hashes), every element of the operand counting.
  * replaces: jitsmv / jitsmm (brainevent/_jit_scalar/float.py:838-905, :1331-1420), jitumv / jitumm, jitnmv / jitnmm
