@@ -26,7 +26,6 @@ arrays:
   forward pass of the Function IS the existing path (same route, same kernels, same bits).  Higher-order gradients are not
   supported (``once_differentiable``).
 """
-import ctypes
 from typing import Callable, Optional
 
 import torch
@@ -34,13 +33,9 @@ from torch.autograd.function import once_differentiable
 
 from . import _array as A
 from ._error import UnsupportedOperationError
-from ._lib import check, fn
+from ._lib import call, fn
 
 __all__ = ['RowsProduct', 'DenseProduct', 'needed']
-
-c_i64, c_int, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
-_ROWS_ARGS = [c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]
-_DENSE_ARGS = [c_int, c_vp, c_int, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp]
 
 
 def _value(x):
@@ -83,9 +78,8 @@ def activity(operand, layout: str):
         nb, n = (int(s) for s in (sp.shape if sd != A.BE_SPIKE_BITS else (sp.shape[0], operand.shape[-1])))
     if sd not in (A.BE_SPIKE_BITS, A.BE_SPIKE_IDS):
         sp = sp.contiguous()
-    mask = torch.empty(max(fn('be_grad_mask_bytes', c_i64, [c_i64, c_i64])(n, nb), 4) // 4, dtype=torch.int32, device=A.device())
-    f = fn('be_grad_pack_activity', c_int, [c_vp, c_int, c_i64, c_i64, c_vp, c_vp])
-    check(f(A.ptr(sp), sd, n, nb, A.ptr(mask), A.stream_ptr()), 'be_grad_pack_activity')
+    mask = torch.empty(max(fn('be_grad_mask_bytes')(n, nb), 4) // 4, dtype=torch.int32, device=A.device())
+    call('be_grad_pack_activity', A.ptr(sp), sd, n, nb, A.ptr(mask), A.stream_ptr())
     return mask, nb
 
 
@@ -97,12 +91,10 @@ def rows_weight_grad(w_meta, indices, indptr, row_len: int, n_rows: int, transpo
     nse = int(indices.numel())
     dw = torch.empty(1 if homo else nse, dtype=dtype, device=A.device())
     g = g_nm.to(dtype).contiguous()
-    ws = A.workspace(fn('be_grad_rows_workspace_bytes', c_i64, [c_i64])(nse)) if homo else None
+    ws = A.workspace(fn('be_grad_rows_workspace_bytes')(nse)) if homo else None
     is64 = int(indptr is not None and indptr.dtype == torch.int64)
-    f = fn('be_grad_rows', c_int, _ROWS_ARGS)
-    check(f(int(transpose), A.ptr(dw), int(homo), A.wcode(dw), A.ptr(indices), A.ptr(indptr), is64, int(row_len), int(n_rows),
-            nse, A.ptr(mask), int(nb), A.ptr(g), int(nb), 1, A.ptr(ws), 0 if ws is None else ws.numel(), A.stream_ptr()),
-          'be_grad_rows')
+    call('be_grad_rows', int(transpose), A.ptr(dw), int(homo), A.wcode(dw), A.ptr(indices), A.ptr(indptr), is64, int(row_len),
+         int(n_rows), nse, A.ptr(mask), int(nb), A.ptr(g), int(nb), 1, A.ptr(ws), 0 if ws is None else ws.numel(), A.stream_ptr())
     return dw.reshape(shape)
 
 
@@ -125,9 +117,8 @@ def dense_weight_grad(w_meta, transpose: bool, mask, nb: int, g_nm) -> torch.Ten
     else:             # one output neuron per row: neuron-major g, a broadcast per row
         g = g_nm.to(dtype).contiguous()
         g_sn, g_sb = nb, 1
-    f = fn('be_grad_dense', c_int, _DENSE_ARGS)
-    check(f(int(transpose), A.ptr(dw), A.wcode(dw), n_rows, n_cols, A.ptr(mask), int(nb), A.ptr(g), g_sn, g_sb,
-            A.stream_ptr()), 'be_grad_dense')
+    call('be_grad_dense', int(transpose), A.ptr(dw), A.wcode(dw), n_rows, n_cols, A.ptr(mask), int(nb), A.ptr(g), g_sn, g_sb,
+         A.stream_ptr())
     return dw
 
 

@@ -20,9 +20,7 @@ import numpy as np
 import torch
 
 from . import _array as A
-from ._lib import check, fn
-
-c_i64, c_int, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
+from ._lib import call, fn
 
 __all__ = ['csr_to_coo_index', 'coo_to_csc_index', 'coo2csr', 'csr_to_csc_index', 'csc_to_csr_index',
            'fixed_conn_num_csr_indptr', 'fixed_conn_num_csc_structure', 'fixed_conn_num_to_csc', 'CscBuilder']
@@ -81,14 +79,12 @@ class CscBuilder:
         self.nnz = int(self.indices.numel())
         dev, st = A.device(), A.stream_ptr()
         self.counts = torch.empty(self.k, dtype=torch.int64, device=dev)
-        check(fn('be_csr_to_csc_count', c_int, [c_vp, c_i64, c_i64, c_vp, c_vp])(
-            A.ptr(self.indices), self.nnz, self.k, A.ptr(self.counts), st), 'be_csr_to_csc_count')
+        call('be_csr_to_csc_count', A.ptr(self.indices), self.nnz, self.k, A.ptr(self.counts), st)
         self.csc_indptr = torch.empty(self.k + 1, dtype=torch.int64, device=dev)
-        scratch = A.workspace(fn('be_csr_to_csc_scratch_bytes', c_i64, [c_i64])(self.k))
-        total = c_i64(0)
-        check(fn('be_csr_to_csc_indptr', c_int, [c_vp, c_i64, c_vp, c_int, ctypes.POINTER(c_i64), c_vp, c_i64, c_vp])(
-            A.ptr(self.counts), self.k, A.ptr(self.csc_indptr), 1, ctypes.byref(total), A.ptr(scratch), scratch.numel(), st),
-            'be_csr_to_csc_indptr')
+        scratch = A.workspace(fn('be_csr_to_csc_scratch_bytes')(self.k))
+        total = ctypes.c_int64(0)
+        call('be_csr_to_csc_indptr', A.ptr(self.counts), self.k, A.ptr(self.csc_indptr), 1, ctypes.byref(total), A.ptr(scratch),
+             scratch.numel(), st)
         if int(total.value) != self.nnz:
             raise ValueError(f"csr_to_csc: {self.nnz - int(total.value)} of {self.nnz} column ids lie outside [0, {self.k}).")
 
@@ -123,11 +119,8 @@ class CscBuilder:
             p_out = torch.empty(n, dtype=torch.int64 if p64 else torch.int32, device=dev)
         cursor = torch.empty(max(c1 - c0, 1), dtype=torch.int64, device=dev)
         is64 = int(self.indptr is not None and self.indptr.dtype == torch.int64)
-        f = fn('be_csr_to_csc_fill_block', c_int,
-               [c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp])
-        check(f(A.ptr(self.indices), A.ptr(self.indptr), is64, self.row_len, self.m, self.nnz, c0, c1, A.ptr(self.csc_indptr),
-                A.ptr(cursor), A.ptr(rows), A.ptr(p_out), p64, A.ptr(data if wb else None), wb, A.ptr(w_out), st),
-              'be_csr_to_csc_fill_block')
+        call('be_csr_to_csc_fill_block', A.ptr(self.indices), A.ptr(self.indptr), is64, self.row_len, self.m, self.nnz, c0, c1,
+             A.ptr(self.csc_indptr), A.ptr(cursor), A.ptr(rows), A.ptr(p_out), p64, A.ptr(data if wb else None), wb, A.ptr(w_out), st)
         return rows, w_out, p_out
 
     def offsets(self) -> torch.Tensor:
@@ -142,9 +135,8 @@ def gather_by_perm(src: torch.Tensor, perm: torch.Tensor, out: Optional[torch.Te
     if out is None:
         out = torch.empty(perm.numel(), dtype=src.dtype, device=src.device)
     assert out.dtype == src.dtype and out.numel() == perm.numel() and out.is_contiguous()
-    check(fn('be_gather_by_perm', c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_vp, c_vp])(
-        A.ptr(src), src.element_size(), A.ptr(perm), int(perm.dtype == torch.int64), perm.numel(), A.ptr(out), A.stream_ptr()),
-        'be_gather_by_perm')
+    call('be_gather_by_perm', A.ptr(src), src.element_size(), A.ptr(perm), int(perm.dtype == torch.int64), perm.numel(), A.ptr(out),
+         A.stream_ptr())
     return out
 
 

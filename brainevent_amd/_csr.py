@@ -28,7 +28,7 @@ from . import _array as A
 from ._data import DataRepresentation
 from ._error import MathError
 from ._event import BinaryArray, is_event, event_operand
-from ._lib import check, fn
+from ._lib import call, check, fn, last_error
 from ._misc import _as_indptr, _as_int32_indices, _check_compressed_structure
 from ._op import OpKernel
 from ._plasticity import PlasticityMixin
@@ -38,7 +38,13 @@ __all__ = ['CSR', 'CSC', 'ScatterPlan', 'BinnedScatter', 'Mirror', 'binary_csrmv
            'binary_csrmm_p', 'binary_csrmv_p_call', 'binary_csrmm_p_call', 'binary_csrmv_indexed', 'binary_csrmm_indexed',
            'indexed_workspace', 'build_mirror_of', 'hybrid_task_capacity']
 
-c_i64, c_int, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
+
+def _check_exponent(rc: int, what: str) -> None:
+    """``check`` for the ``be_*_exponent`` entry points: BE_ERR_RANGE (-4: inf / nan weights or a dynamic range the sums cannot
+    resolve) is a ``MathError`` — the caller falls back to another route."""
+    if rc == -4:
+        raise MathError(last_error())
+    check(rc, what)
 
 
 # =====================================================================================================
@@ -228,7 +234,7 @@ class ScatterPlan:
         # with room for the pre-gathered segment table only when this plan's blocks are short enough for the step to use it
         # (up to 8 GiB at 100 slices x 10M rows); if that does not fit the device, the smaller workspace does: the step
         # then gathers from the plan's own table
-        f = fn('be_binary_csrmm_t_plan_workspace_bytes_for', c_i64, [c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int])
+        f = fn('be_binary_csrmm_t_plan_workspace_bytes_for')
         args = (self.m, self.k, n_batch, self.slice_shift, self.slice_width, parts, int(self.homo))
         need, base = f(*args, int(self.block_hint)), f(*args, 0)
         key = (parts, n_batch, need > base)
@@ -317,9 +323,8 @@ class ScatterPlan:
             max_row = int(row_len) if indptr is None else (int((indptr[1:] - indptr[:-1]).max().item()) if m > 0 else 0)
         lay, slice_shift, slice_width, n_slices = cls._choose_geometry(m, k, nnz, homo, max_row, slice_shift, slice_width, layout)
         seg = torch.empty(n_slices * m * 2, dtype=torch.int32, device=dev)   # {uint32 start, uint32 n4} pairs
-        f_scr = fn('be_scatter_plan_scratch_bytes', c_i64, [c_i64, c_i64, c_int, c_int])
-        scratch = A.workspace(f_scr(m, k, slice_shift, slice_width))
-        blob_bytes = c_i64(0)
+        scratch = A.workspace(fn('be_scatter_plan_scratch_bytes')(m, k, slice_shift, slice_width))
+        blob_bytes = ctypes.c_int64(0)
         order = None
         if keep_order is None and os.environ.get('BE_PLAN_KEEP_ORDER'):          # (A/B runs)
             keep_order = os.environ['BE_PLAN_KEEP_ORDER'] == '1'
@@ -328,11 +333,8 @@ class ScatterPlan:
                 order = torch.empty(nnz, dtype=torch.int16, device=dev)
             except getattr(torch, 'OutOfMemoryError', RuntimeError):
                 torch.cuda.empty_cache()
-        f_cnt = fn('be_scatter_plan_count_ordered', c_int,
-                   [c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, ctypes.POINTER(c_i64),
-                    c_vp, c_vp])
-        check(f_cnt(A.ptr(indices), A.ptr(indptr), is64, row_len, m, k, slice_shift, slice_width, int(homo), lay, A.ptr(seg),
-                    A.ptr(scratch), scratch.numel(), ctypes.byref(blob_bytes), A.ptr(order), st), 'be_scatter_plan_count_ordered')
+        call('be_scatter_plan_count_ordered', A.ptr(indices), A.ptr(indptr), is64, row_len, m, k, slice_shift, slice_width, int(homo),
+             lay, A.ptr(seg), A.ptr(scratch), scratch.numel(), ctypes.byref(blob_bytes), A.ptr(order), st)
         try:
             blob = torch.empty(int(blob_bytes.value) + 128, dtype=torch.uint8, device=dev)
         except getattr(torch, 'OutOfMemoryError', RuntimeError):
@@ -379,12 +381,8 @@ class ScatterPlan:
                                                                        slice_width, layout)
         dev, st = A.device(), A.stream_ptr()
         seg = torch.empty(n_slices * m * 2, dtype=torch.int32, device=dev)
-        f_scr = fn('be_scatter_plan_scratch_bytes', c_i64, [c_i64, c_i64, c_int, c_int])
-        scratch = A.workspace(f_scr(m, k, slice_shift, slice_width))
-        check(fn('be_scatter_plan_begin', c_int, [c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_vp])(
-            m, k, slice_shift, slice_width, A.ptr(scratch), scratch.numel(), st), 'be_scatter_plan_begin')
-        f_cnt = fn('be_scatter_plan_count_rows', c_int,
-                   [c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp, c_i64, c_vp, c_vp])
+        scratch = A.workspace(fn('be_scatter_plan_scratch_bytes')(m, k, slice_shift, slice_width))
+        call('be_scatter_plan_begin', m, k, slice_shift, slice_width, A.ptr(scratch), scratch.numel(), st)
         seg_rows = seg.view(m, n_slices * 2)
 
         def block_args(r0, r1):
@@ -401,14 +399,13 @@ class ScatterPlan:
             r1 = min(m, r0 + int(block_rows))
             w, idx, ptr, is64, rl = block_args(r0, r1)
             n_seen += int(idx.numel())
-            check(f_cnt(A.ptr(idx), A.ptr(ptr), is64, rl, r1 - r0, m, k, slice_shift, slice_width, int(homo), lay,
-                        A.ptr(seg_rows[r0]), A.ptr(scratch), scratch.numel(), None, st), 'be_scatter_plan_count_rows')
+            call('be_scatter_plan_count_rows', A.ptr(idx), A.ptr(ptr), is64, rl, r1 - r0, m, k, slice_shift, slice_width, int(homo),
+                 lay, A.ptr(seg_rows[r0]), A.ptr(scratch), scratch.numel(), None, st)
             torch.cuda.current_stream().synchronize()         # the block's arrays may be released by the caller's next get_block
         assert n_seen == int(nnz), f"build_from_blocks: the blocks hold {n_seen} entries, nnz says {nnz}"
-        blob_bytes = c_i64(0)
-        check(fn('be_scatter_plan_scan', c_int, [c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_i64, ctypes.POINTER(c_i64), c_vp])(
-            m, k, slice_shift, slice_width, A.ptr(seg), A.ptr(scratch), scratch.numel(), ctypes.byref(blob_bytes), st),
-            'be_scatter_plan_scan')
+        blob_bytes = ctypes.c_int64(0)
+        call('be_scatter_plan_scan', m, k, slice_shift, slice_width, A.ptr(seg), A.ptr(scratch), scratch.numel(),
+             ctypes.byref(blob_bytes), st)
         blob = torch.empty(int(blob_bytes.value) + 128, dtype=torch.uint8, device=dev)
         plan = cls(m, k, bool(homo), slice_shift, seg, blob, 0, weight_dtype, slice_width, lay)
         plan.nnz, plan.order, plan.row_len, plan.split_f64 = int(nnz), None, -1, False
@@ -416,15 +413,13 @@ class ScatterPlan:
             n_blk = m * n_slices
             ng = seg.view(n_blk, 2)[::max(1, n_blk >> 22), 1] & 0xffff
             plan.items_hint = max(1, min(1 << 20, int(round(4.0 * ng.double().mean().item()))))
-        f_fill = fn('be_scatter_plan_fill_ordered', c_int,
-                    [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp])
         maxabs = torch.zeros(2, dtype=torch.int32, device=dev)
         stats = torch.tensor([0, 0xffffffff], dtype=torch.int64, device=dev)          # max |w| bits, smallest non-zero |w| bits
         for r0 in range(0, m, int(block_rows)):
             r1 = min(m, r0 + int(block_rows))
             w, idx, ptr, is64, rl = block_args(r0, r1)
-            check(f_fill(A.ptr(w), int(homo), A.wcode(w), A.ptr(idx), A.ptr(ptr), is64, rl, r1 - r0, k, slice_shift, slice_width,
-                         lay, A.ptr(seg_rows[r0]), A.ptr(blob), A.ptr(maxabs), None, st), 'be_scatter_plan_fill_ordered')
+            call('be_scatter_plan_fill_ordered', A.ptr(w), int(homo), A.wcode(w), A.ptr(idx), A.ptr(ptr), is64, rl, r1 - r0, k,
+                 slice_shift, slice_width, lay, A.ptr(seg_rows[r0]), A.ptr(blob), A.ptr(maxabs), None, st)
             mb = maxabs.to(torch.int64) & 0xffffffff                                   # (every fill call starts its own statistics)
             stats = torch.stack([torch.maximum(stats[0], mb[0]), torch.minimum(stats[1], mb[1])])
             torch.cuda.current_stream().synchronize()
@@ -441,12 +436,10 @@ class ScatterPlan:
         is64 = int(indptr is not None and indptr.dtype == torch.int64)
         self.slot = None        # block positions belong to the pass that drew them (u16: an LDS counter): a fill voids the table
         maxabs = torch.zeros(2, dtype=torch.int32, device=self.seg.device)   # f32 bits of max |w| / smallest non-zero |w|
-        name = 'be_scatter_plan_refresh_weights_ordered' if keep_exp else 'be_scatter_plan_fill_ordered'
-        f_fill = fn(name, c_int,
-                    [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp])
-        check(f_fill(A.ptr(weights), int(self.homo), A.wcode(weights), A.ptr(indices), A.ptr(indptr), is64, self.row_len,
-                     self.m, self.k, self.slice_shift, self.slice_width, self.layout, A.ptr(self.seg), A.ptr(self.blob),
-                     A.ptr(maxabs), A.ptr(getattr(self, 'order', None)), A.stream_ptr()), name)
+        call('be_scatter_plan_refresh_weights_ordered' if keep_exp else 'be_scatter_plan_fill_ordered', A.ptr(weights),
+             int(self.homo), A.wcode(weights), A.ptr(indices), A.ptr(indptr), is64, self.row_len, self.m, self.k, self.slice_shift,
+             self.slice_width, self.layout, A.ptr(self.seg), A.ptr(self.blob), A.ptr(maxabs), A.ptr(getattr(self, 'order', None)),
+             A.stream_ptr())
         self.stamp = weights_stamp(weights)
         if not self.homo:
             # a refresh keeps the exponent it was built with while that still cannot overflow (it is a launch argument: a
@@ -457,16 +450,11 @@ class ScatterPlan:
 
     def _plan_exponent(self, maxabs: torch.Tensor, keep: Optional[int] = None) -> int:
         scratch = A.workspace(256)
-        out = c_int(0)
-        f = fn('be_scatter_plan_exponent', c_int,
-               [c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_int, c_i64, c_vp, c_int, c_int, c_vp, c_i64, ctypes.POINTER(c_int), c_vp])
-        rc = f(A.ptr(self.blob), A.ptr(self.seg), self.m, self.k, self.slice_shift, self.slice_width, self.layout, self.nnz,
-               A.ptr(maxabs), self.MIN_WEIGHT_BITS, -(1 << 31) if keep is None else int(keep), A.ptr(scratch), scratch.numel(),
-               ctypes.byref(out), A.stream_ptr())
-        if rc == -4:               # BE_ERR_RANGE: inf / nan or a dynamic range the sums cannot resolve -> the caller falls back
-            from ._lib import lib
-            raise MathError((lib().be_last_error() or b'').decode())
-        check(rc, 'be_scatter_plan_exponent')
+        out = ctypes.c_int(0)
+        _check_exponent(fn('be_scatter_plan_exponent')(
+            A.ptr(self.blob), A.ptr(self.seg), self.m, self.k, self.slice_shift, self.slice_width, self.layout, self.nnz,
+            A.ptr(maxabs), self.MIN_WEIGHT_BITS, -(1 << 31) if keep is None else int(keep), A.ptr(scratch), scratch.numel(),
+            ctypes.byref(out), A.stream_ptr()), 'be_scatter_plan_exponent')
         return int(out.value)
 
     def refresh_weights(self, weights, indices, indptr) -> None:
@@ -525,19 +513,12 @@ def fixed_point_exponent(weights: torch.Tensor, indices: Optional[torch.Tensor],
     of weights: captured graphs hold it as a launch argument).  Raises ``MathError`` for inf / nan weights or a dynamic range
     the 64-bit sums cannot resolve.  One or two passes of global atomics over the entries, build time only (~1 s at 1e10)."""
     flat_w = weights.reshape(-1)
-    f_scr = fn('be_fixed_point_scratch_bytes', c_i64, [c_i64])
-    scratch = A.workspace(f_scr(int(k)))
-    out = c_int(0)
-    f = fn('be_fixed_point_exponent', c_int,
-           [c_vp, c_int, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_i64, ctypes.POINTER(c_int), c_vp])
-    rc = f(A.ptr(flat_w), A.wcode(flat_w), A.ptr(None if indices is None else indices.reshape(-1)), flat_w.numel(), int(k),
-           ScatterPlan.MIN_WEIGHT_BITS if min_bits is None else int(min_bits), -(1 << 31) if keep is None else int(keep),
-           A.ptr(scratch), scratch.numel(),
-           ctypes.byref(out), A.stream_ptr())
-    if rc == -4:            # BE_ERR_RANGE: not representable
-        from ._lib import lib
-        raise MathError((lib().be_last_error() or b'').decode())
-    check(rc, 'be_fixed_point_exponent')
+    scratch = A.workspace(fn('be_fixed_point_scratch_bytes')(int(k)))
+    out = ctypes.c_int(0)
+    _check_exponent(fn('be_fixed_point_exponent')(
+        A.ptr(flat_w), A.wcode(flat_w), A.ptr(None if indices is None else indices.reshape(-1)), flat_w.numel(), int(k),
+        ScatterPlan.MIN_WEIGHT_BITS if min_bits is None else int(min_bits), -(1 << 31) if keep is None else int(keep),
+        A.ptr(scratch), scratch.numel(), ctypes.byref(out), A.stream_ptr()), 'be_fixed_point_exponent')
     return int(out.value)
 
 
@@ -697,7 +678,7 @@ class BinnedScatter:
     def serves(k: int, slice_shift: int = 16, homo: bool = False) -> bool:
         """Whether the binned route has a geometry for ``k`` outputs at this ``slice_shift`` (``be_binned_bins`` > 0: the
         write-combining blocks of all bins have to fit pass B's LDS)."""
-        return int(fn('be_binned_bins', c_int, [c_i64, c_int, c_int])(int(k), int(slice_shift), int(bool(homo)))) > 0
+        return _binned_bins(k, slice_shift, int(bool(homo))) > 0
 
     SHORT_ROW_ENTRIES = 256      # BE_BINNED_SHORT_ROWS: average stored row length up to which pass B runs one step ahead
 
@@ -708,23 +689,17 @@ class BinnedScatter:
         return self.kind | (8 if self.nnz <= self.SHORT_ROW_ENTRIES * max(self.m, 1) else 0)
 
     def _set_geometry(self) -> None:
-        self.n_slices = int(fn('be_binned_bins', c_int, [c_i64, c_int, c_int])(self.k, self.slice_shift, self.kind))
+        self.n_slices = _binned_bins(self.k, self.slice_shift, self.kind)
         if self.n_slices <= 0:
             raise ValueError(f"the binned route does not serve {self.k} outputs at slice_shift={self.slice_shift}")
-        expect = self.max_active_fraction * self.nnz / max(self.n_slices, 1)
-        self.bin_capacity = int(max(1024, min(2 ** 31, 1.25 * expect + 6 * math.sqrt(max(expect, 1.0)) + 64)))
+        self.bin_capacity = _bin_capacity(self.max_active_fraction * self.nnz / max(self.n_slices, 1))
 
     def workspace(self, n_batch: int = 1) -> torch.Tensor:
         """The workspace of steps over ``n_batch`` spike vectors (created and initialised once per batch size; never evicted:
         a captured HIP graph keeps its raw pointer)."""
         ws = self._ws.get(int(n_batch))
         if ws is None:
-            f = fn('be_binary_csrmm_t_binned_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int, c_i64])
-            ws = A.workspace(f(self.m, self.k, int(n_batch), self.slice_shift, self.bin_capacity))      # (sized for every kind)
-            f = fn('be_binary_csrmm_t_binned_workspace_init', c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_i64, c_vp])
-            check(f(A.ptr(ws), ws.numel(), self.m, self.k, int(n_batch), self.slice_shift, self.bin_capacity, A.stream_ptr()),
-                  'be_binary_csrmm_t_binned_workspace_init')
-            self._ws[int(n_batch)] = ws
+            ws = self._ws[int(n_batch)] = _binned_workspace(self.m, self.k, int(n_batch), self.slice_shift, self.bin_capacity)
         return ws
 
     def audit(self, n_batch: int = 1):
@@ -732,8 +707,7 @@ class BinnedScatter:
         (``be_binned_workspace_audit``): entries in the active rows, tickets drawn by pass B, entries accumulated by pass C,
         entries delivered through the overflow image — ``a == b == c + d`` after complete steps.  Synchronises."""
         c = (ctypes.c_uint64 * 4)()
-        check(fn('be_binned_workspace_audit', c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), c_vp])(
-            A.ptr(self.workspace(n_batch)), c, A.stream_ptr()), 'be_binned_workspace_audit')
+        call('be_binned_workspace_audit', A.ptr(self.workspace(n_batch)), c, A.stream_ptr())
         return tuple(int(x) for x in c)
 
     def check_status(self, clear: bool = True) -> None:
@@ -744,11 +718,10 @@ class BinnedScatter:
         read between its passes — a spurious conservation error — and ``clear`` would zero the counters under it), and reads a
         workspace through its own device; call it at a point that synchronises anyway (the containers do after a mirror build;
         ``bench.py`` at its parity check)."""
-        f = fn('be_binned_workspace_status', c_int, [c_vp, c_int, c_vp])
         for ws in self._ws.values():
             with torch.cuda.device(ws.device):
                 torch.cuda.synchronize(ws.device)
-                check(f(A.ptr(ws), int(clear), A.stream_ptr()), 'be_binned_workspace_status')
+                call('be_binned_workspace_status', A.ptr(ws), int(clear), A.stream_ptr())
 
     def _column_stats_by_steps(self, weights: torch.Tensor, indices: torch.Tensor):
         """``(largest column sum of |w|, smallest column mean of |w| over the non-empty columns, max |w|, min non-zero |w|)``
@@ -760,31 +733,18 @@ class BinnedScatter:
         indptr, row_len = self._rows
         m, k, dev = self.m, self.k, weights.device
         flat = weights.reshape(-1)
-        mx, mn = ctypes.c_uint32(0), ctypes.c_uint32(0)
-        scr = A.workspace(256)
-        check(fn('be_weight_stats', c_int, [c_vp, c_int, c_i64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), c_vp,
-                                            c_i64, c_vp])(A.ptr(flat), A.wcode(flat), flat.numel(), ctypes.byref(mx), ctypes.byref(mn),
-                                                          A.ptr(scr), scr.numel(), A.stream_ptr()), 'be_weight_stats')
-        if mx.value >= 0x7f800000:
+        wmax, wmin = _weight_stats(flat)
+        if not math.isfinite(wmax):
             raise MathError("weights contain inf / nan: the fixed-point routes do not apply")
-        as_f32 = lambda b: float(np.array([b], dtype=np.uint32).view(np.float32)[0])
-        wmax = as_f32(mx.value)
-        wmin = as_f32(mn.value) if mn.value != 0xffffffff else float('inf')
         if wmax == 0.0:
             return 0.0, float('inf'), 0.0, float('inf')
         e0 = 62 - math.frexp(wmax * (self.nnz + 1) * 1.001)[1]             # every entry in one column could not overflow this
         e0 = max(-90, min(150, e0))
-        n_slices = int(fn('be_binned_bins', c_int, [c_i64, c_int, c_int])(k, self.slice_shift, 0))
+        n_slices = _binned_bins(k, self.slice_shift, 0)
         if n_slices <= 0:
             raise ValueError(f"the binned route does not serve {k} outputs at slice_shift={self.slice_shift}")
-        expect = self.max_active_fraction * self.nnz / n_slices
-        cap = int(max(1024, min(2 ** 31, 1.25 * expect + 6 * math.sqrt(max(expect, 1.0)) + 64)))
-        f_bytes = fn('be_binary_csrmm_t_binned_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int, c_i64])
-        ws = A.workspace(f_bytes(m, k, 1, self.slice_shift, cap))
-        check(fn('be_binary_csrmm_t_binned_workspace_init', c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_i64, c_vp])(
-            A.ptr(ws), ws.numel(), m, k, 1, self.slice_shift, cap, A.stream_ptr()), 'be_binary_csrmm_t_binned_workspace_init')
-        f = fn('be_binary_csrmv_t_binned', c_int,
-               [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_vp, c_i64, c_i64, c_int, c_i64, c_int, c_vp, c_i64, c_vp])
+        cap = _bin_capacity(self.max_active_fraction * self.nnz / n_slices)
+        ws = _binned_workspace(m, k, 1, self.slice_shift, cap)
         is64 = int(indptr is not None and indptr.dtype == torch.int64)
         one = torch.ones(1, dtype=torch.float32, device=dev)
         chunk = max(1, int(self.max_active_fraction * m))       # rows per step: what the bins are sized for (past it: the overflow image, still |w|)
@@ -797,12 +757,12 @@ class BinnedScatter:
             n_act = torch.tensor([min(chunk, m - lo)], dtype=torch.int32, device=dev)
             ev = A.ActiveIds(ids[lo:lo + chunk], n_act, m)
             for kind, w_arg, code, acc in ((4, flat, wcode, colsum), (1, one, A.BE_F32, count)):
-                check(f(A.ptr(w_arg), kind, code, A.ptr(indices), A.ptr(indptr), is64, row_len, A.ptr(ev), A.BE_SPIKE_IDS, A.ptr(out),
-                        m, k, self.slice_shift, cap, e0, A.ptr(ws), ws.numel(), A.stream_ptr()), 'be_binary_csrmv_t_binned')
+                call('be_binary_csrmv_t_binned', A.ptr(w_arg), kind, code, A.ptr(indices), A.ptr(indptr), is64, row_len, A.ptr(ev),
+                     A.BE_SPIKE_IDS, A.ptr(out), m, k, self.slice_shift, cap, e0, A.ptr(ws), ws.numel(), A.stream_ptr())
                 acc += out
         # the statistics decide the exponent of every later step: the steps that made them must have conserved their entries
         # (the reductions below synchronise anyway)
-        check(fn('be_binned_workspace_status', c_int, [c_vp, c_int, c_vp])(A.ptr(ws), 1, A.stream_ptr()), 'be_binned_workspace_status')
+        call('be_binned_workspace_status', A.ptr(ws), 1, A.stream_ptr())
         live = count > 0
         mean_min = float((colsum[live] / count[live]).min()) if bool(live.any()) else float('inf')
         return float(colsum.max()), mean_min, wmax, wmin
@@ -871,13 +831,7 @@ class BinnedScatter:
         """Smallest non-zero |w| (inf if there is none): from the statistics already taken, else one streaming pass."""
         if getattr(self, '_stats_stamp', None) == weights_stamp(weights):
             return self._stats[3]
-        flat = weights.reshape(-1)
-        mx, mn = ctypes.c_uint32(0), ctypes.c_uint32(0)
-        scr = A.workspace(256)
-        check(fn('be_weight_stats', c_int, [c_vp, c_int, c_i64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), c_vp,
-                                            c_i64, c_vp])(A.ptr(flat), A.wcode(flat), flat.numel(), ctypes.byref(mx), ctypes.byref(mn),
-                                                          A.ptr(scr), scr.numel(), A.stream_ptr()), 'be_weight_stats')
-        return float(np.array([mn.value], dtype=np.uint32).view(np.float32)[0]) if mn.value != 0xffffffff else float('inf')
+        return _weight_stats(weights.reshape(-1))[1]
 
     def refresh_weights(self, weights, indices, indptr=None) -> None:
         """The bins are refilled from the matrix on every call; only the fixed-point exponent derives from the weights."""
@@ -898,17 +852,42 @@ class BinnedScatter:
     def applicable(weights: torch.Tensor, k: int) -> bool:
         if weights.dtype not in (torch.float32, torch.float16, torch.bfloat16):
             return False                  # f64: the bins carry f32 weights (per-entry f64 weights take the planned route)
-        return fn('be_binned_bins', c_int, [c_i64, c_int, c_int])(int(k), 16, int(weights.numel() == 1)) > 0      # (kind 0 / 1)
+        return _binned_bins(k, 16, int(weights.numel() == 1)) > 0      # (kind 0 / 1)
+
+
+def _binned_bins(k: int, slice_shift: int, kind: int) -> int:
+    """``be_binned_bins``: the bins ``k`` outputs are cut into for steps of this kind, 0 when the route has no geometry."""
+    return int(fn('be_binned_bins')(int(k), int(slice_shift), int(kind)))
+
+
+def _bin_capacity(expect: float) -> int:
+    """Entries a bin is sized for when ``expect`` are expected in a step: the mean plus a margin of a quarter and six sigma."""
+    return int(max(1024, min(2 ** 31, 1.25 * expect + 6 * math.sqrt(max(expect, 1.0)) + 64)))
+
+
+def _binned_workspace(m: int, k: int, n_batch: int, slice_shift: int, bin_capacity: int) -> torch.Tensor:
+    """A binned workspace (sized for every kind of step), initialised for its first step."""
+    ws = A.workspace(fn('be_binary_csrmm_t_binned_workspace_bytes')(m, k, n_batch, slice_shift, bin_capacity))
+    call('be_binary_csrmm_t_binned_workspace_init', A.ptr(ws), ws.numel(), m, k, n_batch, slice_shift, bin_capacity, A.stream_ptr())
+    return ws
+
+
+def _weight_stats(flat: torch.Tensor) -> Tuple[float, float]:
+    """``(max |w|, smallest non-zero |w|)`` of a flat weight array in one streaming pass (``be_weight_stats``); the maximum is
+    inf / nan when a weight is, the minimum inf when every weight is zero."""
+    mx, mn = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    scr = A.workspace(256)
+    call('be_weight_stats', A.ptr(flat), A.wcode(flat), flat.numel(), ctypes.byref(mx), ctypes.byref(mn), A.ptr(scr), scr.numel(),
+         A.stream_ptr())
+    as_f32 = lambda b: float(np.array([b], dtype=np.uint32).view(np.float32)[0])
+    return as_f32(mx.value), (as_f32(mn.value) if mn.value != 0xffffffff else float('inf'))
 
 
 def _binned_call(ws: 'BinnedScatter', weights, indices, indptr, row_len, spikes, sd, out) -> None:
-    f = fn('be_binary_csrmv_t_binned', c_int,
-           [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_vp, c_i64, c_i64, c_int, c_i64, c_int, c_vp, c_i64,
-            c_vp])
     is64 = int(indptr is not None and indptr.dtype == torch.int64)
-    check(f(A.ptr(weights), ws.step_kind, A.wcode(weights), A.ptr(indices), A.ptr(indptr), is64, row_len, A.ptr(spikes), sd,
-            A.ptr(out), ws.m, ws.k, ws.slice_shift, ws.bin_capacity, ws.scale_exp, A.ptr(ws.ws), ws.ws.numel(),
-            A.stream_ptr()), 'be_binary_csrmv_t_binned')
+    call('be_binary_csrmv_t_binned', A.ptr(weights), ws.step_kind, A.wcode(weights), A.ptr(indices), A.ptr(indptr), is64, row_len,
+         A.ptr(spikes), sd, A.ptr(out), ws.m, ws.k, ws.slice_shift, ws.bin_capacity, ws.scale_exp, A.ptr(ws.ws), ws.ws.numel(),
+         A.stream_ptr())
 
 
 def binned_batch(ws: 'BinnedScatter', weights, indices, indptr, row_len, spikes_bm, sd, out_bm) -> None:
@@ -920,13 +899,10 @@ def binned_batch(ws: 'BinnedScatter', weights, indices, indptr, row_len, spikes_
         return
     nb = int(out_bm.shape[0])
     wsb = ws.workspace(nb)
-    f = fn('be_binary_csrmm_t_binned', c_int,
-           [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_int, c_vp, c_i64,
-            c_vp])
     is64 = int(indptr is not None and indptr.dtype == torch.int64)
-    check(f(A.ptr(weights), ws.kind, A.wcode(weights), A.ptr(indices), A.ptr(indptr), is64, row_len, A.ptr(spikes_bm), sd,
-            A.ptr(out_bm), ws.m, ws.k, nb, ws.slice_shift, ws.bin_capacity, ws.scale_exp, A.ptr(wsb), wsb.numel(),
-            A.stream_ptr()), 'be_binary_csrmm_t_binned')
+    call('be_binary_csrmm_t_binned', A.ptr(weights), ws.kind, A.wcode(weights), A.ptr(indices), A.ptr(indptr), is64, row_len,
+         A.ptr(spikes_bm), sd, A.ptr(out_bm), ws.m, ws.k, nb, ws.slice_shift, ws.bin_capacity, ws.scale_exp, A.ptr(wsb), wsb.numel(),
+         A.stream_ptr())
 
 
 def _plan_call(plan: ScatterPlan, weights: torch.Tensor, spikes_bm: torch.Tensor, sd: int, out_bm: torch.Tensor,
@@ -937,14 +913,9 @@ def _plan_call(plan: ScatterPlan, weights: torch.Tensor, spikes_bm: torch.Tensor
     if nb > 1:
         parts = max(1, min(parts, 512 // (plan.n_slices * nb)))
     ws = plan.workspace(parts, nb)
-    f = fn('be_binary_csrmm_t_plan', c_int,
-           [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
-            c_i64, c_vp])
-    check(f(A.ptr(weights), int(plan.homo), A.wcode(out_bm), A.ptr(plan.blob), A.ptr(plan.seg), A.ptr(spikes_bm), sd,
-            A.ptr(out_bm), plan.m, plan.k, nb, plan.slice_shift, plan.slice_width, plan.layout, plan.block_hint, parts,
-            plan.scale_exp, A.ptr(ws),
-            ws.numel(),
-            A.stream_ptr()), 'be_binary_csrmm_t_plan')
+    call('be_binary_csrmm_t_plan', A.ptr(weights), int(plan.homo), A.wcode(out_bm), A.ptr(plan.blob), A.ptr(plan.seg),
+         A.ptr(spikes_bm), sd, A.ptr(out_bm), plan.m, plan.k, nb, plan.slice_shift, plan.slice_width, plan.layout, plan.block_hint,
+         parts, plan.scale_exp, A.ptr(ws), ws.numel(), A.stream_ptr())
 
 
 # =====================================================================================================
@@ -1098,27 +1069,21 @@ class StoredRows(NamedTuple):
     k: int
 
 
-_CSRMM_GENERIC_ARGS = [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]
-_CSRMM_INDEXED_ARGS = _CSRMM_GENERIC_ARGS[:7] + [c_vp, c_int] + _CSRMM_GENERIC_ARGS[7:]
-
-
 def _csrmm_direct(weights, indices, indptr, row_len, perm, spikes_bm, sd, out, m, k, nb, transpose) -> None:
     """``be_binary_csrmm_t`` (global atomics) / ``be_binary_csrmm_nt`` (gather) with explicit dtype codes: any spike encoding;
     ``indptr=None`` = rows of ``row_len`` entries.  With ``perm`` the ``_indexed`` twins: slot ``j`` reads ``weights[perm[j]]``."""
     if transpose:
-        ws = A.workspace(fn('be_binary_csrmm_t_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int])(m, k, nb, A.wcode(weights)))
-        name = 'be_binary_csrmm_t'
+        ws = A.workspace(fn('be_binary_csrmm_t_workspace_bytes')(m, k, nb, A.wcode(weights)))
     else:
-        ws = A.workspace(fn('be_binary_csrmm_nt_workspace_bytes', c_i64, [c_i64, c_i64, c_i64])(m, k, nb))
-        name = 'be_binary_csrmm_nt'
+        ws = A.workspace(fn('be_binary_csrmm_nt_workspace_bytes')(m, k, nb))
     is64 = int(indptr is not None and indptr.dtype == torch.int64)
     head = (A.ptr(weights), int(weights.numel() == 1), A.wcode(weights), A.ptr(indices), A.ptr(indptr), is64, row_len)
     tail = (A.ptr(spikes_bm), sd, A.ptr(out), m, k, nb, A.ptr(ws), ws.numel(), A.stream_ptr())
     if perm is None:
-        check(fn(name, c_int, _CSRMM_GENERIC_ARGS)(*head, *tail), name)
+        call('be_binary_csrmm_t' if transpose else 'be_binary_csrmm_nt', *head, *tail)
     else:
-        name += '_indexed'
-        check(fn(name, c_int, _CSRMM_INDEXED_ARGS)(*head, A.ptr(perm), int(perm.dtype == torch.int64), *tail), name)
+        call('be_binary_csrmm_t_indexed' if transpose else 'be_binary_csrmm_nt_indexed', *head, A.ptr(perm),
+             int(perm.dtype == torch.int64), *tail)
 
 
 def rows_step(weights, indices, indptr, row_len, spikes_bm, sd, *, m, k, transpose, workspace=None, perm=None):

@@ -10,7 +10,6 @@ Reference surface (read as text): ``brainevent/_dense/binary.py:79-165`` (``bina
 Non-bool, non-float spikes are cast to bool first (reference ``:162-163``); float spikes are active when
 ``> 0`` (the documented binary semantics; the reference's ``jax_raw`` multiply-by-value shortcut is not followed).
 """
-import ctypes
 from typing import Optional
 
 import numpy as np
@@ -18,16 +17,13 @@ import torch
 
 from . import _array as A
 from ._data import DataRepresentation
-from ._lib import check, fn
+from ._lib import call, fn
 from ._op import OpKernel
 from ._plasticity import PlasticityMixin
 from . import _autograd as _ag
 
 __all__ = ['Dense', 'binary_densemv', 'binary_densemm', 'binary_densemv_p', 'binary_densemm_p', 'binary_densemv_p_call',
            'binary_densemm_p_call']
-
-c_i64, c_int, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
-_MM_ARGS = [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]
 
 
 def _dense_batched(weights: torch.Tensor, spikes_bm: torch.Tensor, sd: int, transpose: bool) -> torch.Tensor:
@@ -38,17 +34,14 @@ def _dense_batched(weights: torch.Tensor, spikes_bm: torch.Tensor, sd: int, tran
     out = torch.empty((nb, out_len), dtype=weights.dtype, device=weights.device)
     if out_len == 0 or nb == 0:
         return out
-    f_ws = fn('be_binary_densemm_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int, c_int])
-    ws = A.workspace(f_ws(rows_w, cols_w, nb, int(transpose), A.wcode(weights)))
+    ws = A.workspace(fn('be_binary_densemm_workspace_bytes')(rows_w, cols_w, nb, int(transpose), A.wcode(weights)))
     if sd == A.BE_SPIKE_BITS:      # bit-packed rows [nb, ceil(k / 32)] words: the generic entry point (the per-variant names cover bool / float)
-        f = fn('be_binary_densemm', c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp])
-        check(f(A.ptr(weights), A.wcode(weights), A.ptr(spikes_bm), sd, A.ptr(out), rows_w, cols_w, nb, int(transpose), A.ptr(ws),
-                ws.numel(), A.stream_ptr()), 'be_binary_densemm')
+        call('be_binary_densemm', A.ptr(weights), A.wcode(weights), A.ptr(spikes_bm), sd, A.ptr(out), rows_w, cols_w, nb,
+             int(transpose), A.ptr(ws), ws.numel(), A.stream_ptr())
         return out
     name = (f"be_binary_densemm_{'transpose' if transpose else 'no_transpose'}_{A.wsuffix(weights)}_"
             f"{'bool' if sd == A.BE_SPIKE_BOOL else 'float'}")
-    f = fn(name, c_int, _MM_ARGS)
-    check(f(A.ptr(weights), A.ptr(spikes_bm), A.ptr(out), rows_w, cols_w, nb, A.ptr(ws), ws.numel(), A.stream_ptr()), name)
+    call(name, A.ptr(weights), A.ptr(spikes_bm), A.ptr(out), rows_w, cols_w, nb, A.ptr(ws), ws.numel(), A.stream_ptr())
     return out
 
 

@@ -187,14 +187,11 @@ class SpikeExchange:
             return local_words
         assert local_spikes.numel() == n_local
         if local_spikes.is_cuda:
-            import ctypes
             from . import _array as A
-            from ._lib import fn, check
+            from ._lib import call
             sp, sd = A.spikes_to_device(local_spikes)
             if n_local:
-                f = fn('be_pack_spikes', ctypes.c_int,
-                       [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p])
-                check(f(A.ptr(sp), sd, n_local, A.ptr(local_words), A.stream_ptr()), 'be_pack_spikes')
+                call('be_pack_spikes', A.ptr(sp), sd, n_local, A.ptr(local_words), A.stream_ptr())
         else:           # CPU tensors (gloo tests): same words through tensor arithmetic
             by = _pack_bits(_active(local_spikes))
             buf = local_words.view(torch.uint8)
@@ -300,7 +297,7 @@ class NativeSpikeExchange:
 
     def __init__(self, n_pre: int, world: int, rank: int, unique_id: bytes, device=None):
         import ctypes
-        from ._lib import fn, check
+        from ._lib import call, fn
         self._ct = ctypes
         self.n_pre, self.world, self.rank = int(n_pre), int(world), int(rank)
         # GPU only (unlike SpikeExchange, which also serves gloo): the receive buffer is handed to ncclAllGather as it is
@@ -310,18 +307,14 @@ class NativeSpikeExchange:
         self.device = device
         self._h = ctypes.c_void_p(0)
         buf = ctypes.create_string_buffer(bytes(unique_id), len(unique_id))
-        f = fn('be_exchange_init', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
-                                                  ctypes.POINTER(ctypes.c_void_p)])
-        check(f(buf, self.world, self.rank, self.n_pre, ctypes.byref(self._h)), 'be_exchange_init')
+        call('be_exchange_init', buf, self.world, self.rank, self.n_pre, ctypes.byref(self._h))
         lo, hi = ctypes.c_int64(0), ctypes.c_int64(0)
-        f = fn('be_exchange_slice', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
-                                                   ctypes.POINTER(ctypes.c_int64)])
-        check(f(self._h, self.rank, ctypes.byref(lo), ctypes.byref(hi)), 'be_exchange_slice')
+        call('be_exchange_slice', self._h, self.rank, ctypes.byref(lo), ctypes.byref(hi))
         try:
             self.lo, self.hi = int(lo.value), int(hi.value)
             if (self.lo, self.hi) != word_aligned_bounds(self.n_pre, self.world, self.rank):
                 raise RuntimeError(f"be_exchange_slice disagrees with word_aligned_bounds: {(self.lo, self.hi)}")
-            n_words = int(fn('be_exchange_full_words', ctypes.c_int64, [ctypes.c_void_p])(self._h))
+            n_words = int(fn('be_exchange_full_words')(self._h))
             self._full_words = torch.zeros(max(n_words, 1), dtype=torch.int32, device=device)
         except Exception:
             self.close()                  # the communicator must not outlive a failed constructor
@@ -330,21 +323,18 @@ class NativeSpikeExchange:
     @staticmethod
     def unique_id() -> bytes:
         import ctypes
-        from ._lib import fn, check
-        n = int(fn('be_exchange_unique_id_bytes', ctypes.c_int, [])())
-        buf = ctypes.create_string_buffer(n)
-        check(fn('be_exchange_get_unique_id', ctypes.c_int, [ctypes.c_void_p])(buf), 'be_exchange_get_unique_id')
+        from ._lib import call, fn
+        buf = ctypes.create_string_buffer(int(fn('be_exchange_unique_id_bytes')()))
+        call('be_exchange_get_unique_id', buf)
         return buf.raw
 
     def gather_events(self, local_spikes: torch.Tensor):
         """This rank's spikes ``[hi - lo]`` -> the full spike vector as a bit-packed event container."""
         from . import _array as A
         from ._event import BitPackedBinary
-        from ._lib import fn, check
+        from ._lib import call
         sp, sd = _local_operand(local_spikes, self.hi - self.lo)
-        ct = self._ct
-        f = fn('be_exchange_allgather_bits', ct.c_int, [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_void_p])
-        check(f(self._h, A.ptr(sp), sd, A.ptr(self._full_words), A.stream_ptr()), 'be_exchange_allgather_bits')
+        call('be_exchange_allgather_bits', self._h, A.ptr(sp), sd, A.ptr(self._full_words), A.stream_ptr())
         return BitPackedBinary.from_packed(self._full_words, self.n_pre)
 
     def gather(self, local_spikes: torch.Tensor) -> torch.Tensor:
@@ -358,14 +348,11 @@ class NativeSpikeExchange:
         another is consumed.  ``ids=True`` (``be_exchange_post_ids``): the gathered words are also compacted into the list of
         active pre neurons on the exchange's stream; :meth:`wait_ids` hands that list to a scatter (``BE_SPIKE_IDS``)."""
         from . import _array as A
-        from ._lib import fn, check
+        from ._lib import call
         slot = getattr(self, '_next', 0)
         self._next = slot ^ 1
         sp, sd = _local_operand(local_spikes, self.hi - self.lo)
-        ct = self._ct
-        name = 'be_exchange_post_ids' if ids else 'be_exchange_post'
-        f = fn(name, ct.c_int, [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_void_p])
-        check(f(self._h, A.ptr(sp), sd, slot, A.stream_ptr()), name)
+        call('be_exchange_post_ids' if ids else 'be_exchange_post', self._h, A.ptr(sp), sd, slot, A.stream_ptr())
         return slot, sp, bool(ids)           # (the spikes stay referenced until the ticket is consumed)
 
     def wait_ids(self, ticket):
@@ -373,7 +360,7 @@ class NativeSpikeExchange:
         struct (host memory holding two device pointers into the handle) is what a scatter entry point takes as its ``spikes``
         argument with ``BE_SPIKE_IDS``.  Valid until the slot is posted again."""
         from . import _array as A
-        from ._lib import fn, check
+        from ._lib import call
         ct = self._ct
         if not hasattr(self, '_ids_structs'):
             class _Ids(ct.Structure):
@@ -382,19 +369,16 @@ class NativeSpikeExchange:
         slot = ticket[0]
         st_ = self._ids_structs[slot]
         words = ct.c_void_p(0)
-        f = fn('be_exchange_wait_ids', ct.c_int, [ct.c_void_p, ct.c_int, ct.c_void_p, ct.POINTER(ct.c_void_p), ct.c_void_p])
-        check(f(self._h, slot, ct.byref(st_), ct.byref(words), A.stream_ptr()), 'be_exchange_wait_ids')
+        call('be_exchange_wait_ids', self._h, slot, ct.byref(st_), ct.byref(words), A.stream_ptr())
         return st_, words.value
 
     def wait_events(self, ticket):
         from . import _array as A
         from ._event import BitPackedBinary
-        from ._lib import fn, check
+        from ._lib import call
         slot = ticket[0]
-        ct = self._ct
-        out = ct.c_void_p(0)
-        f = fn('be_exchange_wait', ct.c_int, [ct.c_void_p, ct.c_int, ct.POINTER(ct.c_void_p), ct.c_void_p])
-        check(f(self._h, slot, ct.byref(out), A.stream_ptr()), 'be_exchange_wait')
+        out = self._ct.c_void_p(0)
+        call('be_exchange_wait', self._h, slot, self._ct.byref(out), A.stream_ptr())
         if not hasattr(self, '_views'):
             self._views = {}
         view = self._views.get(slot)
@@ -407,15 +391,13 @@ class NativeSpikeExchange:
         """Tell the exchange that the consumer has queued its last read of the ticket's buffer (``be_exchange_release``).
         Only needed when the products that consume the events run on another stream than the one ``post`` was called on."""
         from . import _array as A
-        from ._lib import fn, check
-        ct = self._ct
-        check(fn('be_exchange_release', ct.c_int, [ct.c_void_p, ct.c_int, ct.c_void_p])(self._h, ticket[0], A.stream_ptr()),
-              'be_exchange_release')
+        from ._lib import call
+        call('be_exchange_release', self._h, ticket[0], A.stream_ptr())
 
     def close(self) -> None:
         if self._h:
             from ._lib import fn
-            fn('be_exchange_destroy', self._ct.c_int, [self._ct.c_void_p])(self._h)
+            fn('be_exchange_destroy')(self._h)
             self._h = self._ct.c_void_p(0)
 
     def __del__(self):
@@ -437,7 +419,6 @@ class RankStep:
     the general path."""
 
     def __init__(self, exchange, shard):
-        import ctypes as ct
         from . import _array as A, _csr as C
         from ._lib import fn
         self.exchange, self.shard = exchange, shard
@@ -448,9 +429,8 @@ class RankStep:
         if (not isinstance(exchange, NativeSpikeExchange) or not isinstance(shard, C.CSR)
                 or not isinstance(ws, (C.ScatterPlan, C.BinnedScatter))):
             return
-        vp, i64, ci = ct.c_void_p, ct.c_int64, ct.c_int
         data = shard.data
-        self._gather = fn('be_exchange_allgather_bits', ci, [vp, vp, ci, vp, vp])
+        self._gather = fn('be_exchange_allgather_bits')
         self._words = exchange._full_words
         self._n_local = exchange.hi - exchange.lo
         self._ws_obj, self._data = ws, data
@@ -460,7 +440,7 @@ class RankStep:
         if isinstance(ws, C.ScatterPlan):
             parts = ws.default_parts()
             wsp = ws.workspace(parts, 1)
-            f = fn('be_binary_csrmm_t_plan', ci, [vp, ci, ci, vp, vp, vp, ci, vp, i64, i64, i64, ci, ci, ci, ci, ci, ci, vp, i64, vp])
+            f = fn('be_binary_csrmm_t_plan')
             head = (A.ptr(data), int(ws.homo), A.wcode(data), A.ptr(ws.blob), A.ptr(ws.seg))
             tail = (m, k, 1, ws.slice_shift, ws.slice_width, ws.layout, ws.block_hint, parts)
             self._keep = (wsp,)
@@ -474,7 +454,7 @@ class RankStep:
             indices, indptr = shard.indices, getattr(shard, 'indptr', None)
             row_len = -1 if indptr is not None else int(indices.numel() // max(m, 1))
             is64 = int(indptr is not None and indptr.dtype == torch.int64)
-            f = fn('be_binary_csrmv_t_binned', ci, [vp, ci, ci, vp, vp, ci, i64, vp, ci, vp, i64, i64, ci, i64, ci, vp, i64, vp])
+            f = fn('be_binary_csrmv_t_binned')
             head = (A.ptr(data), ws.step_kind, A.wcode(data), A.ptr(indices), A.ptr(indptr), is64, row_len)
             self._keep = (indices, indptr)
             self._fast = lambda out_ptr, words_ptr, st: f(*head, words_ptr, A.BE_SPIKE_BITS, out_ptr, m, k, ws.slice_shift,
@@ -532,7 +512,7 @@ class RankStep:
     def step_posted(self):
         """The step whose exchange was posted first: wait for its gathered words on this stream, then ``events @ shard``."""
         from . import _array as A
-        from ._lib import check, fn
+        from ._lib import call, check
         import ctypes as ct
         ticket = self._pending.pop(0)
         ex = self.exchange
@@ -545,8 +525,7 @@ class RankStep:
             check(self._fast_ids(A.ptr(out), ct.addressof(ids_struct), st), self._what)
             return out
         words = ct.c_void_p(0)
-        check(fn('be_exchange_wait', ct.c_int, [ct.c_void_p, ct.c_int, ct.POINTER(ct.c_void_p), ct.c_void_p])(
-            ex._h, ticket[0], ct.byref(words), st), 'be_exchange_wait')
+        call('be_exchange_wait', ex._h, ticket[0], ct.byref(words), st)
         out = torch.empty(self._out_shape, dtype=self._out_dtype, device=self._dev)
         check(self._fast(A.ptr(out), words.value, st), self._what)
         return out

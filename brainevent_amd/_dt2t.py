@@ -23,23 +23,19 @@ whatever the row lengths.  Deviations from the reference, both this project's ru
 No autograd: the reference defines forward-mode rules only ("the transpose rule is not yet implemented") and D-RTRL does not
 back-propagate through the trace, so tensors that require grad are taken by value, as the float twins take them.  Not here:
 ``jit{s,u,n}mv_dt2t`` (out of scope)."""
-import ctypes
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _array as A
-from ._lib import check, fn
+from ._lib import call
 from ._misc import _as_indptr, _as_int32_indices
 from ._op import OpKernel
 
 __all__ = ['csrmv_dt2t', 'csrmm_dt2t', 'cscmv_dt2t', 'cscmm_dt2t', 'fcnmv_dt2t', 'fcnmm_dt2t',
            'csrmv_dt2t_p', 'csrmm_dt2t_p', 'fcnmv_dt2t_p', 'fcnmm_dt2t_p',
            'csrmv_dt2t_p_call', 'csrmm_dt2t_p_call', 'fcnmv_dt2t_p_call', 'fcnmm_dt2t_p_call']
-
-c_i64, c_int, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
-_ARGS = [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_vp]
 
 
 # ------------------------------------------------------------------------------------------------ operands, host or device
@@ -81,9 +77,8 @@ def _check_out(out, shape, dtype_name: str) -> None:
 
 def _launch(w, homo, y, indices, indptr, row_len, out, n_rows, n_cols, n_batch, nnz, by_col) -> None:
     is64 = int(indptr is not None and indptr.dtype == torch.int64)
-    check(fn('be_dt2t', c_int, _ARGS)(A.ptr(w), int(homo), A.wcode(w), A.ptr(y), A.ptr(indices), A.ptr(indptr), is64,
-                                      int(row_len), A.ptr(out), int(n_rows), int(n_cols), int(n_batch), int(nnz), int(by_col),
-                                      A.stream_ptr()), 'be_dt2t')
+    call('be_dt2t', A.ptr(w), int(homo), A.wcode(w), A.ptr(y), A.ptr(indices), A.ptr(indptr), is64, int(row_len), A.ptr(out),
+         int(n_rows), int(n_cols), int(n_batch), int(nnz), int(by_col), A.stream_ptr())
 
 
 def _product(w, y, indices, indptr, row_len, *, n_rows, n_cols, n_batch, nnz, by_col, result_shape, out):

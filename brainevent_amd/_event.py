@@ -158,9 +158,8 @@ def _is_float_payload(v) -> bool:
 def bitpack(arr, axis: int):
     """Pack a binary array into uint32 words along ``axis``: bit ``b`` of word ``w`` is element ``32 w + b``
     (reference ``brainevent/_event/bitpack_binary.py:32-75``; non-zero values are ``True``).  numpy in -> numpy ``uint32`` out; device tensor in -> ``int32`` tensor holding the words."""
-    import ctypes
     from . import _array as A
-    from ._lib import fn, check
+    from ._lib import call
     as_np = not isinstance(arr, torch.Tensor)
     t = A.to_device(arr)
     axis = axis % t.ndim
@@ -173,9 +172,7 @@ def bitpack(arr, axis: int):
     if rows and n:
         if rows <= 65535:
             sp, sd = _nonzero_mask(moved.reshape(rows, n)).contiguous(), A.BE_SPIKE_BOOL
-            f = fn('be_pack_spikes_batched', ctypes.c_int,
-                   [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p])
-            check(f(A.ptr(sp.contiguous()), sd, n, rows, A.ptr(words), A.stream_ptr()), 'be_pack_spikes_batched')
+            call('be_pack_spikes_batched', A.ptr(sp.contiguous()), sd, n, rows, A.ptr(words), A.stream_ptr())
         else:   # very many short rows (e.g. packing the batch axis of an (n, batch) matrix): plain tensor arithmetic
             m = _nonzero_mask(moved.reshape(rows, n))
             m = torch.nn.functional.pad(m, (0, nw * 32 - n)).view(rows, nw, 32).to(torch.int64)
@@ -213,13 +210,11 @@ class BitPackedBinary(EventRepresentation):
     @property
     def value(self):
         if self._value is None:           # packed-only vector: unpack once
-            import ctypes
             from . import _array as A
-            from ._lib import fn, check
+            from ._lib import call
             n = self._original_shape[0]
             out = torch.empty(n, dtype=torch.bool, device=self._packed[0].device)
-            f = fn('be_unpack_spikes', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p])
-            check(f(A.ptr(self._packed[0]), n, A.ptr(out), A.stream_ptr()), 'be_unpack_spikes')
+            call('be_unpack_spikes', A.ptr(self._packed[0]), n, A.ptr(out), A.stream_ptr())
             self._value = out
         return self._value
 
@@ -300,17 +295,14 @@ class CompactBinary:
     @staticmethod
     def _compact(mask_source):
         """device spikes [n] -> (active_ids int32 [n], n_active int32 [1]) through ``be_compact_spikes``."""
-        import ctypes
         from . import _array as A
-        from ._lib import fn, check
+        from ._lib import call
         sp, sd = _nonzero_mask(A.to_device(mask_source)).contiguous(), A.BE_SPIKE_BOOL
         n = int(sp.shape[0])
         ids = torch.zeros(n, dtype=torch.int32, device=sp.device)
         cnt = torch.zeros(1, dtype=torch.int32, device=sp.device)
         if n:
-            f = fn('be_compact_spikes', ctypes.c_int,
-                   [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
-            check(f(A.ptr(sp), sd, n, A.ptr(ids), A.ptr(cnt), A.stream_ptr()), 'be_compact_spikes')
+            call('be_compact_spikes', A.ptr(sp), sd, n, A.ptr(ids), A.ptr(cnt), A.stream_ptr())
         return ids, cnt
 
     @classmethod

@@ -11,23 +11,19 @@ Reference surface (read as text): ``brainevent/_csr/float.py:49-150`` (``csrmv``
 Output dtype = weights dtype; the operand is cast to it.  Not on the event-driven hot path (no autodiff, no units here): these
 exist so that a container accepts a dense operand at all, through hand-written kernels like everything else — gather rows in
 aligned groups of four entries, scatter through float atomics (``csrc/be_float.hip``)."""
-import ctypes
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _array as A
-from ._lib import check, fn
+from ._lib import call, fn
 from ._csr import _check_csr_structure_dtypes
 from ._misc import _as_indptr, _as_int32_indices
 from ._op import OpKernel
 
 __all__ = ['csrmv', 'csrmm', 'csrmv_p', 'csrmm_p', 'csrmv_p_call', 'csrmm_p_call', 'fcnmv', 'fcnmm', 'fcnmv_p', 'fcnmm_p',
            'fcnmv_p_call', 'fcnmm_p_call']
-
-c_i64, c_int, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
-_ARGS = [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp]
 
 
 def _aligned16(t: torch.Tensor) -> torch.Tensor:
@@ -51,12 +47,10 @@ def _float_csr(weights, indices, indptr, row_len, operand, *, m: int, k: int, tr
         return out
     if idx.numel() == 0:                 # no stored entry: every output is an empty sum
         return out.zero_()
-    f_ws = fn('be_csrmm_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int, c_int])
-    ws = A.workspace(f_ws(m, k, n, int(transpose), A.wcode(w)))
+    ws = A.workspace(fn('be_csrmm_workspace_bytes')(m, k, n, int(transpose), A.wcode(w)))
     is64 = int(indptr is not None and indptr.dtype == torch.int64)
-    check(fn('be_csrmm', c_int, _ARGS)(A.ptr(flat), int(homo), A.wcode(w), A.ptr(idx), A.ptr(indptr), is64, int(row_len), A.ptr(x),
-                                       A.ptr(out), m, k, n, int(idx.numel()), int(transpose), A.ptr(ws), ws.numel(),
-                                       A.stream_ptr()), 'be_csrmm')
+    call('be_csrmm', A.ptr(flat), int(homo), A.wcode(w), A.ptr(idx), A.ptr(indptr), is64, int(row_len), A.ptr(x), A.ptr(out), m, k,
+         n, int(idx.numel()), int(transpose), A.ptr(ws), ws.numel(), A.stream_ptr())
     return out
 
 

@@ -14,7 +14,6 @@ input rows); ``transpose`` only fixes which side of ``shape`` is the output.  ``
 The matrix drawn by the ``mv`` ops (lane stride 32) differs from the one drawn by the ``mm`` ops (stride 4),
 exactly as in the reference (``brainevent/_misc.py:32-38``).
 """
-import ctypes
 import math
 from typing import Dict, Optional
 
@@ -24,7 +23,7 @@ import torch
 from . import _array as A
 from ._data import DataRepresentation
 from ._event import BinaryArray, is_event, event_operand
-from ._lib import check, fn
+from ._lib import check, fn      # (not `call`: every lookup goes through this module's own `fn`, where the scale tests log it)
 from ._op import OpKernel
 
 __all__ = [
@@ -36,9 +35,6 @@ __all__ = [
     'jit_edge_weights',
 ]
 
-c_i64, c_int, c_vp, c_dbl, c_u32 = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_uint32
-_MV_ARGS = [c_dbl, c_dbl, c_i64, c_u32, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp]
-_MM_ARGS = [c_dbl, c_dbl, c_i64, c_u32, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]
 _FAMILY = {'s': 0, 'u': 1, 'n': 2}
 
 
@@ -127,8 +123,7 @@ def _armed_scatter_workspace(nbytes: int, layout: tuple = ('mv',)) -> torch.Tens
         while len(_armed) >= _ARMED_MAX:
             _drop_armed(next(iter(_armed)))
         ws = A.workspace(nbytes)
-        check(fn('be_jit_scatter_workspace_arm', c_int, [c_vp, c_i64, c_vp])(A.ptr(ws), ws.numel(), A.stream_ptr()),
-              'be_jit_scatter_workspace_arm')
+        check(fn('be_jit_scatter_workspace_arm')(A.ptr(ws), ws.numel(), A.stream_ptr()), 'be_jit_scatter_workspace_arm')
     _armed[key] = ws                      # (re-inserted: most recently used last)
     return ws
 
@@ -136,7 +131,7 @@ def _armed_scatter_workspace(nbytes: int, layout: tuple = ('mv',)) -> torch.Tens
 def _drop_armed(key) -> None:
     ws = _armed.pop(key, None)
     if ws is not None:
-        fn('be_jit_scatter_workspace_disarm', c_int, [c_vp])(A.ptr(ws))
+        fn('be_jit_scatter_workspace_disarm')(A.ptr(ws))
 
 
 def _drop_armed_tensor(ws: torch.Tensor) -> None:
@@ -154,11 +149,11 @@ def _jitmv_hip(family, a, b, clen, vector, seed, *, shape, transpose, corder, ou
         return out
     w0, w1, wmax = _jit_params(family, a, b)
     gather = 1 if corder else 0
-    f_ws = fn('be_binary_jitmv_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int])
+    f_ws = fn('be_binary_jitmv_workspace_bytes')
     nbytes = f_ws(int(shape[1]), in_len, out_len, gather)
     ws = A.workspace(nbytes) if gather else _armed_scatter_workspace(nbytes)
     name = f"be_binary_jit{family}mv_{'notrans' if corder else 'trans'}_{A.wsuffix(out)}"
-    f = fn(name, c_int, _MV_ARGS)
+    f = fn(name)
     try:
         check(f(w0, w1, int(clen), seed & 0xFFFFFFFF, A.ptr(spikes), sd, A.ptr(out), int(shape[1]), in_len, out_len,
                 _fixed_scale_exp(wmax, in_len), A.ptr(ws), ws.numel(), A.stream_ptr()), name)
@@ -177,11 +172,11 @@ def _jitmm_hip(family, a, b, clen, B, seed, *, shape, transpose, corder, out_dty
     if out_len == 0 or n == 0:
         return out_bm.T
     w0, w1, _ = _jit_params(family, a, b)
-    f_ws = fn('be_binary_jitmm_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_i64, c_int])
+    f_ws = fn('be_binary_jitmm_workspace_bytes')
     nbytes = f_ws(int(shape[1]), in_len, out_len, n, 1 if corder else 0)
     ws = A.workspace(nbytes) if corder else _armed_scatter_workspace(nbytes, ('mm', n))
     name = f"be_binary_jit{family}mm_{'notrans' if corder else 'trans'}_{A.wsuffix(out_bm)}"
-    f = fn(name, c_int, _MM_ARGS)
+    f = fn(name)
     try:
         check(f(w0, w1, int(clen), seed & 0xFFFFFFFF, A.ptr(spikes_bm), sd, A.ptr(out_bm), int(shape[1]), in_len,
                 out_len, n, A.ptr(ws), ws.numel(), A.stream_ptr()), name)
@@ -386,18 +381,15 @@ def _jit_float_hip(family, a, b, clen, X, seed, *, shape, transpose, corder, out
             x_bm = x.reshape(1, -1) if vec else x.T.contiguous()
             out_bm = torch.empty((n, out_len), dtype=out_dtype, device=A.device())
             stride = 4 if mm else 32
-            ws = A.workspace(fn('be_jitmm_float_scatter_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int])(int(shape[1]), out_len,
-                                                                                                             n, stride))
-            f = fn('be_jitmm_float_scatter', c_int, [c_int, c_dbl, c_dbl, c_int, c_i64, c_u32, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
-                                                     c_int, c_int, c_vp, c_i64, c_vp])
+            ws = A.workspace(fn('be_jitmm_float_scatter_workspace_bytes')(int(shape[1]), out_len, n, stride))
+            f = fn('be_jitmm_float_scatter')
             check(f(_FAMILY[family], w0, w1, A.wcode(out), int(clen), seed & 0xFFFFFFFF, A.ptr(x_bm), A.ptr(out_bm), int(shape[1]),
                     in_len, out_len, n, stride, e_fix, A.ptr(ws), ws.numel(), A.stream_ptr()),
                   'be_jitmm_float_scatter')
             return out_bm[0] if vec else out_bm.T
-    f_ws = fn('be_jitmm_float_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_i64, c_int, c_int])
+    f_ws = fn('be_jitmm_float_workspace_bytes')
     ws = A.workspace(f_ws(int(shape[1]), in_len, out_len, n, gather, A.wcode(out)))
-    f = fn('be_jitmm_float', c_int, [c_int, c_dbl, c_dbl, c_int, c_i64, c_u32, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_int,
-                                     c_vp, c_i64, c_vp])
+    f = fn('be_jitmm_float')
     check(f(_FAMILY[family], w0, w1, A.wcode(out), int(clen), seed & 0xFFFFFFFF, A.ptr(x), A.ptr(out), int(shape[1]), in_len,
             out_len, n, 4 if mm else 32, gather, A.ptr(ws), ws.numel(), A.stream_ptr()), 'be_jitmm_float')
     return out
@@ -521,7 +513,7 @@ def jit_edge_weights(family: str, a, b, seed, rows, cols):
     w0, w1, _ = _jit_params(family, a, b)
     mode = _FAMILY[family]
     out = torch.empty(r.numel(), dtype=torch.float32, device=r.device)
-    f = fn('be_jit_edge_weights', c_int, [c_int, c_dbl, c_dbl, c_u32, c_vp, c_vp, c_i64, c_vp, c_vp])
+    f = fn('be_jit_edge_weights')
     check(f(mode, w0, w1, _initialize_seed(seed) & 0xFFFFFFFF, A.ptr(r), A.ptr(c), r.numel(), A.ptr(out), A.stream_ptr()),
           'be_jit_edge_weights')
     return A.to_result(out, as_np)
@@ -729,7 +721,7 @@ class JITCMatrix(DataRepresentation):
         dev = A.device()
         clen = _initialize_conn_length(self.prob)
         counts = torch.empty(max(n_rows, 1), dtype=torch.int32, device=dev)
-        f_cnt = fn('be_jitc_csr_count', c_int, [c_i64, c_u32, c_i64, c_i64, c_i64, c_int, c_vp, c_vp])
+        f_cnt = fn('be_jitc_csr_count')
         check(f_cnt(clen, self.seed & 0xFFFFFFFF, int(gshape[1]), n_rows, walk, stride, A.ptr(counts), A.stream_ptr()),
               'be_jitc_csr_count')
         return counts, (gshape, n_rows, walk, stride, clen, corder)
@@ -758,8 +750,7 @@ class JITCMatrix(DataRepresentation):
         indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
         mode = _FAMILY[self._family]
         weights = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev) if mode else None
-        f_fill = fn('be_jitc_csr_fill', c_int, [c_int, c_dbl, c_dbl, c_i64, c_u32, c_i64, c_i64, c_i64, c_int, c_vp, c_vp,
-                                               c_vp, c_vp, c_vp])
+        f_fill = fn('be_jitc_csr_fill')
         check(f_fill(mode, w0, w1, clen, self.seed & 0xFFFFFFFF, int(gshape[1]), n_rows, walk, stride, A.ptr(indptr),
                      A.ptr(counts), A.ptr(indices), A.ptr(weights), A.stream_ptr()), 'be_jitc_csr_fill')
         data = weights[:nnz] if mode else torch.full((1,), float(w0), dtype=torch.float32, device=dev)
@@ -945,11 +936,9 @@ class JITCScatterShard:
         a = m._weights[0]
         b = m._weights[1] if m._family != 's' else 0.0
         w0, w1, wmax = _jit_params(m._family, a, b)
-        f_ws = fn('be_binary_jitmv_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int])
+        f_ws = fn('be_binary_jitmv_workspace_bytes')
         ws = _armed_scatter_workspace(f_ws(self.shape1, in_len, out_len, 0))
-        f = fn('be_binary_jitmv_sharded', c_int,
-               [c_int, c_dbl, c_dbl, c_int, c_i64, c_u32, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_vp,
-                c_i64, c_vp])
+        f = fn('be_binary_jitmv_sharded')
         check(f(_FAMILY[m._family], w0, w1, A.wcode(out), _initialize_conn_length(m.prob), m.seed & 0xFFFFFFFF, A.ptr(spikes),
                 sd, A.ptr(out), self.shape1, in_len, out_len, self.class_begin, self.class_end - self.class_begin,
                 _fixed_scale_exp(wmax, in_len), A.ptr(ws), ws.numel(), A.stream_ptr()), 'be_binary_jitmv_sharded')
@@ -999,10 +988,9 @@ class JITCGatherShard:
         a = m._weights[0]
         b = m._weights[1] if m._family != 's' else 0.0
         w0, w1, _ = _jit_params(m._family, a, b)
-        f_ws = fn('be_binary_jitmv_workspace_bytes', c_i64, [c_i64, c_i64, c_i64, c_int])
+        f_ws = fn('be_binary_jitmv_workspace_bytes')
         ws = A.workspace(f_ws(self.shape1, self.in_len, n_rows, 1))
-        f = fn('be_binary_jitmv_rows', c_int,
-               [c_int, c_dbl, c_dbl, c_int, c_i64, c_u32, c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp])
+        f = fn('be_binary_jitmv_rows')
         check(f(_FAMILY[m._family], w0, w1, A.wcode(out), _initialize_conn_length(m.prob), m.seed & 0xFFFFFFFF, A.ptr(spikes), sd,
                 A.ptr(out), self.shape1, self.in_len, self.lo, n_rows, A.ptr(ws), ws.numel(), A.stream_ptr()), 'be_binary_jitmv_rows')
         return m._out(out, v)

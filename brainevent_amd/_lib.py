@@ -103,16 +103,21 @@ def lib() -> ctypes.CDLL:
                     handle = ctypes.CDLL(str(path))
                 except OSError as e:
                     raise KernelLoadError(f"cannot load {path}: {e}") from e
-                handle.be_last_error.restype = ctypes.c_char_p
-                handle.be_build_arch.restype = ctypes.c_char_p
+                from ._abi import PROTOTYPES        # (here, not at the top: the build hook loads this module by path, alone)
+                handle.be_last_error.restype = PROTOTYPES['be_last_error'][0]
+                handle.be_build_arch.restype = PROTOTYPES['be_build_arch'][0]
                 _lib = handle
     return _lib
 
 
 def check(rc: int, what: str = '') -> None:
     if rc < 0:
-        msg = lib().be_last_error()
-        raise KernelExecutionError(f"{what or 'brainevent_amd'}: status {rc}: {msg.decode() if msg else '?'}")
+        raise KernelExecutionError(f"{what or 'brainevent_amd'}: status {rc}: {last_error() or '?'}")
+
+
+def last_error() -> str:
+    """The library's thread-local message of the last failing call."""
+    return (fn('be_last_error')() or b'').decode()
 
 
 _device_ok: Optional[bool] = None
@@ -133,19 +138,48 @@ def require_device() -> None:
 _fn_cache = {}
 
 
-def fn(name: str, restype=ctypes.c_int, argtypes=None):
-    """Symbol ``name`` with its prototype set (cached: the hot path calls this every step)."""
+def fn(name: str, restype=None, argtypes=None):
+    """Symbol ``name`` with the prototype that ``_abi.PROTOTYPES`` declares for it (cached: the hot path calls this every step).
+
+    ``restype`` / ``argtypes`` are the older calling form, kept for scripts that state a prototype themselves: what is passed
+    is never installed, only compared with the table — every time, pointer types counting as equal — and a difference raises
+    ``TypeError``."""
     f = _fn_cache.get(name)
     if f is None:
+        from ._abi import PROTOTYPES
+        if name not in PROTOTYPES:
+            raise KernelLoadError(f"{name} is not declared in brainevent_amd/_abi.py (the table of include/brainevent_amd.h)")
         try:
             f = getattr(lib(), name)
         except AttributeError as e:
             raise KernelLoadError(f"{lib_path()} does not export {name}") from e
-        f.restype = restype
-        if argtypes is not None:
-            f.argtypes = argtypes
+        f.restype, f.argtypes = PROTOTYPES[name]
         _fn_cache[name] = f
+    if restype is not None or argtypes is not None:
+        _compare(name, f, restype, argtypes)
     return f
+
+
+def _is_pointer(t) -> bool:
+    return t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def _compare(name: str, f, restype, argtypes) -> None:
+    if restype is not None and restype is not f.restype:
+        raise TypeError(f"{name}: return type {restype.__name__} given, {f.restype.__name__} declared")
+    if argtypes is not None:
+        if len(argtypes) != len(f.argtypes):
+            raise TypeError(f"{name}: {len(argtypes)} arguments given, {len(f.argtypes)} declared")
+        for i, (given, want) in enumerate(zip(argtypes, f.argtypes)):
+            if given is not want and not (_is_pointer(given) and _is_pointer(want)):
+                raise TypeError(f"{name}: argument {i} given as {given.__name__}, declared {want.__name__}")
+
+
+def call(name: str, *args) -> None:
+    """``check(fn(name)(*args), name)`` for the entry points that return a status: ``KernelExecutionError`` on a negative one."""
+    rc = (_fn_cache.get(name) or fn(name))(*args)
+    if rc < 0:
+        check(rc, name)
 
 
 if __name__ == '__main__':

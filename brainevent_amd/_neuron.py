@@ -3,13 +3,12 @@ conductance-based LIF neurons with exponential synapses (``be_lif_coba_step``), 
 scatters of a time step.  The reference example composes the same dynamics from brainstate modules
 (``examples/COBA_2005.py:35-87``); as separate elementwise launches they are ~20 launches per step — all a 4000-neuron
 network's step consists of."""
-import ctypes
 import math
 
 import torch
 
 from . import _array as A
-from ._lib import check, fn
+from ._lib import call
 
 __all__ = ['lif_coba_step', 'lif_cuba_step']
 
@@ -59,13 +58,9 @@ def lif_coba_step(v: torch.Tensor, g_exc: torch.Tensor, g_inh: torch.Tensor, ref
 
 def _scaled_step(current_based, v, g_exc, g_inh, refractory, in_exc, in_inh, s_exc, s_inh, spikes, spike_bits, spike_count, n, dt,
                  tau_m, v_rest, v_th, v_reset, t_ref, e_exc, e_inh, tau_exc, tau_inh, i_ext, syn_scale) -> None:
-    c_d, c_vp = ctypes.c_double, ctypes.c_void_p
-    f = fn('be_lif_step_scaled_packed', ctypes.c_int, [ctypes.c_int] + [c_vp] * 6 + [c_d, c_d] + [c_vp] * 3 + [ctypes.c_int64]
-           + [c_d] * 12 + [c_vp])
-    check(f(int(current_based), A.ptr(v), A.ptr(g_exc), A.ptr(g_inh), A.ptr(refractory), A.ptr(in_exc), A.ptr(in_inh),
-            float(s_exc), float(s_inh), A.ptr(spikes), A.ptr(spike_bits), A.ptr(spike_count), n, dt, tau_m, v_rest, v_th, v_reset,
-            t_ref, e_exc, e_inh, math.exp(-dt / tau_exc), math.exp(-dt / tau_inh), i_ext, syn_scale, A.stream_ptr()),
-          'be_lif_step_scaled_packed')
+    call('be_lif_step_scaled_packed', int(current_based), A.ptr(v), A.ptr(g_exc), A.ptr(g_inh), A.ptr(refractory), A.ptr(in_exc),
+         A.ptr(in_inh), float(s_exc), float(s_inh), A.ptr(spikes), A.ptr(spike_bits), A.ptr(spike_count), n, dt, tau_m, v_rest, v_th,
+         v_reset, t_ref, e_exc, e_inh, math.exp(-dt / tau_exc), math.exp(-dt / tau_inh), i_ext, syn_scale, A.stream_ptr())
 
 
 def lif_cuba_step(v: torch.Tensor, g_exc: torch.Tensor, g_inh: torch.Tensor, refractory: torch.Tensor,

@@ -19,7 +19,6 @@ Captured graphs (``capture_step``): the calls never synchronise the host, but a 
 (certified or not).  A step captured on the certified path assumes that nothing else writes ``data`` out of range between
 replays — the same contract as :meth:`CSR.refresh_weights`.
 """
-import ctypes
 import math
 import numbers
 from typing import Optional
@@ -29,13 +28,12 @@ import torch
 
 from . import _array as A
 from ._event import is_event, event_operand
-from ._lib import check, fn
+from ._lib import check, fn      # (not `call`: every lookup goes through this module's own `fn`, which the validation tests bar)
 
 __all__ = ['update_csr_on_binary_pre', 'update_csr_on_binary_post', 'update_csc_on_binary_pre', 'update_csc_on_binary_post',
            'update_dense_on_binary_pre', 'update_dense_on_binary_post', 'update_fixed_post_conn_on_binary_pre',
            'update_fixed_pre_conn_on_binary_post']
 
-c_i64, c_int, c_vp, c_dbl = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_double
 
 _HOMO_MSG = ("Plasticity updates require per-synapse (heterogeneous) weights, but received "
              "a homogeneous (size-1) weight. Materialize per-synapse weights first "
@@ -126,13 +124,8 @@ def _clip_args(w: torch.Tensor, lo, hi):
         (0.0 if hi is None else _rounded(hi, w.dtype))
 
 
-_ROWS_ARGS = [c_vp, c_int, c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_vp, c_int, c_i64, c_vp, c_int, c_dbl, c_int, c_dbl,
-              c_vp, c_i64, c_vp]
-_DENSE_ARGS = [c_int, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_vp, c_int, c_dbl, c_int, c_dbl, c_vp, c_i64, c_vp]
-
-
 def _workspace(n: int) -> torch.Tensor:
-    return A.workspace(fn('be_plasticity_workspace_bytes', c_i64, [c_i64])(int(n)))
+    return A.workspace(fn('be_plasticity_workspace_bytes')(int(n)))
 
 
 def _run_rows(w: torch.Tensor, col, indptr, row_len: int, perm, spikes, n_rows: int, trace, clip=(None, None)) -> None:
@@ -140,7 +133,7 @@ def _run_rows(w: torch.Tensor, col, indptr, row_len: int, perm, spikes, n_rows: 
     sp, sd = _spikes(spikes)
     tr = A.to_device(trace).to(w.dtype).contiguous()
     ws = _workspace(n_rows)
-    f = fn('be_plasticity_rows', c_int, _ROWS_ARGS)
+    f = fn('be_plasticity_rows')
     lo_on, lo, hi_on, hi = _clip_args(w, *clip)
     check(f(A.ptr(w), A.wcode(w), A.ptr(col), A.ptr(indptr), int(indptr is not None and indptr.dtype == torch.int64),
             int(row_len), int(col.numel()), A.ptr(perm), int(perm is not None and perm.dtype == torch.int64), A.ptr(sp), sd,
@@ -152,7 +145,7 @@ def _run_dense(w: torch.Tensor, pre: bool, spikes, trace, clip=(None, None)) -> 
     tr = A.to_device(trace).to(w.dtype).contiguous()
     n_rows, n_cols = int(w.shape[0]), int(w.shape[1])
     ws = _workspace(n_rows if pre else n_cols)
-    f = fn('be_plasticity_dense', c_int, _DENSE_ARGS)
+    f = fn('be_plasticity_dense')
     lo_on, lo, hi_on, hi = _clip_args(w, *clip)
     check(f(int(pre), A.ptr(w), A.wcode(w), n_rows, n_cols, A.ptr(sp), sd, A.ptr(tr), lo_on, lo, hi_on, hi, A.ptr(ws),
             ws.numel(), A.stream_ptr()), 'be_plasticity_dense')
@@ -524,10 +517,6 @@ def _plastic_ready(M, lo, hi):
     return None
 
 
-_PLAN_GEOM = [c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp]        # m, k, slice_shift, slice_width, layout, seg, blob
-_ROWS_HEAD = [c_vp, c_int, c_vp, c_vp, c_int, c_i64]                 # weights, wdtype, indices, indptr, is64, row_len
-
-
 def _geom(plan):
     return plan.m, plan.k, plan.slice_shift, plan.slice_width, plan.layout, A.ptr(plan.seg), A.ptr(plan.blob)
 
@@ -538,7 +527,7 @@ def _rows_head(w, rows):
 
 
 def _refresh_workspace(n: int) -> torch.Tensor:
-    return A.workspace(fn('be_scatter_plan_refresh_workspace_bytes', c_i64, [c_i64])(int(n)))
+    return A.workspace(fn('be_scatter_plan_refresh_workspace_bytes')(int(n)))
 
 
 def _plan_slots(plan, st, w, rows) -> bool:
@@ -553,7 +542,7 @@ def _plan_slots(plan, st, w, rows) -> bool:
                       "the container is disarmed and refreshes in full.", stacklevel=4)
         return False
     plan.slot = torch.empty(int(rows.indices.numel()), dtype=torch.int16, device=plan.blob.device)
-    f = fn('be_scatter_plan_slots', c_int, _ROWS_HEAD + _PLAN_GEOM + [c_vp, c_vp, c_vp])
+    f = fn('be_scatter_plan_slots')
     check(f(*_rows_head(w, rows), *_geom(plan), A.ptr(getattr(plan, 'order', None)), A.ptr(plan.slot), A.stream_ptr()),
           'be_scatter_plan_slots')
     return True
@@ -562,7 +551,7 @@ def _plan_slots(plan, st, w, rows) -> bool:
 def _plan_refresh_rows(plan, w, rows, sp, sd) -> None:
     """``be_scatter_plan_refresh_rows``: the blocks of the active stored rows rewritten from ``w``."""
     ws = _refresh_workspace(plan.m)
-    f = fn('be_scatter_plan_refresh_rows', c_int, _ROWS_HEAD + _PLAN_GEOM + [c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp])
+    f = fn('be_scatter_plan_refresh_rows')
     # (d8 positions follow from the structure alone: only a u16 refresh, which draws them anew, has slots to rewrite)
     slot = plan.slot if plan.layout == plan.LAYOUT_U16 else None
     check(f(*_rows_head(w, rows), *_geom(plan), A.ptr(getattr(plan, 'order', None)), A.ptr(slot), A.ptr(sp), sd,
@@ -573,8 +562,7 @@ def _plan_patch_entries(plan, w, index, sp, sd) -> None:
     """``be_scatter_plan_patch_entries``: the entries on the active secondary ids stored into their blocks."""
     t_ptr, t_rows, perm = index
     ws = _refresh_workspace(plan.k)
-    f = fn('be_scatter_plan_patch_entries', c_int,
-           [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_i64, c_vp] + _PLAN_GEOM + [c_vp, c_int, c_vp, c_i64, c_vp])
+    f = fn('be_scatter_plan_patch_entries')
     check(f(A.ptr(w), A.wcode(w), A.ptr(t_ptr), int(t_ptr.dtype == torch.int64), A.ptr(t_rows), A.ptr(perm),
             int(perm.dtype == torch.int64), int(t_rows.numel()), A.ptr(plan.slot), *_geom(plan), A.ptr(sp), sd, A.ptr(ws),
             ws.numel(), A.stream_ptr()), 'be_scatter_plan_patch_entries')

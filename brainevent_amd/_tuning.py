@@ -201,9 +201,8 @@ def push_to_library(tuning: Optional[ScatterTuning] = None) -> None:
     key = (t.binned_task_groups, t.binned_min_tasks)
     if _pushed[0] == key:
         return
-    import ctypes
-    from ._lib import fn, check
-    check(fn('be_binned_set_tuning', ctypes.c_int, [ctypes.c_int, ctypes.c_int])(*key), 'be_binned_set_tuning')
+    from ._lib import call
+    call('be_binned_set_tuning', *key)
     _pushed[0] = key
 
 

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import brainevent_amd as be
-from brainevent_amd import _dt2t, _lib
+from brainevent_amd import _abi, _dt2t, _lib
 from brainevent_amd._error import KernelNotAvailableError
 from test_dt2t_gpu import CONSTS
 
@@ -51,7 +51,7 @@ def test_header_declares_the_entry_point():
     """(tests/test_host_cpu.py::test_library_exports_every_declared_symbol then holds the library to it)"""
     m = re.search(r'\bint\s+be_dt2t\s*\(([^;]*?)\)\s*;', HEADER.read_text(), re.S)
     assert m, "be_dt2t is not declared"
-    assert len(m.group(1).split(',')) == len(_dt2t._ARGS) == 15
+    assert len(m.group(1).split(',')) == len(_abi.PROTOTYPES['be_dt2t'][1]) == 15
     from test_host_cpu import declared_symbols
     assert 'be_dt2t' in declared_symbols()
 

@@ -28,7 +28,8 @@ spk = [torch.rand(n, device=dev, generator=g) < 0.01 for _ in range(4)]
 for i in range(5):
     be.BinaryArray(spk[i % 4]) @ conn
 torch.cuda.synchronize()
-f = _lib.fn('be_debug_bin_prof', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int])
+f = _lib.lib().be_debug_bin_prof          # (exported by this profiling build only, not declared in the header: outside _lib.fn's table)
+f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]
 f(None, 1)
 steps = 20
 for i in range(steps):

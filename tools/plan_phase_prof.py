@@ -24,7 +24,8 @@ out = torch.empty(n_post, dtype=torch.float32, device=dev)
 for i in range(5):
     C._plan_call(plan, w, spikes[i % 4], A.BE_SPIKE_BOOL, out)
 torch.cuda.synchronize()
-f = _lib.fn('be_debug_plan_prof', ctypes.c_int, [ctypes.c_void_p, ctypes.c_int])
+f = _lib.lib().be_debug_plan_prof          # (exported by this profiling build only, not declared in the header: outside _lib.fn's table)
+f.restype, f.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]
 f(None, 1)
 steps = 20
 for i in range(steps):
