@@ -26,6 +26,8 @@ from ._float import (csrmv, csrmm, csrmv_p, csrmm_p, csrmv_p_call, csrmm_p_call,
                      fcnmm_p_call)
 from ._dt2t import (csrmv_dt2t, csrmm_dt2t, cscmv_dt2t, cscmm_dt2t, fcnmv_dt2t, fcnmm_dt2t, csrmv_dt2t_p, csrmm_dt2t_p,
                     fcnmv_dt2t_p, fcnmm_dt2t_p, csrmv_dt2t_p_call, csrmm_dt2t_p_call, fcnmv_dt2t_p_call, fcnmm_dt2t_p_call)
+from ._slice import (csr_slice_rows, csr_slice_rows_p, csr_slice_rows_p_call, csr_slice_rows_grad, csr_slice_rows_grad_p,
+                     csr_slice_rows_grad_p_call)
 from ._graph import GraphedStep, capture_step
 from ._tuning import (ScatterTuning, DEFAULT_SCATTER_TUNING, get_scatter_tuning, save_scatter_tuning, apply_scatter_tuning,
                       tune_scatter_routes)

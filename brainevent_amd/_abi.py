@@ -48,7 +48,10 @@ _SIGNATURES = dict(
     be_csr_to_csc_scratch_bytes='l:l', be_csr_to_csc_count='i:pllpp', be_csr_to_csc_indptr='i:plpiLplp',
     be_csr_to_csc_fill_block='i:ppilllllppppipipp', be_gather_by_perm='i:pipilpp',
     be_csrmm_workspace_bytes='l:lllii', be_csrmm='i:piippilpplllliplp', be_csrmv='i:piippilppllliplp',
-    be_dt2t='i:piipppilpllllip', be_jitmm_float_workspace_bytes='l:llllii', be_jitmm_float='i:iddilupplllliiplp',
+    be_dt2t='i:piipppilpllllip',
+    be_slice_rows_tile_cols='i:i', be_slice_rows='i:piippilplplllp', be_slice_rows_grad_workspace_bytes='l:li',
+    be_slice_rows_grad='i:pippilpppllpilllplp', be_slice_rows_copy='i:ppipilppllllppp',
+    be_jitmm_float_workspace_bytes='l:llllii', be_jitmm_float='i:iddilupplllliiplp',
     be_jitmm_float_scatter_workspace_bytes='l:llli', be_jitmm_float_scatter='i:iddilupplllliiplp',
     be_jitmv_float='i:iddiluppllliplp',
     be_binary_csrmm_t_indexed='i:piippilpipiplllplp', be_binary_csrmm_nt_indexed='i:piippilpipiplllplp',

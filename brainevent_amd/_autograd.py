@@ -35,7 +35,7 @@ from . import _array as A
 from ._error import UnsupportedOperationError
 from ._lib import call, fn
 
-__all__ = ['RowsProduct', 'DenseProduct', 'needed']
+__all__ = ['RowsProduct', 'DenseProduct', 'SliceRows', 'needed']
 
 
 def _value(x):
@@ -238,6 +238,29 @@ def dense_product(run: Callable, weights, spikes_arg, operand, layout: str, *, t
     if weights.requires_grad:
         spec.mask, spec.nb = activity(operand, layout)
     return DenseProduct.apply(weights, s, spec)
+
+
+class SliceRows(torch.autograd.Function):
+    """``W[rows]`` (``_slice``: CSR, CSC, ``FixedNumPerPre`` / ``FixedNumPerPost`` and the functional ``csr_slice_rows``).  The
+    read is linear in the weights; its transpose is ``be_slice_rows_grad``: per stored entry of a selected row the sum of the
+    incoming gradient over the selections of that row, ascending, one rounding, no atomics.  ``run`` is the existing forward
+    path; ``grad(g)`` returns the gradient in ``data``'s shape (for the containers that store the transpose: moved back from
+    the mirror's order through its permutation).  Nothing is saved: the structure lives in the two closures."""
+
+    @staticmethod
+    def forward(ctx, data, run: Callable, grad: Callable):
+        ctx.grad = grad
+        return run()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return ctx.grad(g), None, None
+
+
+def slice_rows(data, run: Callable, grad: Callable):
+    """Run ``run()`` as a :class:`SliceRows` node whose backward is ``grad``."""
+    return SliceRows.apply(data, run, grad)
 
 
 def refuse_planned() -> None:

@@ -1055,6 +1055,11 @@ class PlannedMatrix:
 
     dt2t_transposed = dt2t
 
+    def __getitem__(self, index):
+        raise NotImplementedError("PlannedMatrix holds no raw structure: row slicing needs the stored rows.")
+
+    slice_rows = __getitem__
+
 
 class StoredRows(NamedTuple):
     """The rows a container stores, as every kernel takes them: ``indices`` (flat, or ``[m, row_len]`` for fixed-length rows),
@@ -1696,6 +1701,21 @@ class StoredRowsData(PlasticityMixin, DataRepresentation):
         """``w * y[post]`` for every stored entry: ``y_dim_arr`` has ``shape[1]`` elements and is indexed by the column."""
         from ._dt2t import container_dt2t
         return container_dt2t(self, y_dim_arr, w_dim_arr, False, out)
+
+    # -- row slicing (reference ``_csr/main.py:1458-1499``, ``:2361-2415``, ``_fcn/main.py:918-960``, ``:1182-1240``) ---------
+    def __getitem__(self, index):
+        """Rows of this matrix as a dense array, NumPy's rules: ``index`` is an ``int`` (-> ``(shape[1],)``), a list / tuple /
+        array / tensor of integers or a ``slice`` (-> ``(len(rows), shape[1])``) over ``shape[0]``, whatever the storage axis;
+        negative numbers count from the end, a number out of range raises ``IndexError``.  Differentiable in ``data``.  CSC
+        and ``FixedNumPerPost`` read through their transposed mirror (built and cached on first use)."""
+        from ._slice import container_getitem
+        return container_getitem(self, index)
+
+    def slice_rows(self, index):
+        """``W[rows, :]`` as a sparse matrix: CSR -> CSR, CSC -> CSC, ``FixedNumPerPre`` -> ``FixedNumPerPre``,
+        ``FixedNumPerPost`` -> CSR.  Same selectors as ``[]``; an ``int`` gives a ``1 x shape[1]`` matrix."""
+        from ._slice import container_slice_rows
+        return container_slice_rows(self, index)
 
 
 class CompressedSparseData(StoredRowsData):

@@ -65,3 +65,14 @@ class DataRepresentation:
     def dt2t_transposed(self, y_dim_arr, w_dim_arr):
         """Per-synapse ``w * y`` with ``y`` indexed by the column (post axis) of the matrix."""
         raise NotImplementedError(f"{type(self).__name__}.dt2t_transposed")
+
+    def __getitem__(self, index):
+        """Rows of the matrix as a dense array (``brainevent_amd._slice``); served by the four stored-rows containers and
+        ``Dense``."""
+        raise NotImplementedError(f"{type(self).__name__}.__getitem__: row slicing is served by CSR, CSC, FixedNumPerPre, "
+                                  f"FixedNumPerPost and Dense only.")
+
+    def slice_rows(self, index):
+        """``W[rows, :]`` as a sparse matrix (``brainevent_amd._slice``)."""
+        raise NotImplementedError(f"{type(self).__name__}.slice_rows: row slicing is served by CSR, CSC, FixedNumPerPre and "
+                                  f"FixedNumPerPost only.")

@@ -131,3 +131,83 @@ def check_fixed_conn_num_shape(weights, indices, vector, shape: Tuple[int, int],
         else:
             assert vector.shape[0] == n_post, f"vector length {vector.shape[0]} != shape[1] {n_post}"
     return (n_post if transpose else n_pre), n_pre, n_post
+
+
+# ------------------------------------------------------------------------------------------------ row slicing
+def normalize_row_index(index, n_rows: int):
+    """A row selector of ``W[index]`` / ``slice_rows(index)`` as int64 row numbers in ``[0, n_rows)``.
+
+    Takes an ``int``, a ``list`` / ``tuple`` / numpy array / tensor of integers, or a ``slice`` (the reference's
+    ``_misc.py:1156``, NumPy's rules: negative numbers count from the end, a slice is resolved against ``n_rows``).  An ``int``
+    comes back 0-d — the mark of a scalar selection: its dense row is 1-D — everything else 1-D; a tensor stays a tensor on its
+    device, anything else is a numpy array.  ``IndexError``: a dtype that is not an integer (``bool`` and floats included), or a
+    number outside ``[-n_rows, n_rows)``."""
+    n_rows = int(n_rows)
+    if isinstance(index, slice):
+        return np.arange(*index.indices(n_rows), dtype=np.int64)
+    if isinstance(index, torch.Tensor):
+        if not _is_int_dtype(index.dtype):
+            raise IndexError(f"Row index must be integer, got dtype {index.dtype}.")
+        if index.ndim > 1:
+            raise IndexError(f"Row index must be a scalar or 1-D, got {index.ndim}-D.")
+        rows = index.detach().to(torch.int64)
+        rows = torch.where(rows < 0, rows + n_rows, rows)
+        if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= n_rows):
+            raise IndexError(f"Row index out of bounds for axis 0 with size {n_rows}.")
+        return rows
+    arr = np.asarray(index)
+    if arr.size == 0 and arr.ndim == 1:           # ([] has no dtype of its own)
+        return np.zeros(0, dtype=np.int64)
+    if not np.issubdtype(arr.dtype, np.integer):
+        raise IndexError(f"Row index must be integer, got dtype {arr.dtype}.")
+    if arr.ndim > 1:
+        raise IndexError(f"Row index must be a scalar or 1-D, got {arr.ndim}-D.")
+    rows = arr.astype(np.int64)
+    rows = np.where(rows < 0, rows + n_rows, rows)
+    if rows.size and (rows.min() < 0 or rows.max() >= n_rows):
+        raise IndexError(f"Row index out of bounds for axis 0 with size {n_rows}.")
+    return rows
+
+
+def build_sub_csr(data, indices, indptr, rows, n_cols: int, *, row_len: int = -1):
+    """The CSR arrays of ``W[rows, :]`` from the CSR arrays of ``W`` (the reference's ``_misc.py:1199``), built on the device:
+    the new ``indptr`` is a prefix sum of the selected rows' lengths (torch), the segments are moved by ``be_slice_rows_copy``,
+    balanced per entry.  ``indptr=None`` + ``row_len``: fixed-length rows.  One shared weight (size-1 ``data``) is returned as
+    it is.  The number of stored entries of the result depends on values, so one scalar is read back.
+
+    Returns ``(new_data, new_indices, new_indptr, (len(rows), n_cols))``; ``new_indptr`` is int32, or int64 when the source's
+    is.  ``IndexError``: a row outside ``[0, n_rows)``."""
+    from . import _array as A
+    from ._lib import call
+    idx = A.to_device(indices).reshape(-1)
+    if idx.dtype != torch.int32:
+        idx = _as_int32_indices(idx, None, 'build_sub_csr', check_values=False)
+    nse = int(idx.numel())
+    if indptr is None:
+        ptr_, n_rows = None, (nse // int(row_len) if int(row_len) > 0 else 0)
+    else:
+        ptr_ = A.to_device(indptr)
+        if ptr_.dtype not in (torch.int32, torch.int64):
+            ptr_ = _as_indptr(ptr_, nse, 'auto', 'build_sub_csr')
+        n_rows, row_len = int(ptr_.numel()) - 1, -1
+    sel = A.to_device(rows, dtype=torch.int64).reshape(-1)
+    n_sel = int(sel.numel())
+    if n_sel and (int(sel.min()) < 0 or int(sel.max()) >= n_rows):
+        raise IndexError(f"Row index out of bounds for axis 0 with size {n_rows}.")
+    new_ptr = torch.zeros(n_sel + 1, dtype=torch.int64, device=idx.device)
+    if n_sel:
+        counts = (ptr_[sel + 1] - ptr_[sel]).to(torch.int64) if ptr_ is not None else torch.full_like(sel, int(row_len))
+        torch.cumsum(counts, 0, out=new_ptr[1:])
+    new_nse = int(new_ptr[-1]) if n_sel else 0
+    w = A.to_device(data)
+    homo = w.numel() == 1
+    new_idx = torch.empty(new_nse, dtype=torch.int32, device=idx.device)
+    new_w = w if homo else torch.empty(new_nse, dtype=w.dtype, device=idx.device)
+    if new_nse:
+        flat = None if homo else w.detach().reshape(-1)
+        call('be_slice_rows_copy', A.ptr(idx), A.ptr(flat), 0 if homo else flat.element_size(), A.ptr(ptr_),
+             int(ptr_ is not None and ptr_.dtype == torch.int64), int(row_len), A.ptr(sel), A.ptr(new_ptr), n_sel, n_rows, nse,
+             new_nse, A.ptr(new_idx), A.ptr(None if homo else new_w), A.stream_ptr())
+    if (ptr_ is None or ptr_.dtype == torch.int32) and new_nse <= _INT32_MAX:
+        new_ptr = new_ptr.to(torch.int32)
+    return new_w, new_idx, new_ptr, (n_sel, int(n_cols))

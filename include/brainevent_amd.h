@@ -583,6 +583,39 @@ int be_dt2t(const void* w, int homo, int wdtype, const void* y, const int32_t* i
             int64_t row_len, void* out, int64_t n_rows, int64_t n_cols, int64_t n_batch, int64_t nnz, int by_col,
             be_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * row slicing: rows of a stored matrix as a dense block (W[rows]), the gradient of that read, and the sparse sub-matrix.
+ * replaces: csr_slice_rows / csr_slice_rows_grad (brainevent/_csr/slice.py:39-120, :300-365; slice_csr_slice_rows.cu) and the
+ *           host-side gather of build_sub_csr (brainevent/_misc.py:1199-1252) — indptr NULL + row_len = n_conn for the
+ *           fixed-number containers.  rows / urows / ks / seg / new_indptr are int64.
+ *   be_slice_rows:       out[k, c] = sum of data[j] over the entries j of row rows[k] with indices[j] == c; out [n_sel, n_cols],
+ *                        contiguous, wdtype, EVERY element written (no memset needed; rows of out may start off 16 bytes).  A
+ *                        row index outside [0, n_rows) gives a zero row.  Duplicates of a column are added in ascending j, in
+ *                        f32 (f64 for f64), one rounding; homo != 0: out = (number of entries on the column) * data[0], one
+ *                        product (+0 where there is none, whatever the sign of data[0]).  No float atomics: bit-reproducible.  Cost: ceil(n_cols / be_slice_rows_tile_cols) passes
+ *                        over each selected row.
+ *   be_slice_rows_grad:  dw[j] = sum over k with rows[k] == row(j) of ct[k, indices[j]], ascending k, f32 (f64), one rounding;
+ *                        zero for entries of rows not selected (the entry point fills dw itself, on the stream).  The caller
+ *                        groups the selection: urows [n_u] the distinct rows, seg [n_u + 1] the offsets of each one's k's in
+ *                        ks [n_sel] (ascending k inside a row).  Rows outside [0, n_rows) contribute nothing.  homo != 0:
+ *                        dw [1] = the sum over everything: one partial per distinct row in workspace
+ *                        (be_slice_rows_grad_workspace_bytes), then one workgroup sums them in a fixed order.  No atomics.
+ *   be_slice_rows_copy:  out_indices[new_indptr[k] + i] = indices[indptr[rows[k]] + i] (and data alike when data != NULL,
+ *                        elem_bytes 2 / 4 / 8) for every selected row; new_indptr [n_sel + 1] is the prefix sum of the selected
+ *                        rows' lengths, new_nse its last element.  Balanced per entry.
+ * ---------------------------------------------------------------------------------------------- */
+int be_slice_rows_tile_cols(int wdtype);
+int be_slice_rows(const void* data, int homo, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64,
+                  int64_t row_len, const int64_t* rows, int64_t n_sel, void* out, int64_t n_rows, int64_t n_cols, int64_t nse,
+                  be_stream_t stream);
+int64_t be_slice_rows_grad_workspace_bytes(int64_t n_sel, int wdtype);
+int be_slice_rows_grad(const void* ct, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t row_len,
+                       const int64_t* urows, const int64_t* seg, const int64_t* ks, int64_t n_u, int64_t n_sel, void* dw, int homo,
+                       int64_t n_rows, int64_t n_cols, int64_t nse, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+int be_slice_rows_copy(const int32_t* indices, const void* data, int elem_bytes, const void* indptr, int indptr_is_i64,
+                       int64_t row_len, const int64_t* rows, const int64_t* new_indptr, int64_t n_sel, int64_t n_rows, int64_t nse,
+                       int64_t new_nse, int32_t* out_indices, void* out_data, be_stream_t stream);
+
 /* JIT connectivity against a dense operand: the same on-the-fly matrices as be_binary_jitmv / be_binary_jitmm (same walks, same
  * per-edge weight hashes), every element of the operand counting.
  * replaces: jitsmv / jitsmm (brainevent/_jit_scalar/float.py:838-905, :1331-1420), jitumv / jitumm, jitnmv / jitnmm
