@@ -4,7 +4,8 @@ Only the spike-triggered SpMV/SpMM hot path of chaobrain/brainevent is provided:
 ``BinaryArray @ {CSR, CSC, dense, JITC{Scalar,Normal,Uniform}{R,C}, FixedNumPerPre/PerPost}`` and the
 functional ``binary_*`` operators, running hand-written HIP kernels (gfx950) through a C ABI, and the spike-triggered
 plasticity updates (``update_*_on_binary_pre/post``, ``update_on_pre`` / ``update_on_post``).  The products are
-differentiable under ``torch.autograd`` (weights and float spikes; ``brainevent_amd._autograd``).
+differentiable under ``torch.autograd`` (weights and float spikes; ``brainevent_amd._autograd``), and so are the float-operand
+products of the same containers (``csr @ x``); ``sddmm_*`` / ``M.sddmm`` sample a dense-dense product on a sparsity pattern.
 """
 from ._version import __version__
 __version_info__ = tuple(int(p) for p in __version__.split('.')[:3] if p.isdigit())
@@ -26,6 +27,7 @@ from ._float import (csrmv, csrmm, csrmv_p, csrmm_p, csrmv_p_call, csrmm_p_call,
                      fcnmm_p_call)
 from ._dt2t import (csrmv_dt2t, csrmm_dt2t, cscmv_dt2t, cscmm_dt2t, fcnmv_dt2t, fcnmm_dt2t, csrmv_dt2t_p, csrmm_dt2t_p,
                     fcnmv_dt2t_p, fcnmm_dt2t_p, csrmv_dt2t_p_call, csrmm_dt2t_p_call, fcnmv_dt2t_p_call, fcnmm_dt2t_p_call)
+from ._sddmm import sddmm_indices, sddmm_coo_indices, sddmm_p, sddmm_p_call
 from ._slice import (csr_slice_rows, csr_slice_rows_p, csr_slice_rows_p_call, csr_slice_rows_grad, csr_slice_rows_grad_p,
                      csr_slice_rows_grad_p_call)
 from ._graph import GraphedStep, capture_step

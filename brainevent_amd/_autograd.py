@@ -22,6 +22,9 @@ arrays:
   entry written once, no atomics (bit-reproducible).  Spike gradients reuse the float-operand kernels (``_float``; through the
   container's mirror when the direction is a scatter and a mirror exists); dense spike gradients are plain GEMMs
   (``torch.matmul``: there is no event structure in them).
+* The float-operand products (``csr @ x`` with a plain array, ``csrmv / csrmm / fcnmv / fcnmm``) have a Function of their own,
+  :class:`FloatRowsProduct`: the weight gradient is a sampled dense-dense product (``csrc/be_sddmm.hip``), the operand gradient
+  the transposed float product.  Not differentiable: the JITC float twins, ``Dense`` with a plain array, ``PlannedMatrix``.
 * Wrapping happens only when grad mode is on and an operand requires grad; otherwise the existing path runs untouched.  The
   forward pass of the Function IS the existing path (same route, same kernels, same bits).  Higher-order gradients are not
   supported (``once_differentiable``).
@@ -35,7 +38,7 @@ from . import _array as A
 from ._error import UnsupportedOperationError
 from ._lib import call, fn
 
-__all__ = ['RowsProduct', 'DenseProduct', 'SliceRows', 'needed']
+__all__ = ['RowsProduct', 'FloatRowsProduct', 'DenseProduct', 'SliceRows', 'needed']
 
 
 def _value(x):
@@ -193,6 +196,89 @@ def rows_product(run: Callable, weights, spikes_arg, operand, layout: str, rows,
     if weights.requires_grad:
         spec.mask, spec.nb = activity(operand, layout)
     return RowsProduct.apply(weights, s, spec)
+
+
+class FloatRowsProduct(torch.autograd.Function):
+    """The float-operand products over stored rows ``A [m, k]`` (``csrmv / csrmm / fcnmv / fcnmm`` and the containers' ``@``
+    with a plain array): every element of the operand ``X`` counts.  With ``g`` the incoming gradient, both neuron-major
+    ``[., nb]`` (a vector is ``nb = 1``), and ``sddmm(P, Q)[j] = sum_b P[r(j), b] Q[c(j), b]`` (``csrc/be_sddmm.hip``):
+
+      ``A @ X``   (``transpose=False``)  ->  ``dw = sddmm(P = g, Q = X)``,  ``dX = A.T @ g``
+      ``A.T @ X`` (``transpose=True``)   ->  ``dw = sddmm(P = X, Q = g)``,  ``dX = A @ g``
+      one shared weight: the scalar ``sum(P * (A1 @ Q))``, ``A1`` the structure with weight 1 — the float product in the
+      gather direction, then one ``torch.sum``: no float atomics.
+
+    ``dX`` is :func:`_rows_spike_grad` (a live mirror serves the scatter direction; none is built).  The backward pass reads
+    the raw stored rows only, so ``dw`` arrives in ``data``'s own order and shape whichever route the forward pass took.
+    Saved: the operand when the weights need a gradient, the weights when the operand does."""
+
+    @staticmethod
+    def forward(ctx, weights, x, x_nm, spec: RowsSpec):
+        out = spec.run()
+        ctx.spec = spec
+        ctx.save_for_backward(weights if x is not None else None, x_nm)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        spec = ctx.spec
+        r = spec.rows
+        weights, x_nm = ctx.saved_tensors
+        g_nm = _to_nm(g, spec.layout)
+        dw = dx = None
+        if ctx.needs_input_grad[0]:
+            dw = float_rows_weight_grad(spec.w_meta, r, (x_nm, g_nm) if spec.transpose else (g_nm, x_nm))
+        if ctx.needs_input_grad[1]:
+            shape, dtype, dev = spec.s_meta
+            dx = _from_nm(_rows_spike_grad(weights, spec, g_nm), spec.layout, shape, dtype).to(dev)
+        return dw, dx, None, None
+
+
+def float_rows_weight_grad(w_meta, rows, pq) -> torch.Tensor:
+    """The weight gradient of a float-operand product over ``rows``: ``sddmm(P, Q)`` per stored entry in the weights' shape, or
+    the scalar of a shared weight.  ``pq = (P [m, nb], Q [k, nb])``."""
+    from ._float import _float_csr
+    from ._sddmm import sddmm_rows
+    shape, dtype = w_meta
+    P, Q = (t.to(dtype) for t in pq)
+    if _numel(shape) == 1 and int(rows.indices.numel()) != 1:
+        one = torch.ones(1, dtype=dtype, device=A.device())
+        aq = _float_csr(one, rows.indices, rows.indptr, rows.row_len, Q, m=rows.m, k=rows.k, transpose=False)     # A1 @ Q [m, nb]
+        acc = torch.float64 if dtype == torch.float64 else torch.float32
+        return torch.sum(P.to(acc) * aq.to(acc)).to(dtype).reshape(shape)
+    return sddmm_rows(rows.indices, rows.indptr, rows.row_len, None, rows.m, rows.k, P, Q).reshape(shape)
+
+
+def float_rows_product(run: Callable, weights, x, layout: str, rows, transpose: bool, mirror=None):
+    """Run ``run()`` (the existing forward path) as a :class:`FloatRowsProduct` over the stored ``rows``.  ``x``: the dense
+    operand as the caller gave it (a tensor), ``layout`` as for :func:`rows_product`."""
+    spec = RowsSpec(run, rows, transpose, layout, mirror)
+    spec.w_meta = (tuple(weights.shape), weights.dtype)
+    xd = x if (x.requires_grad and x.dtype.is_floating_point) else None
+    if xd is not None:
+        spec.s_meta = (x.shape, x.dtype, x.device)
+    x_nm = None
+    if weights.requires_grad:          # the operand by value, neuron-major in the weights' dtype
+        x_nm = _to_nm(A.to_device(x.detach(), dtype=weights.dtype), layout)
+    return FloatRowsProduct.apply(weights, xd, x_nm, spec)
+
+
+def float_needed(weights, x) -> bool:
+    """Whether a float-operand product is to be recorded: grad mode is on, the operand is a tensor (numpy operands give numpy
+    results without autograd), and the weights or the operand require grad."""
+    return isinstance(x, torch.Tensor) and isinstance(weights, torch.Tensor) and needed(weights, x)
+
+
+def container_float_product(M, other, left: bool, run: Callable):
+    """``other @ M`` (``left``) or ``M @ other`` of a CSR / CSC / fixed-number container with a dense tensor operand, as a
+    :class:`FloatRowsProduct` over the container's own arrays (whichever route — direct or mirror — ``run`` takes)."""
+    if other.ndim not in (1, 2):
+        with torch.no_grad():
+            return run()               # (raises: the forward path's own error)
+    t = M._scatter_side(left)
+    layout = 'vec' if other.ndim == 1 else ('bm' if left else 'nm')
+    return float_rows_product(run, M.data, other, layout, M._stored_rows(), t, mirror=None if t else (lambda: _live_mirror(M)))
 
 
 class DenseSpec:

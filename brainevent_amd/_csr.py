@@ -1702,6 +1702,14 @@ class StoredRowsData(PlasticityMixin, DataRepresentation):
         from ._dt2t import container_dt2t
         return container_dt2t(self, y_dim_arr, w_dim_arr, False, out)
 
+    # -- sampled dense-dense product (reference ``brainevent/_sddmm.py``) ---------------------------------------------------
+    def sddmm(self, A_mat, B_mat):
+        """``A @ B`` sampled on this matrix's pattern: ``A (shape[0], nb)``, ``B (nb, shape[1])`` -> a matrix of the same type
+        and structure (the structure arrays are shared, not copied) whose entry at ``(i, j)`` is ``sum_b A[i, b] B[b, j]``, in
+        storage order and in ``data``'s dtype.  A matrix with one shared weight raises ``UnsupportedOperationError``."""
+        from ._sddmm import container_sddmm
+        return container_sddmm(self, A_mat, B_mat)
+
     # -- row slicing (reference ``_csr/main.py:1458-1499``, ``:2361-2415``, ``_fcn/main.py:918-960``, ``:1182-1240``) ---------
     def __getitem__(self, index):
         """Rows of this matrix as a dense array, NumPy's rules: ``index`` is an ``int`` (-> ``(shape[1],)``), a list / tuple /
@@ -1885,6 +1893,8 @@ def _dense_product(M, other, left: bool):
     ``A`` — ``A.T @ x`` on the scatter side, ``A @ x`` on the gather side.  Float-operand twins (``_float.csrmv`` / ``csrmm``;
     reference ``_csr/main.py:1595-1697``, ``:1699-1776``); ``x @ op(A) = (op(A).T @ x.T).T``."""
     from ._float import csrmv_p_call, csrmm_p_call
+    if _ag.float_needed(M.data, other):
+        return _ag.container_float_product(M, other, left, lambda: _dense_product(M, other, left))
     x = other if isinstance(other, torch.Tensor) else np.asarray(other)
     rows = M._stored_rows()
     t = M._scatter_side(left)

@@ -185,6 +185,8 @@ class FixedNumConn(StoredRowsData):
     def _dispatch(self, other, transpose_W: bool):
         if is_event(other) and _ag.needed(self.data, other):
             return _ag.container_product(self, other, transpose_W, lambda: self._dispatch(other, transpose_W))
+        if not is_event(other) and _ag.float_needed(self.data, other):
+            return _ag.container_float_product(self, other, transpose_W, lambda: self._dispatch(other, transpose_W))
         scatter = transpose_W != self._stored_transposed
         if not is_event(other):     # a dense operand: the float twins (reference ``_fcn/main.py:308-460`` dispatches them alike)
             from ._float import fcnmv_p_call, fcnmm_p_call

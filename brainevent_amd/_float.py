@@ -8,17 +8,22 @@ Reference surface (read as text): ``brainevent/_csr/float.py:49-150`` (``csrmv``
   transpose=False: ``A[m, k] @ v[k] -> [m]``            / ``A[m, k] @ B[k, n] -> [m, n]``
   transpose=True : ``A[m, k].T @ v[m] -> [k]``          / ``A[m, k].T @ B[m, n] -> [k, n]``
 
-Output dtype = weights dtype; the operand is cast to it.  Not on the event-driven hot path (no autodiff, no units here): these
-exist so that a container accepts a dense operand at all, through hand-written kernels like everything else — gather rows in
-aligned groups of four entries, scatter through float atomics (``csrc/be_float.hip``)."""
+Output dtype = weights dtype; the operand is cast to it.  Not on the event-driven hot path (no units here): these exist so that
+a container accepts a dense operand at all, through hand-written kernels like everything else — gather rows in aligned groups
+of four entries, scatter through float atomics (``csrc/be_float.hip``).
+
+Differentiable under ``torch.autograd`` in the weights and in a float tensor operand (``_autograd.FloatRowsProduct``; reference
+rules ``brainevent/_csr/float.py:287-330``, ``:825-860``): the functions and the containers' ``@`` record a node only when grad
+mode is on and one of the two requires grad; otherwise — and for numpy operands — nothing changes."""
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _array as A
+from . import _autograd as _ag
 from ._lib import call, fn
-from ._csr import _check_csr_structure_dtypes
+from ._csr import StoredRows, _check_csr_structure_dtypes
 from ._misc import _as_indptr, _as_int32_indices
 from ._op import OpKernel
 
@@ -124,13 +129,24 @@ def _operand(x):
     return x if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
+def _recorded(run, weights, x, rows: StoredRows, transpose: bool, ndim: int):
+    """``run()`` — the forward path as it is — recorded for ``torch.autograd`` when the weights or a float tensor operand need
+    a gradient (``_autograd.float_needed``); an operand of another rank goes straight to ``run``'s own validation."""
+    if not _ag.float_needed(weights, x) or x.ndim != ndim:
+        return run()
+    return _ag.float_rows_product(run, weights, x, 'vec' if ndim == 1 else 'nm', rows, bool(transpose))
+
+
 def csrmv(data, indices, indptr, v, *, shape, transpose: bool = False, backend: Optional[str] = None):
     """``A @ v`` (``transpose=False``) or ``A.T @ v`` for a CSR matrix and a dense vector (reference
     ``brainevent/_csr/float.py:49-150``): every element of ``v`` contributes, whatever its sign."""
     as_np = A.wants_numpy(data, indices, indptr, v)
     idx, ptr_ = _structure(indices, indptr, 'csrmv')
-    res = csrmv_p_call(A.to_device(data), idx, ptr_, _operand(v), shape=tuple(shape), transpose=transpose, backend=backend)[0]
-    return A.to_result(res, as_np)
+    w = A.to_device(data)
+
+    def run():
+        return csrmv_p_call(w, idx, ptr_, _operand(v), shape=tuple(shape), transpose=transpose, backend=backend)[0]
+    return A.to_result(_recorded(run, w, v, StoredRows(idx, ptr_, -1, int(shape[0]), int(shape[1])), transpose, 1), as_np)
 
 
 def csrmm(data, indices, indptr, B, *, shape, transpose: bool = False, backend: Optional[str] = None):
@@ -138,8 +154,11 @@ def csrmm(data, indices, indptr, B, *, shape, transpose: bool = False, backend: 
     ``brainevent/_csr/float.py:559-668``)."""
     as_np = A.wants_numpy(data, indices, indptr, B)
     idx, ptr_ = _structure(indices, indptr, 'csrmm')
-    res = csrmm_p_call(A.to_device(data), idx, ptr_, _operand(B), shape=tuple(shape), transpose=transpose, backend=backend)[0]
-    return A.to_result(res, as_np)
+    w = A.to_device(data)
+
+    def run():
+        return csrmm_p_call(w, idx, ptr_, _operand(B), shape=tuple(shape), transpose=transpose, backend=backend)[0]
+    return A.to_result(_recorded(run, w, B, StoredRows(idx, ptr_, -1, int(shape[0]), int(shape[1])), transpose, 2), as_np)
 
 
 # ------------------------------------------------------------------------------------------------ fixed-number connectivity
@@ -192,18 +211,26 @@ def _fcn_indices(indices):
     return idx
 
 
+def _fcn_rows(idx, shape) -> StoredRows:
+    return StoredRows(idx, None, int(idx.shape[-1]) if idx.ndim == 2 else 0, int(shape[0]), int(shape[1]))
+
+
 def fcnmv(weights, indices, vector, *, shape, transpose: bool, backend: Optional[str] = None):
     """``W @ v`` / ``W.T @ v`` for fixed-number connectivity (reference ``brainevent/_fcn/float.py:33-134``): ``indices [rows,
     n_conn]`` lists each row's columns, ``weights`` matches it or is one shared value; ``shape = (rows, columns)``."""
     as_np = A.wants_numpy(weights, indices, vector)
-    res = fcnmv_p_call(A.to_device(weights), _fcn_indices(indices), _operand(vector), shape=tuple(shape), transpose=transpose,
-                       backend=backend)[0]
-    return A.to_result(res, as_np)
+    w, idx = A.to_device(weights), _fcn_indices(indices)
+
+    def run():
+        return fcnmv_p_call(w, idx, _operand(vector), shape=tuple(shape), transpose=transpose, backend=backend)[0]
+    return A.to_result(_recorded(run, w, vector, _fcn_rows(idx, shape), transpose, 1), as_np)
 
 
 def fcnmm(weights, indices, matrix, *, shape, transpose: bool, backend: Optional[str] = None):
     """``W @ M`` / ``W.T @ M`` for fixed-number connectivity (reference ``brainevent/_fcn/float.py:136-240``)."""
     as_np = A.wants_numpy(weights, indices, matrix)
-    res = fcnmm_p_call(A.to_device(weights), _fcn_indices(indices), _operand(matrix), shape=tuple(shape), transpose=transpose,
-                       backend=backend)[0]
-    return A.to_result(res, as_np)
+    w, idx = A.to_device(weights), _fcn_indices(indices)
+
+    def run():
+        return fcnmm_p_call(w, idx, _operand(matrix), shape=tuple(shape), transpose=transpose, backend=backend)[0]
+    return A.to_result(_recorded(run, w, matrix, _fcn_rows(idx, shape), transpose, 2), as_np)

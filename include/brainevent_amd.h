@@ -867,6 +867,25 @@ int64_t be_grad_dense_workspace_bytes(int64_t n_rows, int64_t n_cols);
 int be_grad_dense(int transpose, void* dw, int wdtype, int64_t n_rows, int64_t n_cols, const uint32_t* mask, int64_t n_batch,
                   const void* g, int64_t g_sn, int64_t g_sb, be_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * the sampled dense-dense product on a stored pattern (SDDMM): one value per stored entry e of row r(e) and stored index c(e),
+ *   out[e] = sum_{b < n_batch} p[r(e) * n_batch + b] * q[c(e) * n_batch + b]
+ * replaces: sddmm_indices / sddmm_coo_indices (brainevent/_sddmm.py) and the mm weight rule of the float-operand products
+ *           (brainevent/_csr/float.py:825-860; mv, :287-330, is n_batch = 1): A @ X -> p = g, q = X; A.T @ X -> p = X, q = g.
+ * p [n_rows, n_batch], q [n_cols, n_batch] and out [nse] are in the weight dtype (f32 / f64 / f16 / bf16), p and q contiguous.
+ * The row of an entry comes from row_ids [nse] when it is not NULL (COO), else from indptr (int32 / int64, n_rows + 1 entries
+ * ascending from 0 to nse; empty rows allowed), else from the fixed row length row_len > 0 (r = e / row_len).  An entry whose
+ * row or stored index lies outside [0, n_rows) / [0, n_cols) gets 0; nothing is read through it.
+ * Sums run in f32 (f64 for f64) and are rounded once.  The lanes that share an entry, and with them the order of its sum,
+ * depend on n_batch and the dtype only — not on the grid, the row lengths, the row source or the alignment of p and q (which
+ * only picks 16-byte or element loads) — so results are bit-identical across runs and across the three row sources.  Every
+ * entry is written exactly once: no memset, no atomics, no workspace, no host synchronisation (graph-capturable).  Work is
+ * balanced per entry; entry offsets are 64-bit.  nse = 0, n_batch = 0 or n_rows = 0 returns without a launch.
+ * ---------------------------------------------------------------------------------------------- */
+int be_sddmm_rows(void* out, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t row_len,
+                  const int32_t* row_ids, int64_t n_rows, int64_t n_cols, int64_t nse, const void* p, const void* q,
+                  int64_t n_batch, be_stream_t stream);
+
 #define BE_FOR_ALL_VARIANTS(X) \
   X(f32, BE_F32, bool, BE_SPIKE_BOOL)   X(f32, BE_F32, float, BE_SPIKE_FLOAT)   \
   X(f64, BE_F64, bool, BE_SPIKE_BOOL)   X(f64, BE_F64, float, BE_SPIKE_FLOAT)   \
