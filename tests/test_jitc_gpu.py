@@ -149,6 +149,9 @@ def test_jit_small_prob_many_chunks(be, oracle):
 def test_jit_scatter_large_walk_pieces(be):
     # a walk long enough to need several LDS pieces per residue class (uniform: 16384 accumulators per piece);
     # gather and scatter over the same generator orientation must agree: M (corder=False rows=inputs) vs its transpose
+    # (3 M columns give several pieces to the uniform family only, and nothing here is an oracle's number: the several-piece
+    #  kernels of all three families against the oracle are tests/test_event_jit_kernels_at_scale_gpu.py::
+    #  test_mv_scatter_several_pieces and ::test_mm_scatter_several_pieces_and_parts)
     n_in, n_out, prob, seed = 64, 3_000_000, 0.0005, 11
     rng = np.random.default_rng(1)
     v = spikes_of(rng, n_in, 0.5, 'bool')
@@ -397,7 +400,9 @@ def test_prepare_serves_both_directions_from_the_stored_matrix(be, oracle, famil
 def test_scalar_mm_gather_counts_are_bit_sliced_and_exact(be, oracle):
     """Round 4: the scalar mm gather keeps its per-column counts bit-sliced (a ripple-carry add of the edge's column mask);
     32 batch columns at 50 % firing drive the counts through several carries — still the oracle's integers times the weight,
-    for the LDS-mask kernel and (one wide chunk) the global-mask kernel, narrow and wide batches."""
+    narrow and wide batches.  Every shape here, (200, 40000) with its chunks of 10 000 included, takes the LDS-mask kernel
+    (k_jit_mm_gather_lds) in one window; several windows and the global-mask kernel (k_jit_mm_gather: more than 256 windows)
+    are run by tests/test_event_jit_kernels_at_scale_gpu.py (test_mm_gather_lds_windows, test_mm_gather_global_masks)."""
     rng = np.random.default_rng(52)
     for shape, prob, n in (((300, 2000), 0.2, 32), ((64, 900), 0.5, 17), ((500, 700), 0.1, 8), ((200, 40000), 0.01, 32)):
         B = rng.random((shape[1], n)) < 0.5

@@ -181,7 +181,7 @@ def test_c_oracle_jit_float_matches_numpy_oracle():
     ULPs of libm's logf against numpy's log, as in the pin above.  Shapes: the usual one, one walked over its long side
     (19 chunks of 2) and one whose walk (3) is shorter than one chunk (10) and than both lane strides."""
     rng = np.random.default_rng(6)
-    checked = 0
+    checked = checked_01 = 0
     for shape in ((19, 37), (37, 5), (3, 40)):
         for mode, (w0, w1) in {'s': (0.5, 0.0), 'u': (0.1, 0.9), 'n': (0.2, 1.3)}.items():
             for transpose in (False, True):
@@ -206,8 +206,14 @@ def test_c_oracle_jit_float_matches_numpy_oracle():
                             if n == 1:      # a 1-D operand gives a 1-D result with the same numbers
                                 np.testing.assert_array_equal(oracle_c.jit_float(mode, w0, w1, prob, X[:, 0], seed, stride=stride, **kw),
                                                               a[:, 0])
+                            if n == 1:      # on a 0/1 vector it is oracle_c.jitmv (the at-scale event-driven tests' reference)
+                                v = X[:, 0] != 0
+                                c = oracle_c.jitmv(mode, w0, w1, prob, v, seed, stride=stride, **kw)
+                                np.testing.assert_array_equal(oracle_c.jit_float(mode, w0, w1, prob, v.astype(np.float64), seed,
+                                                                                 stride=stride, **kw), c)
+                                checked_01 += int(np.count_nonzero(c))
                             checked += int(np.count_nonzero(b))
-    assert checked > 2000, 'the pin must compare edges, not zeros'
+    assert checked > 2000 and checked_01 > 500, 'the pin must compare edges, not zeros'
     assert not oracle_c.jit_float('u', 0.1, 0.9, 0.0, np.ones(37), 1, shape=(19, 37), transpose=False, corder=True, stride=32).any()
 
 
