@@ -46,4 +46,5 @@ from ._jitc import (JITCScalarMatrix, JITCUniformMatrix, JITCNormalMatrix, JITCM
                     binary_jitsmv_p_call, binary_jitsmm_p_call, binary_jitumv_p_call, binary_jitumm_p_call,
                     binary_jitnmv_p_call, binary_jitnmm_p_call, JITCScatterShard, JITCGatherShard,
                     jitsmv, jitsmm, jitumv, jitumm, jitnmv, jitnmm, jitsmv_p, jitsmm_p, jitumv_p, jitumm_p, jitnmv_p, jitnmm_p,
-                    jitsmv_p_call, jitsmm_p_call, jitumv_p_call, jitumm_p_call, jitnmv_p_call, jitnmm_p_call)
+                    jitsmv_p_call, jitsmm_p_call, jitumv_p_call, jitumm_p_call, jitnmv_p_call, jitnmm_p_call,
+                    jitsmv_dt2t, jitumv_dt2t, jitnmv_dt2t)

@@ -60,6 +60,7 @@ _SIGNATURES = dict(
     be_binary_jitmv='i:iddilupipllliiplp', be_jit_scatter_classes='i:lli', be_binary_jitmv_sharded='i:iddilupipllliiiplp',
     be_binary_jitmv_rows='i:iddilupipllllplp', be_binary_jitmm_workspace_bytes='l:lllli', be_binary_jitmm='i:iddilupiplllliplp',
     be_jit_edge_weights='i:iddupplpp', be_jitc_csr_count='i:lulllipp', be_jitc_csr_fill='i:iddlulllippppp',
+    be_jitc_fill_sorted='i:iddlulllippippp',
     be_plasticity_workspace_bytes='l:l', be_plasticity_rows='i:pippillpipilpididplp', be_plasticity_dense='i:ipillpipididplp',
     be_grad_mask_bytes='l:ll', be_grad_pack_activity='i:pillpp', be_grad_rows_workspace_bytes='l:l',
     be_grad_rows='i:ipiippilllplpllplp', be_grad_dense_workspace_bytes='l:ll', be_grad_dense='i:ipillplpllp',

@@ -21,8 +21,8 @@ whatever the row lengths.  Deviations from the reference, both this project's ru
   it is: nothing is cloned.
 
 No autograd: the reference defines forward-mode rules only ("the transpose rule is not yet implemented") and D-RTRL does not
-back-propagate through the trace, so tensors that require grad are taken by value, as the float twins take them.  Not here:
-``jit{s,u,n}mv_dt2t`` (out of scope)."""
+back-propagate through the trace, so tensors that require grad are taken by value, as the float twins take them.  The
+JIT-connectivity twins ``jit{s,u,n}mv_dt2t`` live in ``_jitc.py``."""
 from typing import Optional
 
 import numpy as np

@@ -32,7 +32,7 @@ __all__ = [
     'binary_jitsmv_p', 'binary_jitsmm_p', 'binary_jitumv_p', 'binary_jitumm_p', 'binary_jitnmv_p', 'binary_jitnmm_p',
     'binary_jitsmv_p_call', 'binary_jitsmm_p_call', 'binary_jitumv_p_call', 'binary_jitumm_p_call',
     'binary_jitnmv_p_call', 'binary_jitnmm_p_call', 'JITCScatterShard', 'JITCGatherShard', 'jit_scatter_class_columns',
-    'jit_edge_weights',
+    'jit_edge_weights', 'jitsmv_dt2t', 'jitumv_dt2t', 'jitnmv_dt2t',
 ]
 
 _FAMILY = {'s': 0, 'u': 1, 'n': 2}
@@ -501,6 +501,178 @@ def jitnmm(w_loc, w_scale, prob, B, seed: Optional[int] = None, *, shape, transp
 
 
 # =====================================================================================================
+# per-synapse products (dt2t): one value per drawn edge, in the flat order of the canonical (column-sorted) CSR of ``shape``
+#   reference: brainevent/_jit_scalar/dt2t.py:57-107 (jitsmv_dt2t), _jit_uniform/dt2t.py, _jit_normal/dt2t.py (the twins);
+#   the sort that defines the order: _jit_scalar/csr.py:562-570
+# =====================================================================================================
+#: geometry of the sorted fill (``k_jit_fill_sorted`` in ``csrc/be_jitc.hip``: ``kSortedWindow`` columns per LDS bitmap window,
+#: ``kSortedGridCap`` workgroups — one owner row each — per launch; the rows beyond are taken grid-stride)
+JIT_SORTED_WINDOW = 65536
+JIT_SORTED_GRID_CAP = 4096
+
+_INDPTR_KEY = 'materialized_mv_indptr'      # (dropped by transpose() with everything else that begins 'materialized_')
+
+
+def _fill_sorted(mode, w0, w1, clen, seed, shape1, n_rows, walk, stride, indptr, y, y_by_owner, indices_out, values_out):
+    check(fn('be_jitc_fill_sorted')(int(mode), w0, w1, int(clen), seed & 0xFFFFFFFF, int(shape1), int(n_rows), int(walk),
+                                    int(stride), A.ptr(indptr), A.ptr(y), int(bool(y_by_owner)), A.ptr(indices_out),
+                                    A.ptr(values_out), A.stream_ptr()), 'be_jitc_fill_sorted')
+
+
+def _count_indptr(clen, seed, shape1, n_rows, walk, stride):
+    """The count walk and its scan: ``(counts uint32-as-int32 [n_rows], indptr int64 [n_rows + 1])`` on the device."""
+    dev = A.device()
+    counts = torch.empty(max(n_rows, 1), dtype=torch.int32, device=dev)
+    check(fn('be_jitc_csr_count')(int(clen), seed & 0xFFFFFFFF, int(shape1), int(n_rows), int(walk), int(stride), A.ptr(counts),
+                                  A.stream_ptr()), 'be_jitc_csr_count')
+    indptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts[:n_rows].to(torch.int64), 0, out=indptr[1:])
+    return counts, indptr
+
+
+def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
+    if a.device != b.device or a.numel() == 0 or b.numel() == 0:
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def _jit_dt2t(family, a, b, prob, y, seed, *, gshape, transpose, corder, by_row, out=None, indptr=None):
+    """The per-synapse product of the matrix ``M (out_len, in_len)`` that ``(gshape, transpose, corder)`` draws for the mv ops
+    (``M = G`` when ``corder``, else ``G.T``, ``G`` the generator matrix: rows = walk owners): ``w(i, j) * y[i]`` (``by_row``) or
+    ``w(i, j) * y[j]`` for every drawn entry, row-major with ascending columns.  Returns ``(result, indptr)`` — a device tensor
+    (a host array of length 0 where nothing is drawn and the inputs were host arrays), and the int64 row offsets where the
+    fused route scanned them (``None`` otherwise); ``indptr=`` hands such offsets back in and skips the count walk."""
+    from ._dt2t import _check_out, _dtype_name, _product
+    ws = (a,) if family == 's' else (a, b)
+    y_ = _arr(y)
+    wdt = _weight_dtype(*ws)
+    if wdt != torch.float32 or _dtype_name(y_) != 'float32':
+        raise ValueError(f"the JIT-connectivity per-synapse products compute in float32 (as prepare() stores): got weights "
+                         f"of {wdt} and y of {_dtype_name(y_)}.")
+    assert len(gshape) == 2, "The matrix shape should be a tuple of two integers."
+    assert y_.ndim == 1, "y must be 1D."
+    in_len = int(gshape[0] if transpose else gshape[1])
+    out_len = int(gshape[1] if transpose else gshape[0])
+    if by_row:
+        assert out_len == y_.shape[0], "Shape mismatch for non-transpose operation."
+    else:
+        assert in_len == y_.shape[0], "Shape mismatch for transpose operation."
+    if out is not None:
+        _check_out(out, tuple(getattr(out, 'shape', ())), 'float32')   # (type, dtype, placement; the length once nnz is known)
+        if out.ndim != 1:
+            raise ValueError(f"out must be 1-D, got shape {tuple(out.shape)}.")
+        if isinstance(y_, torch.Tensor) and _overlaps(out, y_):
+            raise ValueError("out must not alias y: an entry's y is read after other entries have been written.")
+    clen = _initialize_conn_length(_validate_prob(prob))
+    seed = _initialize_seed(seed)
+
+    def finish(nnz):
+        if out is not None:
+            _check_out(out, (nnz,), 'float32')
+            return out
+        return None
+
+    if clen == 0 or in_len == 0 or out_len == 0:
+        res = finish(0)
+        if res is None:
+            res = np.zeros(0, np.float32) if A.wants_numpy(y, *ws) else torch.empty(0, dtype=torch.float32, device=A.device())
+        return res, None
+    w0, w1, _ = _jit_params(family, *(ws + (None,))[:2])
+    mode = _FAMILY[family]
+    n_rows, walk = (out_len, in_len) if corder else (in_len, out_len)
+    shape1 = int(gshape[1])
+    yd = A.to_device(y_, dtype=torch.float32).detach()
+    if corder:
+        # fused: the walk owners are the rows of M — count, scan, then one sorted fill that writes the products alone
+        if indptr is None:
+            _, indptr = _count_indptr(clen, seed, shape1, n_rows, walk, 32)
+        nnz = int(indptr[-1].item())
+        res = finish(nnz)
+        if res is None:
+            res = torch.empty(nnz, dtype=torch.float32, device=A.device())
+        if nnz:
+            _fill_sorted(mode, w0, w1, clen, seed, shape1, n_rows, walk, 32, indptr, yd, by_row, None, res)
+        return res, indptr
+    # composed: the walk owners are the COLUMNS of M.  A row-major result over column-owned walks is a transposition, and a walk
+    # cannot be entered in the middle of a chunk (the hash chain is sequential), so the structure is stored for the length of the
+    # call: the column-major fill, a stable CSC -> CSR conversion (columns are visited in order: ascending within every row),
+    # then the stored-rows product.
+    from ._convert import csc_to_csr_index, gather_by_perm
+    dev = A.device()
+    counts, cptr = _count_indptr(clen, seed, shape1, n_rows, walk, 32)
+    nnz = int(cptr[-1].item())
+    res = finish(nnz)
+    if nnz == 0:
+        return (res if res is not None else torch.empty(0, dtype=torch.float32, device=dev)), None
+    if nnz > np.iinfo(np.int32).max:
+        raise MemoryError(f"the per-synapse product of a column-owned JIT matrix sorts its {nnz} entries on the device "
+                          f"(limit 2^31 - 1): use the orientation whose walk owners are the rows (corder).")
+    rows = torch.empty(nnz, dtype=torch.int32, device=dev)
+    wts = torch.empty(nnz, dtype=torch.float32, device=dev) if mode else None
+    check(fn('be_jitc_csr_fill')(mode, w0, w1, clen, seed & 0xFFFFFFFF, shape1, n_rows, walk, 32, A.ptr(cptr), A.ptr(counts),
+                                 A.ptr(rows), A.ptr(wts), A.stream_ptr()), 'be_jitc_csr_fill')
+    homo = torch.full((1,), float(w0), dtype=torch.float32, device=dev)
+    if mode == 0 and by_row:
+        # constant weight, y by the row: only the row COUNTS matter — no sort, no index in row order
+        rptr = torch.zeros(out_len + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.bincount(rows, minlength=out_len), 0, out=rptr[1:])
+        r = _product(homo, yd, None, rptr, -1, n_rows=out_len, n_cols=in_len, n_batch=1, nnz=nnz, by_col=False,
+                     result_shape=(nnz,), out=res)
+        return r, None
+    rptr, cols, perm = csc_to_csr_index(cptr, rows, shape=(out_len, in_len), include_perm=bool(mode))
+    w = gather_by_perm(wts, perm) if mode else homo
+    r = _product(w, yd, cols, rptr, -1, n_rows=out_len, n_cols=in_len, n_batch=1, nnz=nnz, by_col=not by_row,
+                 result_shape=(nnz,), out=res)
+    return r, None
+
+
+_DT2T_DOC = """Per-synapse products of the matrix the ``mv`` ops draw for ``(shape, corder)`` — ``M @ v`` with ``transpose=False``:
+    one value per drawn entry, ``w(i, j) * y[i]`` (``transpose=False``; ``y`` has ``shape[0]`` elements) or ``w(i, j) * y[j]``
+    (``transpose=True``; ``shape[1]``), in the flat order of the canonical CSR of ``shape``: row-major, ascending columns —
+    the order of ``materialize('mv', canonical=True)`` / ``tocsr``.  Length ``nnz`` of the draw; 0 for ``prob == 0`` or an empty
+    shape.  float32 only (``ValueError`` otherwise).  ``out=``: a contiguous f32 device tensor of length ``nnz`` that is written
+    and returned; it must not overlap ``y``.
+
+    ``corder=True`` (the walk owners are the rows of ``shape``): fused — a count walk, a scan, and one sorted fill
+    (``be_jitc_fill_sorted``) that writes the products; neither indices nor weights are stored.  ``corder=False`` (the owners
+    are the columns): the matrix IS stored for the length of the call (4 or 8 bytes per entry, at most 2^31 - 1 entries): a
+    row-major result over column-owned walks is a transposition and a walk cannot be entered mid-chunk, so the column-major
+    fill is converted (stable CSC -> CSR) and multiplied as a stored CSR (``be_dt2t``); the scalar family with
+    ``transpose=False`` needs the row counts only and skips the conversion."""
+
+
+def _dt2t_functional(family, a, b, prob, y, seed, shape, transpose, corder, backend, out):
+    if backend not in (None, 'hip'):
+        raise ValueError(f"unknown backend {backend!r}: the per-synapse products have the 'hip' kernels only.")
+    ws = (a,) if family == 's' else (a, b)
+    as_np = out is None and A.wants_numpy(y, *ws)
+    res, _ = _jit_dt2t(family, a, b, prob, y, seed, gshape=(int(shape[0]), int(shape[1])), transpose=False, corder=bool(corder),
+                       by_row=not transpose, out=out)
+    return res if isinstance(res, np.ndarray) else A.to_result(res, as_np)
+
+
+def jitsmv_dt2t(weight, prob, y, seed=None, *, shape, transpose: bool = False, corder: bool = True,
+                backend: Optional[str] = None, out=None):
+    return _dt2t_functional('s', weight, None, prob, y, seed, shape, transpose, corder, backend, out)
+
+
+def jitumv_dt2t(w_low, w_high, prob, y, seed=None, *, shape, transpose: bool = False, corder: bool = True,
+                backend: Optional[str] = None, out=None):
+    return _dt2t_functional('u', w_low, w_high, prob, y, seed, shape, transpose, corder, backend, out)
+
+
+def jitnmv_dt2t(w_loc, w_scale, prob, y, seed=None, *, shape, transpose: bool = False, corder: bool = True,
+                backend: Optional[str] = None, out=None):
+    return _dt2t_functional('n', w_loc, w_scale, prob, y, seed, shape, transpose, corder, backend, out)
+
+
+jitsmv_dt2t.__doc__ = "Constant ``weight`` (reference ``brainevent/_jit_scalar/dt2t.py:57-107``).  " + _DT2T_DOC
+jitumv_dt2t.__doc__ = "Weights ``U(w_low, w_high)`` per edge (reference ``brainevent/_jit_uniform/dt2t.py``).  " + _DT2T_DOC
+jitnmv_dt2t.__doc__ = "Weights ``N(w_loc, w_scale)`` per edge (reference ``brainevent/_jit_normal/dt2t.py``).  " + _DT2T_DOC
+
+
+# =====================================================================================================
 # containers
 # =====================================================================================================
 def jit_edge_weights(family: str, a, b, seed, rows, cols):
@@ -694,15 +866,16 @@ class JITCMatrix(DataRepresentation):
             raise ValueError("todense() is ambiguous for a JIT-connectivity matrix: use mat.mv.todense() or mat.mm.todense().")
         return self.materialize(matrix_mode).todense()
 
-    def tocsr(self, matrix_mode: str = 'mv'):
+    def tocsr(self, matrix_mode: str = 'mv', *, canonical: bool = False):
         """The drawn connectivity as a :class:`CSR` of ``self.shape`` (reference ``mat.mv.tocsr()`` / ``mat.mm.tocsr()``).
         When the walk owners are the logical columns the native form is column-major and this re-encodes it (a device
-        sort: sizes up to 2^31 entries); :meth:`materialize` returns the native form without that step."""
-        return self.materialize(matrix_mode).tocsr()
+        sort: sizes up to 2^31 entries); :meth:`materialize` returns the native form without that step.  ``canonical``: as
+        in :meth:`materialize`."""
+        return self.materialize(matrix_mode, canonical=canonical).tocsr()
 
-    def tocsc(self, matrix_mode: str = 'mv'):
-        """The drawn connectivity as a :class:`CSC` of ``self.shape``."""
-        return self.materialize(matrix_mode).tocsc()
+    def tocsc(self, matrix_mode: str = 'mv', *, canonical: bool = False):
+        """The drawn connectivity as a :class:`CSC` of ``self.shape`` (``canonical``: as in :meth:`materialize`)."""
+        return self.materialize(matrix_mode, canonical=canonical).tocsc()
 
     def _owner_counts(self, matrix_mode: str = 'mv'):
         """The count pass of :meth:`materialize` (``be_jitc_csr_count``): stored entries per generator row — the rows of
@@ -732,13 +905,18 @@ class JITCMatrix(DataRepresentation):
         counts, (_, n_rows, *_rest) = self._owner_counts(matrix_mode)
         return counts[:n_rows]
 
-    def materialize(self, matrix_mode: str = 'mv'):
+    def materialize(self, matrix_mode: str = 'mv', *, canonical: bool = False):
         """Materialise the drawn connectivity on the device.  ``matrix_mode`` picks the matrix of the ``mv`` ops
         (lane stride 32) or of the ``mm`` ops (stride 4) — they differ, as in the reference.
 
         The generator matrix has the walk owners as rows; for a logical matrix it is the CSR form when the walk
         owners are the logical rows and the CSC form otherwise, so this returns a :class:`CSR` or a :class:`CSC`
         of ``self.shape`` (both multiply identically).  f32 weights.
+
+        ``canonical=False``: the entries of an owner come in the order the fill's tasks reserved their ranges — it differs
+        from call to call.  ``canonical=True``: the sorted fill (``be_jitc_fill_sorted``): the indices ascend within every
+        owner, as after the reference's sort (``_jit_scalar/csr.py:562-570``), and ``indices`` / ``data`` are bit-identical
+        from call to call — the order the per-synapse products (:meth:`dt2t`) are defined on.
         """
         from ._csr import CSR, CSC
         counts, (gshape, n_rows, walk, stride, clen, corder) = self._owner_counts(matrix_mode)
@@ -750,15 +928,44 @@ class JITCMatrix(DataRepresentation):
         indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
         mode = _FAMILY[self._family]
         weights = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev) if mode else None
-        f_fill = fn('be_jitc_csr_fill')
-        check(f_fill(mode, w0, w1, clen, self.seed & 0xFFFFFFFF, int(gshape[1]), n_rows, walk, stride, A.ptr(indptr),
-                     A.ptr(counts), A.ptr(indices), A.ptr(weights), A.stream_ptr()), 'be_jitc_csr_fill')
+        if canonical:
+            _fill_sorted(mode, w0, w1, clen, self.seed, int(gshape[1]), n_rows, walk, stride, indptr, None, False, indices, weights)
+        else:
+            f_fill = fn('be_jitc_csr_fill')
+            check(f_fill(mode, w0, w1, clen, self.seed & 0xFFFFFFFF, int(gshape[1]), n_rows, walk, stride, A.ptr(indptr),
+                         A.ptr(counts), A.ptr(indices), A.ptr(weights), A.stream_ptr()), 'be_jitc_csr_fill')
         data = weights[:nnz] if mode else torch.full((1,), float(w0), dtype=torch.float32, device=dev)
         # generator rows are the outputs of ``M @ v`` iff corder: then G is M row-wise (CSR), else column-wise (CSC)
         cls = CSR if corder else CSC
         out = cls._from_parts(data, indices[:nnz], indptr, shape=self.shape if self._is_row else self.shape,
                               numpy_result=not any(isinstance(w, torch.Tensor) for w in self._weights))
         return out
+
+    # -- per-synapse products (reference ``_jit_scalar/main.py:415-459`` and the uniform / normal twins) ------------------
+    def _dt2t(self, y, by_row: bool, out):
+        if self._is_row:                   # the orientation of ``M @ v`` (see __matmul__, _owner_counts)
+            gshape, transpose, corder = self.shape, False, self.corder
+        else:
+            gshape, transpose, corder = self.shape[::-1], True, self.corder
+        a, b = (self._weights + (None,))[:2]
+        as_np = out is None and A.wants_numpy(y, *self._weights)
+        res, indptr = _jit_dt2t(self._family, a, b, self.prob, y, self.seed, gshape=gshape, transpose=transpose, corder=corder,
+                                by_row=by_row, out=out, indptr=self.buffers.get(_INDPTR_KEY) if corder else None)
+        if indptr is not None:
+            self.buffers[_INDPTR_KEY] = indptr         # (the row offsets of the draw: a second call skips the count walk)
+        return res if isinstance(res, np.ndarray) else A.to_result(res, as_np)
+
+    def dt2t(self, y, w=None, out=None):
+        """``w(i, j) * y[i]`` for every drawn entry of the ``mv`` matrix (``y`` has ``self.shape[0]`` elements), in the flat
+        order of its canonical CSR — row-major, ascending columns: ``materialize('mv', canonical=True)`` / ``tocsr``.  ``w`` is
+        the protocol's argument and is ignored, as in the reference: the weights are this matrix's own.  Fused (nothing but the
+        result is stored; the int64 row offsets are cached on the object) exactly when :meth:`materialize` returns a
+        :class:`CSR`; otherwise the matrix is stored for the length of the call (see :func:`jitsmv_dt2t`).  f32 only."""
+        return self._dt2t(y, True, out)
+
+    def dt2t_transposed(self, y, w=None, out=None):
+        """``w(i, j) * y[j]`` (``y`` has ``self.shape[1]`` elements); otherwise as :meth:`dt2t`."""
+        return self._dt2t(y, False, out)
 
     def transpose(self, axes=None):
         assert axes is None, "transpose does not support axes argument."
@@ -860,14 +1067,14 @@ class _JITCModeView:
     def __init__(self, mat, mode):
         self._mat, self._mode = mat, mode
 
-    def todense(self):
-        return self._mat.materialize(self._mode).todense()
+    def todense(self, *, canonical: bool = False):
+        return self._mat.materialize(self._mode, canonical=canonical).todense()
 
-    def tocsr(self):
-        return self._mat.tocsr(self._mode)
+    def tocsr(self, *, canonical: bool = False):
+        return self._mat.tocsr(self._mode, canonical=canonical)
 
-    def tocsc(self):
-        return self._mat.tocsc(self._mode)
+    def tocsc(self, *, canonical: bool = False):
+        return self._mat.tocsc(self._mode, canonical=canonical)
 
 
 # =====================================================================================================

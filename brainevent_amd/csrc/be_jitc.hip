@@ -439,6 +439,127 @@ __global__ void __launch_bounds__(256) k_jit_csr_fill(JitP p, int64_t n_rows, co
   }
 }
 
+// ------------------------------------------------------------------------------------------------ sorted fill
+// The same generator rows with every owner's entries in ASCENDING walk coordinate — the canonical, column-sorted CSR the
+// reference sorts its materialisation into (brainevent/_jit_scalar/csr.py:562-570) — and, optionally, the per-synapse
+// product w(r, j) * y[r | j] written instead of (or beside) the indices, so that nothing but the result has to exist
+// (brainevent/_jit_{scalar,uniform,normal}/dt2t.py).
+//
+// One workgroup serves one owner row at a time (grid-stride over the rows: the result does not depend on the grid).  The
+// chunks are consecutive column ranges, so the row is swept in ascending GROUPS of kSortedBlock / stride chunks — one walker
+// thread per (chunk, lane) of the group, its (state, q) kept in registers for the whole group (the hash chain is sequential:
+// a walk is never restarted) — and each group in ascending WINDOWS of kSortedWindow columns:
+//   1. every walker sets its hits inside the window in an LDS bitmap of global columns (LDS atomicOr; a window that straddles
+//      a chunk boundary is just two walkers' bits side by side);
+//   2. each thread takes kSortedWords consecutive words, a block-wide exclusive scan of the popcounts gives its offset;
+//   3. it emits its set bits in order at indptr[row] + (entries of the earlier windows) + offset and clears its words.
+// No global atomics; the order is a function of the drawn matrix alone.  The mv draw of a row-owned matrix has at most
+// 4 x 32 walkers (one group); a walk over the long side (n_chunks > 4) or the mm draw (stride 4) takes more groups.
+constexpr int kSortedWindow = 65536;                                   // columns per window: 8 KiB of bitmap
+constexpr int kSortedBlock = 256;                                      // threads per workgroup
+constexpr int kSortedGridCap = 4096;                                   // workgroups per launch (rows beyond: grid-stride)
+constexpr int kSortedWords = kSortedWindow / 32 / kSortedBlock;        // bitmap words per thread (8)
+
+template <int MODE>
+__global__ void __launch_bounds__(kSortedBlock) k_jit_fill_sorted(JitP p, int64_t n_rows, const int64_t* __restrict__ indptr,
+                                                                  const float* __restrict__ y, int y_by_owner,
+                                                                  int32_t* __restrict__ indices_out,
+                                                                  float* __restrict__ values_out) {
+  __shared__ uint32_t bitmap[kSortedWindow / 32];
+  __shared__ uint32_t wave_total[kSortedBlock / 64];
+  const int t = threadIdx.x;
+  const int S = p.stride;
+  const int group_chunks = kSortedBlock / S;               // chunks whose walkers fit the workgroup (8 for mv, 64 for mm)
+  const int my_chunk = t / S;
+  const uint32_t l = (uint32_t)(t - my_chunk * S);
+  constexpr int64_t kEnd = INT64_MAX;
+  for (int i = t; i < kSortedWindow / 32; i += kSortedBlock) bitmap[i] = 0u;
+  __syncthreads();
+  for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
+    int64_t pos = indptr[row];                             // where the next window's first entry goes (uniform over the block)
+    const float y_row = (y != nullptr && y_by_owner) ? y[row] : 1.0f;
+    for (int c0 = 0; c0 < p.n_chunks; c0 += group_chunks) {
+      // ---- this thread's walker: chunk c0 + my_chunk, lane l
+      const int chunk = c0 + my_chunk;
+      int64_t cs = 0, width = 0;
+      uint32_t state = 1u, q = 0u;
+      int64_t j = kEnd;                                    // global column of the walker's next hit
+      if (chunk < p.n_chunks) {
+        cs = (int64_t)chunk * p.chunk_size;
+        const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
+        width = ce - cs;
+        state = lr_init(p.seed, (uint32_t)row, (uint32_t)chunk, l);
+        q = lr_initial_q(state, p.cl);
+        const uint64_t lj = (uint64_t)l + (uint64_t)S * q;
+        j = (int64_t)lj < width ? cs + (int64_t)lj : kEnd;
+      }
+      const int64_t g_begin = (int64_t)c0 * p.chunk_size;
+      const int64_t g_last = ((int64_t)c0 + group_chunks) * p.chunk_size;
+      const int64_t g_end = g_last < p.walk_len ? g_last : p.walk_len;
+      for (int64_t wb = g_begin; wb < g_end; wb += kSortedWindow) {
+        const int64_t we = wb + kSortedWindow < g_end ? wb + kSortedWindow : g_end;
+        // ---- 1. hits of this window
+        while (j < we) {
+          const uint32_t b = (uint32_t)(j - wb);
+          atomicOr(&bitmap[b >> 5], 1u << (b & 31u));
+          state = lr_next_nz(state);
+          q = q + 1u + lr_bounded(state, p.cl - 1u);
+          const uint64_t lj = (uint64_t)l + (uint64_t)S * q;
+          j = (int64_t)lj < width ? cs + (int64_t)lj : kEnd;
+        }
+        __syncthreads();
+        // ---- 2. offsets: popcount of this thread's words, scanned over the workgroup
+        uint32_t w[kSortedWords];
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int k = 0; k < kSortedWords; ++k) {
+          w[k] = bitmap[t * kSortedWords + k];
+          cnt += (uint32_t)__popc(w[k]);
+        }
+        uint32_t incl = cnt;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+          const uint32_t up = __shfl_up(incl, off, 64);
+          if ((t & 63) >= off) incl += up;
+        }
+        if ((t & 63) == 63) wave_total[t >> 6] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (int v = 0; v < kSortedBlock / 64; ++v) {
+          const uint32_t wt = wave_total[v];
+          before += v < (t >> 6) ? wt : 0u;
+          total += wt;
+        }
+        // ---- 3. emit in order, clear
+        if (cnt) {
+          int64_t o = pos + before + (incl - cnt);
+#pragma unroll
+          for (int k = 0; k < kSortedWords; ++k) {
+            uint32_t bits = w[k];
+            if (bits) bitmap[t * kSortedWords + k] = 0u;
+            while (bits) {
+              const int b = __ffs((int)bits) - 1;
+              bits &= bits - 1u;
+              const int64_t col = wb + (int64_t)(t * kSortedWords + k) * 32 + b;
+              if (indices_out != nullptr) indices_out[o] = (int32_t)col;
+              if (values_out != nullptr) {
+#pragma clang fp contract(off)
+                float v = edge_weight<MODE, float>(p, (uint32_t)row, (uint32_t)col);
+                if (y != nullptr) v = v * (y_by_owner ? y_row : y[col]);
+                values_out[o] = v;
+              }
+              ++o;
+            }
+          }
+        }
+        pos += total;
+        __syncthreads();                                   // the bitmap is clean and wave_total is free for the next window
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host
 }  // namespace
 
@@ -894,7 +1015,30 @@ int be_jitc_csr_fill(int mode, double w0, double w1, int64_t clen, uint32_t seed
   return BE_OK;
 }
 
-#define BE_DEF_JIT_VARIANT(F, M, W, WD)                                                                               \
+// The sorted, optionally fused fill (k_jit_fill_sorted): every owner's entries in ascending walk coordinate from indptr[r] on.
+// indices_out[pos] = j; values_out[pos] = w(r, j) [* y[r] if y_by_owner else y[j], when y is given]; either output may be NULL.
+// replaces: the sort of brainevent/_jit_scalar/csr.py:562-570 and the fused fill of brainevent/_jit_{scalar,uniform,normal}/dt2t.py.
+int be_jitc_fill_sorted(int mode, double w0, double w1, int64_t clen, uint32_t seed, int64_t shape1, int64_t n_rows,
+                        int64_t walk_len, int stride, const int64_t* indptr, const float* y, int y_by_owner,
+                        int32_t* indices_out, float* values_out, be_stream_t stream) {
+  BE_REQUIRE(mode >= 0 && mode <= 2, BE_ERR_INVALID, "mode must be 0 (scalar), 1 (uniform) or 2 (normal)");
+  BE_REQUIRE(n_rows >= 0 && walk_len >= 0 && shape1 >= 0, BE_ERR_INVALID, "bad shape");
+  BE_REQUIRE(stride == 32 || stride == 4, BE_ERR_INVALID, "stride must be 32 (mv) or 4 (mm)");
+  BE_REQUIRE(n_rows < (1ll << 32) && walk_len < (1ll << 31), BE_ERR_RANGE, "dimensions out of range");
+  BE_REQUIRE(indices_out != nullptr || values_out != nullptr, BE_ERR_INVALID, "neither indices_out nor values_out");
+  if (n_rows == 0 || walk_len == 0 || clen <= 0) return BE_OK;
+  BE_REQUIRE(indptr != nullptr, BE_ERR_INVALID, "null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const JitP p = make_params(shape1, walk_len, seed, clen, stride, w0, w1);
+  const dim3 grid((unsigned)std::min<int64_t>(n_rows, kSortedGridCap)), block(kSortedBlock);
+  if (mode == MODE_SCALAR) hipLaunchKernelGGL(k_jit_fill_sorted<MODE_SCALAR>, grid, block, 0, st, p, n_rows, indptr, y, y_by_owner, indices_out, values_out);
+  else if (mode == MODE_UNIFORM) hipLaunchKernelGGL(k_jit_fill_sorted<MODE_UNIFORM>, grid, block, 0, st, p, n_rows, indptr, y, y_by_owner, indices_out, values_out);
+  else hipLaunchKernelGGL(k_jit_fill_sorted<MODE_NORMAL>, grid, block, 0, st, p, n_rows, indptr, y, y_by_owner, indices_out, values_out);
+  BE_LAUNCH_CHECK();
+  return BE_OK;
+}
+
+#define BE_DEF_JIT_VARIANT(F, M, W, WD)                                                                              \
   int be_binary_jit##F##mv_notrans_##W(BE_JIT_MV_ARGS) {                                                               \
     return be_binary_jitmv(M, w0, w1, WD, clen, seed, spikes, spike_dtype, out, shape1, in_len, out_len, 1, scale_exp,  \
                            workspace, workspace_bytes, stream);                                                        \

@@ -744,6 +744,16 @@ int be_jitc_csr_count(int64_t clen, uint32_t seed, int64_t shape1, int64_t n_row
 int be_jitc_csr_fill(int mode, double w0, double w1, int64_t clen, uint32_t seed, int64_t shape1, int64_t n_rows,
                      int64_t walk_len, int stride, const int64_t* indptr, uint32_t* cursor, int32_t* indices,
                      float* weights, be_stream_t stream);
+/* the same rows in canonical order, optionally fused with the per-synapse product (dt2t): for every walk owner r the entries
+ * are written in ASCENDING walk coordinate j from indptr[r] on — the column-sorted CSR the reference sorts its
+ * materialisation into (brainevent/_jit_scalar/csr.py:562-570) and defines its per-synapse products on
+ * (brainevent/_jit_{scalar,uniform,normal}/dt2t.py).  indptr is the scan of be_jitc_csr_count's counts (int64, n_rows + 1).
+ *   indices_out[pos] = j                                                      (int32; may be NULL)
+ *   values_out[pos]  = w(r, j), times y[r] (y_by_owner) or y[j] when y != NULL  (f32; may be NULL — not both)
+ * w is w0 for mode 0 and the per-edge hash otherwise.  No scratch, no global atomics: bitwise the same from call to call. */
+int be_jitc_fill_sorted(int mode, double w0, double w1, int64_t clen, uint32_t seed, int64_t shape1, int64_t n_rows,
+                        int64_t walk_len, int stride, const int64_t* indptr, const float* y, int y_by_owner,
+                        int32_t* indices_out, float* values_out, be_stream_t stream);
 
 /* named per-family / per-dtype symbols: be_binary_jit{s,u,n}{mv,mm}_{notrans,trans}_{f32,f64,f16,bf16} */
 #define BE_JIT_MV_ARGS double w0, double w1, int64_t clen, uint32_t seed, const void *spikes, int spike_dtype,    \
