@@ -30,6 +30,8 @@ from ._dt2t import (csrmv_dt2t, csrmm_dt2t, cscmv_dt2t, cscmm_dt2t, fcnmv_dt2t, 
 from ._sddmm import sddmm_indices, sddmm_coo_indices, sddmm_p, sddmm_p_call
 from ._slice import (csr_slice_rows, csr_slice_rows_p, csr_slice_rows_p_call, csr_slice_rows_grad, csr_slice_rows_grad_p,
                      csr_slice_rows_grad_p_call)
+from ._arith import ArithmeticMixin, entries_dense_op_p
+from ._diag import csr_diag_position, csr_diag_add
 from ._graph import GraphedStep, capture_step
 from ._tuning import (ScatterTuning, DEFAULT_SCATTER_TUNING, get_scatter_tuning, save_scatter_tuning, apply_scatter_tuning,
                       tune_scatter_routes)

@@ -65,6 +65,8 @@ _SIGNATURES = dict(
     be_grad_mask_bytes='l:ll', be_grad_pack_activity='i:pillpp', be_grad_rows_workspace_bytes='l:l',
     be_grad_rows='i:ipiippilllplpllplp', be_grad_dense_workspace_bytes='l:ll', be_grad_dense='i:ipillplpllp',
     be_sddmm_rows='i:pippilplllpplp',
+    be_entries_dense_op='i:ppiippillllpillip', be_diag_scan='i:ppilllpp', be_diag_move='i:piippillpplpppip',
+    be_diag_fill='i:piillpppplppp',
 )
 
 # be_binary_jit{s,u,n}{mv,mm}_{notrans,trans}_{w}: BE_FOR_JIT_VARIANTS over BE_DECL_JIT_VARIANT (BE_JIT_MV_ARGS / BE_JIT_MM_ARGS)

@@ -32,6 +32,8 @@ from ._lib import call, check, fn, last_error
 from ._misc import _as_indptr, _as_int32_indices, _check_compressed_structure
 from ._op import OpKernel
 from ._plasticity import PlasticityMixin
+from . import _arith
+from ._arith import ArithmeticMixin
 from . import _autograd as _ag
 
 __all__ = ['CSR', 'CSC', 'ScatterPlan', 'BinnedScatter', 'Mirror', 'binary_csrmv', 'binary_csrmm', 'binary_csrmv_p',
@@ -1572,7 +1574,7 @@ def build_mirror_of(data, indices, indptr, row_len, m: int, k: int, *, keep_raw:
     return Mirror((k, m), t_data, t_idx, t_ptr, ws, perm, stamp, homo, b.counts)
 
 
-class StoredRowsData(PlasticityMixin, DataRepresentation):
+class StoredRowsData(PlasticityMixin, ArithmeticMixin, DataRepresentation):
     """Common base of the four containers that hold a matrix as stored rows — :class:`CSR` / :class:`CSC` and
     ``FixedNumPerPre`` / ``FixedNumPerPost``: each says what it stores (:meth:`_stored_rows`, ``_stored_transposed``); the life
     cycle of the two per-matrix workspaces in ``buffers`` — ``'scatter_plan'`` and ``'mirror'`` — is written once over that."""
@@ -1725,6 +1727,21 @@ class StoredRowsData(PlasticityMixin, DataRepresentation):
         from ._slice import container_slice_rows
         return container_slice_rows(self, index)
 
+    # -- arithmetic (``_arith``; reference ``_csr/main.py:1288-1319``, ``:1501-1593``, ``_fcn/main.py:721-780``) --------------
+    def _unitary_op(self, fn):
+        """A new container of this class around ``fn(self.data)`` on the same structure arrays (shared by reference).  The
+        dtype of ``data`` may change, its shape may not; one shared weight stays shared.  Of the cached buffers only the
+        structure-only ``diag_positions`` plan travels: scatter plans and mirrors embed weights.  Allocates a new value
+        array — to rescale every step write in place (``self.data.mul_(x)``, with ``prepare(plastic=...)`` or
+        ``refresh_weights()`` for the cached plans)."""
+        return _arith.rows_unitary(self, fn)
+
+    def _binary_op(self, other, fn):
+        return _arith.rows_binary(self, other, fn, False)
+
+    def _binary_rop(self, other, fn):
+        return _arith.rows_binary(self, other, fn, True)
+
 
 class CompressedSparseData(StoredRowsData):
     """Common base of :class:`CSR` and :class:`CSC` (reference ``_csr/main.py:182-277``)."""
@@ -1811,6 +1828,14 @@ class CompressedSparseData(StoredRowsData):
         else:
             np.add.at(out, (idx, primary), vals)
         return out
+
+    def diag_add(self, other):
+        """``self + diag(other)`` as a new matrix of the same class and shape; diagonal entries missing from the pattern are
+        inserted (reference ``_csr/main.py:878-950``).  ``other`` has shape ``(min(shape),)`` and ``data``'s dtype.  The plan
+        is cached in ``buffers['diag_positions']``; building it reads one number back from the device, later calls (and any
+        call on a result, which carries its own plan) do not.  One shared weight gives per-entry data (``_diag``)."""
+        from ._diag import container_diag_add
+        return container_diag_add(self, other)
 
     # -- per-matrix workspace ----------------------------------------------------------------------
     def _stored_rows(self) -> StoredRows:

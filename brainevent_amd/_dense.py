@@ -20,6 +20,7 @@ from ._data import DataRepresentation
 from ._lib import call, fn
 from ._op import OpKernel
 from ._plasticity import PlasticityMixin
+from ._arith import ArithmeticMixin, as_operand, broadcast_check, is_matrix
 from . import _autograd as _ag
 
 __all__ = ['Dense', 'binary_densemv', 'binary_densemm', 'binary_densemv_p', 'binary_densemm_p', 'binary_densemv_p_call',
@@ -128,7 +129,7 @@ def binary_densemm(weights, spikes, *, transpose, backend: Optional[str] = None)
     return A.to_result(binary_densemm_p_call(w, s, transpose=transpose, backend=backend)[0], as_np)
 
 
-class Dense(PlasticityMixin, DataRepresentation):
+class Dense(PlasticityMixin, ArithmeticMixin, DataRepresentation):
     """Explicit dense matrix with the representation contract of the sparse families (reference
     ``brainevent/_dense/main.py:60-510``, minus units and pytree plumbing): ``data``, ``shape``,
     ``backend``, ``buffers``, ``with_data``, ``todense``, ``T`` / ``transpose`` and event-driven ``@``.
@@ -170,6 +171,47 @@ class Dense(PlasticityMixin, DataRepresentation):
 
     def __getitem__(self, index):
         return self.todense()[index]
+
+    # -- arithmetic: plain torch on ``data`` (reference ``_dense/main.py:231-320``, ``:391-406``) -------------------------
+    def _wrap(self, data) -> 'Dense':
+        out = Dense(data, backend=self.backend, buffers=self.buffers)
+        out._numpy_result = self._numpy_result
+        return out
+
+    def _unitary_op(self, op) -> 'Dense':
+        return self._wrap(op(self.data))
+
+    def _binary_operand_data(self, other):
+        """The operand as torch takes it beside ``data``; it has to broadcast to exactly ``shape`` (``ValueError``)."""
+        if isinstance(other, Dense):
+            if other.shape != self.shape:
+                raise ValueError(f"Dense operand shape {other.shape} is not compatible with shape {self.shape}.")
+            return other.data
+        if is_matrix(other):
+            raise NotImplementedError("binary operation between Dense and sparse objects.")
+        x = as_operand(other)
+        if broadcast_check(self.shape, x.shape, 'Dense') != tuple(self.shape):
+            raise ValueError(f"operand shape {tuple(x.shape)} broadcasts beyond the Dense shape {self.shape}.")
+        if x.ndim == 0 and not isinstance(x, torch.Tensor):
+            return x.item()
+        return A.to_device(x) if not isinstance(x, torch.Tensor) else (x if x.device == self.data.device else x.to(self.data.device))
+
+    def _binary_op(self, other, op) -> 'Dense':
+        return self._wrap(op(self.data, self._binary_operand_data(other)))
+
+    def _binary_rop(self, other, op) -> 'Dense':
+        return self._wrap(op(self._binary_operand_data(other), self.data))
+
+    def diag_add(self, other) -> 'Dense':
+        """``self + diag(other)``: a copy with ``other`` (length ``min(shape)``, ``ValueError`` otherwise) added on the
+        diagonal."""
+        d = as_operand(other)
+        n = min(self.shape)
+        if d.ndim != 1 or int(d.shape[0]) != n:
+            raise ValueError(f"Dense.diag_add: the diagonal must have shape ({n},), got {tuple(d.shape)}.")
+        out = self.data.clone()
+        out.diagonal().add_(A.to_device(d, dtype=out.dtype))
+        return self._wrap(out)
 
     def _event(self, other):
         from ._event import is_event, event_operand

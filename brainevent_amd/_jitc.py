@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _array as A
+from ._arith import ArithmeticMixin, as_operand, is_matrix
 from ._data import DataRepresentation
 from ._event import BinaryArray, is_event, event_operand
 from ._lib import check, fn      # (not `call`: every lookup goes through this module's own `fn`, where the scale tests log it)
@@ -703,7 +704,7 @@ def _validate_prob(prob) -> float:
     return p
 
 
-class JITCMatrix(DataRepresentation):
+class JITCMatrix(ArithmeticMixin, DataRepresentation):
     """Common base of the six JIT-connectivity containers."""
     _family = 's'
     _is_row = True          # R classes: logical orientation == generator orientation; C classes: transposed
@@ -838,6 +839,46 @@ class JITCMatrix(DataRepresentation):
 
     def _params(self):
         return (*self._weights, self.prob, self.seed)
+
+    # -- arithmetic on the parameters (reference ``_jit_{scalar,uniform,normal}/main.py`` ``_unitary_op`` / ``_binary_op`` /
+    #    ``_binary_rop``) -----------------------------------------------------------------------------------------------------
+    #: how many of the weight parameters an operation acts on (Scalar: weight; Uniform: low and high; Normal: loc alone)
+    _arith_params = 1
+
+    def _new_mat(self, *weights):
+        """Same seed, prob, shape, corder and backend around new parameters; no stored twin travels."""
+        return type(self)((*weights, self.prob, self.seed), shape=self.shape, corder=self.corder, backend=self.backend)
+
+    def _unitary_op(self, op):
+        """``op`` on the parameters the family's arithmetic acts on (``_arith_params``); a new matrix with the same draw.
+
+        Equal to the elementwise operation on ``todense()``: Scalar — every ``op`` with ``op(0) == 0`` (``neg``, ``abs``,
+        ``*``, ``/`` by a scalar; ``+`` / ``-`` shift the stored entries only); Uniform — ``*`` / ``/`` by a scalar, ``+``,
+        ``-`` and ``neg`` on the stored entries, as far as the constructor accepts the new bounds (``low <= high``: a negative
+        factor or ``neg`` of a proper interval flips them and raises ``ValueError``, as in the reference) — ``abs`` is NOT
+        (``|low + u (high - low)|`` is no uniform draw between ``|low|`` and ``|high|``); Normal — only ``+`` / ``-`` on the
+        stored entries: ``*``, ``/``, ``neg`` and ``abs`` change ``loc`` and leave ``scale`` untouched (the reference's rule),
+        so ``(2 * M).todense() != 2 * M.todense()``."""
+        n = self._arith_params
+        return self._new_mat(*(op(w) for w in self._weights[:n]), *self._weights[n:])
+
+    def _binary(self, other, op, reverse: bool):
+        if is_matrix(other):
+            raise NotImplementedError(f"binary operation {getattr(op, '__name__', op)} between two sparse objects.")
+        x = as_operand(other)
+        if int(np.prod(x.shape)) != 1:
+            raise NotImplementedError(f"{type(self).__name__}: elementwise operation with an operand of shape {tuple(x.shape)}: "
+                                      "only a size-1 operand acts on the parameters of a JIT-connectivity matrix.")
+        s = x.reshape(()) if isinstance(x, torch.Tensor) else x.reshape(-1)[0].item()
+        return self._unitary_op((lambda w: op(s, w)) if reverse else (lambda w: op(w, s)))
+
+    def _binary_op(self, other, op):
+        """``op(parameter, other)`` for a size-1 ``other`` (``NotImplementedError`` otherwise); see :meth:`_unitary_op` for
+        which cases equal the elementwise operation on ``todense()``."""
+        return self._binary(other, op, False)
+
+    def _binary_rop(self, other, op):
+        return self._binary(other, op, True)
 
     def scatter_shard(self, world: int, rank: int) -> 'JITCScatterShard':
         """This rank's share of ``events @ self`` for a multi-GPU run (nothing is stored; see :class:`JITCScatterShard`)."""
@@ -1001,6 +1042,7 @@ class _ScalarInit(JITCMatrix):
 
 class _UniformInit(JITCMatrix):
     _family = 'u'
+    _arith_params = 2
 
     def __init__(self, low, high=None, prob=None, seed=None, *, shape, corder: bool = False,
                  backend: Optional[str] = None, buffers: Optional[Dict] = None):

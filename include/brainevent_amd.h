@@ -896,6 +896,45 @@ int be_sddmm_rows(void* out, int wdtype, const int32_t* indices, const void* ind
                   const int32_t* row_ids, int64_t n_rows, int64_t n_cols, int64_t nse, const void* p, const void* q,
                   int64_t n_batch, be_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * container arithmetic on a stored pattern (csrc/be_arith.hip).
+ *
+ * be_entries_dense_op: a dense operand sampled on the pattern, one value per stored entry e of row r(e), stored index c(e):
+ *   out[e] = op(weights[w_homo ? 0 : e], dense[r(e) * stride_row + c(e) * stride_col]),  op: 0 take (the dense value alone;
+ *   weights may be NULL), 1 mul (w * d), 2 div (w / d), 3 rdiv (d / w).
+ * replaces: the dense-operand branch of the binary operators (brainevent/_csr/main.py:1532-1543, :1580-1591 and the fixed-number
+ *           twins), without the row id array of nse integers.
+ * weights and out [nse] are in the weight dtype (f32 / f64 / f16 / bf16); dense is read in place through its two int64 ELEMENT
+ * strides, in the weight dtype or (dense_is_u8) as bytes holding a number (a bool / uint8 mask).  The row of an entry comes
+ * from indptr (int32 / int64, n_rows + 1 entries ascending from 0 to nse; empty rows allowed), else from the fixed row length
+ * row_len > 0.  An entry whose row or stored index lies outside [0, n_rows) / [0, n_cols) uses 0 for the dense value; nothing
+ * is read through it.  One operation in f32 (f64 for f64) and one rounding.  Every entry is written exactly once: no memset,
+ * no atomics, no workspace, no host synchronisation (graph-capturable).  Work is balanced per entry; entry offsets are 64-bit.
+ *
+ * be_diag_scan / be_diag_move / be_diag_fill: A + diag(d) on CSR arrays with the missing diagonal entries inserted
+ * replaces: csr_diag_position / csr_diag_add (brainevent/_csr/diag_add.py), on the device and past 2^31 entries.
+ *   scan: found [n_diag, 2] int64, set by the caller to (-1, INT64_MAX) per row: [r][0] <- the largest entry offset of row r
+ *         with index == r, [r][1] <- the smallest with index > r (64-bit integer atomic max / min: order-independent).
+ *   move: entry e of row r goes to dst = e + shift[r] + (0 <= ins[r] <= e): new_indices[dst] = indices[e], new_data[dst] =
+ *         weights[w_homo ? 0 : e], old_to_new[e] = dst (int32 / int64) — each of the three only where its pointer is not NULL.
+ *   fill: per i < n_diag, dest = (exist[i] >= 0 ? exist[i] : ins[i]) + shift[i]: new_indices[dest] = i where exist[i] < 0,
+ *         new_data[dest] = (exist[i] >= 0 ? weights[exist[i]] : 0) + diag[i], one addition in f32 (f64) and one rounding.
+ *         Launch it after move on the same stream: an existing diagonal is written by both, fill last.
+ * shift / ins [n_rows] and exist [n_diag] are int64 (the per-row plan brainevent_amd/_diag.py derives from `found`); a
+ * destination outside [0, new_nse) is skipped.  No memset, no float atomics, no host synchronisation.
+ * ---------------------------------------------------------------------------------------------- */
+int be_entries_dense_op(void* out, const void* weights, int w_homo, int wdtype, const int32_t* indices, const void* indptr,
+                        int indptr_is_i64, int64_t row_len, int64_t n_rows, int64_t n_cols, int64_t nse, const void* dense,
+                        int dense_is_u8, int64_t stride_row, int64_t stride_col, int op, be_stream_t stream);
+int be_diag_scan(const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t n_rows, int64_t n_diag, int64_t nse,
+                 void* found, be_stream_t stream);
+int be_diag_move(const void* weights, int w_homo, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64,
+                 int64_t n_rows, int64_t nse, const int64_t* shift, const int64_t* ins, int64_t new_nse, int32_t* new_indices,
+                 void* new_data, void* old_to_new, int old_to_new_is_i64, be_stream_t stream);
+int be_diag_fill(const void* weights, int w_homo, int wdtype, int64_t nse, int64_t n_diag, const int64_t* shift,
+                 const int64_t* ins, const int64_t* exist, const void* diag, int64_t new_nse, int32_t* new_indices,
+                 void* new_data, be_stream_t stream);
+
 #define BE_FOR_ALL_VARIANTS(X) \
   X(f32, BE_F32, bool, BE_SPIKE_BOOL)   X(f32, BE_F32, float, BE_SPIKE_FLOAT)   \
   X(f64, BE_F64, bool, BE_SPIKE_BOOL)   X(f64, BE_F64, float, BE_SPIKE_FLOAT)   \
