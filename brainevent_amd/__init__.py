@@ -6,6 +6,8 @@ functional ``binary_*`` operators, running hand-written HIP kernels (gfx950) thr
 plasticity updates (``update_*_on_binary_pre/post``, ``update_on_pre`` / ``update_on_post``).  The products are
 differentiable under ``torch.autograd`` (weights and float spikes; ``brainevent_amd._autograd``), and so are the float-operand
 products of the same containers (``csr @ x``); ``sddmm_*`` / ``M.sddmm`` sample a dense-dense product on a sparsity pattern.
+The JIT-connectivity products are differentiable in their parameters (``weight``; ``w_low, w_high``; ``w_loc, w_scale``) and
+their operand: both parameter gradients of a call come out of one walk of the generated edges (``jit_param_sums``).
 """
 from ._version import __version__
 __version_info__ = tuple(int(p) for p in __version__.split('.')[:3] if p.isdigit())
@@ -49,4 +51,4 @@ from ._jitc import (JITCScalarMatrix, JITCUniformMatrix, JITCNormalMatrix, JITCM
                     binary_jitnmv_p_call, binary_jitnmm_p_call, JITCScatterShard, JITCGatherShard,
                     jitsmv, jitsmm, jitumv, jitumm, jitnmv, jitnmm, jitsmv_p, jitsmm_p, jitumv_p, jitumm_p, jitnmv_p, jitnmm_p,
                     jitsmv_p_call, jitsmm_p_call, jitumv_p_call, jitumm_p_call, jitnmv_p_call, jitnmm_p_call,
-                    jitsmv_dt2t, jitumv_dt2t, jitnmv_dt2t)
+                    jitsmv_dt2t, jitumv_dt2t, jitnmv_dt2t, jit_param_sums)

@@ -89,4 +89,7 @@ for _w in ('f32', 'f64', 'f16', 'bf16'):
             _SIGNATURES[f'be_binary_densemv_{_t}_{_w}_{_s}'] = 'i:pppllplp'
             _SIGNATURES[f'be_binary_densemm_{_t}_{_w}_{_s}'] = 'i:ppplllplp'
 
+# declared after the variant wrappers, at the end of the header
+_SIGNATURES.update(be_jit_param_grad_workspace_bytes='l:llli', be_jit_param_grad='i:iiluppllllipplp')
+
 PROTOTYPES = {name: (_TYPES[sig[0]], tuple(_TYPES[c] for c in sig[2:])) for name, sig in _SIGNATURES.items()}

@@ -24,7 +24,10 @@ arrays:
   (``torch.matmul``: there is no event structure in them).
 * The float-operand products (``csr @ x`` with a plain array, ``csrmv / csrmm / fcnmv / fcnmm``) have a Function of their own,
   :class:`FloatRowsProduct`: the weight gradient is a sampled dense-dense product (``csrc/be_sddmm.hip``), the operand gradient
-  the transposed float product.  Not differentiable: the JITC float twins, ``Dense`` with a plain array, ``PlannedMatrix``.
+  the transposed float product.  Not differentiable: ``Dense`` with a plain array, ``PlannedMatrix``.
+* The JIT-connectivity products (``binary_jit{s,u,n}{mv,mm}``, ``jit{s,u,n}{mv,mm}`` and the six containers' ``@``) store no
+  weights; their one or two PARAMETERS are differentiated by :class:`JitProduct`: both parameter gradients of a call come out
+  of one walk of the generated edges (``csrc/be_jitc_grad.hip``), the operand gradient is the float twin of the transposed call.
 * Wrapping happens only when grad mode is on and an operand requires grad; otherwise the existing path runs untouched.  The
   forward pass of the Function IS the existing path (same route, same kernels, same bits).  Higher-order gradients are not
   supported (``once_differentiable``).
@@ -38,7 +41,7 @@ from . import _array as A
 from ._error import UnsupportedOperationError
 from ._lib import call, fn
 
-__all__ = ['RowsProduct', 'FloatRowsProduct', 'DenseProduct', 'SliceRows', 'needed']
+__all__ = ['RowsProduct', 'FloatRowsProduct', 'DenseProduct', 'JitProduct', 'SliceRows', 'needed']
 
 
 def _value(x):
@@ -324,6 +327,131 @@ def dense_product(run: Callable, weights, spikes_arg, operand, layout: str, *, t
     if weights.requires_grad:
         spec.mask, spec.nb = activity(operand, layout)
     return DenseProduct.apply(weights, s, spec)
+
+
+class JitSpec:
+    """What the backward pass of a JITC product needs besides the saved tensors: the generator ``(family, clen, seed, shape,
+    transpose, corder, rank)``, the operand / output layout, the product's dtype, the parameters that are no inputs of the node
+    (python / numpy values, tensors that need no gradient) and the operand's ``(shape, dtype, device)``."""
+    __slots__ = ('run', 'family', 'clen', 'seed', 'shape', 'transpose', 'corder', 'rank', 'layout', 'dtype', 'consts', 's_meta')
+
+    def __init__(self, run, family, clen, seed, shape, transpose, corder, rank, layout, dtype):
+        self.run, self.family, self.clen, self.seed = run, family, int(clen), int(seed)
+        self.shape, self.transpose, self.corder = (int(shape[0]), int(shape[1])), bool(transpose), bool(corder)
+        self.rank, self.layout, self.dtype = int(rank), layout, dtype
+        self.consts, self.s_meta = (None, None), None
+
+
+class JitProduct(torch.autograd.Function):
+    """The JIT-connectivity products, event and float operands alike.  The generator of a call — fixed by ``(shape, transpose,
+    corder, seed, prob, rank)``; rows = walk owners — carries ``w = w0 + t(r, j) w1`` on edge ``(r, j)`` (scalar: ``w = w0``).
+    With ``X`` the operand (event products: the 0/1 activity), ``g`` the incoming gradient, both neuron-major ``[., nb]``, and
+    ``(P, Q) = (g, X)`` when ``corder`` else ``(X, g)``:
+
+      ``S0 = sum_edges sum_b P[r, b] Q[j, b]``,  ``S1 = sum_edges t(r, j) sum_b P[r, b] Q[j, b]``   (``be_jit_param_grad``)
+      scalar: ``d weight = S0``;  uniform: ``d w_low = S0 - S1``, ``d w_high = S1``;  normal: ``d w_loc = S0``, ``d w_scale = S1``
+      ``dX = M.T @ g``: the float twin of the same family and rank with ``transpose`` and ``corder`` both flipped (the same
+      generator, so the same matrix), on the parameter values the forward pass read.
+
+    Inputs: the two parameters (``None`` where they are no size-1 floating tensors that require grad) and the differentiable
+    operand (``None`` otherwise).  Saved: those, and — when a parameter needs a gradient — the operand neuron-major in the
+    product's dtype.  The forward pass is ``spec.run()``: the existing path, the stored twin of ``prepare()`` included."""
+
+    @staticmethod
+    def forward(ctx, a, b, x, x_nm, spec: JitSpec):
+        out = spec.run()
+        ctx.spec = spec
+        ctx.save_for_backward(a, b, x_nm)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import _jitc as J
+        spec = ctx.spec
+        a, b, x_nm = ctx.saved_tensors
+        g_nm = _to_nm(g, spec.layout).to(spec.dtype).contiguous()
+        da = db = dx = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            P, Q = jit_pq(spec.corder, g_nm, x_nm)
+            sums = J.jit_param_sums(spec.family, P, Q, clen=spec.clen, seed=spec.seed, shape1=spec.shape[1],
+                                    stride=32 if spec.rank == 1 else 4)
+            ga, gb = jit_param_grads(spec.family, sums[0], sums[1])
+            if ctx.needs_input_grad[0]:
+                da = ga.to(a.dtype).reshape(a.shape).to(a.device)
+            if ctx.needs_input_grad[1]:
+                db = gb.to(b.dtype).reshape(b.shape).to(b.device)
+        if ctx.needs_input_grad[2]:
+            pa, pb = (a if a is not None else spec.consts[0]), (b if b is not None else spec.consts[1])
+            twin = getattr(J, f"jit{spec.family}{'mv' if spec.rank == 1 else 'mm'}_p_call")
+            t_transpose, t_corder = jit_twin_flags(spec.transpose, spec.corder)
+            d = twin(*((pa,) if spec.family == 's' else (pa, pb)), spec.clen, g_nm[:, 0] if spec.rank == 1 else g_nm, spec.seed,
+                     shape=spec.shape, transpose=t_transpose, corder=t_corder)[0]
+            shape, dtype, dev = spec.s_meta
+            dx = _from_nm(d, spec.layout, shape, dtype).to(dev)
+        return da, db, dx, None, None
+
+
+def jit_pq(corder: bool, g_nm, x_nm):
+    """``(P, Q)`` of the two sums: ``P`` is indexed by generator row, ``Q`` by walk position."""
+    return (g_nm, x_nm) if corder else (x_nm, g_nm)
+
+
+def jit_param_grads(family: str, s0, s1):
+    """The gradients of the family's parameters from ``S0`` / ``S1``: ``w = w0 + t w1`` with ``w1 = high - low`` (uniform)."""
+    if family == 's':
+        return s0, None
+    return (s0 - s1, s1) if family == 'u' else (s0, s1)
+
+
+def jit_twin_flags(transpose: bool, corder: bool):
+    """``(transpose, corder)`` of the float twin that computes ``M.T @ g`` on the same ``shape``: both flipped — the same
+    generator rows and walk, so the same matrix."""
+    return (not transpose, not corder)
+
+
+def _jit_param(p) -> bool:
+    """A differentiable JITC parameter: a size-1 floating tensor that requires grad (``prob`` and ``seed`` never are)."""
+    return isinstance(p, torch.Tensor) and p.requires_grad and p.dtype.is_floating_point and p.numel() == 1
+
+
+def jit_needed(params, x) -> bool:
+    """Whether a JITC product is to be recorded: grad mode is on and a parameter, or a float tensor operand (given as is or as
+    the value of an event container), requires grad."""
+    return torch.is_grad_enabled() and (any(_jit_param(p) for p in params) or diff_spikes(x) is not None)
+
+
+def _jit_operand_nm(x, source, layout: str, event: bool, dtype) -> torch.Tensor:
+    """The operand of a JITC product by value, neuron-major ``[in_len, nb]`` in the product's dtype; for an event product its
+    0/1 activity (the forward kernels' rule), built from the container's value where the kernels received packed words."""
+    if isinstance(x, A.PackedSpikes):
+        if source is not None:
+            x = source.value
+        else:
+            bits, n = x.bits, x.n
+            x = torch.empty(n, dtype=torch.bool, device=A.device())
+            call('be_unpack_spikes', A.ptr(A.to_device(bits)), n, A.ptr(x), A.stream_ptr())
+    elif isinstance(x, A.ActiveIds):
+        raise UnsupportedOperationError("a JIT-connectivity product takes no compacted id list.")
+    t = A.to_device(x.detach() if isinstance(x, torch.Tensor) else x)
+    if event:
+        t = (t > 0) if t.dtype.is_floating_point else (t != 0)
+    return _to_nm(t.to(dtype), layout).contiguous()
+
+
+def jit_product(run: Callable, family: str, a, b, clen, x, seed, *, shape, transpose: bool, corder: bool, rank: int, layout: str,
+                event: bool, dtype, source=None):
+    """Run ``run()`` (the existing forward path) as a :class:`JitProduct`.  ``x``: the operand as the product receives it (a
+    tensor, a numpy array, packed words — ``source`` is then the event container they came out of — or an event container's
+    value); ``layout`` as for :func:`rows_product`."""
+    spec = JitSpec(run, family, clen, seed, shape, transpose, corder, rank, layout, dtype)
+    pa, pb = (a if _jit_param(a) else None), (b if _jit_param(b) else None)
+    spec.consts = (None if pa is not None else a, None if pb is not None else b)
+    xd = diff_spikes(x)
+    if xd is not None:
+        spec.s_meta = (xd.shape, xd.dtype, xd.device)
+    x_nm = _jit_operand_nm(x, source, layout, event, dtype) if (pa is not None or pb is not None) else None
+    return JitProduct.apply(pa, pb, xd, x_nm, spec)
 
 
 class SliceRows(torch.autograd.Function):

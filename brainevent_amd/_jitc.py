@@ -33,7 +33,7 @@ __all__ = [
     'binary_jitsmv_p', 'binary_jitsmm_p', 'binary_jitumv_p', 'binary_jitumm_p', 'binary_jitnmv_p', 'binary_jitnmm_p',
     'binary_jitsmv_p_call', 'binary_jitsmm_p_call', 'binary_jitumv_p_call', 'binary_jitumm_p_call',
     'binary_jitnmv_p_call', 'binary_jitnmm_p_call', 'JITCScatterShard', 'JITCGatherShard', 'jit_scatter_class_columns',
-    'jit_edge_weights', 'jitsmv_dt2t', 'jitumv_dt2t', 'jitnmv_dt2t',
+    'jit_edge_weights', 'jitsmv_dt2t', 'jitumv_dt2t', 'jitnmv_dt2t', 'jit_param_sums',
 ]
 
 _FAMILY = {'s': 0, 'u': 1, 'n': 2}
@@ -233,11 +233,65 @@ def _arr(x):
     return x if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
+# =====================================================================================================
+# autograd: every ``*_p_call`` below runs its product through ``_autograd.JitProduct`` when a parameter or a
+# float tensor operand requires grad; otherwise the call is exactly what it was
+# =====================================================================================================
+#: geometry of the parameter-gradient walk (``k_jit_param_grad`` in ``csrc/be_jitc_grad.hip``: ``kParamGradThreads`` threads walk
+#: ``kParamGradThreads / stride`` generator rows of one chunk; ``kParamGradGridCap`` workgroups per launch, the (row block, chunk)
+#: tasks beyond are taken grid-stride)
+JIT_PARAM_GRAD_THREADS = 256
+JIT_PARAM_GRAD_GRID_CAP = 2048
+
+
+def jit_param_sums(family: str, P, Q, *, clen, seed, shape1, stride) -> torch.Tensor:
+    """``be_jit_param_grad``: the two sums the parameter gradients of a JITC product are made of, as a float64 tensor ``[2]`` on
+    the device (nothing is read back).  The generator is the one of ``(shape1, stride, clen, seed)`` with ``P.shape[0]`` rows
+    walked over ``Q.shape[0]`` positions; ``P [n_rows, nb]`` / ``Q [walk_len, nb]`` (a vector is ``nb = 1``) share a floating
+    dtype:  ``S0 = sum_edges sum_b P[r, b] Q[j, b]``,  ``S1 = sum_edges t(r, j) sum_b P[r, b] Q[j, b]`` (``0`` for ``'s'``)."""
+    if family not in _FAMILY:
+        raise ValueError(f"family must be 's', 'u' or 'n', got {family!r}.")
+    if stride not in (4, 32):
+        raise ValueError(f"stride must be 32 (the mv draw) or 4 (the mm draw), got {stride!r}.")
+    if not (isinstance(P, torch.Tensor) and isinstance(Q, torch.Tensor)):
+        raise TypeError("P and Q must be torch tensors.")
+    P = P.reshape(-1, 1) if P.ndim == 1 else P
+    Q = Q.reshape(-1, 1) if Q.ndim == 1 else Q
+    if P.ndim != 2 or Q.ndim != 2 or P.shape[1] != Q.shape[1]:
+        raise ValueError(f"P and Q must be [n_rows, nb] and [walk_len, nb], got {tuple(P.shape)} and {tuple(Q.shape)}.")
+    if P.dtype != Q.dtype or P.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
+        raise ValueError(f"P and Q must share a floating dtype (f32, f64, f16, bf16), got {P.dtype} and {Q.dtype}.")
+    P, Q = A.to_device(P.detach()), A.to_device(Q.detach())
+    n_rows, walk, nb = int(P.shape[0]), int(Q.shape[0]), int(P.shape[1])
+    sums = torch.empty(2, dtype=torch.float64, device=A.device())
+    ws = A.workspace(fn('be_jit_param_grad_workspace_bytes')(int(shape1), n_rows, walk, int(stride)))
+    check(fn('be_jit_param_grad')(_FAMILY[family], A.wcode(P), int(clen), seed & 0xFFFFFFFF, A.ptr(P), A.ptr(Q), int(shape1), n_rows,
+                                  walk, nb, int(stride), A.ptr(sums), A.ptr(ws), ws.numel(), A.stream_ptr()), 'be_jit_param_grad')
+    return sums
+
+
+def _jit_call(family: str, op, event: bool, a, b, clen, X, seed, *, shape, transpose, corder, backend, source=None):
+    """One ``*_p_call`` after its validation: ``op`` as before, recorded as a ``JitProduct`` when a gradient is asked for.
+    ``source``: the event container ``X`` came out of (its value stands for packed words in the recorded node)."""
+    from . import _autograd as AG
+    ws = (a,) if b is None else (a, b)
+    out_dtype = _weight_dtype(*ws)
+    shape = tuple(shape)
+
+    def run():
+        return op(a, b, clen, X, seed, shape=shape, transpose=transpose, corder=corder, out_dtype=out_dtype, backend=backend)
+
+    if not AG.jit_needed(ws, X):
+        return run()
+    return AG.jit_product(run, family, a, b, clen, X, seed, shape=shape, transpose=transpose, corder=corder, rank=X.ndim,
+                          layout='vec' if X.ndim == 1 else 'nm', event=event, dtype=out_dtype, source=source)
+
+
 # ---- scalar ------------------------------------------------------------------------------------------
 def binary_jitsmv_p_call(weight, clen, vector, seed, *, shape, transpose, corder, backend=None):
     _check_mv(vector, shape, transpose)
-    return [binary_jitsmv_p(weight, None, clen, vector, seed, shape=tuple(shape), transpose=transpose, corder=corder,
-                            out_dtype=_weight_dtype(weight), backend=backend)]
+    return [_jit_call('s', binary_jitsmv_p, True, weight, None, clen, vector, seed, shape=shape, transpose=transpose, corder=corder,
+                      backend=backend)]
 
 
 binary_jitsmv_p.def_call(binary_jitsmv_p_call)
@@ -245,8 +299,8 @@ binary_jitsmv_p.def_call(binary_jitsmv_p_call)
 
 def binary_jitsmm_p_call(weight, clen, B, seed, *, shape, transpose, corder, backend=None):
     _check_mm(B, shape, transpose)
-    return [binary_jitsmm_p(weight, None, clen, B, seed, shape=tuple(shape), transpose=transpose, corder=corder,
-                            out_dtype=_weight_dtype(weight), backend=backend)]
+    return [_jit_call('s', binary_jitsmm_p, True, weight, None, clen, B, seed, shape=shape, transpose=transpose, corder=corder,
+                      backend=backend)]
 
 
 binary_jitsmm_p.def_call(binary_jitsmm_p_call)
@@ -274,8 +328,8 @@ def binary_jitsmm(weight, prob, B, seed: Optional[int] = None, *, shape, transpo
 # ---- uniform -----------------------------------------------------------------------------------------
 def binary_jitumv_p_call(w_low, w_high, clen, vector, seed, *, shape, transpose, corder, backend=None):
     _check_mv(vector, shape, transpose)
-    return [binary_jitumv_p(w_low, w_high, clen, vector, seed, shape=tuple(shape), transpose=transpose, corder=corder,
-                            out_dtype=_weight_dtype(w_low, w_high), backend=backend)]
+    return [_jit_call('u', binary_jitumv_p, True, w_low, w_high, clen, vector, seed, shape=shape, transpose=transpose, corder=corder,
+                      backend=backend)]
 
 
 binary_jitumv_p.def_call(binary_jitumv_p_call)
@@ -283,8 +337,8 @@ binary_jitumv_p.def_call(binary_jitumv_p_call)
 
 def binary_jitumm_p_call(w_low, w_high, clen, B, seed, *, shape, transpose, corder, backend=None):
     _check_mm(B, shape, transpose)
-    return [binary_jitumm_p(w_low, w_high, clen, B, seed, shape=tuple(shape), transpose=transpose, corder=corder,
-                            out_dtype=_weight_dtype(w_low, w_high), backend=backend)]
+    return [_jit_call('u', binary_jitumm_p, True, w_low, w_high, clen, B, seed, shape=shape, transpose=transpose, corder=corder,
+                      backend=backend)]
 
 
 binary_jitumm_p.def_call(binary_jitumm_p_call)
@@ -310,8 +364,8 @@ def binary_jitumm(w_low, w_high, prob, B, seed: Optional[int] = None, *, shape, 
 # ---- normal ------------------------------------------------------------------------------------------
 def binary_jitnmv_p_call(w_loc, w_scale, clen, vector, seed, *, shape, transpose, corder, backend=None):
     _check_mv(vector, shape, transpose)
-    return [binary_jitnmv_p(w_loc, w_scale, clen, vector, seed, shape=tuple(shape), transpose=transpose, corder=corder,
-                            out_dtype=_weight_dtype(w_loc, w_scale), backend=backend)]
+    return [_jit_call('n', binary_jitnmv_p, True, w_loc, w_scale, clen, vector, seed, shape=shape, transpose=transpose, corder=corder,
+                      backend=backend)]
 
 
 binary_jitnmv_p.def_call(binary_jitnmv_p_call)
@@ -319,8 +373,8 @@ binary_jitnmv_p.def_call(binary_jitnmv_p_call)
 
 def binary_jitnmm_p_call(w_loc, w_scale, clen, B, seed, *, shape, transpose, corder, backend=None):
     _check_mm(B, shape, transpose)
-    return [binary_jitnmm_p(w_loc, w_scale, clen, B, seed, shape=tuple(shape), transpose=transpose, corder=corder,
-                            out_dtype=_weight_dtype(w_loc, w_scale), backend=backend)]
+    return [_jit_call('n', binary_jitnmm_p, True, w_loc, w_scale, clen, B, seed, shape=shape, transpose=transpose, corder=corder,
+                      backend=backend)]
 
 
 binary_jitnmm_p.def_call(binary_jitnmm_p_call)
@@ -422,9 +476,8 @@ jitnmv_p, jitnmm_p = _make_float_ops('n', 'normal')
 
 def _float_call(mv: bool, op, a, b, clen, X, seed, *, shape, transpose, corder, backend=None):
     (_check_mv if mv else _check_mm)(X, shape, transpose)
-    ws_ = (a,) if b is None else (a, b)
-    return [op(a, b, clen, X, seed, shape=tuple(shape), transpose=transpose, corder=corder, out_dtype=_weight_dtype(*ws_),
-               backend=backend)]
+    family = op.name[len('jit')]        # jit{s,u,n}{mv,mm}
+    return [_jit_call(family, op, False, a, b, clen, X, seed, shape=shape, transpose=transpose, corder=corder, backend=backend)]
 
 
 def jitsmv_p_call(weight, clen, vector, seed, *, shape, transpose, corder, backend=None):
@@ -732,17 +785,39 @@ class JITCMatrix(ArithmeticMixin, DataRepresentation):
                 f"seed={self.seed}, corder={self.corder}, backend={self.backend})")
 
     # -- family hooks ------------------------------------------------------------------------------
-    def _mv(self, v, *, shape, transpose, corder):
-        f = {'s': binary_jitsmv_p_call, 'u': binary_jitumv_p_call, 'n': binary_jitnmv_p_call}[self._family]
-        args = self._weights if self._family != 's' else (self._weights[0],)
-        return f(*args, _initialize_conn_length(self.prob), v, self.seed, shape=shape, transpose=transpose,
-                 corder=corder, backend=self.backend)[0]
+    def _orientation(self, left: bool):
+        """``(shape, transpose, corder)`` of the functional that computes ``other @ self`` (``left``) or ``self @ other``
+        (reference ``_jit_scalar/main.py:885-1065`` for R, ``:1069+`` for C)."""
+        if left:
+            return (self.shape, True, not self.corder) if self._is_row else (self.shape[::-1], False, not self.corder)
+        return (self.shape, False, self.corder) if self._is_row else (self.shape[::-1], True, self.corder)
 
-    def _mm(self, B, *, shape, transpose, corder):
-        f = {'s': binary_jitsmm_p_call, 'u': binary_jitumm_p_call, 'n': binary_jitnmm_p_call}[self._family]
-        args = self._weights if self._family != 's' else (self._weights[0],)
-        return f(*args, _initialize_conn_length(self.prob), B, self.seed, shape=shape, transpose=transpose,
-                 corder=corder, backend=self.backend)[0]
+    def _event_product(self, mv: bool, v, *, shape, transpose, corder, source=None):
+        """``binary_jit{s,u,n}{mv,mm}_p_call`` on this matrix's parameters; ``source``: the event container ``v`` came out of
+        (its value stands for packed words where a parameter gradient is recorded)."""
+        (_check_mv if mv else _check_mm)(v, shape, transpose)
+        if isinstance(v, torch.Tensor) and source is not None and not isinstance(source, BinaryArray):
+            v = v.detach()                 # (only a BinaryArray's float tensor receives a gradient: DESIGN.md 2.7)
+        ops = {'s': (binary_jitsmv_p, binary_jitsmm_p), 'u': (binary_jitumv_p, binary_jitumm_p), 'n': (binary_jitnmv_p, binary_jitnmm_p)}
+        a, b = (self._weights + (None,))[:2]
+        return _jit_call(self._family, ops[self._family][0 if mv else 1], True, a, b, _initialize_conn_length(self.prob), v, self.seed,
+                         shape=shape, transpose=transpose, corder=corder, backend=self.backend, source=source)
+
+    def _stored_product(self, S, other, left: bool):
+        """The product on the stored twin of :meth:`prepare` — its route and its bits —; a gradient is taken on the on-the-fly
+        generator of the same rank (the same draw: nothing in the stored matrix is differentiated)."""
+        from . import _autograd as AG
+        run = (lambda: other @ S) if left else (lambda: S @ other)
+        if not AG.jit_needed(self._weights, other):
+            return run()
+        shape, transpose, corder = self._orientation(left)
+        a, b = (self._weights + (None,))[:2]
+        layout = 'vec' if other.ndim == 1 else ('bm' if left else 'nm')
+        x = other.value
+        if isinstance(x, torch.Tensor) and not isinstance(other, BinaryArray):
+            x = x.detach()                 # (only a BinaryArray's float tensor receives a gradient: DESIGN.md 2.7)
+        return AG.jit_product(run, self._family, a, b, _initialize_conn_length(self.prob), x, self.seed, shape=shape,
+                              transpose=transpose, corder=corder, rank=other.ndim, layout=layout, event=True, dtype=self.dtype)
 
     def _out(self, r, v):
         as_np = A.wants_numpy(v, *self._weights)
@@ -786,10 +861,7 @@ class JITCMatrix(ArithmeticMixin, DataRepresentation):
         """A plain (non-event) array against the on-the-fly matrix: the float twins, same (shape, transpose, corder) mapping as
         the event-driven products below."""
         x = other if isinstance(other, torch.Tensor) else np.asarray(other)
-        if left:
-            shape, transpose, corder = (self.shape, True, not self.corder) if self._is_row else (self.shape[::-1], False, not self.corder)
-        else:
-            shape, transpose, corder = (self.shape, False, self.corder) if self._is_row else (self.shape[::-1], True, self.corder)
+        shape, transpose, corder = self._orientation(left)
         mvf = {'s': jitsmv_p_call, 'u': jitumv_p_call, 'n': jitnmv_p_call}[self._family]
         mmf = {'s': jitsmm_p_call, 'u': jitumm_p_call, 'n': jitnmm_p_call}[self._family]
         args = self._weights if self._family != 's' else (self._weights[0],)
@@ -808,16 +880,13 @@ class JITCMatrix(ArithmeticMixin, DataRepresentation):
             return self._dense_operand(other, left=False)
         S = self._stored(other.ndim)
         if S is not None:                  # prepare(): the stored matrix, event-driven through its own workspaces
-            return S @ other
+            return self._stored_product(S, other, left=False)
         v = event_operand(other)           # (1-D bit-packed containers: their words, BE_SPIKE_BITS — no unpack launch)
-        if self._is_row:
-            shape, transpose, corder = self.shape, False, self.corder
-        else:
-            shape, transpose, corder = self.shape[::-1], True, self.corder
+        shape, transpose, corder = self._orientation(left=False)
         if v.ndim == 1:
-            return self._out(self._mv(v, shape=shape, transpose=transpose, corder=corder), v)
+            return self._out(self._event_product(True, v, shape=shape, transpose=transpose, corder=corder, source=other), v)
         if v.ndim == 2:
-            return self._out(self._mm(v, shape=shape, transpose=transpose, corder=corder), v)
+            return self._out(self._event_product(False, v, shape=shape, transpose=transpose, corder=corder, source=other), v)
         raise NotImplementedError(f"matmul with object of shape {v.shape}")
 
     def __rmatmul__(self, other):
@@ -825,16 +894,13 @@ class JITCMatrix(ArithmeticMixin, DataRepresentation):
             return self._dense_operand(other, left=True)
         S = self._stored(other.ndim)
         if S is not None:
-            return other @ S
+            return self._stored_product(S, other, left=True)
         v = event_operand(other)           # (1-D bit-packed containers: their words, BE_SPIKE_BITS — no unpack launch)
-        if self._is_row:
-            shape, transpose, corder = self.shape, True, not self.corder
-        else:
-            shape, transpose, corder = self.shape[::-1], False, not self.corder
+        shape, transpose, corder = self._orientation(left=True)
         if v.ndim == 1:
-            return self._out(self._mv(v, shape=shape, transpose=transpose, corder=corder), v)
+            return self._out(self._event_product(True, v, shape=shape, transpose=transpose, corder=corder, source=other), v)
         if v.ndim == 2:
-            return self._out(self._mm(v.T, shape=shape, transpose=transpose, corder=corder).T, v)
+            return self._out(self._event_product(False, v.T, shape=shape, transpose=transpose, corder=corder, source=other).T, v)
         raise NotImplementedError(f"matmul with object of shape {v.shape}")
 
     def _params(self):

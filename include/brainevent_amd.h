@@ -943,6 +943,25 @@ int be_diag_fill(const void* weights, int w_homo, int wdtype, int64_t nse, int64
 
 BE_FOR_ALL_VARIANTS(BE_DECL_VARIANT)
 
+/* ------------------------------------------------------------------------------------------------
+ * be_jit_param_grad: the parameter gradients of a JIT-connectivity product (brainevent_amd/csrc/be_jitc_grad.hip)
+ * replaces: the reference's per-parameter composition — a whole float product with the parameters set to (1, 0) / (0, 1) and a
+ *           dot product each (brainevent/_jit_normal/binary.py:442-505, _jit_normal/float.py:843-910 and the scalar / uniform twins).
+ * The generator of (shape1, n_rows, walk_len, stride, clen, seed) — rows = walk owners, as be_jitmm_float walks it — carries
+ * w = w0 + t(r, j) * w1 on edge (r, j) (t: the uniform / normal hash of the family `mode`; scalar: w = w0).  With P [n_rows, nb]
+ * and Q [walk_len, nb], contiguous, both of `wdtype`:
+ *   sums[0] = S0 = sum_edges sum_b P[r, b] Q[j, b]        sums[1] = S1 = sum_edges t(r, j) sum_b P[r, b] Q[j, b]    (scalar: 0)
+ * One walk whatever nb is; loads are widened to f64, products and sums are f64, t is the f32 value the products use.  A
+ * generator row whose P row is all zero is not walked.  No float atomics: fixed shuffle trees and fixed orders over a grid that
+ * depends on (shape1, n_rows, walk_len, stride) alone, so the 16 bytes are the same from call to call.  clen <= 0, n_rows == 0,
+ * walk_len == 0 or nb == 0: two zeros are written on the stream and nothing is read.  n_rows, walk_len < 2^32; 64-bit offsets.
+ * No host synchronisation (graph-capturable).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t be_jit_param_grad_workspace_bytes(int64_t shape1, int64_t n_rows, int64_t walk_len, int stride);
+int be_jit_param_grad(int mode, int wdtype, int64_t clen, uint32_t seed, const void* P, const void* Q, int64_t shape1,
+                      int64_t n_rows, int64_t walk_len, int64_t nb, int stride, double* sums /* [2]: S0, S1 */,
+                      void* workspace, int64_t workspace_bytes, be_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
