@@ -268,17 +268,11 @@ int be_entries_dense_op(void* out, const void* weights, int w_homo, int wdtype, 
   }
   const RowPtr rp{indptr, indptr_is_i64, row_len};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (wdtype) {
-    case BE_F32:  return entries_dense_op_t<float>(out, weights, w_homo, indices, rp, n_rows, n_cols, nse, dense, dense_is_u8,
-                                                   stride_row, stride_col, op, st);
-    case BE_F64:  return entries_dense_op_t<double>(out, weights, w_homo, indices, rp, n_rows, n_cols, nse, dense, dense_is_u8,
-                                                    stride_row, stride_col, op, st);
-    case BE_F16:  return entries_dense_op_t<__half>(out, weights, w_homo, indices, rp, n_rows, n_cols, nse, dense, dense_is_u8,
-                                                    stride_row, stride_col, op, st);
-    case BE_BF16: return entries_dense_op_t<__hip_bfloat16>(out, weights, w_homo, indices, rp, n_rows, n_cols, nse, dense,
-                                                            dense_is_u8, stride_row, stride_col, op, st);
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;
-  }
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return entries_dense_op_t<W>(out, weights, w_homo, indices, rp, n_rows, n_cols, nse, dense, dense_is_u8, stride_row, stride_col, op,
+                                 st);
+  });
 }
 
 int be_diag_scan(const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t n_rows, int64_t n_diag, int64_t nse,
@@ -306,16 +300,12 @@ int be_diag_move(const void* weights, int w_homo, int wdtype, const int32_t* ind
   BE_REQUIRE(weights || !new_data, BE_ERR_INVALID, "values to move but no weights");
   const RowPtr rp{indptr, indptr_is_i64, -1};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (new_data ? wdtype : BE_F32) {
-    case BE_F32:  return diag_move_t<float>(weights, w_homo, indices, rp, n_rows, nse, shift, ins, new_nse, new_indices, new_data,
-                                            old_to_new, old_to_new_is_i64, st);
-    case BE_F64:  return diag_move_t<double>(weights, w_homo, indices, rp, n_rows, nse, shift, ins, new_nse, new_indices, new_data,
-                                             old_to_new, old_to_new_is_i64, st);
-    case BE_F16:
-    case BE_BF16: return diag_move_t<__half>(weights, w_homo, indices, rp, n_rows, nse, shift, ins, new_nse, new_indices, new_data,
-                                             old_to_new, old_to_new_is_i64, st);      // (a move of 16-bit patterns)
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;
-  }
+  return be_dispatch_wdtype(new_data ? wdtype : BE_F32, [&](auto w) {
+    using T = typename decltype(w)::type;
+    using W = std::conditional_t<std::is_same_v<T, __hip_bfloat16>, __half, T>;      // (a move of 16-bit patterns)
+    return diag_move_t<W>(weights, w_homo, indices, rp, n_rows, nse, shift, ins, new_nse, new_indices, new_data, old_to_new,
+                          old_to_new_is_i64, st);
+  });
 }
 
 int be_diag_fill(const void* weights, int w_homo, int wdtype, int64_t nse, int64_t n_diag, const int64_t* shift,
@@ -326,14 +316,10 @@ int be_diag_fill(const void* weights, int w_homo, int wdtype, int64_t nse, int64
   BE_REQUIRE(shift && ins && exist, BE_ERR_INVALID, "null pointer");
   BE_REQUIRE(!new_data || (diag && (weights || nse == 0)), BE_ERR_INVALID, "values to write but no weights / diagonal");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (new_data ? wdtype : BE_F32) {
-    case BE_F32:  return diag_fill_t<float>(weights, w_homo, nse, n_diag, shift, ins, exist, diag, new_nse, new_indices, new_data, st);
-    case BE_F64:  return diag_fill_t<double>(weights, w_homo, nse, n_diag, shift, ins, exist, diag, new_nse, new_indices, new_data, st);
-    case BE_F16:  return diag_fill_t<__half>(weights, w_homo, nse, n_diag, shift, ins, exist, diag, new_nse, new_indices, new_data, st);
-    case BE_BF16: return diag_fill_t<__hip_bfloat16>(weights, w_homo, nse, n_diag, shift, ins, exist, diag, new_nse, new_indices,
-                                                     new_data, st);
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;
-  }
+  return be_dispatch_wdtype(new_data ? wdtype : BE_F32, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return diag_fill_t<W>(weights, w_homo, nse, n_diag, shift, ins, exist, diag, new_nse, new_indices, new_data, st);
+  });
 }
 
 }  // extern "C"

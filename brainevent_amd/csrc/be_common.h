@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 
 // ---------------------------------------------------------------- error plumbing (never abort)
 #include "../../include/brainevent_amd.h"   // BE_OK / BE_ERR_* codes
@@ -80,6 +81,34 @@ template <> struct WTraits<__hip_bfloat16> {
   __device__ static __forceinline__ void store_d(__hip_bfloat16* p, int64_t i, double v) { p[i] = __float2bfloat16((float)v); }
 };
 
+// ---------------------------------------------------------------- run-time value -> template argument (host)
+// `f` is a generic lambda taking a tag: `using W = typename decltype(tag)::type` for a type, `decltype(tag)::value` for a constant.
+// BE_REQUIRE / BE_HIP name their function by __func__, which is `operator()` inside a lambda: a lambda only launches a kernel or
+// calls a named function; every check stays in a named function.
+template <typename T> struct be_type_tag { using type = T; };
+
+template <typename F>
+inline int be_dispatch_wdtype(int wdtype, F&& f) {
+  switch (wdtype) {
+    case BE_F32: return f(be_type_tag<float>{});
+    case BE_F64: return f(be_type_tag<double>{});
+    case BE_F16: return f(be_type_tag<__half>{});
+    case BE_BF16: return f(be_type_tag<__hip_bfloat16>{});
+    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;
+  }
+}
+template <typename F>
+inline int be_dispatch_bool(bool flag, F&& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+// weight dtype x homo flag: f(be_type_tag<W>, std::bool_constant<HOMO>)
+template <typename F>
+inline int be_dispatch_w_homo(int wdtype, bool homo, F&& f) {
+  return be_dispatch_wdtype(wdtype, [&](auto w) { return be_dispatch_bool(homo, [&](auto h) { return f(w, h); }); });
+}
+// bytes of a weight / output element (an unknown dtype is refused by be_dispatch_wdtype, not here)
+inline size_t be_wbytes(int wdtype) { return wdtype == BE_F64 ? 8 : (wdtype == BE_F32 ? 4 : 2); }
+
 // spike element: bool tag = any 1-byte integer (!= 0), float tag = f32 (> 0)
 struct SpikeBool {
   using type = uint8_t;
@@ -124,6 +153,18 @@ __device__ __forceinline__ T wave_sum(T v) {
 
 __device__ __forceinline__ uint32_t be_mix32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x;
+}
+
+// w * 2^scale_exp as a 64-bit two's-complement integer, built from f32 operations only:
+//   t = w * 2^(scale_exp-32);  hi = floor(t);  lo = (t - hi) * 2^32   (all three steps are exact in f32:
+//   power-of-two scaling, and t - floor(t) has no more significant bits than t).
+// The caller guarantees |w| * 2^scale_exp < 2^62 / m, so hi fits an int32.  `scale` = 2^(scale_exp-32).
+__device__ __forceinline__ unsigned long long fixed_from_f32(float w, float scale) {
+  const float t = w * scale;
+  const float hf = floorf(t);
+  const int hi = (int)hf;
+  const unsigned lo = (unsigned)((t - hf) * 4294967296.0f);
+  return ((unsigned long long)(unsigned)hi << 32) | lo;
 }
 
 static inline int64_t be_align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }

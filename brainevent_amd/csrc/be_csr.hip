@@ -1330,8 +1330,10 @@ int be_binary_csrmm_t(const void* weights, int homo, int wdtype, const int32_t* 
              "workspace too small");
   RowPtr rp{indptr, indptr_is_i64, row_len};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  BE_DISPATCH_W(wdtype, homo, return (csrmv_t_direct<W, HOMO>(weights, indices, rp, spikes, spike_dtype, out, m, k, n_batch, workspace, st)));
-  return BE_OK;
+  return be_dispatch_w_homo(wdtype, homo, [&](auto w, auto h) {
+    using W = typename decltype(w)::type;
+    return csrmv_t_direct<W, decltype(h)::value>(weights, indices, rp, spikes, spike_dtype, out, m, k, n_batch, workspace, st);
+  });
 }
 
 int be_binary_csrmv_t(const void* weights, int homo, int wdtype, const int32_t* indices, const void* indptr,
@@ -1365,8 +1367,10 @@ int be_binary_csrmm_nt(const void* weights, int homo, int wdtype, const int32_t*
   // average row length steers the lanes-per-row choice; for CSR it needs indptr[m] which lives on the
   // device, so the caller's row_len doubles as a hint (row_len >= 0: exact for fixed rows, a hint for CSR)
   const int64_t nnz_hint = (row_len >= 0 ? row_len : 64) * m;
-  BE_DISPATCH_W(wdtype, homo, return (csrmv_nt<W, HOMO>(weights, indices, rp, nnz_hint, spikes, spike_dtype, out, m, k, n_batch, workspace, st)));
-  return BE_OK;
+  return be_dispatch_w_homo(wdtype, homo, [&](auto w, auto h) {
+    using W = typename decltype(w)::type;
+    return csrmv_nt<W, decltype(h)::value>(weights, indices, rp, nnz_hint, spikes, spike_dtype, out, m, k, n_batch, workspace, st);
+  });
 }
 
 int be_binary_csrmv_nt(const void* weights, int homo, int wdtype, const int32_t* indices, const void* indptr,
@@ -1394,8 +1398,10 @@ int be_binary_csrmm_t_indexed(const void* weights, int homo, int wdtype, const i
              "workspace too small");
   RowPtr rp{indptr, indptr_is_i64, row_len};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  BE_DISPATCH_W(wdtype, 0, return (csrmv_t_direct<W, HOMO>(weights, indices, rp, spikes, spike_dtype, out, m, k, n_batch, workspace, st, perm, perm_is_i64)));
-  return BE_OK;
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return csrmv_t_direct<W, false>(weights, indices, rp, spikes, spike_dtype, out, m, k, n_batch, workspace, st, perm, perm_is_i64);
+  });
 }
 
 int be_binary_csrmm_nt_indexed(const void* weights, int homo, int wdtype, const int32_t* indices, const void* indptr,
@@ -1417,13 +1423,10 @@ int be_binary_csrmm_nt_indexed(const void* weights, int homo, int wdtype, const 
              BE_ERR_WORKSPACE, "workspace too small");
   RowPtr rp{indptr, indptr_is_i64, row_len};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (wdtype) {
-    case BE_F32: return csrmv_nt_indexed<float>(weights, indices, rp, perm, perm_is_i64, spikes, spike_dtype, out, m, k, n_batch, workspace, st);
-    case BE_F64: return csrmv_nt_indexed<double>(weights, indices, rp, perm, perm_is_i64, spikes, spike_dtype, out, m, k, n_batch, workspace, st);
-    case BE_F16: return csrmv_nt_indexed<__half>(weights, indices, rp, perm, perm_is_i64, spikes, spike_dtype, out, m, k, n_batch, workspace, st);
-    case BE_BF16: return csrmv_nt_indexed<__hip_bfloat16>(weights, indices, rp, perm, perm_is_i64, spikes, spike_dtype, out, m, k, n_batch, workspace, st);
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;
-  }
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return csrmv_nt_indexed<W>(weights, indices, rp, perm, perm_is_i64, spikes, spike_dtype, out, m, k, n_batch, workspace, st);
+  });
 }
 
 // ---------------------------------------------------------------- per-variant symbols

@@ -2270,10 +2270,15 @@ int be_scatter_plan_fill_ordered(const void* weights, int homo, int wdtype, cons
   }
   BE_REQUIRE(layout == BE_PLAN_U16, BE_ERR_INVALID, "unknown plan layout");
   const int grid = grid_for(m, 1, 256 * 16);
-  BE_DISPATCH_W(wdtype, homo,
-                hipLaunchKernelGGL((k_plan_fill<W, HOMO>), dim3(grid), dim3(256), 0, st, static_cast<const W*>(weights),
-                                   indices, rp, m, slice_shift, (uint32_t)width_of(slice_shift, slice_width), n_slices,
-                                   static_cast<const uint2*>(seg), static_cast<unsigned char*>(blob), maxabs_bits));
+  const int rc = be_dispatch_w_homo(wdtype, homo, [&](auto w, auto h) {
+    using W = typename decltype(w)::type;
+    constexpr bool HOMO = decltype(h)::value;
+    hipLaunchKernelGGL((k_plan_fill<W, HOMO>), dim3(grid), dim3(256), 0, st, static_cast<const W*>(weights),
+                       indices, rp, m, slice_shift, (uint32_t)width_of(slice_shift, slice_width), n_slices,
+                       static_cast<const uint2*>(seg), static_cast<unsigned char*>(blob), maxabs_bits);
+    return BE_OK;
+  });
+  if (rc != BE_OK) return rc;
   BE_LAUNCH_CHECK();
   return BE_OK;
 }
@@ -2713,10 +2718,15 @@ int be_binary_csrmm_t_plan(const void* weights, int homo, int wdtype, const void
   BE_LAUNCH_CHECK();
   const int rgrid = grid_for(k, 256, n_batch >= 8 ? 256 : 2048);
   const int64_t pstride = (int64_t)n_tasks * S;
-  BE_DISPATCH_W(wdtype, homo,
-                hipLaunchKernelGGL((k_plan_reduce<W, HOMO>), dim3(rgrid, (unsigned)n_batch), dim3(256), 0, st,
-                                   static_cast<const typename PlanAcc<HOMO>::type*>(partial), parts, n_slices, (int)S,
-                                   (uint32_t)width_of(slice_shift, slice_width), k, inv_scale, static_cast<const W*>(weights), static_cast<W*>(out), pstride, count));
+  const int rc = be_dispatch_w_homo(wdtype, homo, [&](auto w, auto h) {
+    using W = typename decltype(w)::type;
+    constexpr bool HOMO = decltype(h)::value;
+    hipLaunchKernelGGL((k_plan_reduce<W, HOMO>), dim3(rgrid, (unsigned)n_batch), dim3(256), 0, st,
+                       static_cast<const typename PlanAcc<HOMO>::type*>(partial), parts, n_slices, (int)S,
+                       (uint32_t)width_of(slice_shift, slice_width), k, inv_scale, static_cast<const W*>(weights), static_cast<W*>(out), pstride, count);
+    return BE_OK;
+  });
+  if (rc != BE_OK) return rc;
   BE_LAUNCH_CHECK();
   return BE_OK;
 }

@@ -21,15 +21,6 @@ constexpr int64_t kFusedMinWork = 768; // ... when (average row length x columns
 static inline int64_t counts_bytes(int64_t nb) { return be_align_up(nb * 4, 256); }
 static inline int64_t active_stride_of(int64_t m) { return be_align_up(m * 4, 256) / 4; }   // in uint32 elements
 
-#define BE_DISPATCH_W(wdtype, HOMO_FLAG, CALL)                                  \
-  switch (wdtype) {                                                              \
-    case BE_F32:  { using W = float;          if (HOMO_FLAG) { constexpr bool HOMO = true; CALL; } else { constexpr bool HOMO = false; CALL; } } break; \
-    case BE_F64:  { using W = double;         if (HOMO_FLAG) { constexpr bool HOMO = true; CALL; } else { constexpr bool HOMO = false; CALL; } } break; \
-    case BE_F16:  { using W = __half;         if (HOMO_FLAG) { constexpr bool HOMO = true; CALL; } else { constexpr bool HOMO = false; CALL; } } break; \
-    case BE_BF16: { using W = __hip_bfloat16; if (HOMO_FLAG) { constexpr bool HOMO = true; CALL; } else { constexpr bool HOMO = false; CALL; } } break; \
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;       \
-  }
-
 static inline bool check_rows(const void* indptr, int64_t row_len) { return indptr != nullptr || row_len >= 0; }
 
 static inline int64_t width_of(int slice_shift, int slice_width) { return slice_width > 0 ? slice_width : (1ll << slice_shift); }
@@ -79,18 +70,7 @@ template <bool HOMO> struct PlanAcc;
 template <> struct PlanAcc<true> { using type = uint32_t; };
 template <> struct PlanAcc<false> { using type = unsigned long long; };
 
-// w * 2^scale_exp as a 64-bit two's-complement integer, built from f32 operations only:
-//   t = w * 2^(scale_exp-32);  hi = floor(t);  lo = (t - hi) * 2^32   (all three steps are exact in f32:
-//   power-of-two scaling, and t - floor(t) has no more significant bits than t).
-// The caller guarantees |w| * 2^scale_exp < 2^62 / m, so hi fits an int32.  `scale` = 2^(scale_exp-32).
-__device__ __forceinline__ unsigned long long fixed_from_f32(float w, float scale) {
-  const float t = w * scale;
-  const float hf = floorf(t);
-  const int hi = (int)hf;
-  const unsigned lo = (unsigned)((t - hf) * 4294967296.0f);
-  return ((unsigned long long)(unsigned)hi << 32) | lo;
-}
-
+// (the fixed-point encoding itself, fixed_from_f32, is in be_common.h: the JITC scatter kernels use it too)
 template <bool HOMO>
 __device__ __forceinline__ void plan_add4(typename PlanAcc<HOMO>::type* acc, uint2 iv, float4 wv, float scale) {
   const uint32_t i0 = iv.x & 0xffffu, i1 = iv.x >> 16, i2 = iv.y & 0xffffu, i3 = iv.y >> 16;

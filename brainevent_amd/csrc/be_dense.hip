@@ -1339,7 +1339,7 @@ int be_binary_densemm(const void* weights, int wdtype, const void* spikes_bm, in
   if (out_len == 0 || n_batch == 0) return BE_OK;
   BE_REQUIRE(out_bm != nullptr, BE_ERR_INVALID, "out is NULL");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t esz = (wdtype == BE_F64) ? 8 : (wdtype == BE_F32 ? 4 : 2);
+  const size_t esz = be_wbytes(wdtype);
   if (k == 0) {
     BE_HIP(be_fill_async(out_bm, 0, (size_t)out_len * n_batch * esz, st));
     return BE_OK;
@@ -1349,13 +1349,12 @@ int be_binary_densemm(const void* weights, int wdtype, const void* spikes_bm, in
              "unknown spike dtype");
   BE_REQUIRE(workspace != nullptr && workspace_bytes >= dense_ws_bytes(rows_w, cols_w, n_batch, transpose, wdtype),
              BE_ERR_WORKSPACE, "workspace too small");
-  switch (wdtype) {
-    case BE_F32: return densemm_any<float>(weights, spikes_bm, spike_dtype, out_bm, rows_w, cols_w, n_batch, transpose, workspace, st);
-    case BE_F64: return densemm_any<double>(weights, spikes_bm, spike_dtype, out_bm, rows_w, cols_w, n_batch, transpose, workspace, st);
-    case BE_F16: return densemm_any<__half>(weights, spikes_bm, spike_dtype, out_bm, rows_w, cols_w, n_batch, transpose, workspace, st);
-    case BE_BF16: return densemm_any<__hip_bfloat16>(weights, spikes_bm, spike_dtype, out_bm, rows_w, cols_w, n_batch, transpose, workspace, st);
-    default: be_set_error("be_binary_densemm: unknown weight dtype"); return BE_ERR_INVALID;
-  }
+  // (checked here, by name: this entry point's message carries its name, the dispatcher's does not)
+  BE_REQUIRE(wdtype == BE_F32 || wdtype == BE_F64 || wdtype == BE_F16 || wdtype == BE_BF16, BE_ERR_INVALID, "unknown weight dtype");
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return densemm_any<W>(weights, spikes_bm, spike_dtype, out_bm, rows_w, cols_w, n_batch, transpose, workspace, st);
+  });
 }
 
 #define BE_DEF_DENSE_VARIANT(W, WD, S, SD)                                                                              \

@@ -276,13 +276,10 @@ int be_dt2t(const void* w, int homo, int wdtype, const void* y, const int32_t* i
   const RowPtr rp{by_col ? nullptr : indptr, indptr_is_i64, row_len};
   const int64_t n_y = by_col ? n_cols : n_rows;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (wdtype) {
-    case BE_F32:  return dt2t_t<float>(mode, homo, w, y, indices, rp, out, n_rows, n_y, n_batch, nnz, st);
-    case BE_F64:  return dt2t_t<double>(mode, homo, w, y, indices, rp, out, n_rows, n_y, n_batch, nnz, st);
-    case BE_F16:  return dt2t_t<__half>(mode, homo, w, y, indices, rp, out, n_rows, n_y, n_batch, nnz, st);
-    case BE_BF16: return dt2t_t<__hip_bfloat16>(mode, homo, w, y, indices, rp, out, n_rows, n_y, n_batch, nnz, st);
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;
-  }
+  return be_dispatch_wdtype(wdtype, [&](auto tag) {
+    using W = typename decltype(tag)::type;
+    return dt2t_t<W>(mode, homo, w, y, indices, rp, out, n_rows, n_y, n_batch, nnz, st);
+  });
 }
 
 }  // extern "C"

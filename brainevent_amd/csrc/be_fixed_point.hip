@@ -1,6 +1,6 @@
 // be_fixed_point.hip — the fixed-point exponent of a matrix, chosen by the library (so that a scatter plan or a binned
 // workspace can be set up from C alone).  The fast scatter routes accumulate a weight w as round(w * 2^e) in a 64-bit
-// integer (be_csr_shared.h: fixed_from_f32); e must be small enough that no output can overflow with every row active,
+// integer (be_common.h: fixed_from_f32); e must be small enough that no output can overflow with every row active,
 // and large enough that every output keeps the accuracy of the path.  No counterpart in the reference: its GPU kernels
 // add floats with atomics (brainevent/_csr/binary_csrmv_hybrid.cu:199-234), which this chip retires at 21 G/s.
 #include "be_csr_shared.h"
@@ -88,13 +88,12 @@ int be_weight_stats(const void* weights, int wdtype, int64_t n, uint32_t* max_bi
     const int grid = grid_for(n, 256, 256 * 16);
     const int32_t* no_idx = nullptr;
     float* no_col = nullptr;
-    switch (wdtype) {
-      case BE_F32: hipLaunchKernelGGL(k_fp_colsum<float>, dim3(grid), dim3(256), 0, st, static_cast<const float*>(weights), no_idx, n, no_col, stats); break;
-      case BE_F64: hipLaunchKernelGGL(k_fp_colsum<double>, dim3(grid), dim3(256), 0, st, static_cast<const double*>(weights), no_idx, n, no_col, stats); break;
-      case BE_F16: hipLaunchKernelGGL(k_fp_colsum<__half>, dim3(grid), dim3(256), 0, st, static_cast<const __half*>(weights), no_idx, n, no_col, stats); break;
-      case BE_BF16: hipLaunchKernelGGL(k_fp_colsum<__hip_bfloat16>, dim3(grid), dim3(256), 0, st, static_cast<const __hip_bfloat16*>(weights), no_idx, n, no_col, stats); break;
-      default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;
-    }
+    const int rc = be_dispatch_wdtype(wdtype, [&](auto w) {
+      using W = typename decltype(w)::type;
+      hipLaunchKernelGGL(k_fp_colsum<W>, dim3(grid), dim3(256), 0, st, static_cast<const W*>(weights), no_idx, n, no_col, stats);
+      return BE_OK;
+    });
+    if (rc != BE_OK) return rc;
     BE_LAUNCH_CHECK();
   }
   uint32_t h[2];

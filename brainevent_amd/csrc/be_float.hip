@@ -258,7 +258,7 @@ int be_csrmm(const void* weights, int homo, int wdtype, const int32_t* indices, 
   const int64_t out_rows = transpose ? k : m;
   if (out_rows == 0) return BE_OK;
   BE_REQUIRE(out != nullptr, BE_ERR_INVALID, "out is NULL");
-  const size_t esz = wdtype == BE_F64 ? 8 : (wdtype == BE_F32 ? 4 : 2);
+  const size_t esz = be_wbytes(wdtype);
   if (m == 0 || (transpose ? m : k) == 0) {             // nothing to sum: zeros
     BE_HIP(be_fill_async(out, 0, (size_t)out_rows * (size_t)n * esz, st));
     return BE_OK;
@@ -268,8 +268,10 @@ int be_csrmm(const void* weights, int homo, int wdtype, const int32_t* indices, 
              BE_ERR_WORKSPACE, "workspace too small");
   RowPtr rp{indptr, indptr_is_i64, row_len};
   const int64_t avg = indptr == nullptr ? row_len : (nnz_hint > 0 ? nnz_hint / m : 64);
-  BE_DISPATCH_W(wdtype, homo, return (run_float_csr<W, HOMO>(weights, indices, rp, B, out, m, k, n, avg, transpose, workspace, st)));
-  return BE_OK;
+  return be_dispatch_w_homo(wdtype, homo, [&](auto w, auto h) {
+    using W = typename decltype(w)::type;
+    return run_float_csr<W, decltype(h)::value>(weights, indices, rp, B, out, m, k, n, avg, transpose, workspace, st);
+  });
 }
 
 int be_csrmv(const void* weights, int homo, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t row_len,

@@ -235,15 +235,6 @@ int grad_dense_t(int t, void* dw, int64_t n_rows, int64_t n_cols, const uint32_t
   return BE_OK;
 }
 
-#define BE_GRAD_DISPATCH(wdtype, CALL)                                           \
-  switch (wdtype) {                                                              \
-    case BE_F32:  { using W = float;          return CALL; }                     \
-    case BE_F64:  { using W = double;         return CALL; }                     \
-    case BE_F16:  { using W = __half;         return CALL; }                     \
-    case BE_BF16: { using W = __hip_bfloat16; return CALL; }                     \
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;       \
-  }
-
 }  // namespace
 
 extern "C" {
@@ -273,7 +264,7 @@ int be_grad_pack_activity(const void* spikes, int spike_dtype, int64_t n, int64_
       break;
     case BE_SPIKE_IDS: {
       const be_spike_ids_t* ids = static_cast<const be_spike_ids_t*>(spikes);
-      BE_HIP(hipMemsetAsync(mask, 0, (size_t)n * 4, st));
+      BE_HIP(be_fill_async(mask, 0, (size_t)n * 4, st));
       hipLaunchKernelGGL(k_grad_pack_ids, dim3(grid_for(n, 256, 4096)), dim3(256), 0, st, ids->active_ids, ids->n_active, mask);
       break;
     }
@@ -295,15 +286,17 @@ int be_grad_rows(int transpose, void* dw, int homo, int wdtype, const int32_t* i
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (nse == 0 || n_rows == 0) {
     if (homo) {    // an empty sum
-      const int64_t wbytes = wdtype == BE_F64 ? 8 : wdtype == BE_F32 ? 4 : 2;
-      BE_HIP(hipMemsetAsync(dw, 0, (size_t)wbytes, st));
+      BE_HIP(be_fill_async(dw, 0, be_wbytes(wdtype), st));
     }
     return BE_OK;
   }
   BE_REQUIRE(indices && mask && g, BE_ERR_INVALID, "null pointer");
   const RowPtr rp{indptr, indptr_is_i64, row_len};
   const int nw = (int)((n_batch + 31) / 32);
-  BE_GRAD_DISPATCH(wdtype, grad_rows_t<W>(transpose, homo, dw, indices, rp, n_rows, nse, mask, nw, g, g_sn, g_sb, workspace, st));
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return grad_rows_t<W>(transpose, homo, dw, indices, rp, n_rows, nse, mask, nw, g, g_sn, g_sb, workspace, st);
+  });
 }
 
 int64_t be_grad_dense_workspace_bytes(int64_t n_rows, int64_t n_cols) {
@@ -317,7 +310,10 @@ int be_grad_dense(int transpose, void* dw, int wdtype, int64_t n_rows, int64_t n
   BE_REQUIRE(dw && mask && g, BE_ERR_INVALID, "null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nw = (int)((n_batch + 31) / 32);
-  BE_GRAD_DISPATCH(wdtype, grad_dense_t<W>(transpose, dw, n_rows, n_cols, mask, nw, g, g_sn, g_sb, st));
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return grad_dense_t<W>(transpose, dw, n_rows, n_cols, mask, nw, g, g_sn, g_sb, st);
+  });
 }
 
 }  // extern "C"

@@ -41,9 +41,8 @@ __global__ void __launch_bounds__(1024) k_jit_mv_gather(JitP p, const uint32_t* 
   using AccT = typename GatherAcc<MODE>::type;
   extern __shared__ uint32_t bits_s[];
   const int chunk = blockIdx.y;
-  const int64_t cs = (int64_t)chunk * p.chunk_size;
-  const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-  const int64_t width = ce - cs;
+  const JitSpan span = jit_chunk_span(p, chunk);
+  const int64_t cs = span.cs, width = span.width, ce = cs + width;
   const int64_t w_first = cs >> 5;
   const uint32_t* bsrc = bits;
   int64_t w_off = 0;
@@ -65,20 +64,18 @@ __global__ void __launch_bounds__(1024) k_jit_mv_gather(JitP p, const uint32_t* 
       // the walk in the q domain: lane l visits chunk-local columns l + 32 q, i.e. always bit ((cs + l) & 31) of
       // consecutive 32-bit words of the packed spike vector — one LDS word per step, no 64-bit arithmetic
       const uint32_t grow = (uint32_t)row + p.row0;          // the generator row (the RNG is keyed by it; `row` indexes the output)
-      uint32_t state = lr_init(p.seed, grow, (uint32_t)chunk, l);
-      uint32_t q = lr_initial_q(state, p.cl);
-      const uint32_t qmax = width > (int64_t)l ? (uint32_t)((width - l + 31) >> 5) : 0u;   // l + 32 q < width
+      JitWalk w(p, grow, (uint32_t)chunk, l);
+      const uint32_t qmax = jit_positions<uint32_t>(width, l, 32);   // l + 32 q < width
       const int64_t bit0 = cs + l;
       const uint32_t sh = (uint32_t)(bit0 & 31);
       const uint32_t* wp = bsrc + ((bit0 >> 5) - w_off);
-      while (q < qmax) {
-        const bool on = (wp[q] >> sh) & 1u;
+      while (w.q < qmax) {
+        const bool on = (wp[w.q] >> sh) & 1u;
         if (on) {
           if (MODE == MODE_SCALAR) acc += 1;
-          else acc += (AccT)edge_weight<MODE, float>(p, grow, (uint32_t)(bit0 + 32ll * q));
+          else acc += (AccT)edge_weight<MODE, float>(p, grow, (uint32_t)(bit0 + 32ll * w.q));
         }
-        state = lr_next_nz(state);
-        q = q + 1u + lr_bounded(state, p.cl - 1u);
+        w.next(p);
       }
     }
 #pragma unroll
@@ -123,11 +120,8 @@ __global__ void __launch_bounds__(1024) k_jit_mv_scatter(JitP p, const uint32_t*
   const uint32_t chunk = (uint32_t)cls / S, l = (uint32_t)cls - chunk * S;
   active += (int64_t)blockIdx.y * active_stride;
   partial += (int64_t)blockIdx.y * gridDim.x * piece_len;
-  const int64_t cs = (int64_t)chunk * p.chunk_size;
-  const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-  const int64_t width = ce - cs;
-  // positions q with l + stride * q < width
-  const int64_t Q = width > (int64_t)l ? (width - l + S - 1) / S : 0;
+  const JitSpan span = jit_chunk_span(p, chunk);
+  const int64_t cs = span.cs, Q = jit_positions<int64_t>(span.width, l, S);
   const int64_t q_begin = (int64_t)piece * piece_len;
   const int64_t q_end = q_begin + piece_len < Q ? q_begin + piece_len : Q;
   for (uint32_t i = threadIdx.x; i < piece_len; i += blockDim.x) acc[i] = 0;
@@ -143,16 +137,14 @@ __global__ void __launch_bounds__(1024) k_jit_mv_scatter(JitP p, const uint32_t*
     // refilling at 64 (= never early) / 32 / 16 / 8 idle lanes, with the next row id prefetched (tools/ab_c3.sh).
     for (uint64_t a = (uint64_t)part * blockDim.x + threadIdx.x; a < n_active; a += (uint64_t)parts * blockDim.x) {
       const uint32_t row = active[a];
-      uint32_t state = lr_init(p.seed, row, chunk, l);
-      uint32_t q = lr_initial_q(state, p.cl);
-      while (q < qe) {
-        if (ONE_PIECE || q >= qb) {        // one piece per class: qb == 0, no test in the loop
-          const uint32_t slot = ONE_PIECE ? q : q - qb;       // one piece: qb == 0, one vector operation less per edge
+      JitWalk w(p, row, chunk, l);
+      while (w.q < qe) {
+        if (ONE_PIECE || w.q >= qb) {        // one piece per class: qb == 0, no test in the loop
+          const uint32_t slot = ONE_PIECE ? w.q : w.q - qb;       // one piece: qb == 0, one vector operation less per edge
           if (MODE == MODE_SCALAR) atomicAdd(&acc[slot], (AccT)1);
-          else atomicAdd(&acc[slot], (AccT)jit_fixed_from_f32(edge_weight<MODE, float>(p, row, j0 + S * q), fx_scale));
+          else atomicAdd(&acc[slot], (AccT)fixed_from_f32(edge_weight<MODE, float>(p, row, j0 + S * w.q), fx_scale));
         }
-        state = lr_next_nz(state);
-        q = q + 1u + lr_bounded(state, p.cl - 1u);
+        w.next(p);
       }
     }
   }
@@ -207,26 +199,23 @@ __global__ void __launch_bounds__(256) k_jit_mm_gather(JitP p, const uint32_t* _
       for (int c = 0; c < NCOL; ++c) acc[c] = A(0);
     }
     for (int chunk = 0; chunk < p.n_chunks; ++chunk) {
-      const int64_t cs = (int64_t)chunk * p.chunk_size;
-      const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-      const int64_t width = ce - cs;
+      const JitSpan span = jit_chunk_span(p, chunk);
+      const int64_t cs = span.cs, width = span.width;
       for (uint32_t l = 0; l < (uint32_t)p.stride; ++l) {
-        uint32_t state = lr_init(p.seed, (uint32_t)row, (uint32_t)chunk, l);
-        uint32_t q = lr_initial_q(state, p.cl);
-        uint64_t lj = (uint64_t)l + (uint64_t)p.stride * q;
+        JitWalk w(p, (uint32_t)row, (uint32_t)chunk, l);
+        uint64_t lj = (uint64_t)l + (uint64_t)p.stride * w.q;
         while ((int64_t)lj < width) {
           const int64_t j = cs + (int64_t)lj;
           const uint32_t mk = mask[j];
           if constexpr (MODE == MODE_SCALAR) {
             sc.add(mk);
           } else if (mk) {
-            const A w = edge_weight<MODE, A>(p, (uint32_t)row, (uint32_t)j);
+            const A wt = edge_weight<MODE, A>(p, (uint32_t)row, (uint32_t)j);
 #pragma unroll
-            for (int c = 0; c < NCOL; ++c) acc_add_inplace(acc[c], ((mk >> c) & 1u) ? w : A(0));
+            for (int c = 0; c < NCOL; ++c) acc_add_inplace(acc[c], ((mk >> c) & 1u) ? wt : A(0));
           }
-          state = lr_next_nz(state);
-          q = q + 1u + lr_bounded(state, p.cl - 1u);
-          lj = (uint64_t)l + (uint64_t)p.stride * q;
+          w.next(p);
+          lj = (uint64_t)l + (uint64_t)p.stride * w.q;
         }
       }
     }
@@ -261,17 +250,13 @@ __global__ void __launch_bounds__(1024) k_jit_mm_gather_lds(JitP p, const uint32
   }
   constexpr int kMmStride = 4;                               // lane stride of the mm matrix (brainevent/_misc.py:37-38)
   for (int chunk = 0; chunk < p.n_chunks; ++chunk) {
-    const int64_t cs = (int64_t)chunk * p.chunk_size;
-    const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-    const int64_t width = ce - cs;
+    const JitSpan span = jit_chunk_span(p, chunk);
+    const int64_t cs = span.cs, width = span.width;
     // the four walks of this row in this chunk keep their generator state across the windows (round 2 restarted every
     // walk at every window: W windows cost (W + 1) / 2 walks of the chunk, which ruled windows out for wide batches)
-    uint32_t wstate[kMmStride], wq[kMmStride];
+    JitWalk walks[kMmStride];
 #pragma unroll
-    for (int l = 0; l < kMmStride; ++l) {
-      wstate[l] = lr_init(p.seed, (uint32_t)row, (uint32_t)chunk, (uint32_t)l);
-      wq[l] = lr_initial_q(wstate[l], p.cl);
-    }
+    for (int l = 0; l < kMmStride; ++l) walks[l] = JitWalk(p, (uint32_t)row, (uint32_t)chunk, (uint32_t)l);
     for (int64_t w_lo = 0; w_lo < width; w_lo += win_cols) {
       const int64_t w_hi = w_lo + win_cols < width ? w_lo + win_cols : width;
       const int64_t w_n = w_hi - w_lo;
@@ -293,24 +278,21 @@ __global__ void __launch_bounds__(1024) k_jit_mm_gather_lds(JitP p, const uint32
       if (row < m) {
 #pragma unroll
         for (int l = 0; l < kMmStride; ++l) {
-          uint32_t state = wstate[l], q = wq[l];
-          uint64_t lj = (uint64_t)l + (uint64_t)kMmStride * q;
+          JitWalk& w = walks[l];
+          uint64_t lj = (uint64_t)l + (uint64_t)kMmStride * w.q;
           while ((int64_t)lj < w_hi) {
             uint32_t mk = (uint32_t)ms[(int64_t)lj - w_lo];
             if constexpr (MODE == MODE_SCALAR) {
               sc.add(mk);
             } else if (mk) {
               asm volatile("" : "+v"(mk));                   // keeps the per-column adds behind the branch
-              const A w = edge_weight<MODE, A>(p, (uint32_t)row, (uint32_t)(cs + (int64_t)lj));
+              const A wt = edge_weight<MODE, A>(p, (uint32_t)row, (uint32_t)(cs + (int64_t)lj));
 #pragma unroll
-              for (int c = 0; c < NCOL; ++c) acc_add_inplace(acc[c], ((mk >> c) & 1u) ? w : A(0));
+              for (int c = 0; c < NCOL; ++c) acc_add_inplace(acc[c], ((mk >> c) & 1u) ? wt : A(0));
             }
-            state = lr_next_nz(state);
-            q = q + 1u + lr_bounded(state, p.cl - 1u);
-            lj = (uint64_t)l + (uint64_t)kMmStride * q;
+            w.next(p);
+            lj = (uint64_t)l + (uint64_t)kMmStride * w.q;
           }
-          wstate[l] = state;
-          wq[l] = q;
         }
       }
     }
@@ -379,18 +361,14 @@ __global__ void __launch_bounds__(256) k_jit_csr_count(JitP p, int64_t n_rows, u
     const int rem = (int)(t - row * tasks_per_row);
     const int chunk = rem / p.stride;
     const uint32_t l = (uint32_t)(rem - chunk * p.stride);
-    const int64_t cs = (int64_t)chunk * p.chunk_size;
-    const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-    const int64_t width = ce - cs;
-    uint32_t state = lr_init(p.seed, (uint32_t)row, (uint32_t)chunk, l);
-    uint32_t q = lr_initial_q(state, p.cl);
-    uint64_t lj = (uint64_t)l + (uint64_t)p.stride * q;
+    const int64_t width = jit_chunk_span(p, chunk).width;
+    JitWalk w(p, (uint32_t)row, (uint32_t)chunk, l);
+    uint64_t lj = (uint64_t)l + (uint64_t)p.stride * w.q;
     uint32_t cnt = 0;
     while ((int64_t)lj < width) {
       ++cnt;
-      state = lr_next_nz(state);
-      q = q + 1u + lr_bounded(state, p.cl - 1u);
-      lj = (uint64_t)l + (uint64_t)p.stride * q;
+      w.next(p);
+      lj = (uint64_t)l + (uint64_t)p.stride * w.q;
     }
     if (cnt) atomicAdd(&row_counts[row], cnt);
   }
@@ -408,33 +386,28 @@ __global__ void __launch_bounds__(256) k_jit_csr_fill(JitP p, int64_t n_rows, co
     const int rem = (int)(t - row * tasks_per_row);
     const int chunk = rem / p.stride;
     const uint32_t l = (uint32_t)(rem - chunk * p.stride);
-    const int64_t cs = (int64_t)chunk * p.chunk_size;
-    const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-    const int64_t width = ce - cs;
-    const uint32_t state0 = lr_init(p.seed, (uint32_t)row, (uint32_t)chunk, l);
-    uint32_t state = state0;
-    const uint32_t q0 = lr_initial_q(state, p.cl);
-    const uint32_t state1 = state;
-    uint32_t q = q0, cnt = 0;
-    uint64_t lj = (uint64_t)l + (uint64_t)p.stride * q;
+    const JitSpan span = jit_chunk_span(p, chunk);
+    const int64_t cs = span.cs, width = span.width;
+    const JitWalk start(p, (uint32_t)row, (uint32_t)chunk, l);
+    JitWalk w = start;
+    uint32_t cnt = 0;
+    uint64_t lj = (uint64_t)l + (uint64_t)p.stride * w.q;
     while ((int64_t)lj < width) {
       ++cnt;
-      state = lr_next_nz(state);
-      q = q + 1u + lr_bounded(state, p.cl - 1u);
-      lj = (uint64_t)l + (uint64_t)p.stride * q;
+      w.next(p);
+      lj = (uint64_t)l + (uint64_t)p.stride * w.q;
     }
     if (cnt == 0) continue;
     int64_t pos = indptr[row] + atomicAdd(&cursor[row], cnt);
-    state = state1; q = q0;
-    lj = (uint64_t)l + (uint64_t)p.stride * q;
+    w = start;                                               // the same walk again, now writing
+    lj = (uint64_t)l + (uint64_t)p.stride * w.q;
     while ((int64_t)lj < width) {
       const int64_t j = cs + (int64_t)lj;
       indices[pos] = (int32_t)j;
       if (MODE != MODE_SCALAR) weights[pos] = edge_weight<MODE, float>(p, (uint32_t)row, (uint32_t)j);
       ++pos;
-      state = lr_next_nz(state);
-      q = q + 1u + lr_bounded(state, p.cl - 1u);
-      lj = (uint64_t)l + (uint64_t)p.stride * q;
+      w.next(p);
+      lj = (uint64_t)l + (uint64_t)p.stride * w.q;
     }
   }
 }
@@ -481,17 +454,14 @@ __global__ void __launch_bounds__(kSortedBlock) k_jit_fill_sorted(JitP p, int64_
     for (int c0 = 0; c0 < p.n_chunks; c0 += group_chunks) {
       // ---- this thread's walker: chunk c0 + my_chunk, lane l
       const int chunk = c0 + my_chunk;
-      int64_t cs = 0, width = 0;
-      uint32_t state = 1u, q = 0u;
+      JitSpan span{0, 0};
+      JitWalk w;                                           // (idle beyond the last chunk: j stays kEnd, never stepped)
       int64_t j = kEnd;                                    // global column of the walker's next hit
       if (chunk < p.n_chunks) {
-        cs = (int64_t)chunk * p.chunk_size;
-        const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-        width = ce - cs;
-        state = lr_init(p.seed, (uint32_t)row, (uint32_t)chunk, l);
-        q = lr_initial_q(state, p.cl);
-        const uint64_t lj = (uint64_t)l + (uint64_t)S * q;
-        j = (int64_t)lj < width ? cs + (int64_t)lj : kEnd;
+        span = jit_chunk_span(p, chunk);
+        w = JitWalk(p, (uint32_t)row, (uint32_t)chunk, l);
+        const uint64_t lj = (uint64_t)l + (uint64_t)S * w.q;
+        j = (int64_t)lj < span.width ? span.cs + (int64_t)lj : kEnd;
       }
       const int64_t g_begin = (int64_t)c0 * p.chunk_size;
       const int64_t g_last = ((int64_t)c0 + group_chunks) * p.chunk_size;
@@ -502,19 +472,18 @@ __global__ void __launch_bounds__(kSortedBlock) k_jit_fill_sorted(JitP p, int64_
         while (j < we) {
           const uint32_t b = (uint32_t)(j - wb);
           atomicOr(&bitmap[b >> 5], 1u << (b & 31u));
-          state = lr_next_nz(state);
-          q = q + 1u + lr_bounded(state, p.cl - 1u);
-          const uint64_t lj = (uint64_t)l + (uint64_t)S * q;
-          j = (int64_t)lj < width ? cs + (int64_t)lj : kEnd;
+          w.next(p);
+          const uint64_t lj = (uint64_t)l + (uint64_t)S * w.q;
+          j = (int64_t)lj < span.width ? span.cs + (int64_t)lj : kEnd;
         }
         __syncthreads();
         // ---- 2. offsets: popcount of this thread's words, scanned over the workgroup
-        uint32_t w[kSortedWords];
+        uint32_t words[kSortedWords];
         uint32_t cnt = 0;
 #pragma unroll
         for (int k = 0; k < kSortedWords; ++k) {
-          w[k] = bitmap[t * kSortedWords + k];
-          cnt += (uint32_t)__popc(w[k]);
+          words[k] = bitmap[t * kSortedWords + k];
+          cnt += (uint32_t)__popc(words[k]);
         }
         uint32_t incl = cnt;
 #pragma unroll
@@ -536,7 +505,7 @@ __global__ void __launch_bounds__(kSortedBlock) k_jit_fill_sorted(JitP p, int64_
           int64_t o = pos + before + (incl - cnt);
 #pragma unroll
           for (int k = 0; k < kSortedWords; ++k) {
-            uint32_t bits = w[k];
+            uint32_t bits = words[k];
             if (bits) bitmap[t * kSortedWords + k] = 0u;
             while (bits) {
               const int b = __ffs((int)bits) - 1;
@@ -697,22 +666,6 @@ inline int jit_scale_exp(int mode, double w0, double w1, int64_t n_rows) {
   return std::max(-90, std::min(150, 62 - e - lg));
 }
 
-template <int MODE>
-int jit_mv_dispatch(const JitP& p, int wdtype, const void* spikes, int sd, void* out, int64_t in_len, int64_t out_len,
-                    int gather, int scale_exp, void* ws, hipStream_t st) {
-#define BE_JIT_CASE(WT)                                                                       \
-  return gather ? jit_mv_gather<MODE, WT>(p, spikes, sd, out, out_len, ws, st)                \
-                : jit_mv_scatter<MODE, WT>(p, spikes, sd, out, in_len, scale_exp, ws, st)
-  switch (wdtype) {
-    case BE_F32: BE_JIT_CASE(float);
-    case BE_F64: BE_JIT_CASE(double);
-    case BE_F16: BE_JIT_CASE(__half);
-    case BE_BF16: BE_JIT_CASE(__hip_bfloat16);
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;
-  }
-#undef BE_JIT_CASE
-}
-
 template <int MODE, typename A>
 int jit_mm_run(const JitP& p, const uint32_t* mask, int64_t rows, int nc, int gather, A* out_bm, hipStream_t st) {
   (void)gather;   // only the gather ("notrans") direction comes here; the scatter runs jit_scatter_batched
@@ -826,7 +779,7 @@ static int jitmv_impl(int mode, double w0, double w1, int wdtype, int64_t clen, 
   if (out_len == 0) return BE_OK;
   BE_REQUIRE(out != nullptr, BE_ERR_INVALID, "out is NULL");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t esz = (wdtype == BE_F64) ? 8 : (wdtype == BE_F32 ? 4 : 2);
+  const size_t esz = be_wbytes(wdtype);
   if (in_len == 0 || clen <= 0) {   // empty walk or prob == 0: all zeros (documented choice)
     BE_HIP(be_fill_async(out, 0, (size_t)out_len * esz, st));
     return BE_OK;
@@ -848,11 +801,14 @@ static int jitmv_impl(int mode, double w0, double w1, int wdtype, int64_t clen, 
       return BE_OK;
     }
   }
-  switch (mode) {
-    case MODE_SCALAR: return jit_mv_dispatch<MODE_SCALAR>(p, wdtype, spikes, spike_dtype, out, in_len, out_len, gather, scale_exp, workspace, st);
-    case MODE_UNIFORM: return jit_mv_dispatch<MODE_UNIFORM>(p, wdtype, spikes, spike_dtype, out, in_len, out_len, gather, scale_exp, workspace, st);
-    default: return jit_mv_dispatch<MODE_NORMAL>(p, wdtype, spikes, spike_dtype, out, in_len, out_len, gather, scale_exp, workspace, st);
-  }
+  return jit_dispatch_mode(mode, [&](auto md) {
+    return be_dispatch_wdtype(wdtype, [&](auto w) {
+      constexpr int MODE = decltype(md)::value;
+      using W = typename decltype(w)::type;
+      return gather ? jit_mv_gather<MODE, W>(p, spikes, spike_dtype, out, out_len, workspace, st)
+                    : jit_mv_scatter<MODE, W>(p, spikes, spike_dtype, out, in_len, scale_exp, workspace, st);
+    });
+  });
 }
 
 int64_t be_binary_jitmm_workspace_bytes(int64_t shape1, int64_t in_len, int64_t out_len, int64_t n_batch, int gather) {
@@ -873,7 +829,7 @@ int be_binary_jitmm(int mode, double w0, double w1, int wdtype, int64_t clen, ui
   if (out_len == 0 || n_batch == 0) return BE_OK;
   BE_REQUIRE(out_bm != nullptr, BE_ERR_INVALID, "out is NULL");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t esz = (wdtype == BE_F64) ? 8 : (wdtype == BE_F32 ? 4 : 2);
+  const size_t esz = be_wbytes(wdtype);
   if (in_len == 0 || clen <= 0) {
     BE_HIP(be_fill_async(out_bm, 0, (size_t)out_len * n_batch * esz, st));
     return BE_OK;
@@ -887,18 +843,12 @@ int be_binary_jitmm(int mode, double w0, double w1, int wdtype, int64_t clen, ui
     const JitP ps = make_params(shape1, out_len, seed, clen, 4, w0, w1);
     BE_REQUIRE_CHUNK_GRID(ps);
     const int se = jit_scale_exp(mode, w0, w1, in_len);
-#define BE_JITMM_SC(MODE_)                                                                                              \
-    switch (wdtype) {                                                                                                   \
-      case BE_F32: return jit_scatter_batched<MODE_, float>(ps, spikes_bm, spike_dtype, out_bm, in_len, n_batch, se, workspace, st);          \
-      case BE_F64: return jit_scatter_batched<MODE_, double>(ps, spikes_bm, spike_dtype, out_bm, in_len, n_batch, se, workspace, st);         \
-      case BE_F16: return jit_scatter_batched<MODE_, __half>(ps, spikes_bm, spike_dtype, out_bm, in_len, n_batch, se, workspace, st);         \
-      case BE_BF16: return jit_scatter_batched<MODE_, __hip_bfloat16>(ps, spikes_bm, spike_dtype, out_bm, in_len, n_batch, se, workspace, st); \
-      default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;                                             \
-    }
-    if (mode == MODE_SCALAR) { BE_JITMM_SC(MODE_SCALAR) }
-    else if (mode == MODE_UNIFORM) { BE_JITMM_SC(MODE_UNIFORM) }
-    else { BE_JITMM_SC(MODE_NORMAL) }
-#undef BE_JITMM_SC
+    return jit_dispatch_mode(mode, [&](auto md) {
+      return be_dispatch_wdtype(wdtype, [&](auto w) {
+        using W = typename decltype(w)::type;
+        return jit_scatter_batched<decltype(md)::value, W>(ps, spikes_bm, spike_dtype, out_bm, in_len, n_batch, se, workspace, st);
+      });
+    });
   }
   unsigned char* wsb = static_cast<unsigned char*>(workspace);
   uint32_t* mask = reinterpret_cast<uint32_t*>(wsb);
@@ -930,14 +880,11 @@ int be_binary_jitmm(int mode, double w0, double w1, int wdtype, int64_t clen, ui
                          static_cast<const uint8_t*>(chunk), in_len, nc, mask);
     BE_LAUNCH_CHECK();
     void* o = static_cast<unsigned char*>(dst) + (size_t)b0 * out_len * asz;
-    int rc;
-#define BE_JITMM(MODE_)                                                                                                  \
-    rc = f64 ? jit_mm_run<MODE_, double>(p, mask, gen_rows, nc, gather, static_cast<double*>(o), st)                     \
-             : jit_mm_run<MODE_, float>(p, mask, gen_rows, nc, gather, static_cast<float*>(o), st)
-    if (mode == MODE_SCALAR) { BE_JITMM(MODE_SCALAR); }
-    else if (mode == MODE_UNIFORM) { BE_JITMM(MODE_UNIFORM); }
-    else { BE_JITMM(MODE_NORMAL); }
-#undef BE_JITMM
+    const int rc = jit_dispatch_mode(mode, [&](auto md) {
+      constexpr int MODE = decltype(md)::value;
+      return f64 ? jit_mm_run<MODE, double>(p, mask, gen_rows, nc, gather, static_cast<double*>(o), st)
+                 : jit_mm_run<MODE, float>(p, mask, gen_rows, nc, gather, static_cast<float*>(o), st);
+    });
     if (rc != BE_OK) return rc;
   }
   be_prof_end(prof, st);
@@ -968,9 +915,10 @@ int be_jit_edge_weights(int mode, double w0, double w1, uint32_t seed, const int
   p.w0 = w0;
   p.w1 = w1;
   const dim3 grid(gcap(n, 256, 8192)), block(256);
-  if (mode == MODE_UNIFORM) hipLaunchKernelGGL(k_jit_edge_weights<MODE_UNIFORM>, grid, block, 0, st, p, rows, cols, n, out);
-  else if (mode == MODE_NORMAL) hipLaunchKernelGGL(k_jit_edge_weights<MODE_NORMAL>, grid, block, 0, st, p, rows, cols, n, out);
-  else hipLaunchKernelGGL(k_jit_edge_weights<MODE_SCALAR>, grid, block, 0, st, p, rows, cols, n, out);
+  jit_dispatch_mode(mode, [&](auto md) {
+    hipLaunchKernelGGL(k_jit_edge_weights<decltype(md)::value>, grid, block, 0, st, p, rows, cols, n, out);
+    return BE_OK;
+  });
   BE_LAUNCH_CHECK();
   return BE_OK;
 }
@@ -1008,9 +956,10 @@ int be_jitc_csr_fill(int mode, double w0, double w1, int64_t clen, uint32_t seed
   BE_HIP(be_fill_async(cursor, 0, (size_t)n_rows * 4, st));
   const JitP p = make_params(shape1, walk_len, seed, clen, stride, w0, w1);
   const dim3 grid(gcap(n_rows * p.n_chunks * stride, 256, 8192));
-  if (mode == MODE_SCALAR) hipLaunchKernelGGL(k_jit_csr_fill<MODE_SCALAR>, grid, dim3(256), 0, st, p, n_rows, indptr, cursor, indices, weights);
-  else if (mode == MODE_UNIFORM) hipLaunchKernelGGL(k_jit_csr_fill<MODE_UNIFORM>, grid, dim3(256), 0, st, p, n_rows, indptr, cursor, indices, weights);
-  else hipLaunchKernelGGL(k_jit_csr_fill<MODE_NORMAL>, grid, dim3(256), 0, st, p, n_rows, indptr, cursor, indices, weights);
+  jit_dispatch_mode(mode, [&](auto md) {
+    hipLaunchKernelGGL(k_jit_csr_fill<decltype(md)::value>, grid, dim3(256), 0, st, p, n_rows, indptr, cursor, indices, weights);
+    return BE_OK;
+  });
   BE_LAUNCH_CHECK();
   return BE_OK;
 }
@@ -1031,9 +980,11 @@ int be_jitc_fill_sorted(int mode, double w0, double w1, int64_t clen, uint32_t s
   hipStream_t st = static_cast<hipStream_t>(stream);
   const JitP p = make_params(shape1, walk_len, seed, clen, stride, w0, w1);
   const dim3 grid((unsigned)std::min<int64_t>(n_rows, kSortedGridCap)), block(kSortedBlock);
-  if (mode == MODE_SCALAR) hipLaunchKernelGGL(k_jit_fill_sorted<MODE_SCALAR>, grid, block, 0, st, p, n_rows, indptr, y, y_by_owner, indices_out, values_out);
-  else if (mode == MODE_UNIFORM) hipLaunchKernelGGL(k_jit_fill_sorted<MODE_UNIFORM>, grid, block, 0, st, p, n_rows, indptr, y, y_by_owner, indices_out, values_out);
-  else hipLaunchKernelGGL(k_jit_fill_sorted<MODE_NORMAL>, grid, block, 0, st, p, n_rows, indptr, y, y_by_owner, indices_out, values_out);
+  jit_dispatch_mode(mode, [&](auto md) {
+    hipLaunchKernelGGL(k_jit_fill_sorted<decltype(md)::value>, grid, block, 0, st, p, n_rows, indptr, y, y_by_owner, indices_out,
+                       values_out);
+    return BE_OK;
+  });
   BE_LAUNCH_CHECK();
   return BE_OK;
 }

@@ -20,10 +20,9 @@ __global__ void __launch_bounds__(256) k_jit_f_gather(JitP p, const W* __restric
   const uint32_t l = threadIdx.x % S;
   const int64_t tpb = 256 / S;
   const int chunk = blockIdx.y;
-  const int64_t cs = (int64_t)chunk * p.chunk_size;
-  const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-  const int64_t width = ce - cs;
-  const uint32_t qmax = width > (int64_t)l ? (uint32_t)((width - l + S - 1) / S) : 0u;      // l + S q < width
+  const JitSpan span = jit_chunk_span(p, chunk);
+  const int64_t cs = span.cs;
+  const uint32_t qmax = jit_positions<uint32_t>(span.width, l, S);      // l + S q < width
   for (int64_t r0 = (int64_t)blockIdx.x * tpb; r0 < m; r0 += (int64_t)gridDim.x * tpb) {   // (whole waves stay in: shuffles below)
     const int64_t row = r0 + threadIdx.x / S;
     double acc[NC];
@@ -31,16 +30,14 @@ __global__ void __launch_bounds__(256) k_jit_f_gather(JitP p, const W* __restric
     for (int c = 0; c < NC; ++c) acc[c] = 0.0;
     if (row < m) {
       const uint32_t grow = (uint32_t)row;
-      uint32_t state = lr_init(p.seed, grow, (uint32_t)chunk, l);
-      uint32_t q = lr_initial_q(state, p.cl);
-      while (q < qmax) {
-        const int64_t col = cs + l + (int64_t)S * q;
+      JitWalk walk(p, grow, (uint32_t)chunk, l);
+      while (walk.q < qmax) {
+        const int64_t col = cs + l + (int64_t)S * walk.q;
         const float w = MODE == MODE_SCALAR ? 1.0f : edge_weight<MODE, float>(p, grow, (uint32_t)col);
 #pragma unroll
         for (int c = 0; c < NC; ++c)
           if (c0 + c < n) acc[c] += (double)w * (double)WTraits<W>::load(X, col * n + c0 + c);
-        state = lr_next_nz(state);
-        q = q + 1u + lr_bounded(state, p.cl - 1u);
+        walk.next(p);
       }
     }
 #pragma unroll
@@ -92,20 +89,17 @@ __global__ void __launch_bounds__(256) k_jit_f_scatter(JitP p, const W* __restri
 #pragma unroll
       for (int c = 0; c < NC; ++c) x[c] *= (ACC)p.w0;
     }
-    const int64_t cs = (int64_t)chunk * p.chunk_size;
-    const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-    const int64_t width = ce - cs;
-    const uint32_t qmax = width > (int64_t)l ? (uint32_t)((width - l + S - 1) / S) : 0u;
-    uint32_t state = lr_init(p.seed, (uint32_t)row, (uint32_t)chunk, l);
-    uint32_t q = lr_initial_q(state, p.cl);
-    while (q < qmax) {
-      const int64_t col = cs + l + (int64_t)S * q;
+    const JitSpan span = jit_chunk_span(p, chunk);
+    const int64_t cs = span.cs;
+    const uint32_t qmax = jit_positions<uint32_t>(span.width, l, S);
+    JitWalk walk(p, (uint32_t)row, (uint32_t)chunk, l);
+    while (walk.q < qmax) {
+      const int64_t col = cs + l + (int64_t)S * walk.q;
       const ACC w = MODE == MODE_SCALAR ? ACC(1) : (ACC)edge_weight<MODE, float>(p, (uint32_t)row, (uint32_t)col);
 #pragma unroll
       for (int c = 0; c < NC; ++c)
         if (c0 + c < n && x[c] != ACC(0)) atomicAdd(img + col * n + c0 + c, w * x[c]);
-      state = lr_next_nz(state);
-      q = q + 1u + lr_bounded(state, p.cl - 1u);
+      walk.next(p);
     }
   }
 }
@@ -128,10 +122,8 @@ __global__ void __launch_bounds__(1024) k_jit_f_scatter_lds(JitP p, const W* __r
   const uint32_t chunk = (uint32_t)cls / S, l = (uint32_t)cls - chunk * S;
   const W* x = X_bm + (int64_t)blockIdx.y * in_len;
   partial += (int64_t)blockIdx.y * gridDim.x * piece_len;
-  const int64_t cs = (int64_t)chunk * p.chunk_size;
-  const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-  const int64_t width = ce - cs;
-  const int64_t Q = width > (int64_t)l ? (width - l + S - 1) / S : 0;
+  const JitSpan span = jit_chunk_span(p, chunk);
+  const int64_t cs = span.cs, Q = jit_positions<int64_t>(span.width, l, S);
   const int64_t q_begin = (int64_t)piece * piece_len;
   const int64_t q_end = q_begin + piece_len < Q ? q_begin + piece_len : Q;
   for (uint32_t i = threadIdx.x; i < piece_len; i += blockDim.x) acc[i] = 0;
@@ -142,17 +134,15 @@ __global__ void __launch_bounds__(1024) k_jit_f_scatter_lds(JitP p, const W* __r
     for (int64_t row = (int64_t)part * blockDim.x + threadIdx.x; row < in_len; row += (int64_t)parts * blockDim.x) {
       const float xv = (float)WTraits<W>::load(x, row);
       if (xv == 0.f) continue;                                 // a zero of the operand adds nothing
-      const unsigned long long fixed_row = jit_fixed_from_f32(xv * (float)p.w0, fx_scale);      // (one shared weight: per row)
-      uint32_t state = lr_init(p.seed, (uint32_t)row, chunk, l);
-      uint32_t q = lr_initial_q(state, p.cl);
-      while (q < qe) {
-        if (ONE_PIECE || q >= qb) {
-          const uint32_t slot = ONE_PIECE ? q : q - qb;
+      const unsigned long long fixed_row = fixed_from_f32(xv * (float)p.w0, fx_scale);      // (one shared weight: per row)
+      JitWalk walk(p, (uint32_t)row, chunk, l);
+      while (walk.q < qe) {
+        if (ONE_PIECE || walk.q >= qb) {
+          const uint32_t slot = ONE_PIECE ? walk.q : walk.q - qb;
           if (MODE == MODE_SCALAR) atomicAdd(&acc[slot], fixed_row);
-          else atomicAdd(&acc[slot], jit_fixed_from_f32(edge_weight<MODE, float>(p, (uint32_t)row, j0 + S * q) * xv, fx_scale));
+          else atomicAdd(&acc[slot], fixed_from_f32(edge_weight<MODE, float>(p, (uint32_t)row, j0 + S * walk.q) * xv, fx_scale));
         }
-        state = lr_next_nz(state);
-        q = q + 1u + lr_bounded(state, p.cl - 1u);
+        walk.next(p);
       }
     }
   }
@@ -217,18 +207,6 @@ int run_jit_float(const JitP& p, const void* Xv, void* outv, int64_t in_len, int
   return BE_OK;
 }
 
-template <int MODE>
-int dispatch_jit_float(const JitP& p, int wdtype, const void* X, void* out, int64_t in_len, int64_t out_len, int64_t n, int gather,
-                       void* ws, hipStream_t st) {
-  switch (wdtype) {
-    case BE_F32: return run_jit_float<MODE, float>(p, X, out, in_len, out_len, n, gather, ws, st);
-    case BE_F64: return run_jit_float<MODE, double>(p, X, out, in_len, out_len, n, gather, ws, st);
-    case BE_F16: return run_jit_float<MODE, __half>(p, X, out, in_len, out_len, n, gather, ws, st);
-    case BE_BF16: return run_jit_float<MODE, __hip_bfloat16>(p, X, out, in_len, out_len, n, gather, ws, st);
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;
-  }
-}
-
 template <int MODE, typename W>
 int run_jit_float_scatter_lds(const JitP& p, const void* X_bm, void* out_bm, int64_t in_len, int64_t n, int scale_exp, void* ws,
                               hipStream_t st) {
@@ -282,7 +260,7 @@ int be_jitmm_float_scatter(int mode, double w0, double w1, int wdtype, int64_t c
   if (out_len == 0) return BE_OK;
   BE_REQUIRE(out_bm != nullptr, BE_ERR_INVALID, "out is NULL");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t esz = wdtype == BE_F64 ? 8 : (wdtype == BE_F32 ? 4 : 2);
+  const size_t esz = be_wbytes(wdtype);
   if (in_len == 0 || clen <= 0) {
     BE_HIP(be_fill_async(out_bm, 0, (size_t)out_len * (size_t)n * esz, st));
     return BE_OK;
@@ -292,18 +270,12 @@ int be_jitmm_float_scatter(int mode, double w0, double w1, int wdtype, int64_t c
              BE_ERR_WORKSPACE, "workspace too small");
   const JitP p = make_params(shape1, out_len, seed, clen, stride, w0, w1);
   BE_REQUIRE_CHUNK_GRID(p);
-#define BE_JFS(MODE_)                                                                                                            \
-  switch (wdtype) {                                                                                                             \
-    case BE_F32: return run_jit_float_scatter_lds<MODE_, float>(p, X_bm, out_bm, in_len, n, scale_exp, workspace, st);          \
-    case BE_F64: return run_jit_float_scatter_lds<MODE_, double>(p, X_bm, out_bm, in_len, n, scale_exp, workspace, st);         \
-    case BE_F16: return run_jit_float_scatter_lds<MODE_, __half>(p, X_bm, out_bm, in_len, n, scale_exp, workspace, st);         \
-    case BE_BF16: return run_jit_float_scatter_lds<MODE_, __hip_bfloat16>(p, X_bm, out_bm, in_len, n, scale_exp, workspace, st); \
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;                                                       \
-  }
-  if (mode == MODE_SCALAR) { BE_JFS(MODE_SCALAR) }
-  else if (mode == MODE_UNIFORM) { BE_JFS(MODE_UNIFORM) }
-  else { BE_JFS(MODE_NORMAL) }
-#undef BE_JFS
+  return jit_dispatch_mode(mode, [&](auto md) {
+    return be_dispatch_wdtype(wdtype, [&](auto w) {
+      using W = typename decltype(w)::type;
+      return run_jit_float_scatter_lds<decltype(md)::value, W>(p, X_bm, out_bm, in_len, n, scale_exp, workspace, st);
+    });
+  });
 }
 
 int64_t be_jitmm_float_workspace_bytes(int64_t shape1, int64_t in_len, int64_t out_len, int64_t n, int gather, int wdtype) {
@@ -326,7 +298,7 @@ int be_jitmm_float(int mode, double w0, double w1, int wdtype, int64_t clen, uin
   if (out_len == 0) return BE_OK;
   BE_REQUIRE(out != nullptr, BE_ERR_INVALID, "out is NULL");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t esz = wdtype == BE_F64 ? 8 : (wdtype == BE_F32 ? 4 : 2);
+  const size_t esz = be_wbytes(wdtype);
   if (in_len == 0 || clen <= 0) {      // empty walk or prob == 0: all zeros (as the event-driven twins)
     BE_HIP(be_fill_async(out, 0, (size_t)out_len * (size_t)n * esz, st));
     return BE_OK;
@@ -336,11 +308,12 @@ int be_jitmm_float(int mode, double w0, double w1, int wdtype, int64_t clen, uin
              BE_ERR_WORKSPACE, "workspace too small");
   const JitP p = make_params(shape1, gather ? in_len : out_len, seed, clen, stride, w0, w1);
   if (gather) BE_REQUIRE_CHUNK_GRID(p);      // (the atomic scatter walks its chunks in a flat task loop)
-  switch (mode) {
-    case MODE_SCALAR: return dispatch_jit_float<MODE_SCALAR>(p, wdtype, X, out, in_len, out_len, n, gather, workspace, st);
-    case MODE_UNIFORM: return dispatch_jit_float<MODE_UNIFORM>(p, wdtype, X, out, in_len, out_len, n, gather, workspace, st);
-    default: return dispatch_jit_float<MODE_NORMAL>(p, wdtype, X, out, in_len, out_len, n, gather, workspace, st);
-  }
+  return jit_dispatch_mode(mode, [&](auto md) {
+    return be_dispatch_wdtype(wdtype, [&](auto w) {
+      using W = typename decltype(w)::type;
+      return run_jit_float<decltype(md)::value, W>(p, X, out, in_len, out_len, n, gather, workspace, st);
+    });
+  });
 }
 
 int be_jitmv_float(int mode, double w0, double w1, int wdtype, int64_t clen, uint32_t seed, const void* v, void* out, int64_t shape1,

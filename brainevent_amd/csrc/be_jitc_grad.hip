@@ -69,16 +69,14 @@ __global__ void __launch_bounds__(kParamGradThreads) k_jit_param_grad(JitP p, co
       for (int off = S / 2; off > 0; off >>= 1) any |= __shfl_xor(any, off, kWave);
     }
     if (any) {
-      const int64_t cs = (int64_t)chunk * p.chunk_size;
-      const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-      const int64_t width = ce - cs;
-      const uint32_t qmax = width > (int64_t)l ? (uint32_t)((width - l + S - 1) / S) : 0u;      // l + S q < width
+      const JitSpan span = jit_chunk_span(p, chunk);
+      const int64_t cs = span.cs;
+      const uint32_t qmax = jit_positions<uint32_t>(span.width, l, S);      // l + S q < width
       const uint32_t grow = (uint32_t)row;
       const W* prow = P + row * nb;
-      uint32_t state = lr_init(p.seed, grow, (uint32_t)chunk, l);
-      uint32_t q = lr_initial_q(state, p.cl);
-      while (q < qmax) {
-        const int64_t col = cs + l + (int64_t)S * q;
+      JitWalk walk(p, grow, (uint32_t)chunk, l);
+      while (walk.q < qmax) {
+        const int64_t col = cs + l + (int64_t)S * walk.q;
         double d;
         if (VEC) {
           d = p0 * (double)WTraits<W>::load(Q, col);
@@ -90,8 +88,7 @@ __global__ void __launch_bounds__(kParamGradThreads) k_jit_param_grad(JitP p, co
         s0 += d;
         if (MODE == MODE_UNIFORM) s1 += (double)lr_uniform01(p.seed, grow, (uint32_t)col) * d;
         if (MODE == MODE_NORMAL) s1 += (double)lr_normal01(p.seed, grow, (uint32_t)col) * d;
-        state = lr_next_nz(state);
-        q = q + 1u + lr_bounded(state, p.cl - 1u);
+        walk.next(p);
       }
     }
   }
@@ -146,18 +143,6 @@ int run_param_grad(const JitP& p, const ParamGradGeom& g, const void* P, const v
   return BE_OK;
 }
 
-template <int MODE>
-int dispatch_param_grad(const JitP& p, const ParamGradGeom& g, int wdtype, const void* P, const void* Q, int64_t n_rows, int64_t nb,
-                        double* partial, hipStream_t st) {
-  switch (wdtype) {
-    case BE_F32: return run_param_grad<MODE, float>(p, g, P, Q, n_rows, nb, partial, st);
-    case BE_F64: return run_param_grad<MODE, double>(p, g, P, Q, n_rows, nb, partial, st);
-    case BE_F16: return run_param_grad<MODE, __half>(p, g, P, Q, n_rows, nb, partial, st);
-    case BE_BF16: return run_param_grad<MODE, __hip_bfloat16>(p, g, P, Q, n_rows, nb, partial, st);
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -188,12 +173,12 @@ int be_jit_param_grad(int mode, int wdtype, int64_t clen, uint32_t seed, const v
              BE_ERR_WORKSPACE, "workspace too small");
   const JitP p = make_params(shape1, walk_len, seed, clen, stride, 0.0, 0.0);      // (the chunks are a loop here, not a grid dimension)
   double* partial = static_cast<double*>(workspace);
-  int rc;
-  switch (mode) {
-    case MODE_SCALAR: rc = dispatch_param_grad<MODE_SCALAR>(p, g, wdtype, P, Q, n_rows, nb, partial, st); break;
-    case MODE_UNIFORM: rc = dispatch_param_grad<MODE_UNIFORM>(p, g, wdtype, P, Q, n_rows, nb, partial, st); break;
-    default: rc = dispatch_param_grad<MODE_NORMAL>(p, g, wdtype, P, Q, n_rows, nb, partial, st); break;
-  }
+  const int rc = jit_dispatch_mode(mode, [&](auto md) {
+    return be_dispatch_wdtype(wdtype, [&](auto w) {
+      using W = typename decltype(w)::type;
+      return run_param_grad<decltype(md)::value, W>(p, g, P, Q, n_rows, nb, partial, st);
+    });
+  });
   if (rc != BE_OK) return rc;
   hipLaunchKernelGGL(k_jit_param_grad_reduce, dim3(1), dim3(kParamGradThreads), 0, st, (const double*)partial, g.grid, sums);
   BE_LAUNCH_CHECK();

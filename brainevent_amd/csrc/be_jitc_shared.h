@@ -1,6 +1,6 @@
 // be_jitc_shared.h — the light_rng sampler, the walk parameters and the per-edge weight hashes shared by the JIT-connectivity
 // translation units (be_jitc.hip: the event-driven products; be_jitc_float.hip: their float-operand twins).  Reproduced bit for
-// bit from the reference (uint32 arithmetic): brainevent/_numba_random.py:385-502; the walk itself is documented in be_jitc.hip.
+// bit from the reference (uint32 arithmetic): brainevent/_numba_random.py:385-502; the walk is stated once, below (JitWalk), and documented in be_jitc.hip.
 #pragma once
 #include "be_common.h"
 #include <algorithm>
@@ -97,7 +97,58 @@ __device__ __forceinline__ A edge_weight(const JitP& p, uint32_t row, uint32_t c
   return (A)p.w0;
 }
 
+// ------------------------------------------------------------------------------------------------ the walk
+// The single statement of the generator: every kernel that draws the matrix starts and steps its walks through these three pieces
+// and nothing else, so all of them draw the same matrix from (seed, row, chunk, lane).  Loop condition and loop body stay with
+// the kernel (the hot loops are VALU-bound and tuned one by one).
+// JitP goes in BY VALUE: the compiler scalarises a kernel's parameter block before it inlines these helpers, and a block whose
+// address has been handed to a callee stays in memory through that stage — the loops that follow then come out differently (the
+// scalar mm gather lost a third of its instructions to a rotated loop, others were rescheduled).  A copy costs nothing once inlined.
+
+// columns [cs, cs + width) of the walk dimension that chunk `chunk` covers (the last chunk may be partial)
+struct JitSpan { int64_t cs, width; };
+__device__ __forceinline__ JitSpan jit_chunk_span(JitP p, int64_t chunk) {
+  const int64_t cs = chunk * p.chunk_size;
+  const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
+  return {cs, ce - cs};
+}
+
+// number of positions q with l + S q < width, as an R (uint32_t where the walk compares it with q, int64_t where pieces are cut
+// from it: the conversion sits inside the branch, where every kernel had it)
+template <typename R>
+__device__ __forceinline__ R jit_positions(int64_t width, int64_t l, int64_t S) {
+  return width > l ? (R)((width - l + S - 1) / S) : R(0);
+}
+
+// one walk (row, chunk, lane): its next position q (chunk-local column lane + stride * q) and the generator state behind it.
+// A copy replays the walk from where the original stood.  The copy is memberwise on purpose: the implicit one moves the pair as
+// one 64-bit word, and the kernels that keep walks (the LDS mm gather: four per thread) then carry 64-bit values through the loop.
+struct JitWalk {
+  uint32_t state = 1u, q = 0u;      // (a default-constructed walk is never stepped: the sorted fill's idle walkers)
+  JitWalk() = default;
+  __device__ __forceinline__ JitWalk(const JitWalk& o) : state(o.state), q(o.q) {}
+  __device__ __forceinline__ JitWalk& operator=(const JitWalk& o) { state = o.state; q = o.q; return *this; }
+  // the stationary start (lr_init, then the rejection loop of lr_initial_q)
+  __device__ __forceinline__ JitWalk(JitP p, uint32_t row, uint32_t chunk, uint32_t lane) {
+    state = lr_init(p.seed, row, chunk, lane);
+    q = lr_initial_q(state, p.cl);
+  }
+  // to the next edge: a gap of 1 + bounded(next, cl - 1) positions
+  __device__ __forceinline__ void next(JitP p) {
+    state = lr_next_nz(state);
+    q = q + 1u + lr_bounded(state, p.cl - 1u);
+  }
+};
+
 // ------------------------------------------------------------------------------------------------ host
+// the family (MODE_*) as a template argument: f(std::integral_constant<int, MODE>); callers have checked 0 <= mode <= 2
+template <typename F>
+inline int jit_dispatch_mode(int mode, F&& f) {
+  if (mode == MODE_SCALAR) return f(std::integral_constant<int, MODE_SCALAR>{});
+  if (mode == MODE_UNIFORM) return f(std::integral_constant<int, MODE_UNIFORM>{});
+  return f(std::integral_constant<int, MODE_NORMAL>{});
+}
+
 inline int gcap(int64_t n, int block, int cap) {
   int64_t g = (n + block - 1) / block;
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -137,15 +188,6 @@ inline JitP make_params(int64_t shape1, int64_t walk_len, uint32_t seed, int64_t
 template <int MODE> struct ScatterAcc { using type = unsigned long long; };
 template <> struct ScatterAcc<MODE_SCALAR> { using type = uint32_t; };
 
-__device__ __forceinline__ unsigned long long jit_fixed_from_f32(float w, float scale) {
-  // same construction as fixed_from_f32 in be_csr.hip: w * 2^scale_exp split into (hi, lo) words in f32
-  const float t = w * scale;
-  const float hf = floorf(t);
-  const int hi = (int)hf;
-  const unsigned lo = (unsigned)((t - hf) * 4294967296.0f);
-  return ((unsigned long long)(unsigned)hi << 32) | lo;
-}
-
 // partial is class-major ([class][piece][part][piece_len], class = chunk * stride + lane residue) while the output is
 // column-major in (q, lane): out[chunk_start + stride * q + l].  One workgroup transposes a tile of `stride` classes x
 // 256 q through LDS: coalesced reads per class row, coalesced writes of stride * 256 consecutive outputs.
@@ -163,9 +205,8 @@ __global__ void __launch_bounds__(256) k_jit_scatter_reduce(const typename Scatt
   out += (int64_t)blockIdx.z * p.walk_len;
   const int S = p.stride;
   const int chunk = blockIdx.y;
-  const int64_t cs = (int64_t)chunk * p.chunk_size;
-  const int64_t ce = cs + p.chunk_size < p.walk_len ? cs + p.chunk_size : p.walk_len;
-  const int64_t width = ce - cs;
+  const JitSpan span = jit_chunk_span(p, chunk);
+  const int64_t cs = span.cs, width = span.width;
   const int64_t q0 = (int64_t)blockIdx.x * 256;
   if (q0 * S >= width) return;
   const int64_t piece = q0 / piece_len, i0 = q0 - piece * piece_len;

@@ -286,15 +286,6 @@ int plast_dense_t(bool pre, void* weights, int64_t n_rows, int64_t n_cols, const
   return BE_OK;
 }
 
-#define BE_PLAST_DISPATCH(wdtype, CALL)                                          \
-  switch (wdtype) {                                                              \
-    case BE_F32:  { using W = float;          return CALL; }                     \
-    case BE_F64:  { using W = double;         return CALL; }                     \
-    case BE_F16:  { using W = __half;         return CALL; }                     \
-    case BE_BF16: { using W = __hip_bfloat16; return CALL; }                     \
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;       \
-  }
-
 }  // namespace
 
 // the active list (and, with `rp`, the entry offsets) of a spike vector for the plan upkeep of be_csr_plan.hip (declared in
@@ -336,7 +327,10 @@ int be_plasticity_rows(void* weights, int wdtype, const int32_t* indices, const 
   hipLaunchKernelGGL(k_plast_offsets, dim3(1), dim3(kScanThreads), 0, st, rp, al.ids, al.count, ws.offs);
   BE_LAUNCH_CHECK();
   const ClipArgs c{clip_lo, clip_hi, w_lo, w_hi};
-  BE_PLAST_DISPATCH(wdtype, plast_rows_t<W>(weights, indices, rp, perm, perm_is_i64, trace, al, ws.offs, c, nnz, st));
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return plast_rows_t<W>(weights, indices, rp, perm, perm_is_i64, trace, al, ws.offs, c, nnz, st);
+  });
 }
 
 int be_plasticity_dense(int pre, void* weights, int wdtype, int64_t n_rows, int64_t n_cols, const void* spikes,
@@ -354,7 +348,10 @@ int be_plasticity_dense(int pre, void* weights, int wdtype, int64_t n_rows, int6
   int rc = plast_active(spikes, spike_dtype, n_spk, ws, st, &al);
   if (rc != BE_OK) return rc;
   const ClipArgs c{clip_lo, clip_hi, w_lo, w_hi};
-  BE_PLAST_DISPATCH(wdtype, plast_dense_t<W>(pre != 0, weights, n_rows, n_cols, trace, al, n_spk, c, st));
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return plast_dense_t<W>(pre != 0, weights, n_rows, n_cols, trace, al, n_spk, c, st);
+  });
 }
 
 }  // extern "C"

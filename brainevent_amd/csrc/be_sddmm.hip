@@ -190,13 +190,10 @@ int be_sddmm_rows(void* out, int wdtype, const int32_t* indices, const void* ind
   const RowPtr rp{src == kSrcPtr ? indptr : nullptr, indptr_is_i64, row_len};
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nb = (int)n_batch;
-  switch (wdtype) {
-    case BE_F32:  return sddmm_t<float>(src, out, indices, rp, row_ids, n_rows, n_cols, nse, p, q, nb, st);
-    case BE_F64:  return sddmm_t<double>(src, out, indices, rp, row_ids, n_rows, n_cols, nse, p, q, nb, st);
-    case BE_F16:  return sddmm_t<__half>(src, out, indices, rp, row_ids, n_rows, n_cols, nse, p, q, nb, st);
-    case BE_BF16: return sddmm_t<__hip_bfloat16>(src, out, indices, rp, row_ids, n_rows, n_cols, nse, p, q, nb, st);
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;
-  }
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return sddmm_t<W>(src, out, indices, rp, row_ids, n_rows, n_cols, nse, p, q, nb, st);
+  });
 }
 
 }  // extern "C"

@@ -319,15 +319,6 @@ bool structure_ok(const void* indptr, int64_t row_len, int64_t n_rows, int64_t n
 
 }  // namespace
 
-#define BE_SLICE_DISPATCH(wdtype, CALL)                                        \
-  switch (wdtype) {                                                            \
-    case BE_F32:  { using W = float; return CALL; }                            \
-    case BE_F64:  { using W = double; return CALL; }                           \
-    case BE_F16:  { using W = __half; return CALL; }                           \
-    case BE_BF16: { using W = __hip_bfloat16; return CALL; }                   \
-    default: be_set_error("unknown weight dtype"); return BE_ERR_INVALID;      \
-  }
-
 extern "C" {
 
 int be_slice_rows_tile_cols(int wdtype) {
@@ -352,7 +343,10 @@ int be_slice_rows(const void* data, int homo, int wdtype, const int32_t* indices
   BE_REQUIRE(structure_ok(indptr, row_len, n_rows, nse), BE_ERR_INVALID, "fixed row length does not fit n_rows and nse");
   const RowPtr rp{indptr, indptr_is_i64, indptr ? -1 : row_len};
   hipStream_t st = static_cast<hipStream_t>(stream);
-  BE_SLICE_DISPATCH(wdtype, slice_rows_t<W>(data, homo, indices, rp, rows, n_sel, out, n_rows, n_cols, nse, st));
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return slice_rows_t<W>(data, homo, indices, rp, rows, n_sel, out, n_rows, n_cols, nse, st);
+  });
 }
 
 int64_t be_slice_rows_grad_workspace_bytes(int64_t n_sel, int wdtype) {
@@ -377,8 +371,10 @@ int be_slice_rows_grad(const void* ct, int wdtype, const int32_t* indices, const
   BE_REQUIRE(!homo || (workspace != nullptr && workspace_bytes >= be_slice_rows_grad_workspace_bytes(n_sel, wdtype)),
              BE_ERR_WORKSPACE, "workspace too small");
   const RowPtr rp{indptr, indptr_is_i64, indptr ? -1 : row_len};
-  BE_SLICE_DISPATCH(wdtype, slice_rows_grad_t<W>(ct, indices, rp, urows, seg, ks, n_u, n_sel, dw, homo, n_rows, n_cols, nse,
-                                                 workspace, st));
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return slice_rows_grad_t<W>(ct, indices, rp, urows, seg, ks, n_u, n_sel, dw, homo, n_rows, n_cols, nse, workspace, st);
+  });
 }
 
 int be_slice_rows_copy(const int32_t* indices, const void* data, int elem_bytes, const void* indptr, int indptr_is_i64,

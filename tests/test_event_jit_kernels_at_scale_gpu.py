@@ -134,7 +134,7 @@ def event_bound(key, route, dtype, ref, in_len):
     A <= S / W_MIN.  The oracle forms every weight in f32 and sums in double.
       mv_gather:  k_jit_mv_gather forms the weight in f32 (edge_weight<MODE, float>: the oracle's own), sums a lane's edges, the
                   32 lanes and (k_jit_gather_reduce) the chunk partials in double and stores once:            A 2^-53 S
-      scatter:    (mv and mm) the f32 weight is cut to a multiple of 2^-e by jit_fixed_from_f32 (it floors: the negative side too);
+      scatter:    (mv and mm) the f32 weight is cut to a multiple of 2^-e by fixed_from_f32 (it floors: the negative side too);
                   the 64-bit integer sums are exact; k_jit_scatter_reduce converts (long long) sum * 2^-e in double and passes it
                   through an f32 tile for every output type but f64.  e = _jitc._fixed_scale_exp(wmax, in_len) on the mv path,
                   jit_scale_exp (the same formula, restated in fixed_scale_exp) on the mm path:                A 2^-e + u |ref|,

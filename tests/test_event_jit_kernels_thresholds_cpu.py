@@ -102,3 +102,28 @@ def test_dispatch_conditions_are_the_ones_restated(name):
 def test_every_gpu_case_crosses_its_bound():
     """The crossing assertions of the GPU cases (rows per trip against m, pieces, windows, parts, tasks against grid), here without a device."""
     check_all_crossings()
+
+
+# ---- the walk and the weight-dtype dispatch are each stated once
+WALK_SPELLINGS = ('lr_initial_q(', 'lr_next_nz(', 'q + 1u + lr_bounded(')      # start, step, step: the generator of every JITC kernel
+# BE_REQUIRE checks of a weight dtype ahead of the dispatch (entry points that need the element size, or whose message carries their name)
+DTYPE_CHECKS = {'be_dense.hip': 1, 'be_jitc_grad.hip': 1, 'be_slice.hip': 2}
+# the one other place that sets the message itself: BE_FP_PASS, a launcher macro with its own arguments (be_fixed_point.hip)
+DTYPE_SETTERS = {'be_common.h': 1, 'be_fixed_point.hip': 1}
+
+
+def test_the_walk_and_the_dtype_dispatch_are_stated_once():
+    """Every JITC kernel draws its matrix through JitWalk (be_jitc_shared.h): a second spelling of the start or the step anywhere
+    under csrc/ is a second generator that only a full GPU parity run would tell apart.  Likewise the weight-dtype switch: its
+    default case lives in be_dispatch_wdtype (be_common.h)."""
+    texts = {p.name: p.read_text() for p in sorted(CSRC.iterdir()) if p.suffix in ('.hip', '.h')}
+    for spelling in WALK_SPELLINGS:
+        holders = sorted(name for name, text in texts.items() if spelling in text)
+        assert holders == ['be_jitc_shared.h'], f"{spelling!r} is spelled in {holders}: the walk belongs to be_jitc_shared.h alone"
+    message = '"unknown weight dtype"'
+    setters = {name: text.count('be_set_error(' + message + ')') for name, text in texts.items()}
+    assert {n: c for n, c in setters.items() if c} == DTYPE_SETTERS, "a hand-written weight-dtype switch: use be_dispatch_wdtype"
+    checks = {name: len(re.findall(r'BE_REQUIRE\([^;]*' + re.escape(message) + r'\);', text)) for name, text in texts.items()}
+    assert {n: c for n, c in checks.items() if c} == DTYPE_CHECKS
+    for name, text in texts.items():      # nothing else mentions the message
+        assert text.count('unknown weight dtype') == setters[name] + checks[name], name

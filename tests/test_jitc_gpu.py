@@ -511,3 +511,42 @@ def test_scalar_scatter_counts_agree_with_the_materialised_matrix_at_any_firing_
     assert torch.equal(got.double(), ref.double())
     if n_rows == 300_000:
         assert int(ref.max()) > 2 * 65535
+
+
+def test_every_consumer_draws_the_matrix_the_materialiser_draws(be):
+    """The walk is stated once (be_jitc_shared.h: JitWalk): the event-driven products, the float twins, the per-synapse products and
+    the parameter-gradient sums all draw the matrix ``tocsr`` stores, entry for entry.  (37, 203): chunks of 51, 51, 51 and 50 over
+    the 203 side (none a multiple of 32 or 4), one partial chunk over the 37 side; weight 1 and 0 / 1 operands, so every result is
+    an exact integer and every comparison is an equality."""
+    import torch
+    from brainevent_amd import _jitc
+    shape, prob, seed, nb = (37, 203), 0.2, 29, 5
+    rng = np.random.default_rng(7)
+    v, s = spikes_of(rng, shape[1], 0.5, 'bool'), spikes_of(rng, shape[0], 0.5, 'bool')
+    B = rng.random((shape[1], nb)) < 0.5            # M @ B
+    Bt = rng.random((nb, shape[0])) < 0.5           # Bt @ M
+    for corder in (True, False):
+        M = be.JITCScalarR((np.float32(1.0), prob, seed), shape=shape, corder=corder)
+        D = {mode: np.asarray(M.tocsr(mode).todense(), dtype=np.float64) for mode in ('mv', 'mm')}
+        for mode in D:
+            assert D[mode].shape == shape and set(np.unique(D[mode])) == {0.0, 1.0}
+        assert not np.array_equal(D['mv'], D['mm'])      # (two draws: stride 32 and stride 4)
+        f32 = lambda a: np.asarray(a, dtype=np.float32)
+        for right, left, mode in ((v, s, 'mv'), (B, Bt, 'mm')):
+            # the event-driven products (gather one way, scatter the other: corder picks which) ...
+            np.testing.assert_array_equal(np.asarray(M @ be.BinaryArray(right)), D[mode] @ right)
+            np.testing.assert_array_equal(np.asarray(be.BinaryArray(left) @ M), left @ D[mode])
+            # ... and their float twins
+            np.testing.assert_array_equal(np.asarray(M @ f32(right)), D[mode] @ right)
+            np.testing.assert_array_equal(np.asarray(f32(left) @ M), left @ D[mode])
+        # dt2t with y = 1: one value per entry of the mv draw, row-major with ascending columns
+        entries = D['mv'][D['mv'] != 0].astype(np.float32)
+        for fn, n in ((M.dt2t, shape[0]), (M.dt2t_transposed, shape[1])):
+            got = fn(np.ones(n, dtype=np.float32))
+            np.testing.assert_array_equal(got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got), entries)
+        # S0 with all-ones P and Q counts the entries (generator rows = walk owners: the rows when corder, else the columns)
+        n_rows, walk = shape if corder else shape[::-1]
+        for mode, stride in (('mv', 32), ('mm', 4)):
+            sums = _jitc.jit_param_sums('s', torch.ones(n_rows, 1, device='cuda'), torch.ones(walk, 1, device='cuda'),
+                                        clen=_jitc._initialize_conn_length(prob), seed=seed, shape1=shape[1], stride=stride)
+            assert sums.cpu().tolist() == [D[mode].sum(), 0.0]
