@@ -28,6 +28,8 @@ arrays:
 * The JIT-connectivity products (``binary_jit{s,u,n}{mv,mm}``, ``jit{s,u,n}{mv,mm}`` and the six containers' ``@``) store no
   weights; their one or two PARAMETERS are differentiated by :class:`JitProduct`: both parameter gradients of a call come out
   of one walk of the generated edges (``csrc/be_jitc_grad.hip``), the operand gradient is the float twin of the transposed call.
+* ``solve`` (``_solve``) is differentiated by :class:`Solve`: ``db = A^-T g`` is one more solve on the transposed arrays, the
+  weight gradient ``-db[row] * x[col]`` the SDDMM with one batch column.  No new kernel.
 * Wrapping happens only when grad mode is on and an operand requires grad; otherwise the existing path runs untouched.  The
   forward pass of the Function IS the existing path (same route, same kernels, same bits).  Higher-order gradients are not
   supported (``once_differentiable``).
@@ -41,7 +43,7 @@ from . import _array as A
 from ._error import UnsupportedOperationError
 from ._lib import call, fn
 
-__all__ = ['RowsProduct', 'FloatRowsProduct', 'DenseProduct', 'JitProduct', 'SliceRows', 'needed']
+__all__ = ['RowsProduct', 'FloatRowsProduct', 'DenseProduct', 'JitProduct', 'SliceRows', 'Solve', 'needed']
 
 
 def _value(x):
@@ -475,6 +477,54 @@ class SliceRows(torch.autograd.Function):
 def slice_rows(data, run: Callable, grad: Callable):
     """Run ``run()`` as a :class:`SliceRows` node whose backward is ``grad``."""
     return SliceRows.apply(data, run, grad)
+
+
+class Solve(torch.autograd.Function):
+    """``x = A^-1 b`` (``_solve``: ``CSR.solve`` / ``CSC.solve`` / ``csr_solve``) over the CSR arrays ``(data, indices, indptr)`` of
+    ``A``.  With ``g`` the incoming gradient: ``db = A^-T g`` — one more solve, on the CSR arrays of ``A.T`` (the arrays of
+    ``tocsc()``), to the forward call's ``rtol`` and ``maxiter`` — and ``ddata[e] = -db[row(e)] * x[col(e)]``, the SDDMM of
+    ``csrc/be_sddmm.hip`` with one batch column; one shared weight receives the sum.  ``spec = (run, indices, indptr, n, rtol,
+    maxiter, who)``; ``run()`` is the existing forward path and returns ``(x, info)``; ``info`` is handed back through
+    ``spec``.  A backward solve that does not converge raises ``MathError``.  ``x0`` is not differentiated.  ``run`` is dropped
+    once it has run, so that the node does not keep its closure (``b``, ``x0``) alive until the backward.  The backward
+    rebuilds the index of ``A.T`` (``csr_to_csc_index``) on every call: nothing is cached on the node."""
+
+    @staticmethod
+    def forward(ctx, data, b, spec: dict):
+        x, spec['info'] = spec.pop('run')()
+        ctx.spec = spec
+        ctx.save_for_backward(data, x)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from ._convert import csr_to_csc_index
+        from ._sddmm import sddmm_rows
+        from ._solve import solve_arrays, _raise_unless_converged
+        spec = ctx.spec
+        data, x = ctx.saved_tensors
+        idx, ptr_, n = spec['indices'], spec['indptr'], spec['n']
+        w = data.detach().reshape(-1)
+        nse = int(idx.numel())
+        shared = w.numel() == 1 and nse != 1
+        tptr, tidx, perm = csr_to_csc_index(ptr_, idx, shape=(n, n))
+        tw = w.expand(nse).contiguous() if shared else w
+        db, info = solve_arrays(tw[perm.long()], tidx, tptr.to(ptr_.dtype), A.to_device(g.detach(), dtype=w.dtype), n,
+                                rtol=spec['rtol'], maxiter=spec['maxiter'])
+        _raise_unless_converged(info, spec['rtol'], spec['who'] + ' (backward)')
+        dw = None
+        if ctx.needs_input_grad[0]:
+            dw = -sddmm_rows(idx, ptr_, -1, None, n, n, db.reshape(n, 1), x.reshape(n, 1))
+            dw = (dw.sum() if shared else dw).reshape(data.shape)
+        return dw, (db if ctx.needs_input_grad[1] else None), None
+
+
+def solve(run: Callable, data, b, indices, indptr, n: int, *, rtol: float, maxiter: int, who: str):
+    """Run ``run()`` (the existing solve, ``(x, info)``) as a :class:`Solve` node; returns ``(x, info)``."""
+    spec = dict(run=run, indices=indices, indptr=indptr, n=int(n), rtol=rtol, maxiter=maxiter, who=who, info=None)
+    x = Solve.apply(data, b, spec)
+    return x, spec['info']
 
 
 def refuse_planned() -> None:

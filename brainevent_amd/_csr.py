@@ -1837,6 +1837,25 @@ class CompressedSparseData(StoredRowsData):
         from ._diag import container_diag_add
         return container_diag_add(self, other)
 
+    def solve(self, b, tol=1e-6, reorder=1, *, rtol=None, maxiter=1000, x0=None, return_info=False):
+        """Solve ``A x = b`` where ``A`` is this matrix (reference ``_csr/main.py:1778-1814``, ``:2698-2734``).  ``b`` is 1-D of
+        length ``shape[0]`` and is converted to ``data``'s dtype (f32 / f64), which the result has.
+
+        The method here is ITERATIVE — Jacobi-preconditioned BiCGSTAB on the device (``_solve``) — where the
+        reference calls a sparse QR: ``tol`` and ``reorder`` are accepted and unused.  On return ``|b - A x|_2 <= rtol |b|_2``
+        for the residual recomputed from ``x`` (``rtol=None``: ``1e-5`` for f32, ``1e-10`` for f64); ``MathError``, with the
+        residual reached and the iteration count, when ``maxiter`` iterations do not get there or the recurrence breaks down (a
+        matrix with no useful diagonal can).  ``x0``: a warm start (unused for a diagonal matrix, which one division solves).
+        ``return_info=True``: ``(x, {'iterations', 'residual', 'restarts', 'converged'})`` and nothing is raised for
+        non-convergence.  A square matrix (``ValueError``) and a 1-D ``b`` (``NotImplementedError`` for 2-D) only.
+        Differentiable in ``data`` and ``b``; bit-identical from call to call.
+
+        ``CSC.solve`` solves ``A x = b`` with the matrix this container stands for, as the reference's docstring promises,
+        through ``tocsr()``; the reference's code path (``_csr/main.py:2698-2734``) hands the arrays of ``self.T`` to the
+        solver, i.e. solves with the transposed matrix."""
+        from ._solve import container_solve
+        return container_solve(self, b, rtol=rtol, maxiter=maxiter, x0=x0, return_info=return_info)
+
     # -- per-matrix workspace ----------------------------------------------------------------------
     def _stored_rows(self) -> StoredRows:
         m, k = self.shape[::-1] if self._stored_transposed else self.shape          # (CSC stores the transpose)

@@ -66,6 +66,10 @@ class DataRepresentation:
         """Per-synapse ``w * y`` with ``y`` indexed by the column (post axis) of the matrix."""
         raise NotImplementedError(f"{type(self).__name__}.dt2t_transposed")
 
+    def solve(self, b, tol=1e-6, reorder=1, **kwargs):
+        """Solve ``A x = b`` (``brainevent_amd._solve``); served by CSR, CSC and ``Dense``."""
+        raise NotImplementedError(f"{type(self).__name__}.solve: linear systems are served by CSR, CSC and Dense only.")
+
     def __getitem__(self, index):
         """Rows of the matrix as a dense array (``brainevent_amd._slice``); served by the four stored-rows containers and
         ``Dense``."""

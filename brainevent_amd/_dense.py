@@ -213,6 +213,15 @@ class Dense(PlasticityMixin, ArithmeticMixin, DataRepresentation):
         out.diagonal().add_(A.to_device(d, dtype=out.dtype))
         return self._wrap(out)
 
+    def solve(self, b, tol=1e-6, reorder=1, *, rtol=None, maxiter=1000, x0=None, return_info=False):
+        """Solve the dense system ``self @ x = b`` by ``torch.linalg.solve`` (reference ``_dense/main.py:408-424``, with its two
+        assertions).  ``tol`` and ``reorder`` are accepted for parity with the sparse solvers and unused, as in the reference; so
+        are ``rtol``, ``maxiter`` and ``x0`` of the iterative sparse method.  ``return_info=True`` adds the dict of a direct
+        solve: zero iterations and restarts, ``residual`` the measured ``|b - A x|_2 / |b|_2`` (one dense product; 0 for
+        ``b == 0``) and ``converged`` whether that figure is finite — a direct solve has no ``rtol`` to meet."""
+        from ._solve import dense_solve
+        return dense_solve(self, b, return_info=return_info)
+
     def _event(self, other):
         from ._event import is_event, event_operand
         if not is_event(other):

@@ -935,6 +935,39 @@ int be_diag_fill(const void* weights, int w_homo, int wdtype, int64_t nse, int64
                  const int64_t* ins, const int64_t* exist, const void* diag, int64_t new_nse, int32_t* new_indices,
                  void* new_data, be_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * A x = b on CSR arrays (csrc/be_solve.hip): right-preconditioned BiCGSTAB with the Jacobi preconditioner D^-1 (D_ii = the sum
+ * of the stored (i, i) entries, 1 where that sum is zero or the diagonal is absent).
+ * replaces: CSR.solve / csr_solve (brainevent/_csr/main.py:1778-1814, _csr/spsolve.py: cuSOLVER sparse QR) — the method here is
+ *           ITERATIVE; brainevent_amd/_solve.py drives it and states its contract.
+ * The matrix is n x n with n < 2^31, weights f32 / f64 (per entry, nnz of them), indices int32, indptr int32 / int64 (n + 1
+ * entries ascending from 0 to nnz); entries of a row in any order, duplicates add.  weights, indices and x are 16-byte aligned;
+ * b, x and the work vectors are in the weight dtype.  One workspace of be_solve_workspace_bytes(n, wdtype) bytes holds the state
+ * (first 72 bytes: doubles rho, rho_old, alpha, omega, rr; int32 status (0 running, 1 converged, 2 breakdown), iterations,
+ * first, offdiag, n_rr, half), the partial sums, seven work vectors and D^-1; the same workspace goes to every call of one solve.
+ *   setup:    zeroes the state, writes D^-1 (and D, for `diagonal`); offdiag <- 1 when a nonzero entry lies off the diagonal.
+ *   residual: r = b - A x (x = NULL: r = b, the matrix is not read), rh = r, rr <- |r|^2, status, half <- 0, first <- 1: the start,
+ *             a restart with residual replacement, and the TRUE residual of a result.  Two launches.
+ *   diagonal: x = b / D, one rounding per element (for a matrix with offdiag = 0).
+ *   iterate:  n_iter (1..64) iterations of five launches each and one single-workgroup launch that leaves rr and status for the
+ *             host.  |r|^2 <= thr2 sets status 1, a vanishing or non-finite rho, rh.v, t.t or omega sets status 2; |s|^2 <= thr2
+ *             at the half step sets `half` (every workgroup of that launch still applies x += alpha y; the next launch turns
+ *             `half` into status 1, so the host reads status alone); from then on every kernel of the chunk returns at once.
+ *             iterations counts the iterations done.
+ * Dot products accumulate in f64 and are reduced in a fixed order over grids that depend on (n, nnz) alone; no float atomics,
+ * no cooperative launch, no host synchronisation (the caller reads the state back between chunks): bit-identical results
+ * from call to call.  Offsets are 64-bit.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t be_solve_workspace_bytes(int64_t n, int wdtype);
+int be_solve_setup(const void* weights, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t n,
+                   int64_t nnz, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+int be_solve_residual(const void* weights, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t n,
+                      int64_t nnz, const void* b, const void* x, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+int be_solve_diagonal(int wdtype, int64_t n, const void* b, void* x, void* workspace, int64_t workspace_bytes,
+                      be_stream_t stream);
+int be_solve_iterate(const void* weights, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t n,
+                     int64_t nnz, void* x, int n_iter, double thr2, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+
 #define BE_FOR_ALL_VARIANTS(X) \
   X(f32, BE_F32, bool, BE_SPIKE_BOOL)   X(f32, BE_F32, float, BE_SPIKE_FLOAT)   \
   X(f64, BE_F64, bool, BE_SPIKE_BOOL)   X(f64, BE_F64, float, BE_SPIKE_FLOAT)   \
