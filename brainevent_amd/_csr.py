@@ -1971,6 +1971,12 @@ class CSR(CompressedSparseData):
     def tocsr(self):
         return self
 
+    def with_delays(self, delays, depth: int):
+        """This matrix with one conduction delay per stored entry (integer steps in ``[0, depth)``, in the order of ``data``): a
+        :class:`~brainevent_amd.DelayedCSR`, multiplied from the left by a :class:`~brainevent_amd.SpikeRing`."""
+        from ._delay import DelayedCSR
+        return DelayedCSR.of_container(self, self.indptr, delays, depth)
+
     def tocsc(self):
         """The *same* matrix (same ``shape``) re-encoded column-major (reference ``_csr/main.py:1198-1218``); unlike
         :meth:`transpose`, which reinterprets the arrays as ``W.T``."""

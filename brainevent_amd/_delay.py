@@ -1,0 +1,343 @@
+"""Synaptic delays on the presynaptic side: :class:`SpikeRing` and :class:`DelayedCSR`.
+
+The last ``depth`` spike vectors are kept bit-packed (:class:`SpikeRing`); every stored row of the matrix is split by delay once
+(:class:`DelayedCSR`): stored row ``d * n_pre + i`` of the *stacked* matrix holds the synapses of neuron ``i`` whose delay is ``d``.
+``ring @ D`` is then one ordinary event-driven scatter over the stacked rows ``{d * n_pre + i : neuron i fired d steps ago}``: the
+ring is compacted into that id list (``csrc/be_delay.hip``) and the list goes through the scatter routes that exist (planned,
+binned, direct) as an :class:`~brainevent_amd._array.ActiveIds` operand.  The reference has no delays.
+
+Everything that can be refused is refused before the first device call (shapes, dtypes, the ``depth`` range), so the validation
+runs without a GPU."""
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _array as A
+from ._event import BinaryArray, BitPackedBinary, CompactBinary
+from ._lib import call, fn
+
+__all__ = ['SpikeRing', 'DelayedCSR', 'MAX_DELAY_DEPTH', 'check_ring_matches']
+
+#: largest ``depth`` of a :class:`DelayedCSR` (the split kernels keep one LDS counter per delay and wave: kMaxDepth)
+MAX_DELAY_DEPTH = 256
+#: largest number of ages one compaction covers (its grid's second dimension)
+MAX_RING_AGES = 65535
+_ID_LIMIT = 1 << 31
+
+
+def _check_ring_size(n: int, depth: int) -> None:
+    if n < 1:
+        raise ValueError(f"SpikeRing: n must be >= 1; got {n}.")
+    if depth < 1:
+        raise ValueError(f"SpikeRing: depth must be >= 1; got {depth}.")
+    if depth * n >= _ID_LIMIT:
+        raise ValueError(f"SpikeRing: depth * n = {depth * n} must stay below 2^31 (the ids of the stacked rows are int32).")
+
+
+def check_ring_matches(ring_n: int, ring_depth: int, shape, depth: int) -> None:
+    """``ring @ D`` needs a ring over ``D``'s pre population that remembers at least ``D.depth`` steps (``ValueError``)."""
+    if int(ring_n) != int(shape[0]):
+        raise ValueError(f"ring @ DelayedCSR: the ring holds {int(ring_n)} neurons, the matrix has {int(shape[0])} rows.")
+    if int(ring_depth) < int(depth):
+        raise ValueError(f"ring @ DelayedCSR: the ring remembers {int(ring_depth)} steps, the matrix needs depth {int(depth)}.")
+
+
+class SpikeRing:
+    """The last ``depth`` spike vectors of ``n`` neurons, bit-packed on the device.
+
+    ``bits`` is int32 ``[depth, ceil(n / 32)]`` (the ``BitPackedBinary`` layout per slot), ``head`` a device int32 ``[1]``.
+    :meth:`push` writes the spikes of the current step into slot ``head`` and advances ``head`` on the device, so a captured step
+    (``capture_step(fn, repeat=r)``) stays correct when replayed; the spikes of *age* ``a`` (0: just pushed) lie in slot
+    ``(head - 1 - a) mod depth``.  History before the first push is silent.  One vector per step (no batch)."""
+
+    def __init__(self, n: int, depth: int, device=None):
+        n, depth = int(n), int(depth)
+        _check_ring_size(n, depth)
+        self.n, self.depth = n, depth
+        dev = torch.device(device) if device is not None else A.device()
+        self._words = (n + 31) // 32
+        self.bits = torch.zeros((depth, self._words), dtype=torch.int32, device=dev)
+        self._state = torch.zeros(2, dtype=torch.int32, device=dev)       # head, and the push kernel's arrival ticket
+        self.head = self._state[:1]
+        self._ids = None        # the id buffer (depth * n), its counter and the operands over it: built by the first ids()
+        self._count = None
+        self._operands = {}
+        self._numpy = True      # numpy in -> numpy out: False once a device tensor was pushed
+
+    # -- writing --------------------------------------------------------------------------------------------------------
+    def push(self, spikes) -> 'SpikeRing':
+        """Store the spikes of the current step.  A tensor or numpy array of ``n`` elements (bool / integer: active when ``!= 0``;
+        float: active when ``> 0``), a ``BinaryArray``, or a ``BitPackedBinary`` / ``CompactBinary`` (their packed words are
+        copied, the bits past ``n`` cleared).  One launch, no host read."""
+        if isinstance(spikes, SpikeRing):
+            raise TypeError("SpikeRing.push takes one spike vector.")
+        if isinstance(spikes, (BitPackedBinary, CompactBinary)):
+            p = spikes._packed_operand()
+            v = p if p is not None else spikes.value
+        elif isinstance(spikes, BinaryArray):
+            v = spikes.value
+        else:
+            v = spikes
+        if isinstance(v, A.ActiveIds):
+            raise TypeError("SpikeRing.push takes spikes by position, not an id list.")
+        shape = tuple(v.shape) if hasattr(v, 'shape') else np.shape(v)
+        if len(shape) != 1:
+            raise NotImplementedError(f"SpikeRing.push takes one 1-D spike vector; got shape {shape} (batched rings are not built).")
+        if shape[0] != self.n:
+            raise ValueError(f"SpikeRing.push: {shape[0]} spikes for a ring of {self.n} neurons.")
+        if not A.wants_numpy(v):
+            self._numpy = False
+        buf, sd = A.spikes_to_device(v)
+        call('be_spike_ring_push', A.ptr(buf), sd, self.n, self.depth, A.ptr(self.bits), A.ptr(self.head),
+             A.ptr(self._state[1:]), A.stream_ptr())
+        return self
+
+    def reset(self) -> 'SpikeRing':
+        """Forget the history (``bits`` and ``head`` back to zero)."""
+        self.bits.zero_()
+        self._state.zero_()
+        return self
+
+    # -- reading --------------------------------------------------------------------------------------------------------
+    def events(self, age: int = 0) -> BitPackedBinary:
+        """The spikes of ``age`` steps ago as a ``BitPackedBinary`` (a copy of that slot): ``ring.events(3) @ csr`` is one delay
+        for a whole projection, with any container.  The slot is picked by a device-side index, so the call captures."""
+        age = int(age)
+        if not 0 <= age < self.depth:
+            raise ValueError(f"SpikeRing.events: age must lie in [0, {self.depth}); got {age}.")
+        slot = torch.remainder(self.head - (1 + age), self.depth)
+        words = self.bits.index_select(0, slot).reshape(-1)
+        return BitPackedBinary.from_packed(words, self.n)
+
+    def ids(self, ages: Optional[int] = None, row_mask: Optional[torch.Tensor] = None) -> A.ActiveIds:
+        """The ring compacted into the list ``{a * n + i : neuron i fired a steps ago, a < ages}`` (default: every age), gated by
+        ``row_mask`` (int32 ``[>= ages, ceil(n / 32)]``, word for word) — an ``ActiveIds`` over ``ages * n`` positions, in no
+        particular order.  The id buffer is allocated once, by the first call; the counter is zeroed on the stream by every call."""
+        ages = self.depth if ages is None else int(ages)
+        if not 1 <= ages <= min(self.depth, MAX_RING_AGES):
+            raise ValueError(f"SpikeRing.ids: ages must lie in [1, {min(self.depth, MAX_RING_AGES)}]; got {ages}.")
+        if row_mask is not None:
+            if row_mask.dtype != torch.int32 or row_mask.ndim != 2 or row_mask.shape[0] < ages or row_mask.shape[1] != self._words \
+                    or not row_mask.is_contiguous():
+                raise ValueError(f"SpikeRing.ids: row_mask must be a contiguous int32 [>= {ages}, {self._words}] tensor.")
+        if self._ids is None:
+            self._ids = torch.zeros(self.depth * self.n, dtype=torch.int32, device=self.bits.device)
+            self._count = torch.zeros(1, dtype=torch.int32, device=self.bits.device)
+        call('be_spike_ring_compact', A.ptr(self.bits), A.ptr(self.head), self.n, self.depth, ages, A.ptr(row_mask),
+             A.ptr(self._ids), A.ptr(self._count), A.stream_ptr())
+        op = self._operands.get(ages)
+        if op is None:
+            op = self._operands[ages] = A.ActiveIds(self._ids, self._count, ages * self.n)
+        op.numpy_result = self._numpy
+        return op
+
+    # -- product --------------------------------------------------------------------------------------------------------
+    shape = property(lambda self: (self.n,))
+    ndim = property(lambda self: 1)
+
+    def __matmul__(self, other):
+        if isinstance(other, DelayedCSR):
+            return other.__rmatmul__(self)
+        raise NotImplementedError("SpikeRing @ x is defined for a DelayedCSR; for one delay of a whole projection use "
+                                  "ring.events(age) @ matrix.")
+
+    def __rmatmul__(self, other):
+        raise NotImplementedError("x @ SpikeRing is not defined: the delays live on the presynaptic side (ring @ D).")
+
+    def __repr__(self):
+        return f"SpikeRing(n={self.n}, depth={self.depth})"
+
+
+def _as_int32_delays(delays, nnz: int):
+    """``delays`` checked without touching a device: an integer array (numpy or torch) with one element per stored entry."""
+    if not isinstance(delays, torch.Tensor):
+        delays = np.asarray(delays)
+        is_int = np.issubdtype(delays.dtype, np.integer)
+    else:
+        is_int = delays.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+    if not is_int:
+        raise TypeError(f"DelayedCSR: delays must be an integer array (steps); got dtype {delays.dtype}.")
+    if int(np.prod(tuple(delays.shape))) != nnz:
+        raise ValueError(f"DelayedCSR: {int(np.prod(tuple(delays.shape)))} delays for {nnz} stored entries.")
+    return delays
+
+
+def _shape_of(x):
+    return tuple(x.shape) if hasattr(x, 'shape') else np.shape(x)
+
+
+class DelayedCSR:
+    """A CSR matrix whose stored entries carry a conduction delay each, in steps: ``(ring @ D)[j]`` is the sum, over the entries
+    ``e`` of column ``j``, of ``w_e`` times the spike of ``row(e)`` at age ``delays[e]``.  Several entries may share ``(row, col)``
+    (parallel synapses with different delays are the normal case); all of them count.
+
+    ``DelayedCSR((data, indices, indptr, delays), shape=(n_pre, n_post), depth=depth)``: ``0 <= delays[e] < depth <= 256``, one
+    integer per stored entry in the order of ``data`` (``ValueError`` naming an offending position otherwise).  ``indptr=None``:
+    rows of fixed length, ``indices`` is ``[n_pre, row_len]``.  ``data`` with one element is one shared weight and stays shared.
+
+    ``stacked`` is a plain :class:`~brainevent_amd.CSR` of shape ``(depth * n_pre, n_post)`` whose row ``d * n_pre + i`` holds the
+    entries of row ``i`` with delay ``d`` in their original order; ``perm`` maps a stacked position to the original one;
+    ``row_mask`` (int32 ``[depth, ceil(n_pre / 32)]``) marks the non-empty stacked rows.  Gradients, STDP on delayed synapses, CSC
+    and JIT-connectivity inputs and batched rings are not built."""
+
+    def __init__(self, args, *, shape, depth: int, backend: Optional[str] = None):
+        if len(args) != 4:
+            raise ValueError("DelayedCSR expects (data, indices, indptr, delays).")
+        data, indices, indptr, delays = args
+        depth = int(depth)
+        shape = (int(shape[0]), int(shape[1]))
+        if not 1 <= depth <= MAX_DELAY_DEPTH:
+            raise ValueError(f"DelayedCSR: depth must lie in [1, {MAX_DELAY_DEPTH}]; got {depth}.")
+        if shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"DelayedCSR: shape must be positive; got {shape}.")
+        if depth * shape[0] >= _ID_LIMIT:
+            raise ValueError(f"DelayedCSR: depth * n_pre = {depth * shape[0]} must stay below 2^31 (stacked row ids are int32).")
+        ishape = _shape_of(indices)
+        if indptr is None:
+            if len(ishape) != 2 or ishape[0] != shape[0]:
+                raise ValueError(f"DelayedCSR: with indptr=None indices must be [n_pre, row_len]; got shape {ishape}.")
+            row_len = int(ishape[1])
+        else:
+            if len(ishape) != 1:
+                raise ValueError(f"DelayedCSR: indices must be 1-D beside an indptr; got shape {ishape}.")
+            if _shape_of(indptr) != (shape[0] + 1,):
+                raise ValueError(f"DelayedCSR: indptr must have n_pre + 1 = {shape[0] + 1} elements; got shape {_shape_of(indptr)}.")
+            row_len = -1
+        nnz = int(np.prod(ishape))
+        n_data = int(np.prod(_shape_of(data)))
+        if n_data != 1 and n_data != nnz:
+            raise ValueError(f"DelayedCSR: data must have one element or one per stored entry ({nnz}); got {n_data}.")
+        delays = _as_int32_delays(delays, nnz)
+        # ---- everything below runs on the device
+        from ._misc import _as_int32_indices, _as_indptr
+        self._numpy_result = A.wants_numpy(data, indices, indptr, delays)
+        self.shape, self.depth, self.backend = shape, depth, backend
+        self.delays = A.to_device(delays, torch.int32).reshape(-1)
+        w = A.to_device(data)
+        if not w.dtype.is_floating_point:
+            raise TypeError('Weights must be a floating-point type.')
+        idx = _as_int32_indices(A.to_device(indices), shape[1], 'DelayedCSR', check_values=True)
+        ptr_ = None
+        if indptr is not None:
+            ptr_ = A.to_device(indptr)
+            if ptr_.dtype not in (torch.int32, torch.int64):
+                ptr_ = _as_indptr(ptr_, nnz, 'auto', 'DelayedCSR')
+            if int(ptr_[0]) != 0 or int(ptr_[-1]) != nnz or bool((ptr_[1:] < ptr_[:-1]).any()):
+                raise ValueError("DelayedCSR: indptr must start at 0, be non-decreasing and end at the number of stored entries.")
+        self._data_shape = tuple(w.shape)
+        indptr_s, perm, indices_s, self.row_mask = _split_by_delay(idx, ptr_, row_len, self.delays, shape[0], depth, nnz)
+        self.perm = perm
+        data_s = w.reshape(-1) if n_data == 1 else w.reshape(-1)[self._gather]
+        self.stacked = _stacked_csr(data_s, indices_s, indptr_s, (depth * shape[0], shape[1]), backend, self._numpy_result)
+
+    @classmethod
+    def of_container(cls, M, indptr, delays, depth: int) -> 'DelayedCSR':
+        """``M.with_delays``: the arrays of a ``CSR`` / ``FixedNumPerPre`` (``indptr=None``); results follow ``M``'s numpy rule."""
+        obj = cls((M.data, M.indices, indptr, delays), shape=M.shape, depth=depth, backend=M.backend)
+        obj._numpy_result = obj.stacked._numpy_result = M._numpy_result
+        return obj
+
+    # -- properties -----------------------------------------------------------------------------------------------------
+    dtype = property(lambda self: self.stacked.data.dtype)
+    ndim = property(lambda self: 2)
+    nse = property(lambda self: int(self.delays.numel()))
+
+    @property
+    def _gather(self) -> torch.Tensor:
+        """``perm`` as torch indexes with it (int64): made when asked for, not kept — 8 bytes per entry."""
+        return self.perm if self.perm.dtype == torch.int64 else self.perm.long()
+
+    @property
+    def data(self):
+        """The weights in the ORIGINAL order (gathered back from ``stacked.data``; one shared weight as it is)."""
+        d = self.stacked.data
+        if int(np.prod(self._data_shape)) == 1:
+            return d.reshape(self._data_shape)
+        out = torch.empty_like(d)
+        out[self._gather] = d
+        return out.reshape(self._data_shape)
+
+    def prepare(self, **kw) -> 'DelayedCSR':
+        """Build the stacked matrix's scatter workspace now (``CSR.prepare``'s keywords)."""
+        self.stacked.prepare(**kw)
+        return self
+
+    def _stacked_order(self, new_data) -> torch.Tensor:
+        w = A.to_device(new_data)
+        old = self.stacked.data
+        if int(w.numel()) != int(np.prod(self._data_shape)) or w.dtype != old.dtype:
+            raise ValueError(f"DelayedCSR: new data must have {int(np.prod(self._data_shape))} elements of {old.dtype} "
+                             f"(the original order); got {int(w.numel())} of {w.dtype}.")
+        return w.reshape(-1) if old.numel() == 1 and w.numel() == 1 else w.reshape(-1)[self._gather]
+
+    def with_data(self, new_data) -> 'DelayedCSR':
+        """Same structure and delays, new weights, given in the original order: a new container that shares ``perm``, ``delays``,
+        ``row_mask`` and the stacked structure (scatter workspaces are not shared: they embed the weights)."""
+        obj = object.__new__(DelayedCSR)
+        obj.__dict__.update(self.__dict__)
+        obj.stacked = _stacked_csr(self._stacked_order(new_data), self.stacked.indices, self.stacked.indptr, self.stacked.shape,
+                                   self.backend, self._numpy_result)
+        return obj
+
+    def set_data_(self, new_data) -> 'DelayedCSR':
+        """:meth:`with_data` in place: writes ``stacked.data`` (``copy_``), under the staleness rules of ``csr.data`` — the next
+        product refreshes a cached workspace by itself; between replays of a captured step call ``stacked.refresh_weights()``."""
+        self.stacked.data.copy_(self._stacked_order(new_data).reshape(self.stacked.data.shape))
+        return self
+
+    # -- product --------------------------------------------------------------------------------------------------------
+    def __rmatmul__(self, ring):
+        if not isinstance(ring, SpikeRing):
+            raise NotImplementedError("x @ DelayedCSR is defined for a SpikeRing (one vector per step); a 2-D or batched "
+                                      "history is not built.")
+        check_ring_matches(ring.n, ring.depth, self.shape, self.depth)
+        if torch.is_grad_enabled() and self.stacked.data.requires_grad:
+            raise NotImplementedError("gradients through the delayed product are not built: detach the weights.")
+        from ._csr import _csr_p_call, binary_csrmv_p
+        ids = ring.ids(ages=self.depth, row_mask=self.row_mask)
+        st = self.stacked
+        rows = st._stored_rows()
+        r = _csr_p_call(binary_csrmv_p, st.data, rows.indices, rows.indptr, ids, st._scatter_workspace(), (rows.m, rows.k), True,
+                        self.backend)[0]
+        return A.to_result(r, self._numpy_result and ring._numpy)
+
+    def __matmul__(self, other):
+        raise NotImplementedError("DelayedCSR @ x is not defined: the delays live on the presynaptic side (ring @ D).")
+
+    def __repr__(self):
+        return f"DelayedCSR(shape={self.shape}, depth={self.depth}, nse={self.nse}, dtype={self.dtype})"
+
+
+def _stacked_csr(data, indices, indptr, shape, backend, numpy_result):
+    from ._csr import CSR
+    st = CSR((data, indices, indptr), shape=shape, backend=backend, indptr_dtype=indptr.dtype, check_structure=False)
+    st._numpy_result = numpy_result
+    return st
+
+
+def _split_by_delay(indices, indptr, row_len: int, delays, m: int, depth: int, nnz: int):
+    """``(indptr_s, perm, indices_s, row_mask)`` of the stacked matrix (``be_delay_split_count`` -> scan -> ``_fill``).  The index
+    type of ``indptr_s`` and ``perm`` is int64 whenever ``indptr`` is, or from 2^31 entries on.  Reads the error word once."""
+    dev = delays.device
+    is64 = int(indptr is not None and indptr.dtype == torch.int64)
+    out64 = int(bool(is64) or nnz >= _ID_LIMIT)
+    pt = torch.int64 if out64 else torch.int32
+    if nnz == 0:
+        return (torch.zeros(depth * m + 1, dtype=pt, device=dev), torch.zeros(0, dtype=pt, device=dev),
+                torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros((depth, (m + 31) // 32), dtype=torch.int32, device=dev))
+    counts = torch.empty(depth * m + 1, dtype=pt, device=dev)
+    ws = A.workspace(fn('be_delay_split_workspace_bytes')(m, depth))
+    call('be_delay_split_count', A.ptr(indptr), is64, row_len, A.ptr(delays), m, depth, A.ptr(counts), out64, A.ptr(ws), ws.numel(),
+         A.stream_ptr())
+    bad = int(ws[:8].view(torch.int64)[0])           # (the error word, read once: a host synchronisation, at build time)
+    if bad >= 0:
+        raise ValueError(f"DelayedCSR: delays[{bad}] = {int(delays[bad])} lies outside [0, depth = {depth}).")
+    indptr_s = torch.cumsum(counts, 0, dtype=pt)
+    del counts
+    perm = torch.empty(nnz, dtype=pt, device=dev)
+    indices_s = torch.empty(nnz, dtype=torch.int32, device=dev)
+    row_mask = torch.zeros((depth, (m + 31) // 32), dtype=torch.int32, device=dev)
+    call('be_delay_split_fill', A.ptr(indptr), is64, row_len, A.ptr(delays), A.ptr(indices), m, depth, A.ptr(indptr_s), out64,
+         A.ptr(perm), A.ptr(indices_s), A.ptr(row_mask), A.stream_ptr())
+    return indptr_s, perm, indices_s, row_mask

@@ -324,6 +324,13 @@ class FixedNumPerPre(FixedNumConn):
     num_pre = property(lambda self: int(self.indices.shape[0]))
     num_post = property(lambda self: int(self.shape[1]))
 
+    def with_delays(self, delays, depth: int):
+        """This matrix with one conduction delay per stored entry (integer steps in ``[0, depth)``, shaped like ``indices``): a
+        :class:`~brainevent_amd.DelayedCSR` (the stacked rows no longer have one length), multiplied from the left by a
+        :class:`~brainevent_amd.SpikeRing`."""
+        from ._delay import DelayedCSR
+        return DelayedCSR.of_container(self, None, delays, depth)
+
     def transpose(self, axes=None):
         assert axes is None, "transpose does not support axes argument."
         obj = FixedNumPerPost((self.data, self.indices), shape=self.shape[::-1], backend=self.backend, check_indices=False)

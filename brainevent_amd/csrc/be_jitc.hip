@@ -588,8 +588,16 @@ inline int64_t jit_active_stride(int64_t m) { return be_align_up(m * 4, 256) / 4
 
 inline int64_t jit_scatter_ws_bytes(const JitP& p, int64_t m, int64_t nb) {
   const ScatterGeom g = scatter_geom(p, false, nb), gs = scatter_geom(p, true, nb);
-  const int64_t a = (int64_t)g.n_classes * g.pieces * g.parts * g.piece_len * 8;
-  const int64_t b = (int64_t)gs.n_classes * gs.pieces * gs.parts * gs.piece_len * 4;
+  // A sharded call (be_binary_jitmv_sharded) runs over a sub-range of the classes on a workspace sized HERE, for all of them, and
+  // scatter_geom gives fewer classes more parts: c classes take c * pieces * parts(c) <= max(all classes * pieces,
+  // BE_JIT_WG_TARGET / nb) workgroups, each with piece_len partial sums.  Sized for that bound: 224 classes (parts 1) cut eight
+  // ways are 28 classes x 9 parts = 252 workgroups, which wrote 28 x piece_len sums past a workspace sized for 224.
+  auto groups = [nb](const ScatterGeom& x) {
+    const int64_t all = (int64_t)x.n_classes * x.pieces;
+    return std::max(all * x.parts, std::min<int64_t>(BE_JIT_WG_TARGET / std::max<int64_t>(1, nb), all * 16));
+  };
+  const int64_t a = groups(g) * g.piece_len * 8;
+  const int64_t b = groups(gs) * gs.piece_len * 4;
   return jit_counts_bytes(nb) + nb * jit_active_stride(m) * 4 + be_align_up(nb * std::max(a, b), 256);
 }
 

@@ -968,6 +968,43 @@ int be_solve_diagonal(int wdtype, int64_t n, const void* b, void* x, void* works
 int be_solve_iterate(const void* weights, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t n,
                      int64_t nnz, void* x, int n_iter, double thr2, void* workspace, int64_t workspace_bytes, be_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * synaptic delays on the presynaptic side (brainevent_amd/csrc/be_delay.hip; the reference has no delays)
+ *
+ * Delay split: the stored rows (indptr, or indptr = NULL and rows of row_len entries) of an m-row matrix and one delay in
+ * [0, depth) per stored entry become the STACKED matrix of depth * m rows: stacked row d * m + i holds the entries of row i whose
+ * delay is d, in their original relative order (stable).  1 <= depth <= 256.
+ *   be_delay_split_count: counts[0] = 0, counts[1 + d * m + i] = entries of row i with delay d (counts: depth * m + 1 elements, int64
+ *     when out_is64, else int32); the inclusive scan of counts is indptr_s (the caller scans).  workspace[0..8): the smallest
+ *     position whose delay lies outside [0, depth), as int64; -1 when there is none (rewritten by every call).  Such an entry is
+ *     skipped by both passes and indexes nothing.
+ *   be_delay_split_fill: perm[p] = original position of stacked position p (the element type of indptr_s: out_is64),
+ *     indices_s[p] = indices[perm[p]] (optional: NULL), row_mask[d * ceil(m/32) + i/32] bit i%32 = stacked row d * m + i is not
+ *     empty (optional: NULL).  No entry-sized temporary, no row-id array, no global atomic places an entry.
+ * Neither call synchronises the host.
+ *
+ * Spike ring: bits[depth][ceil(n/32)] uint32 words (bit i%32 of word i/32, the BE_SPIKE_BITS layout per slot), head[1] and
+ * arrivals[1], all on the device and zero to begin with.  depth * n < 2^31.
+ *   be_spike_ring_push: packs spikes[n] (BE_SPIKE_BOOL, BE_SPIKE_FLOAT, or BE_SPIKE_BITS words, whose bits past n are dropped) into
+ *     slot *head, then *head = (*head + 1) % depth — one launch, no host read; arrivals is the launch's own ticket word and is zero
+ *     again when it ends.  The spikes of age a (0: the last push) lie in slot (*head - 1 - a) mod depth.
+ *   be_spike_ring_compact: for a in [0, ages), ages <= depth, and every bit i set in the slot of age a AND in row_mask[a] (word
+ *     for word; row_mask = NULL keeps all), a * n + i is appended to active_ids (room for ages * n), in no particular order, each
+ *     once; *count = how many.  *count is zeroed on the stream by the call itself.  {active_ids, count} is a be_spike_ids_t over
+ *     ages * n positions: the BE_SPIKE_IDS operand of the scatter entry points for the stacked matrix.
+ * Both are graph-capturable: head is read on the device.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t be_delay_split_workspace_bytes(int64_t m, int depth);
+int be_delay_split_count(const void* indptr, int indptr_is_i64, int64_t row_len, const int32_t* delays, int64_t m, int depth,
+                         void* counts, int out_is_i64, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+int be_delay_split_fill(const void* indptr, int indptr_is_i64, int64_t row_len, const int32_t* delays, const int32_t* indices,
+                        int64_t m, int depth, const void* indptr_s, int out_is_i64, void* perm, int32_t* indices_s,
+                        uint32_t* row_mask, be_stream_t stream);
+int be_spike_ring_push(const void* spikes, int spike_dtype, int64_t n, int depth, uint32_t* bits, int32_t* head,
+                       uint32_t* arrivals, be_stream_t stream);
+int be_spike_ring_compact(const uint32_t* bits, const int32_t* head, int64_t n, int depth, int ages, const uint32_t* row_mask,
+                          uint32_t* active_ids, uint32_t* count, be_stream_t stream);
+
 #define BE_FOR_ALL_VARIANTS(X) \
   X(f32, BE_F32, bool, BE_SPIKE_BOOL)   X(f32, BE_F32, float, BE_SPIKE_FLOAT)   \
   X(f64, BE_F64, bool, BE_SPIKE_BOOL)   X(f64, BE_F64, float, BE_SPIKE_FLOAT)   \
