@@ -117,6 +117,8 @@ class CscBuilder:
         p_out, p64 = None, int(self.nnz > np.iinfo(np.int32).max)
         if perm:
             p_out = torch.empty(n, dtype=torch.int64 if p64 else torch.int32, device=dev)
+        if n == 0:          # nothing stored in these columns: no launch (an empty tensor's pointer is NULL, which the library refuses)
+            return rows, w_out, p_out
         cursor = torch.empty(max(c1 - c0, 1), dtype=torch.int64, device=dev)
         is64 = int(self.indptr is not None and self.indptr.dtype == torch.int64)
         call('be_csr_to_csc_fill_block', A.ptr(self.indices), A.ptr(self.indptr), is64, self.row_len, self.m, self.nnz, c0, c1,
