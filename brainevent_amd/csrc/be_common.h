@@ -101,6 +101,14 @@ template <typename F>
 inline int be_dispatch_bool(bool flag, F&& f) {
   return flag ? f(std::true_type{}) : f(std::false_type{});
 }
+// one of the listed integers: f(std::integral_constant<int, V>); a value outside the list is the caller's bug
+template <int... Vs, typename F>
+inline int be_dispatch_int(int v, F&& f) {
+  int rc = BE_ERR_INVALID;
+  const bool hit = ((v == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  if (!hit) be_set_error("be_dispatch_int: no kernel for the value " + std::to_string(v));
+  return rc;
+}
 // weight dtype x homo flag: f(be_type_tag<W>, std::bool_constant<HOMO>)
 template <typename F>
 inline int be_dispatch_w_homo(int wdtype, bool homo, F&& f) {

@@ -208,26 +208,33 @@ __global__ void __launch_bounds__(256) k_plan_fill(const W* __restrict__ weights
 // the part's region of the workspace instead (all workgroups of the part write identical values there).
 // FUSED: 0 = list from the workspace (compaction kernel or the caller's ids), 1 = bit-packed spikes, 2 = 1-byte spikes.
 // =================================================================================================
-template <int FUSED>
-__device__ __forceinline__ uint32_t fused_word(const void* __restrict__ spikes, int64_t gw, int64_t m) {
+// activity bits of rows [ROWS g, ROWS g + ROWS): a word (32) or half a word (16) of the bit-packed vector, or ROWS 1-byte spikes
+template <int FUSED, int ROWS>
+__device__ __forceinline__ uint32_t fused_bits(const void* __restrict__ spikes, int64_t g, int64_t m) {
+  static_assert(ROWS == 32 || ROWS == 16, "a word or half a word");
   uint32_t w = 0;
   if (FUSED == 1) {
-    w = static_cast<const uint32_t*>(spikes)[gw];
+    const uint32_t* words = static_cast<const uint32_t*>(spikes);
+    w = ROWS == 32 ? words[g] : (words[g >> 1] >> ((uint32_t)(g & 1) * 16u)) & 0xffffu;
   } else {
-    const uint8_t* sp = static_cast<const uint8_t*>(spikes) + gw * 32;
-    if (gw * 32 + 32 <= m) {
-      const uint4 a = reinterpret_cast<const uint4*>(sp)[0], b = reinterpret_cast<const uint4*>(sp)[1];
-      const uint32_t v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const uint8_t* sp = static_cast<const uint8_t*>(spikes) + g * ROWS;
+    if (g * ROWS + ROWS <= m) {
+      uint32_t v[ROWS / 4];
 #pragma unroll
-      for (int q = 0; q < 8; ++q)
+      for (int q = 0; q < ROWS / 16; ++q) {
+        const uint4 a = reinterpret_cast<const uint4*>(sp)[q];
+        v[4 * q] = a.x, v[4 * q + 1] = a.y, v[4 * q + 2] = a.z, v[4 * q + 3] = a.w;
+      }
+#pragma unroll
+      for (int q = 0; q < ROWS / 4; ++q)
 #pragma unroll
         for (int e = 0; e < 4; ++e) w |= (((v[q] >> (8 * e)) & 0xffu) != 0u ? 1u : 0u) << (4 * q + e);
     } else {
-      for (int e = 0; e < 32 && gw * 32 + e < m; ++e) w |= (sp[e] != 0 ? 1u : 0u) << e;
+      for (int e = 0; e < ROWS && g * ROWS + e < m; ++e) w |= (sp[e] != 0 ? 1u : 0u) << e;
     }
   }
-  const int64_t left = m - gw * 32;                        // spikes of the population in this word
-  return left >= 32 ? w : (left > 0 ? (w & ((1u << (uint32_t)left) - 1u)) : 0u);
+  const int64_t left = m - g * ROWS;                       // spikes of the population in this group
+  return left >= ROWS ? w : (left > 0 ? (w & ((1u << (uint32_t)left) - 1u)) : 0u);
 }
 
 // inclusive scan over the 1024 threads + the block total with ONE barrier: consecutive calls alternate between two
@@ -266,7 +273,7 @@ __device__ __forceinline__ uint32_t build_part_list(const void* __restrict__ spi
   for (int64_t u0 = 0; u0 < my_words; u0 += 1024) {
     const int64_t u = u0 + threadIdx.x;
     const int64_t gw = ((u >> 5) * parts + part) * 32 + (u & 31);
-    uint32_t w = (u < my_words && gw < n_words) ? fused_word<FUSED>(spikes, gw, m) : 0u;
+    uint32_t w = (u < my_words && gw < n_words) ? fused_bits<FUSED, 32>(spikes, gw, m) : 0u;
     const uint32_t v = __popc(w);
     uint32_t it_total;
     uint32_t pos = base + block_scan_total_1024(v, wave_tot + 16 * buf, &it_total) - v;
@@ -298,55 +305,38 @@ __device__ __forceinline__ uint32_t build_part_list(const void* __restrict__ spi
 // kernel then gives every part a contiguous range of positions and every wave 64 consecutive ones, reads its 64 entries as
 // one 512-byte load, and never loads a row id at all (FUSED = 3).
 // =================================================================================================
+// one tile of the table (a workgroup of 256): the entries of the n_here <= 64 rows ids[0 .. n_here) in every slice, written
+// transposed to dense_at[slice * a_stride + i] (dense_at = the table at the list position of ids[0])
+__device__ __forceinline__ void gather_tile(uint2 (*tile)[65], const uint2* __restrict__ seg, const uint32_t* ids, uint32_t n_here,
+                                            int n_slices, int64_t a_stride, uint2* __restrict__ dense_at) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // a wave takes 16 of the 64 rows: their ids in one load, then 16 independent row reads in flight (two memory latencies
+  // per tile instead of 32)
+  const uint32_t i_mine = (uint32_t)wave * 16u + (uint32_t)(lane & 15);
+  const uint32_t rid = ids[i_mine < n_here ? i_mine : 0u];
+  for (int s0 = 0; s0 < n_slices; s0 += 64) {
+    const int sl = s0 + lane < n_slices ? s0 + lane : n_slices - 1;
+    uint2 v[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = seg[(uint64_t)__builtin_amdgcn_readlane((int)rid, j) * n_slices + sl];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) tile[wave * 16 + j][lane] = v[j];
+    __syncthreads();
+    for (int s = wave; s < 64 && s0 + s < n_slices; s += 4)      // wave: one slice; lanes: 64 consecutive positions
+      if ((uint32_t)lane < n_here) dense_at[(int64_t)(s0 + s) * a_stride + lane] = tile[lane][s];
+    __syncthreads();
+  }
+}
+
 __global__ void __launch_bounds__(256) k_gather_seg(const uint2* __restrict__ seg, const uint32_t* __restrict__ active,
                                                     const uint32_t* __restrict__ n_active_p, int n_slices, int64_t a_stride,
                                                     uint2* __restrict__ dense) {
   __shared__ uint2 tile[64][65];
   const uint32_t n_active = *n_active_p;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (uint32_t c = blockIdx.x; (uint64_t)c * 64 < n_active; c += gridDim.x) {
     const uint32_t a0 = c * 64;
-    const uint32_t n_here = n_active - a0 < 64u ? n_active - a0 : 64u;
-    // a wave takes 16 of the 64 rows: their ids in one load, then 16 independent row reads in flight (two memory latencies
-    // per tile instead of 32)
-    const uint32_t i_mine = (uint32_t)wave * 16u + (uint32_t)(lane & 15);
-    const uint32_t rid = active[a0 + (i_mine < n_here ? i_mine : 0u)];
-    for (int s0 = 0; s0 < n_slices; s0 += 64) {
-      const int sl = s0 + lane < n_slices ? s0 + lane : n_slices - 1;
-      uint2 v[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = seg[(uint64_t)__builtin_amdgcn_readlane((int)rid, j) * n_slices + sl];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) tile[wave * 16 + j][lane] = v[j];
-      __syncthreads();
-      for (int s = wave; s < 64 && s0 + s < n_slices; s += 4)      // wave: one slice; lanes: 64 consecutive positions
-        if ((uint32_t)lane < n_here) dense[(int64_t)(s0 + s) * a_stride + a0 + lane] = tile[lane][s];
-      __syncthreads();
-    }
+    gather_tile(tile, seg, active + a0, n_active - a0 < 64u ? n_active - a0 : 64u, n_slices, a_stride, dense + a0);
   }
-}
-
-// activity bits of rows [16 g, 16 g + 16) (bit-packed words or 1-byte spikes)
-template <int FUSED>
-__device__ __forceinline__ uint32_t fused_half(const void* __restrict__ spikes, int64_t g, int64_t m) {
-  uint32_t w = 0;
-  if (FUSED == 1) {
-    w = (static_cast<const uint32_t*>(spikes)[g >> 1] >> ((uint32_t)(g & 1) * 16u)) & 0xffffu;
-  } else {
-    const uint8_t* sp = static_cast<const uint8_t*>(spikes) + g * 16;
-    if (g * 16 + 16 <= m) {
-      const uint4 a = reinterpret_cast<const uint4*>(sp)[0];
-      const uint32_t v[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w |= (((v[q] >> (8 * e)) & 0xffu) != 0u ? 1u : 0u) << (4 * q + e);
-    } else {
-      for (int e = 0; e < 16 && g * 16 + e < m; ++e) w |= (sp[e] != 0 ? 1u : 0u) << e;
-    }
-  }
-  const int64_t left = m - g * 16;
-  return left >= 16 ? w : (left > 0 ? (w & ((1u << (uint32_t)left) - 1u)) : 0u);
 }
 
 // Compaction and gather in one launch (bit-packed or 1-byte spikes): a workgroup scans 4096 rows, reserves its range of list
@@ -362,7 +352,7 @@ __global__ void __launch_bounds__(256) k_compact_gather_seg(const void* __restri
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t n_groups = (m + 15) >> 4;
   const int64_t gw = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  uint32_t w = gw < n_groups ? fused_half<FUSED>(spikes, gw, m) : 0u;
+  uint32_t w = gw < n_groups ? fused_bits<FUSED, 16>(spikes, gw, m) : 0u;
   const uint32_t v = __popc(w);
   uint32_t incl = v;
 #pragma unroll
@@ -388,23 +378,8 @@ __global__ void __launch_bounds__(256) k_compact_gather_seg(const void* __restri
   }
   __syncthreads();
   const uint32_t base = s_base;
-  for (uint32_t c0 = 0; c0 < total; c0 += 64) {
-    const uint32_t n_here = total - c0 < 64u ? total - c0 : 64u;
-    const uint32_t i_mine = (uint32_t)wave * 16u + (uint32_t)(lane & 15);
-    const uint32_t rid = ids_s[c0 + (i_mine < n_here ? i_mine : 0u)];
-    for (int s0 = 0; s0 < n_slices; s0 += 64) {
-      const int sl = s0 + lane < n_slices ? s0 + lane : n_slices - 1;
-      uint2 x[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) x[j] = seg[(uint64_t)__builtin_amdgcn_readlane((int)rid, j) * n_slices + sl];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) tile[wave * 16 + j][lane] = x[j];
-      __syncthreads();
-      for (int s = wave; s < 64 && s0 + s < n_slices; s += 4)
-        if ((uint32_t)lane < n_here) dense[(int64_t)(s0 + s) * a_stride + base + c0 + lane] = tile[lane][s];
-      __syncthreads();
-    }
-  }
+  for (uint32_t c0 = 0; c0 < total; c0 += 64)
+    gather_tile(tile, seg, ids_s + c0, total - c0 < 64u ? total - c0 : 64u, n_slices, a_stride, dense + base + c0);
 }
 
 // =================================================================================================
@@ -448,6 +423,23 @@ __device__ __forceinline__ void seg_issue(SegGroup& g, int i, int nvalid, uint32
   }
 }
 
+// lane-groups [o_begin, n) of a u16 block, a wave per block (64 lane-groups per pass): what its decoder's one pass left of a
+// long block (seg_consume, sub_tails), or the whole block (k_plan_single)
+template <bool HOMO>
+__device__ __forceinline__ void u16_walk(typename PlanAcc<HOMO>::type* acc, const unsigned char* blk, uint32_t n, uint32_t o_begin,
+                                         int lane, float scale) {
+  for (uint32_t o = o_begin + lane; o < n; o += 64) {
+    if constexpr (HOMO) {
+      const uint4 c = reinterpret_cast<const uint4*>(blk)[o];
+      plan_count8(reinterpret_cast<uint32_t*>(acc), c.x, c.y, c.z, c.w);
+    } else {
+      const uint2 ivt = reinterpret_cast<const uint2*>(blk + (uint64_t)n * 16u)[o];
+      const float4 wvt = reinterpret_cast<const float4*>(blk)[o];
+      plan_add4<HOMO>(acc, ivt, wvt, scale);
+    }
+  }
+}
+
 template <bool HOMO>
 __device__ __forceinline__ void seg_consume(const SegGroup& g, typename PlanAcc<HOMO>::type* acc, int lane, float scale,
                                             const unsigned char* __restrict__ blob) {
@@ -467,29 +459,10 @@ __device__ __forceinline__ void seg_consume(const SegGroup& g, typename PlanAcc<
   // long segments (> 256 entries): remaining chunks, wave-uniform guard
   if ((g.n4[0] | g.n4[1] | g.n4[2] | g.n4[3]) > 64u) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const unsigned char* blk = blob + ((uint64_t)g.start[q] << 7);
-      for (uint32_t o = 64 + lane; o < g.n4[q]; o += 64) {
-        if (HOMO) {
-          const uint4 c = reinterpret_cast<const uint4*>(blk)[o];
-          plan_count8(reinterpret_cast<uint32_t*>(acc), c.x, c.y, c.z, c.w);
-        } else {
-          const uint2 ivt = reinterpret_cast<const uint2*>(blk + (uint64_t)g.n4[q] * 16u)[o];
-          const float4 wvt = reinterpret_cast<const float4*>(blk)[o];
-          plan_add4<HOMO>(acc, ivt, wvt, scale);
-        }
-      }
-    }
+    for (int q = 0; q < 4; ++q) u16_walk<HOMO>(acc, blob + ((uint64_t)g.start[q] << 7), g.n4[q], 64u, lane, scale);
   }
 }
 
-// Workgroup -> (part, slice).  Blocks b and b + 8 share an XCD (round-robin dispatch, a speed assumption only):
-// block b handles linear task L = (b % 8) * (gridDim.x / 8) + b / 8 with part = L / n_slices, slice = L % n_slices,
-// so the workgroups of one XCD work on the same part (same active rows) and neighbouring slices: the rows'
-// segment-pointer lines (n_slices x 8 B per row, contiguous) are fetched into that XCD's L2 once.
-// gridDim.x is a multiple of 8; tasks L >= n_slices * parts are idle.
-// Each wave keeps two groups of 4 segments in flight (register double buffer) and prefetches the segment
-// pointers of its next 64 rows and the row ids of the 64 after those.
 // ---- counted entries, short blocks: LPB lanes per block (8 columns per lane), 64 / LPB blocks per load instruction.
 // With 31 entries per block (N = 1M, K = 1000, one shared weight) the wave-per-block path keeps 4 of 64 lanes busy.
 struct SubGroup {
@@ -537,16 +510,7 @@ __device__ __forceinline__ void sub_tails(uint32_t st_v, uint32_t n4_v, int nval
     const int src = __ffsll((long long)longm) - 1;
     longm &= longm - 1;
     const uint32_t st = (uint32_t)__builtin_amdgcn_readlane((int)st_v, src), n = (uint32_t)__builtin_amdgcn_readlane((int)n4_v, src);
-    const unsigned char* blk = blob + ((uint64_t)st << 7);
-    for (uint32_t o = LPB + lane; o < n; o += 64) {
-      const uint4 x = reinterpret_cast<const uint4*>(blk)[o];
-      if constexpr (HOMO) {
-        plan_count8(reinterpret_cast<uint32_t*>(acc), x.x, x.y, x.z, x.w);
-      } else {
-        const uint2 iv = reinterpret_cast<const uint2*>(blk + (uint64_t)n * 16u)[o];
-        plan_add4<false>(acc, iv, make_float4(__uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w)), scale);
-      }
-    }
+    u16_walk<HOMO>(acc, blob + ((uint64_t)st << 7), n, (uint32_t)LPB, lane, scale);
   }
 }
 
@@ -566,6 +530,145 @@ __device__ __forceinline__ void store_partials(const unsigned char* smem_raw, vo
     else dst[i] = v;
   }
 }
+// the accumulators' n16 pieces of 16 bytes; ends with a barrier.  How many is the kernel's business: (S + 1) slots rounded up
+// for u16 and d8, S counters for h8 — the host sizes the LDS and the workspace by the same figures
+__device__ __forceinline__ void plan_zero_lds(unsigned char* smem_raw, int n16) {
+  uint4* z = reinterpret_cast<uint4*>(smem_raw);
+  for (int i = threadIdx.x; i < n16; i += blockDim.x) z[i] = make_uint4(0u, 0u, 0u, 0u);
+  __syncthreads();
+}
+
+// =================================================================================================
+// The step's skeleton: what the three accumulate kernels (k_plan_accumulate, _d8, _h8) share.  A kernel is
+//     const PlanTask t(n_slices, parts);
+//     if (t.idle()) return;
+//     PlanRows<FUSED> rows(t, ...);
+//     plan_zero_lds(smem_raw, ...);
+//     rows.list(...);                                // the active rows of this task's part
+//     if (rows.any()) {
+//       rows.start();
+//       while (rows.more()) {
+//         const int nvalid = rows.fetch();
+//         ... its decoder over the batch's blocks: rows.st_v / rows.n4_v, lane l = the l-th row of the batch ...
+//         rows.next();
+//       }
+//     }
+//     __syncthreads();
+//     store_partials<BIT>(smem_raw, partial, ...);
+// and nothing else.
+//
+// Workgroup -> (part, slice).  Blocks b and b + 8 share an XCD (round-robin dispatch, a speed assumption only):
+// block b handles linear task L = (b % 8) * (gridDim.x / 8) + b / 8 with part = L / n_slices, slice = L % n_slices,
+// so the workgroups of one XCD work on the same part (same active rows) and neighbouring slices: the rows'
+// segment-pointer lines (n_slices x 8 B per row, contiguous) are fetched into that XCD's L2 once.
+// gridDim.x is a multiple of 8; tasks L >= n_slices * parts are idle.
+// =================================================================================================
+struct PlanTask {
+  int n_tasks, L;
+  __device__ __forceinline__ PlanTask(int n_slices, int parts) {
+    const int per_xcd = gridDim.x >> 3;
+    L = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    n_tasks = n_slices * parts;
+  }
+  __device__ __forceinline__ bool idle() const { return L >= n_tasks; }
+  // which of the step's [batch][part][slice] partial sums are this task's
+  __device__ __forceinline__ int64_t slot() const { return (int64_t)blockIdx.y * n_tasks + L; }
+};
+
+// The rows of a task, 64 per wave and batch, behind a three-stage pointer pipeline: rows of batch b+2 | bounds of batch b+1 |
+// work on batch b.  Each wave prefetches the segment pointers of its next 64 rows and the row ids of the 64 after those.
+template <int FUSED>
+struct PlanRows {
+  int n_slices, parts, part, slice, lane;
+  const uint32_t* active;
+  uint32_t n_active, pos_lo = 0;
+  const uint2* sp;
+  uint64_t seg_rs, a, a_step, last;
+  uint32_t st_v, n4_v;          // this batch: lane l holds block start and length word of the l-th row
+  bool v_c = false, v_n, v_nn;
+  uint32_t r_n, r_nn;
+  uint2 sgn;
+
+  // (ahead of the LDS zeroing: the division runs under it)
+  __device__ __forceinline__ PlanRows(const PlanTask& t, int n_slices_, int parts_, const uint32_t* active_, int64_t active_stride)
+      : n_slices(n_slices_), parts(parts_), active(active_) {
+    part = t.L / n_slices;
+    slice = t.L - part * n_slices;
+    if constexpr (FUSED == 0) active += (int64_t)blockIdx.y * active_stride;
+  }
+  // the list of this task's part and its length (all threads of the workgroup: build_part_list has barriers), and where this
+  // lane's rows sit in the list and in the segment table
+  __device__ __forceinline__ void list(const uint2* __restrict__ seg, const uint32_t* __restrict__ n_active_p, unsigned char* smem_raw,
+                                       const void* __restrict__ fused_spikes, int64_t fused_m, int64_t fused_stride, uint32_t list_off,
+                                       uint32_t lds_cap, uint32_t* __restrict__ glob_lists, int64_t glob_region) {
+    if constexpr (FUSED == 1 || FUSED == 2) {       // list the active rows of this part in LDS behind the accumulators (or in the part's region)
+      __shared__ uint32_t fused_wtot[32];
+      n_active = build_part_list<FUSED>(static_cast<const unsigned char*>(fused_spikes) + (int64_t)blockIdx.y * fused_stride, fused_m,
+                                        part, parts, reinterpret_cast<uint32_t*>(smem_raw + list_off), lds_cap,
+                                        glob_lists + ((int64_t)blockIdx.y * parts + part) * glob_region, fused_wtot, &active);
+    } else {
+      n_active = n_active_p[blockIdx.y];
+    }
+    // FUSED == 3 (pre-gathered table): part p owns the list positions [p * npp, (p + 1) * npp), a wave 64 consecutive ones
+    if constexpr (FUSED == 3) {
+      const uint32_t npp = (n_active + (uint32_t)parts - 1u) / (uint32_t)parts;
+      pos_lo = (uint32_t)part * npp;
+      const uint32_t hi = pos_lo + npp < n_active ? pos_lo + npp : n_active;
+      n_active = hi > pos_lo ? hi : pos_lo;            // from here on: one past this part's last position
+    }
+    // segment table: [row][slice] as built, or (FUSED == 3) the step's pre-gathered [slice][list position]
+    sp = FUSED == 3 ? seg + (int64_t)slice * glob_region : seg + slice;
+    seg_rs = FUSED == 3 ? 1u : (uint64_t)n_slices;
+    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    lane = threadIdx.x & 63;
+    // list position of this lane's row in batch b of this wave
+    const uint64_t a0 = FUSED == 3 ? (uint64_t)pos_lo + (uint64_t)wave * 64 + lane
+                        : FUSED  ? (uint64_t)wave + (uint64_t)nw * lane
+                                 : (uint64_t)part + (uint64_t)parts * ((uint64_t)wave + (uint64_t)nw * lane);
+    a_step = FUSED ? (uint64_t)nw * 64 : (uint64_t)parts * nw * 64;
+    a = a0;
+  }
+  __device__ __forceinline__ bool any() const { return n_active > pos_lo; }
+
+  // row id at list position a.  All pointer loads are unconditional (clamped index, result masked): with conditional global
+  // loads hipcc falls back to vmcnt(0) before every load, and the waits in front of the decoders' consumes are counted
+  __device__ __forceinline__ uint32_t row_at() const {
+    return FUSED == 3 ? (uint32_t)(a < last ? a : last) : active[a < last ? a : last];
+  }
+  // fills the pipeline: bounds of the first batch, row ids of the second.  Only if any().
+  __device__ __forceinline__ void start() {
+    last = n_active - 1;
+    v_n = a < n_active;
+    r_n = row_at();
+    a += a_step;
+    const uint2 sg = sp[(uint64_t)r_n * seg_rs];
+    st_v = sg.x, n4_v = v_n ? sg.y : 0u;
+    v_c = v_n;
+    v_n = a < n_active;
+    r_n = row_at();
+    a += a_step;
+  }
+  __device__ __forceinline__ bool more() const { return __ballot(v_c) != 0ull; }
+  // opens a batch: issues next batch's bounds and the batch-after-next's row ids before the caller touches this batch's data;
+  // returns the number of rows in this batch (valid lanes form a prefix: a grows with the lane)
+  __device__ __forceinline__ int fetch() {
+    const int nvalid = __popcll(__ballot(v_c));
+    sgn = sp[(uint64_t)r_n * seg_rs];
+    v_nn = a < n_active;
+    r_nn = row_at();
+    a += a_step;
+    return nvalid;
+  }
+  // the rotation of the pipeline
+  __device__ __forceinline__ void next() {
+    st_v = sgn.x;
+    n4_v = v_n ? sgn.y : 0u;
+    v_c = v_n;
+    v_n = v_nn;
+    r_n = r_nn;
+  }
+};
+
 template <bool HOMO, int LPB = 0, int FUSED = 0>
 __global__ void __launch_bounds__(1024) k_plan_accumulate(const unsigned char* __restrict__ blob, const uint2* __restrict__ seg,
                                                           const uint32_t* active,
@@ -582,71 +685,18 @@ __global__ void __launch_bounds__(1024) k_plan_accumulate(const unsigned char* _
   extern __shared__ __align__(16) unsigned char smem_raw[];
   acc_t* acc = reinterpret_cast<acc_t*>(smem_raw);
   const int S = 1 << slice_shift;
-  const int per_xcd = gridDim.x >> 3;
-  const int L = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  const int n_tasks = n_slices * parts;
-  if (L >= n_tasks) return;
-  const int part = L / n_slices;
-  const int slice = L - part * n_slices;
-  if constexpr (FUSED == 0) active += (int64_t)blockIdx.y * active_stride;
-  partial += ((int64_t)blockIdx.y * n_tasks + L) * stride;
-  {
-    uint4* z = reinterpret_cast<uint4*>(smem_raw);
-    const int n16 = (int)(((size_t)(S + 1) * sizeof(acc_t) + 15) / 16);
-    for (int i = threadIdx.x; i < n16; i += blockDim.x) z[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  __syncthreads();
-
-  __shared__ uint32_t fused_wtot[32];
-  uint32_t n_active;
-  if constexpr (FUSED == 1 || FUSED == 2) {       // list the active rows of this part in LDS behind the accumulators (or in the part's region)
-    n_active = build_part_list<FUSED>(static_cast<const unsigned char*>(fused_spikes) + (int64_t)blockIdx.y * fused_stride, fused_m,
-                                      part, parts, reinterpret_cast<uint32_t*>(smem_raw + list_off), lds_cap,
-                                      glob_lists + ((int64_t)blockIdx.y * parts + part) * glob_region, fused_wtot, &active);
-  } else {
-    n_active = n_active_p[blockIdx.y];
-  }
-  // FUSED == 3 (pre-gathered table): part p owns the list positions [p * npp, (p + 1) * npp), a wave 64 consecutive ones
-  uint32_t pos_lo = 0;
-  if constexpr (FUSED == 3) {
-    const uint32_t npp = (n_active + (uint32_t)parts - 1u) / (uint32_t)parts;
-    pos_lo = (uint32_t)part * npp;
-    const uint32_t hi = pos_lo + npp < n_active ? pos_lo + npp : n_active;
-    n_active = hi > pos_lo ? hi : pos_lo;            // from here on: one past this part's last position
-  }
-  // segment table: [row][slice] as built, or (FUSED == 3) the step's pre-gathered [slice][list position]
-  const uint2* sp = FUSED == 3 ? seg + (int64_t)slice * glob_region : seg + slice;
-  const uint64_t seg_rs = FUSED == 3 ? 1u : (uint64_t)n_slices;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  // list position of this lane's row in batch b of this wave
-  const uint64_t a0 = FUSED == 3 ? (uint64_t)pos_lo + (uint64_t)wave * 64 + lane
-                      : FUSED  ? (uint64_t)wave + (uint64_t)nw * lane
-                               : (uint64_t)part + (uint64_t)parts * ((uint64_t)wave + (uint64_t)nw * lane);
-  const uint64_t a_step = FUSED ? (uint64_t)nw * 64 : (uint64_t)parts * nw * 64;
-
-  // pointer pipeline: rows of batch b+2 | bounds of batch b+1 | work on batch b.  All pointer loads are
-  // unconditional (clamped index, result masked) for the same counted-vmcnt reason as above.
-  if (n_active > pos_lo) {
-    const uint64_t last = n_active - 1;
-    uint64_t a = a0;
-    bool v_n = a < n_active;
-    uint32_t r_n = FUSED == 3 ? (uint32_t)(a < last ? a : last) : active[a < last ? a : last];
-    a += a_step;
-    uint2 sg = sp[(uint64_t)r_n * seg_rs];
-    uint32_t st_v = sg.x, n4_v = v_n ? sg.y : 0u;
-    bool v_c = v_n;
-    v_n = a < n_active;
-    r_n = FUSED == 3 ? (uint32_t)(a < last ? a : last) : active[a < last ? a : last];
-    a += a_step;
-
-    while (__ballot(v_c) != 0ull) {
-      const int nvalid = __popcll(__ballot(v_c));   // valid lanes form a prefix: a grows with the lane
-      // issue next batch's bounds and the batch-after-next's row ids before touching this batch's data
-      const uint2 sgn = sp[(uint64_t)r_n * seg_rs];
-      const bool v_nn = a < n_active;
-      const uint32_t r_nn = FUSED == 3 ? (uint32_t)(a < last ? a : last) : active[a < last ? a : last];
-      a += a_step;
-
+  const PlanTask t(n_slices, parts);
+  if (t.idle()) return;
+  PlanRows<FUSED> rows(t, n_slices, parts, active, active_stride);
+  partial += t.slot() * stride;
+  plan_zero_lds(smem_raw, (int)(((size_t)(S + 1) * sizeof(acc_t) + 15) / 16));
+  rows.list(seg, n_active_p, smem_raw, fused_spikes, fused_m, fused_stride, list_off, lds_cap, glob_lists, glob_region);
+  if (rows.any()) {
+    rows.start();
+    while (rows.more()) {
+      const int nvalid = rows.fetch();
+      const uint32_t st_v = rows.st_v, n4_v = rows.n4_v;
+      const int lane = rows.lane;
       if constexpr (LPB > 0) {
         // straight-line over the batch's 64 / BPI groups, DEPTH groups ahead (see k_plan_accumulate_d8)
         constexpr int BPI = 64 / LPB;                       // blocks per load instruction
@@ -658,11 +708,15 @@ __global__ void __launch_bounds__(1024) k_plan_accumulate(const unsigned char* _
 #pragma unroll
         for (int q = 0; q < NGRP; ++q) {
           if (q + DEPTH < NGRP) sub_issue<HOMO, LPB>(g[q + DEPTH], (q + DEPTH) * BPI, nvalid, st_v, n4_v, lane, blob);
+          // nothing crosses: the loads of group q + DEPTH are in flight before the wait for group q.  (Left to itself the
+          // scheduler puts the register copies in front of the consume's opaque use — and the wait with them — ahead of the
+          // issue in some instances and not in others, whatever the source says: the queue is then one group shorter.)
+          __builtin_amdgcn_sched_barrier(0);
           sub_consume<HOMO, LPB>(g[q], acc, lane, scale);
         }
         sub_tails<HOMO, LPB>(st_v, n4_v, nvalid, acc, lane, scale, blob);
       } else {
-        SegGroup gA, gB;
+        SegGroup gA, gB;      // two groups of 4 segments in flight (register double buffer)
         seg_issue<HOMO>(gA, 0, nvalid, st_v, n4_v, lane, blob);
         for (int i = 0; i < nvalid; i += 8) {
           seg_issue<HOMO>(gB, i + 4, nvalid, st_v, n4_v, lane, blob);
@@ -671,18 +725,11 @@ __global__ void __launch_bounds__(1024) k_plan_accumulate(const unsigned char* _
           seg_consume<HOMO>(gB, acc, lane, scale, blob);
         }
       }
-      st_v = sgn.x;
-      n4_v = v_n ? sgn.y : 0u;
-      v_c = v_n;
-      v_n = v_nn;
-      r_n = r_nn;
+      rows.next();
     }
   }
   __syncthreads();
-  {
-    // stride * sizeof(acc_t) is a multiple of 16
-    store_partials<2>(smem_raw, partial, (int)((size_t)stride * sizeof(acc_t) / 16));
-  }
+  store_partials<2>(smem_raw, partial, (int)((size_t)stride * sizeof(acc_t) / 16));   // stride * sizeof(acc_t) is a multiple of 16
 }
 
 // sum of p[q * pstep], q < parts, with up to eight loads in flight (two per iteration left a 64-part reduce latency-bound;
@@ -1147,6 +1194,26 @@ __device__ __forceinline__ void d8_issue(SegGroupD8& g, int i, int nvalid, uint3
   }
 }
 
+// lane-groups [o_begin, ng) of a d8 block, a wave per block (64 lane-groups per pass), from `carry` = the column reached before
+// lane-group o_begin: what its decoder's one pass left of a long block (d8_consume, d8q_tails), or the whole block (k_plan_single)
+__device__ __forceinline__ void d8_walk(unsigned long long* acc, const unsigned char* blk, uint32_t ng, uint32_t o_begin, uint32_t carry,
+                                        int lane, float scale) {
+  for (uint32_t o0 = o_begin; o0 < ng; o0 += 64) {
+    const uint32_t o = o0 + lane;
+    const bool in = o < ng;
+    const uint32_t d = in ? reinterpret_cast<const uint32_t*>(blk + (uint64_t)ng * 16u)[o] : 0u;
+    be_v4u wv = {0u, 0u, 0u, 0u};
+    if (in) {
+      const uint4 x = reinterpret_cast<const uint4*>(blk)[o];
+      wv = be_v4u{x.x, x.y, x.z, x.w};
+    }
+    const uint32_t t = d8_sum4(d);
+    const uint32_t incl = wave_incl_scan_u32(t);
+    if (in) d8_add4(acc, carry + incl - t, d, wv, scale);
+    carry += __builtin_amdgcn_readlane(incl, 63);
+  }
+}
+
 __device__ __forceinline__ void d8_consume(const SegGroupD8& g, unsigned long long* acc, int lane, float scale,
                                            const unsigned char* __restrict__ blob) {
 #pragma unroll
@@ -1160,23 +1227,9 @@ __device__ __forceinline__ void d8_consume(const SegGroupD8& g, unsigned long lo
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       if (g.ng[q] <= 64u) continue;
-      const unsigned char* blk = blob + ((uint64_t)g.start[q] << 7);
       const uint32_t t0 = d8_sum4(g.dv[q]);
-      uint32_t carry = g.base[q] + __builtin_amdgcn_readlane(wave_incl_scan_u32(t0), 63);
-      for (uint32_t o0 = 64; o0 < g.ng[q]; o0 += 64) {
-        const uint32_t o = o0 + lane;
-        const bool in = o < g.ng[q];
-        const uint32_t d = in ? reinterpret_cast<const uint32_t*>(blk + (uint64_t)g.ng[q] * 16u)[o] : 0u;
-        be_v4u wv = {0u, 0u, 0u, 0u};
-        if (in) {
-          const uint4 x = reinterpret_cast<const uint4*>(blk)[o];
-          wv = be_v4u{x.x, x.y, x.z, x.w};
-        }
-        const uint32_t t = d8_sum4(d);
-        const uint32_t incl = wave_incl_scan_u32(t);
-        if (in) d8_add4(acc, carry + incl - t, d, wv, scale);
-        carry += __builtin_amdgcn_readlane(incl, 63);
-      }
+      d8_walk(acc, blob + ((uint64_t)g.start[q] << 7), g.ng[q], 64u,
+              g.base[q] + __builtin_amdgcn_readlane(wave_incl_scan_u32(t0), 63), lane, scale);
     }
   }
 }
@@ -1248,24 +1301,9 @@ __device__ __forceinline__ void d8q_tails(uint32_t st_v, uint32_t n4_v, int nval
     const uint32_t st = (uint32_t)__builtin_amdgcn_readlane((int)st_v, src), y = (uint32_t)__builtin_amdgcn_readlane((int)n4_v, src);
     const uint32_t ng = y & 0xffffu;
     const unsigned char* blk = blob + ((uint64_t)st << 7);
-    const uint32_t* dp = reinterpret_cast<const uint32_t*>(blk + (uint64_t)ng * 16u);
-    const uint32_t d_head = lane < LPB ? dp[lane] : 0u;                 // deltas the pipelined pass has already applied
-    uint32_t carry = (y >> 16) + (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(d8_sum4(d_head)), 63);
-    for (uint32_t o0 = LPB; o0 < ng; o0 += 64) {
-      const uint32_t o = o0 + lane;
-      const bool in = o < ng;
-      uint32_t d = 0u;
-      be_v4u wv = {0u, 0u, 0u, 0u};
-      if (in) {
-        d = dp[o];
-        const uint4 x = reinterpret_cast<const uint4*>(blk)[o];
-        wv = be_v4u{x.x, x.y, x.z, x.w};
-      }
-      const uint32_t t = d8_sum4(d);
-      const uint32_t incl = wave_incl_scan_u32(t);
-      if (in) d8_add4(acc, carry + incl - t, d, wv, scale);
-      carry += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    }
+    const uint32_t d_head = lane < LPB ? reinterpret_cast<const uint32_t*>(blk + (uint64_t)ng * 16u)[lane] : 0u;   // deltas the pipelined pass has already applied
+    d8_walk(acc, blk, ng, (uint32_t)LPB,
+            (y >> 16) + (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(d8_sum4(d_head)), 63), lane, scale);
   }
 }
 
@@ -1293,66 +1331,21 @@ __global__ void __launch_bounds__(1024) k_plan_accumulate_d8(const unsigned char
 #ifdef BE_PLAN_PROF
   unsigned long long plan_t = __builtin_amdgcn_s_memtime();
 #endif
-  const int per_xcd = gridDim.x >> 3;
-  const int L = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  const int n_tasks = n_slices * parts;
-  if (L >= n_tasks) return;
-  const int part = L / n_slices;
-  const int slice = L - part * n_slices;
-  if constexpr (FUSED == 0) active += (int64_t)blockIdx.y * active_stride;
-  partial += ((int64_t)blockIdx.y * n_tasks + L) * S;
-  {
-    uint4* z = reinterpret_cast<uint4*>(smem_raw);
-    const int n16 = (int)(((size_t)(S + 1) * sizeof(acc_t) + 15) / 16);
-    for (int i = threadIdx.x; i < n16; i += blockDim.x) z[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  __syncthreads();
+  const PlanTask t(n_slices, parts);
+  if (t.idle()) return;
+  PlanRows<FUSED> rows(t, n_slices, parts, active, active_stride);
+  partial += t.slot() * S;
+  plan_zero_lds(smem_raw, (int)(((size_t)(S + 1) * sizeof(acc_t) + 15) / 16));
   PLAN_STAMP(0);     // LDS zeroed
-  __shared__ uint32_t fused_wtot[32];
-  uint32_t n_active;
-  if constexpr (FUSED == 1 || FUSED == 2) {       // list the active rows of this part in LDS behind the accumulators (or in the part's region)
-    n_active = build_part_list<FUSED>(static_cast<const unsigned char*>(fused_spikes) + (int64_t)blockIdx.y * fused_stride, fused_m,
-                                      part, parts, reinterpret_cast<uint32_t*>(smem_raw + list_off), lds_cap,
-                                      glob_lists + ((int64_t)blockIdx.y * parts + part) * glob_region, fused_wtot, &active);
-  } else {
-    n_active = n_active_p[blockIdx.y];
-  }
-  // FUSED == 3 (pre-gathered table): part p owns the list positions [p * npp, (p + 1) * npp), a wave 64 consecutive ones
-  uint32_t pos_lo = 0;
-  if constexpr (FUSED == 3) {
-    const uint32_t npp = (n_active + (uint32_t)parts - 1u) / (uint32_t)parts;
-    pos_lo = (uint32_t)part * npp;
-    const uint32_t hi = pos_lo + npp < n_active ? pos_lo + npp : n_active;
-    n_active = hi > pos_lo ? hi : pos_lo;            // from here on: one past this part's last position
-  }
+  rows.list(seg, n_active_p, smem_raw, fused_spikes, fused_m, fused_stride, list_off, lds_cap, glob_lists, glob_region);
   PLAN_STAMP(1);     // spike count / list known
-  // segment table: [row][slice] as built, or (FUSED == 3) the step's pre-gathered [slice][list position]
-  const uint2* sp = FUSED == 3 ? seg + (int64_t)slice * glob_region : seg + slice;
-  const uint64_t seg_rs = FUSED == 3 ? 1u : (uint64_t)n_slices;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  const uint64_t a0 = FUSED == 3 ? (uint64_t)pos_lo + (uint64_t)wave * 64 + lane
-                      : FUSED  ? (uint64_t)wave + (uint64_t)nw * lane
-                               : (uint64_t)part + (uint64_t)parts * ((uint64_t)wave + (uint64_t)nw * lane);
-  const uint64_t a_step = FUSED ? (uint64_t)nw * 64 : (uint64_t)parts * nw * 64;
-  if (n_active > pos_lo) {
-    const uint64_t last = n_active - 1;
-    uint64_t a = a0;
-    bool v_n = a < n_active;
-    uint32_t r_n = FUSED == 3 ? (uint32_t)(a < last ? a : last) : active[a < last ? a : last];
-    a += a_step;
-    uint2 sg = sp[(uint64_t)r_n * seg_rs];
-    uint32_t st_v = sg.x, n4_v = v_n ? sg.y : 0u;
-    bool v_c = v_n;
-    v_n = a < n_active;
-    r_n = FUSED == 3 ? (uint32_t)(a < last ? a : last) : active[a < last ? a : last];
-    a += a_step;
+  if (rows.any()) {
+    rows.start();
     PLAN_STAMP(2);   // first row ids and segment entries landed (wave 0)
-    while (__ballot(v_c) != 0ull) {
-      const int nvalid = __popcll(__ballot(v_c));
-      const uint2 sgn = sp[(uint64_t)r_n * seg_rs];
-      const bool v_nn = a < n_active;
-      const uint32_t r_nn = FUSED == 3 ? (uint32_t)(a < last ? a : last) : active[a < last ? a : last];
-      a += a_step;
+    while (rows.more()) {
+      const int nvalid = rows.fetch();
+      const uint32_t st_v = rows.st_v, n4_v = rows.n4_v;
+      const int lane = rows.lane;
       if constexpr (LPB > 0) {
         // The 64 rows of a batch are 64 / BPI groups; they are walked in STRAIGHT-LINE code, DEPTH groups ahead: hipcc's
         // wait-count pass is exact without a back edge (the rotating four-group loop this replaces drained the queue to one
@@ -1366,6 +1359,7 @@ __global__ void __launch_bounds__(1024) k_plan_accumulate_d8(const unsigned char
 #pragma unroll
         for (int q = 0; q < NGRP; ++q) {
           if (q + DEPTH < NGRP) d8q_issue<LPB>(g[q + DEPTH], (q + DEPTH) * BPI, nvalid, st_v, n4_v, lane, blob);
+          __builtin_amdgcn_sched_barrier(0);                  // issue before the wait: see k_plan_accumulate
           d8q_consume<LPB>(g[q], acc, lane, scale);
         }
         d8q_tails<LPB>(st_v, n4_v, nvalid, acc, lane, scale, blob);
@@ -1379,19 +1373,13 @@ __global__ void __launch_bounds__(1024) k_plan_accumulate_d8(const unsigned char
           d8_consume(gB, acc, lane, scale, blob);
         }
       }
-      st_v = sgn.x;
-      n4_v = v_n ? sgn.y : 0u;
-      v_c = v_n;
-      v_n = v_nn;
-      r_n = r_nn;
+      rows.next();
     }
   }
   PLAN_STAMP(3);     // wave 0 through its blocks
   __syncthreads();
   PLAN_STAMP(4);     // every wave through
-  {
-    store_partials<1>(smem_raw, partial, (int)((size_t)S * sizeof(acc_t) / 16));
-  }
+  store_partials<1>(smem_raw, partial, (int)((size_t)S * sizeof(acc_t) / 16));
 #ifdef BE_PLAN_PROF
   __builtin_amdgcn_s_waitcnt(0);
   PLAN_STAMP(5);     // partial sums stored
@@ -1490,6 +1478,23 @@ __device__ __forceinline__ void h8_issue(SegGroupH8& g, int i, int nvalid, uint3
   }
 }
 
+// lane-groups [o_begin, ng) of an h8 block, a wave per block (64 lane-groups per pass), from `carry` = the column reached before
+// lane-group o_begin: what h8_consume's one pass left of a long block, or the whole block (k_plan_single)
+__device__ __forceinline__ void h8_walk(uint32_t* acc, const unsigned char* blk_bytes, uint32_t ng, uint32_t o_begin, uint32_t carry,
+                                        int lane) {
+  const uint2* blk = reinterpret_cast<const uint2*>(blk_bytes);
+  for (uint32_t o0 = o_begin; o0 < ng; o0 += 64) {
+    const uint32_t o = o0 + lane;
+    const bool in = o < ng;
+    uint2 d = make_uint2(0u, 0u);
+    if (in) d = blk[o];
+    const uint32_t t = h8_sum8(d.x, d.y);
+    const uint32_t incl = wave_incl_scan_u32(t);
+    if (in) h8_add8(acc, carry + incl - t, d.x, d.y);
+    carry += __builtin_amdgcn_readlane(incl, 63);
+  }
+}
+
 __device__ __forceinline__ void h8_consume(const SegGroupH8& g, uint32_t* acc, int lane, const unsigned char* __restrict__ blob) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -1501,18 +1506,8 @@ __device__ __forceinline__ void h8_consume(const SegGroupH8& g, uint32_t* acc, i
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       if (g.ng[q] <= 64u) continue;
-      const uint2* blk = reinterpret_cast<const uint2*>(blob + ((uint64_t)g.start[q] << 7));
-      uint32_t carry = g.base[q] + __builtin_amdgcn_readlane(wave_incl_scan_u32(h8_sum8(g.dv[q].x, g.dv[q].y)), 63);
-      for (uint32_t o0 = 64; o0 < g.ng[q]; o0 += 64) {
-        const uint32_t o = o0 + lane;
-        const bool in = o < g.ng[q];
-        uint2 d = make_uint2(0u, 0u);
-        if (in) d = blk[o];
-        const uint32_t t = h8_sum8(d.x, d.y);
-        const uint32_t incl = wave_incl_scan_u32(t);
-        if (in) h8_add8(acc, carry + incl - t, d.x, d.y);
-        carry += __builtin_amdgcn_readlane(incl, 63);
-      }
+      h8_walk(acc, blob + ((uint64_t)g.start[q] << 7), g.ng[q], 64u,
+              g.base[q] + __builtin_amdgcn_readlane(wave_incl_scan_u32(h8_sum8(g.dv[q].x, g.dv[q].y)), 63), lane);
     }
   }
 }
@@ -1529,63 +1524,18 @@ __global__ void __launch_bounds__(1024) k_plan_accumulate_h8(const unsigned char
   extern __shared__ __align__(16) unsigned char smem_raw[];
   uint32_t* acc = reinterpret_cast<uint32_t*>(smem_raw);
   const int S = cap;                     // multiple of 4; >= slice width
-  const int per_xcd = gridDim.x >> 3;
-  const int L = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  const int n_tasks = n_slices * parts;
-  if (L >= n_tasks) return;
-  const int part = L / n_slices;
-  const int slice = L - part * n_slices;
-  if constexpr (FUSED == 0) active += (int64_t)blockIdx.y * active_stride;
-  partial += ((int64_t)blockIdx.y * n_tasks + L) * S;
-  {
-    uint4* z = reinterpret_cast<uint4*>(smem_raw);
-    const int n16 = (int)((size_t)S * 4 / 16);
-    for (int i = threadIdx.x; i < n16; i += blockDim.x) z[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  __syncthreads();
-  __shared__ uint32_t fused_wtot[32];
-  uint32_t n_active;
-  if constexpr (FUSED == 1 || FUSED == 2) {       // list the active rows of this part in LDS behind the accumulators (or in the part's region)
-    n_active = build_part_list<FUSED>(static_cast<const unsigned char*>(fused_spikes) + (int64_t)blockIdx.y * fused_stride, fused_m,
-                                      part, parts, reinterpret_cast<uint32_t*>(smem_raw + list_off), lds_cap,
-                                      glob_lists + ((int64_t)blockIdx.y * parts + part) * glob_region, fused_wtot, &active);
-  } else {
-    n_active = n_active_p[blockIdx.y];
-  }
-  // FUSED == 3 (pre-gathered table): part p owns the list positions [p * npp, (p + 1) * npp), a wave 64 consecutive ones
-  uint32_t pos_lo = 0;
-  if constexpr (FUSED == 3) {
-    const uint32_t npp = (n_active + (uint32_t)parts - 1u) / (uint32_t)parts;
-    pos_lo = (uint32_t)part * npp;
-    const uint32_t hi = pos_lo + npp < n_active ? pos_lo + npp : n_active;
-    n_active = hi > pos_lo ? hi : pos_lo;            // from here on: one past this part's last position
-  }
-  // segment table: [row][slice] as built, or (FUSED == 3) the step's pre-gathered [slice][list position]
-  const uint2* sp = FUSED == 3 ? seg + (int64_t)slice * glob_region : seg + slice;
-  const uint64_t seg_rs = FUSED == 3 ? 1u : (uint64_t)n_slices;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  const uint64_t a0 = FUSED == 3 ? (uint64_t)pos_lo + (uint64_t)wave * 64 + lane
-                      : FUSED  ? (uint64_t)wave + (uint64_t)nw * lane
-                               : (uint64_t)part + (uint64_t)parts * ((uint64_t)wave + (uint64_t)nw * lane);
-  const uint64_t a_step = FUSED ? (uint64_t)nw * 64 : (uint64_t)parts * nw * 64;
-  if (n_active > pos_lo) {
-    const uint64_t last = n_active - 1;
-    uint64_t a = a0;
-    bool v_n = a < n_active;
-    uint32_t r_n = FUSED == 3 ? (uint32_t)(a < last ? a : last) : active[a < last ? a : last];
-    a += a_step;
-    uint2 sg = sp[(uint64_t)r_n * seg_rs];
-    uint32_t st_v = sg.x, n4_v = v_n ? sg.y : 0u;
-    bool v_c = v_n;
-    v_n = a < n_active;
-    r_n = FUSED == 3 ? (uint32_t)(a < last ? a : last) : active[a < last ? a : last];
-    a += a_step;
-    while (__ballot(v_c) != 0ull) {
-      const int nvalid = __popcll(__ballot(v_c));
-      const uint2 sgn = sp[(uint64_t)r_n * seg_rs];
-      const bool v_nn = a < n_active;
-      const uint32_t r_nn = FUSED == 3 ? (uint32_t)(a < last ? a : last) : active[a < last ? a : last];
-      a += a_step;
+  const PlanTask t(n_slices, parts);
+  if (t.idle()) return;
+  PlanRows<FUSED> rows(t, n_slices, parts, active, active_stride);
+  partial += t.slot() * S;
+  plan_zero_lds(smem_raw, (int)((size_t)S * 4 / 16));      // no pad slot: S counters exactly
+  rows.list(seg, n_active_p, smem_raw, fused_spikes, fused_m, fused_stride, list_off, lds_cap, glob_lists, glob_region);
+  if (rows.any()) {
+    rows.start();
+    while (rows.more()) {
+      const int nvalid = rows.fetch();
+      const uint32_t st_v = rows.st_v, n4_v = rows.n4_v;
+      const int lane = rows.lane;
       SegGroupH8 gA, gB;
       h8_issue(gA, 0, nvalid, st_v, n4_v, lane, blob);
       for (int i = 0; i < nvalid; i += 8) {
@@ -1594,17 +1544,11 @@ __global__ void __launch_bounds__(1024) k_plan_accumulate_h8(const unsigned char
         h8_issue(gA, i + 8, nvalid, st_v, n4_v, lane, blob);
         h8_consume(gB, acc, lane, blob);
       }
-      st_v = sgn.x;
-      n4_v = v_n ? sgn.y : 0u;
-      v_c = v_n;
-      v_n = v_nn;
-      r_n = r_nn;
+      rows.next();
     }
   }
   __syncthreads();
-  {
-    store_partials<4>(smem_raw, partial, (int)((size_t)S * 4 / 16));
-  }
+  store_partials<4>(smem_raw, partial, (int)((size_t)S * 4 / 16));
 }
 
 // =================================================================================================
@@ -1642,49 +1586,9 @@ __global__ void __launch_bounds__(1024) k_plan_single(const unsigned char* __res
     for (uint32_t a = wave; a < n; a += 16) {
       const uint2 sg = seg[list[a]];                       // one slice: seg[row]
       const unsigned char* blk = blob + ((uint64_t)sg.x << 7);
-      if (LAYOUT == 2) {
-        const uint32_t ng = sg.y & 0xffffu;
-        uint32_t carry = sg.y >> 16;
-        for (uint32_t o0 = 0; o0 < ng; o0 += 64) {
-          const uint32_t o = o0 + lane;
-          const bool in = o < ng;
-          const uint32_t d = in ? reinterpret_cast<const uint32_t*>(blk + (uint64_t)ng * 16u)[o] : 0u;
-          be_v4u wv = {0u, 0u, 0u, 0u};
-          if (in) {
-            const uint4 x = reinterpret_cast<const uint4*>(blk)[o];
-            wv = be_v4u{x.x, x.y, x.z, x.w};
-          }
-          const uint32_t t = d8_sum4(d);
-          const uint32_t incl = wave_incl_scan_u32(t);
-          if (in) d8_add4(reinterpret_cast<unsigned long long*>(acc), carry + incl - t, d, wv, scale);
-          carry += __builtin_amdgcn_readlane(incl, 63);
-        }
-      } else if (LAYOUT == 3) {
-        const uint32_t ng = sg.y & 0xffffu;
-        uint32_t carry = sg.y >> 16;
-        for (uint32_t o0 = 0; o0 < ng; o0 += 64) {
-          const uint32_t o = o0 + lane;
-          const bool in = o < ng;
-          uint2 d = make_uint2(0u, 0u);
-          if (in) d = reinterpret_cast<const uint2*>(blk)[o];
-          const uint32_t t = h8_sum8(d.x, d.y);
-          const uint32_t incl = wave_incl_scan_u32(t);
-          if (in) h8_add8(reinterpret_cast<uint32_t*>(acc), carry + incl - t, d.x, d.y);
-          carry += __builtin_amdgcn_readlane(incl, 63);
-        }
-      } else {
-        const uint32_t ng = sg.y;
-        for (uint32_t o = lane; o < ng; o += 64) {
-          if (HOMO) {
-            const uint4 c = reinterpret_cast<const uint4*>(blk)[o];
-            plan_count8(reinterpret_cast<uint32_t*>(acc), c.x, c.y, c.z, c.w);
-          } else {
-            const uint2 iv = reinterpret_cast<const uint2*>(blk + (uint64_t)ng * 16u)[o];
-            const float4 wv = reinterpret_cast<const float4*>(blk)[o];
-            plan_add4<false>(reinterpret_cast<unsigned long long*>(acc), iv, wv, scale);
-          }
-        }
-      }
+      if constexpr (LAYOUT == 2) d8_walk(acc, blk, sg.y & 0xffffu, 0u, sg.y >> 16, lane, scale);
+      else if constexpr (LAYOUT == 3) h8_walk(acc, blk, sg.y & 0xffffu, 0u, sg.y >> 16, lane);
+      else u16_walk<HOMO>(acc, blk, sg.y, 0u, lane, scale);
     }
     __syncthreads();
   }
@@ -1713,6 +1617,14 @@ int launch_plan_single(const void* blob, const void* seg, const void* spikes, in
                        static_cast<W*>(out));
   }
   BE_LAUNCH_CHECK();
+  return BE_OK;
+}
+
+// launch of an accumulate kernel: 1024 threads, `lds` bytes of dynamic LDS
+template <typename K, typename... A>
+int launch_plan_accumulate(K kern, dim3 grid, size_t lds, hipStream_t st, A... args) {
+  BE_HIP(be_allow_lds(reinterpret_cast<const void*>(kern), (int)lds));
+  hipLaunchKernelGGL(kern, grid, dim3(1024), lds, st, args...);
   return BE_OK;
 }
 
@@ -2097,7 +2009,18 @@ static inline int64_t lds_slots_of(int slice_shift, int slice_width, int layout,
   return layout == BE_PLAN_U16 ? (1ll << slice_shift) : cap_of(slice_shift, slice_width, layout, homo);
 }
 
-#define COMMA ,
+// which accumulate kernel a step runs: lanes per block (0 = a wave per block) and, for d8 by the wave, whether its block loads
+// carry the BE_BLOCK_AUX cache policy.  The only place the block-length thresholds above are applied.
+struct PlanVariant { int lpb; bool nt; };
+static inline PlanVariant plan_variant_of(int layout, int homo, int block_hint) {
+  const auto upto = [&](int max_block) { return block_hint > 0 && block_hint <= max_block; };
+  if (layout == BE_PLAN_H8) return {0, false};
+  if (layout == BE_PLAN_D8)
+    return upto(kD8EighthMaxBlock) ? PlanVariant{8, false} : upto(kD8QuarterMaxBlock) ? PlanVariant{16, false}
+                                                                                      : PlanVariant{0, block_hint >= kD8NtMinBlock};
+  if (homo) return {upto(kSub4MaxBlock) ? 4 : upto(kSub8MaxBlock) ? 8 : upto(kSub16MaxBlock) ? 16 : upto(kSub32MaxBlock) ? 32 : 0, false};
+  return {upto(kSubW4MaxBlock) ? 4 : upto(kSubW8MaxBlock) ? 8 : upto(kSubW16MaxBlock) ? 16 : upto(kSubW32MaxBlock) ? 32 : 0, false};
+}
 // The segment table of a step is pre-gathered (k_gather_seg) for short blocks in many slices: the two extra small launches
 // cost ~5 us, the gather they take out of the accumulate kernel grows with the slice count (FixedNumPerPre K = 1000, 1 %
 // firing, weighted / counted, us per step: 25 slices 26 -> 28 / 21 -> 25; 32 slices 30 -> 33 / 37 -> 35; 51 slices
@@ -2603,19 +2526,15 @@ int be_binary_csrmm_t_plan(const void* weights, int homo, int wdtype, const void
     const float sc1 = ldexpf(1.0f, scale_exp - 32);
     const double isc1 = ldexp(1.0, -scale_exp);
     const int lay = homo ? (layout == BE_PLAN_H8 ? 3 : 1) : (layout == BE_PLAN_D8 ? 2 : 0);
+    BE_REQUIRE(wdtype == BE_F32 || wdtype == BE_F16 || wdtype == BE_BF16, BE_ERR_UNSUPPORTED, "planned scatter: f32 / f16 / bf16 outputs");
     const int prof1 = be_prof_begin(st);
-    int rc1 = BE_ERR_INVALID;
-#define BE_SINGLE(LAY, WT) rc1 = launch_plan_single<LAY, WT>(blob, seg, spikes, spike_dtype, m, k, (int)slots, sc1, isc1, weights, out, lds, st)
-#define BE_SINGLE_W(LAY)                                                    \
-    switch (wdtype) {                                                        \
-      case BE_F32: BE_SINGLE(LAY, float); break;                             \
-      case BE_F16: BE_SINGLE(LAY, __half); break;                            \
-      case BE_BF16: BE_SINGLE(LAY, __hip_bfloat16); break;                   \
-      default: be_set_error("planned scatter: f32 / f16 / bf16 outputs"); rc1 = BE_ERR_UNSUPPORTED; \
-    }
-    if (lay == 0) { BE_SINGLE_W(0) } else if (lay == 1) { BE_SINGLE_W(1) } else if (lay == 2) { BE_SINGLE_W(2) } else { BE_SINGLE_W(3) }
-#undef BE_SINGLE_W
-#undef BE_SINGLE
+    const int rc1 = be_dispatch_int<0, 1, 2, 3>(lay, [&](auto l) {
+      return be_dispatch_wdtype(wdtype, [&](auto w) {
+        using W = typename decltype(w)::type;
+        if constexpr (std::is_same_v<W, double>) return (int)BE_ERR_UNSUPPORTED;     // (f64 takes the sliced path: see above)
+        else return launch_plan_single<decltype(l)::value, W>(blob, seg, spikes, spike_dtype, m, k, (int)slots, sc1, isc1, weights, out, lds, st);
+      });
+    });
     be_prof_end(prof1, st);
     return rc1;
   }
@@ -2669,52 +2588,37 @@ int be_binary_csrmm_t_plan(const void* weights, int homo, int wdtype, const void
   const float scale = ldexpf(1.0f, scale_exp - 32);   // see fixed_from_f32
   const double inv_scale = ldexp(1.0, -scale_exp);
   const int n_tasks = n_slices * parts;
-  const dim3 grid((unsigned)((n_tasks + 7) / 8 * 8), (unsigned)n_batch), block(1024);
+  const dim3 grid((unsigned)((n_tasks + 7) / 8 * 8), (unsigned)n_batch);
+  const PlanVariant var = plan_variant_of(layout, homo, block_hint);
   const int prof = be_prof_begin(st);
-#define BE_FUSED_ARGS spikes, m, fused_stride, list_off, lds_cap, active, glob_region
-#define BE_PLAN_LAUNCH(KERN, ...)                                                                              \
-  do {                                                                                                         \
-    auto kern__ = KERN;                                                                                        \
-    BE_HIP(be_allow_lds(reinterpret_cast<const void*>(kern__), (int)lds_dyn));                                 \
-    hipLaunchKernelGGL(kern__, grid, block, lds_dyn, st, static_cast<const unsigned char*>(blob),              \
-                       static_cast<const uint2*>(seg_used), al.ids, al.count, __VA_ARGS__, BE_FUSED_ARGS);     \
-  } while (0)
-#define BE_PLAN_BY_FUSED(TMPL_A, TMPL_B, ...)                                                                 \
-  do {                                                                                                         \
-    if (fused == 1) BE_PLAN_LAUNCH((TMPL_A 1 TMPL_B), __VA_ARGS__);                                           \
-    else if (fused == 2) BE_PLAN_LAUNCH((TMPL_A 2 TMPL_B), __VA_ARGS__);                                      \
-    else if (fused == 3) BE_PLAN_LAUNCH((TMPL_A 3 TMPL_B), __VA_ARGS__);                                      \
-    else BE_PLAN_LAUNCH((TMPL_A 0 TMPL_B), __VA_ARGS__);                                                      \
-  } while (0)
-  if (layout == BE_PLAN_H8) {
-    BE_PLAN_BY_FUSED(k_plan_accumulate_h8<, >, n_slices, (int)S, parts, static_cast<uint32_t*>(partial), astride);
-  } else if (homo) {
-    // short blocks: 4 lanes (<= 32 entries on average) or 16 lanes (<= 128) per block instead of a wave
-    uint32_t* pp = static_cast<uint32_t*>(partial);
-    if (block_hint > 0 && block_hint <= kSub4MaxBlock) BE_PLAN_BY_FUSED(k_plan_accumulate<true COMMA 4 COMMA, >, n_slices, slice_shift, parts, scale, pp, astride, (int)S);
-    else if (block_hint > 0 && block_hint <= kSub8MaxBlock) BE_PLAN_BY_FUSED(k_plan_accumulate<true COMMA 8 COMMA, >, n_slices, slice_shift, parts, scale, pp, astride, (int)S);
-    else if (block_hint > 0 && block_hint <= kSub16MaxBlock) BE_PLAN_BY_FUSED(k_plan_accumulate<true COMMA 16 COMMA, >, n_slices, slice_shift, parts, scale, pp, astride, (int)S);
-    else if (block_hint > 0 && block_hint <= kSub32MaxBlock) BE_PLAN_BY_FUSED(k_plan_accumulate<true COMMA 32 COMMA, >, n_slices, slice_shift, parts, scale, pp, astride, (int)S);
-    else BE_PLAN_BY_FUSED(k_plan_accumulate<true COMMA 0 COMMA, >, n_slices, slice_shift, parts, scale, pp, astride, (int)S);
-  } else if (layout == BE_PLAN_D8) {
-    // short blocks: 8 lanes (<= 24 entries on average) or 16 lanes (<= 48) per block instead of a wave
-    unsigned long long* pp = static_cast<unsigned long long*>(partial);
-    if (block_hint > 0 && block_hint <= kD8EighthMaxBlock) BE_PLAN_BY_FUSED(k_plan_accumulate_d8<8 COMMA, >, n_slices, (int)S, parts, scale, pp, astride);
-    else if (block_hint > 0 && block_hint <= kD8QuarterMaxBlock) BE_PLAN_BY_FUSED(k_plan_accumulate_d8<16 COMMA, >, n_slices, (int)S, parts, scale, pp, astride);
-    else if (block_hint >= kD8NtMinBlock) BE_PLAN_BY_FUSED(k_plan_accumulate_d8<0 COMMA, COMMA BE_BLOCK_AUX>, n_slices, (int)S, parts, scale, pp, astride);
-    else BE_PLAN_BY_FUSED(k_plan_accumulate_d8<0 COMMA, COMMA 0>, n_slices, (int)S, parts, scale, pp, astride);
-  } else {
-    unsigned long long* pw = static_cast<unsigned long long*>(partial);
-    if (block_hint > 0 && block_hint <= kSubW4MaxBlock) BE_PLAN_BY_FUSED(k_plan_accumulate<false COMMA 4 COMMA, >, n_slices, slice_shift, parts, scale, pw, astride, (int)S);
-    else if (block_hint > 0 && block_hint <= kSubW8MaxBlock) BE_PLAN_BY_FUSED(k_plan_accumulate<false COMMA 8 COMMA, >, n_slices, slice_shift, parts, scale, pw, astride, (int)S);
-    else if (block_hint > 0 && block_hint <= kSubW16MaxBlock) BE_PLAN_BY_FUSED(k_plan_accumulate<false COMMA 16 COMMA, >, n_slices, slice_shift, parts, scale, pw, astride, (int)S);
-    else if (block_hint > 0 && block_hint <= kSubW32MaxBlock) BE_PLAN_BY_FUSED(k_plan_accumulate<false COMMA 32 COMMA, >, n_slices, slice_shift, parts, scale, pw, astride, (int)S);
-    else BE_PLAN_BY_FUSED(k_plan_accumulate<false COMMA 0 COMMA, >, n_slices, slice_shift, parts, scale, pw, astride, (int)S);
-  }
-#undef BE_PLAN_BY_FUSED
-#undef BE_PLAN_LAUNCH
-#undef BE_FUSED_ARGS
+  const int rc_acc = be_dispatch_int<0, 1, 2, 3>(fused, [&](auto fz) {
+    constexpr int FUSED = decltype(fz)::value;
+    // every accumulate kernel takes (blob, table, row list, its count | the layout's own arguments | the fused step's)
+    const auto launch = [&](auto kern, auto... own) {
+      return launch_plan_accumulate(kern, grid, lds_dyn, st, static_cast<const unsigned char*>(blob), static_cast<const uint2*>(seg_used),
+                                    al.ids, al.count, own..., spikes, m, fused_stride, list_off, lds_cap, active, glob_region);
+    };
+    if (layout == BE_PLAN_H8) return launch(k_plan_accumulate_h8<FUSED>, n_slices, (int)S, parts, static_cast<uint32_t*>(partial), astride);
+    if (layout == BE_PLAN_D8)
+      return be_dispatch_int<0, 8, 16>(var.lpb, [&](auto l) {
+        constexpr int LPB = decltype(l)::value;
+        unsigned long long* pp = static_cast<unsigned long long*>(partial);
+        if constexpr (LPB == 0)       // the cache policy exists for the wave-per-block loads only
+          return be_dispatch_bool(var.nt, [&](auto nt) {
+            return launch(k_plan_accumulate_d8<0, FUSED, decltype(nt)::value ? BE_BLOCK_AUX : 0>, n_slices, (int)S, parts, scale, pp, astride);
+          });
+        else return launch(k_plan_accumulate_d8<LPB, FUSED>, n_slices, (int)S, parts, scale, pp, astride);
+      });
+    return be_dispatch_bool(homo != 0, [&](auto h) {
+      return be_dispatch_int<0, 4, 8, 16, 32>(var.lpb, [&](auto l) {
+        constexpr bool HOMO = decltype(h)::value;
+        return launch(k_plan_accumulate<HOMO, decltype(l)::value, FUSED>, n_slices, slice_shift, parts, scale,
+                      static_cast<typename PlanAcc<HOMO>::type*>(partial), astride, (int)S);
+      });
+    });
+  });
   be_prof_end(prof, st);
+  if (rc_acc != BE_OK) return rc_acc;
   BE_LAUNCH_CHECK();
   const int rgrid = grid_for(k, 256, n_batch >= 8 ? 256 : 2048);
   const int64_t pstride = (int64_t)n_tasks * S;

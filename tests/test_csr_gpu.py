@@ -727,6 +727,107 @@ def test_pre_gathered_segment_table_counted_and_packed(be, oracle):
         np.testing.assert_array_equal(got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got), ref)
 
 
+_PINNED_STEP = {}
+
+
+def _pinned_step_case():
+    """40 slices of 60 columns (the pre-gather minimum; 60 <= 2^6, so the u16 layout accepts it), rows of 0 ... 40 entries, every
+    17th empty, and a tenth of the rows with 300 ... 700 more entries (duplicate columns) inside ONE slice: blocks longer than one
+    64-lane pass in every layout.  Built once, shared by the cases, never modified."""
+    if not _PINNED_STEP:
+        rng = np.random.default_rng(600)
+        m, k, width = 600, 2400, 60
+        long_rows = np.flatnonzero(rng.random(m) < 0.1)
+        long_rows = long_rows[long_rows % 17 != 0]
+        rows = []
+        for r in range(m):
+            cols = rng.integers(0, k, int(rng.integers(0, 41))) if r % 17 else np.zeros(0, np.int64)
+            if r in long_rows:
+                n = 700 if r == long_rows[0] else int(rng.integers(300, 701))      # (one above 512: 8 entries per lane, counted)
+                cols = np.concatenate([cols, int(rng.integers(0, k // width)) * width + rng.integers(0, width, n)])
+                rng.shuffle(cols)
+            rows.append(cols)
+        ptr = np.concatenate([[0], np.cumsum([len(c) for c in rows])]).astype(np.int32)
+        idx = np.concatenate(rows).astype(np.int32)
+        v = rng.random(m) < 0.5
+        v[long_rows[:4]] = True
+        B = np.stack([v] + [rng.random(m) < 0.3 for _ in range(2)], axis=1)      # column 0: the vector again
+        blocks = np.zeros((m, k // width), np.int64)                              # entries per (row, slice) block
+        np.add.at(blocks, (np.repeat(np.arange(m), np.diff(ptr)), idx // width), 1)
+        _PINNED_STEP.update(m=m, k=k, width=width, idx=idx, ptr=ptr, v=v, B=B, longest=int(blocks.max()),
+                            w=rng.normal(0, 1, idx.size).astype(np.float32), w1=np.asarray([1.5], np.float32))
+    return _PINNED_STEP
+
+
+@pytest.mark.parametrize('layout,homo', [('d8', False), ('u16', False), ('u16', True), ('h8', True)])
+def test_step_skeleton_with_every_decoder_row_list_and_long_blocks(be, oracle, layout, homo):
+    """The step kernels share their skeleton (task mapping, active-row list, pointer pipeline) and differ in the decoder; this
+    pins down, per layout, every decoder (one hint per lanes-per-block class) on every way the skeleton lists its rows — FUSED 0
+    (float spikes / a bool buffer that is not 16-byte aligned: compacted list), 1 (bit-packed), 2 (aligned bool), 3 (hint <= 64 on
+    40 slices, single vector: pre-gathered table, whatever the encoding) — with blocks past one wave pass in the same case, three
+    parts (the rows are one stripe of 1024: parts 1 and 2 of the in-kernel list are empty) and a 3-column batch.  The hint and
+    the encoding only select the kernel: same bits from all; the oracle exactly for one shared weight."""
+    import os
+    from brainevent_amd._csr import ScatterPlan, _plan_call
+    from brainevent_amd import _array as A
+    c = _pinned_step_case()
+    m, k, idx, ptr, v, B = c['m'], c['k'], c['idx'], c['ptr'], c['v'], c['B']
+    w = c['w1'] if homo else c['w']
+    plan = ScatterPlan.build(w, idx, torch.tensor(ptr), shape=(m, k), slice_shift=6, slice_width=c['width'], layout=layout)
+    assert plan.layout == {'d8': ScatterPlan.LAYOUT_D8, 'u16': ScatterPlan.LAYOUT_U16, 'h8': ScatterPlan.LAYOUT_H8}[layout]
+    assert plan.n_slices == 40
+    per_lane = 8 if homo else 4                       # entries a lane decodes per pass (escapes only add to it)
+    assert -(-c['longest'] // per_lane) > 64, "no block past one wave pass"
+    hints = {('d8', False): (18, 19, 43, 44, 159, 160), ('u16', False): (7, 8, 18, 19, 43, 44, 96, 97),
+             ('u16', True): (18, 19, 43, 44, 96, 97, 210, 211), ('h8', True): (64, 65)}[(layout, homo)]
+    # the host's choice of FUSED, restated (be_binary_csrmm_t_plan): the encoding, then the pre-gathered table over it
+    assert os.environ.get('BE_PLAN_FUSED', '1')[0] != '0' and 'BE_PLAN_PREGATHER_SLICES' not in os.environ \
+        and 'BE_PLAN_PREGATHER_MAX' not in os.environ
+
+    def fused_of(sp, sd, hint):
+        nb = 1 if sp.ndim == 1 else sp.shape[0]
+        f = 1 if sd == A.BE_SPIKE_BITS else 2 if (sd == A.BE_SPIKE_BOOL and sp.data_ptr() % 16 == 0 and (nb == 1 or m % 16 == 0)) else 0
+        return 3 if (nb == 1 and plan.n_slices >= 40 and 0 < hint <= 64) else f
+
+    vd = torch.from_numpy(v).cuda()
+    buf = torch.zeros(m + 32, dtype=torch.bool, device='cuda')
+    off = buf[1:m + 1]
+    off.copy_(vd)
+    assert vd.data_ptr() % 16 == 0 and off.data_ptr() % 16 == 1 and off.is_contiguous()
+    spikes = [(torch.from_numpy(np.where(v, 2.5, 0.0).astype(np.float32)).cuda(), A.BE_SPIKE_FLOAT),
+              (be.BitPackedBinary(vd).packed[0], A.BE_SPIKE_BITS), (vd, A.BE_SPIKE_BOOL), (off, A.BE_SPIKE_BOOL)]
+    Bd = torch.from_numpy(np.ascontiguousarray(B.T)).cuda()                     # [3, m]
+    wd = A.to_device(w)
+
+    def run(sp, sd, hint):
+        plan.block_hint_override = hint
+        out = torch.zeros((k,) if sp.ndim == 1 else (sp.shape[0], k), dtype=torch.float32, device='cuda')
+        _plan_call(plan, wd, sp, sd, out, parts=3)
+        return out.cpu().numpy()
+
+    for hint in hints + (100000,):
+        assert [fused_of(sp, sd, hint) for sp, sd in spikes] == ([3, 3, 3, 3] if hint <= 64 else [0, 1, 2, 0])
+        assert fused_of(Bd, A.BE_SPIKE_BOOL, hint) == 0                         # m % 16 != 0: a batch of bool rows is compacted
+    ref = run(vd, A.BE_SPIKE_BOOL, 100000)
+    ref_b = run(Bd, A.BE_SPIKE_BOOL, 100000)
+    want = oracle.binary_csrmv(w, idx, ptr, v, (m, k), True)
+    if homo:
+        np.testing.assert_array_equal(ref, want)
+    else:
+        np.testing.assert_allclose(ref, want, rtol=1e-5, atol=1e-5)
+    np.testing.assert_array_equal(ref_b[0], ref)
+    for j in (1, 2):
+        want_j = oracle.binary_csrmv(w, idx, ptr, B[:, j], (m, k), True)
+        if homo:
+            np.testing.assert_array_equal(ref_b[j], want_j)
+        else:
+            np.testing.assert_allclose(ref_b[j], want_j, rtol=1e-5, atol=1e-5)
+    for hint in hints + (100000,):
+        for sp, sd in spikes:
+            np.testing.assert_array_equal(run(sp, sd, hint), ref, err_msg=f'hint {hint}, FUSED {fused_of(sp, sd, hint)}')
+        np.testing.assert_array_equal(run(Bd, A.BE_SPIKE_BOOL, hint), ref_b, err_msg=f'hint {hint}, batch')
+
+
 def test_d8_layout_falls_back_when_it_does_not_apply(be):
     from brainevent_amd._csr import ScatterPlan
     rng = np.random.default_rng(4)
