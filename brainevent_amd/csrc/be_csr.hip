@@ -361,22 +361,144 @@ __device__ __forceinline__ uint4 gather_ld16(const void* p) {
   if (BE_GATHER_VEC_NT) { const be_nt_v4u t = __builtin_nontemporal_load(reinterpret_cast<const be_nt_v4u*>(p)); return make_uint4(t.x, t.y, t.z, t.w); }
   return *reinterpret_cast<const uint4*>(p);
 }
-constexpr int64_t kGatherVecMaxRow = 200;   // average row length up to which the lanes-per-row vector kernel is used (32 lanes: 256 entries in two passes)
+// ---- the parts the gather kernels share, each stated once.  Forced-inline functions over the callers' own
+// registers: nothing here keeps state of its own alive across a kernel's issue / consume sequence.
+// The exact bitmap (IN_LDS) or the coarse one (spike_mask) into the dynamic LDS allocation, then the barrier.  bits_g is this
+// batch row's; the kernels that test with AT0 have the allocation at LDS address 0 (the host checks that).
+template <bool IN_LDS>
+__device__ __forceinline__ void stage_bitmap(uint32_t* __restrict__ bits_s, const uint32_t* __restrict__ bits_g, int64_t n_words,
+                                             const uint32_t* __restrict__ coarse_g, int64_t n_cwords) {
+  const uint32_t* src = IN_LDS ? bits_g : coarse_g + (int64_t)blockIdx.y * n_cwords;
+  const int64_t nw = IN_LDS ? n_words : n_cwords;
+  for (int64_t i = threadIdx.x; i < nw; i += blockDim.x) bits_s[i] = src[i];
+  __syncthreads();
+}
+// N = 4 or 8 entries of one lane into its partial sum: bit e of onm = entry e is on; wv = the N / 4 streamed 16-byte weight
+// pieces (f32 weights only); entry 4 u + e is at weights[pos0 + u * stride + e].  HOMO counts; f32 weights were streamed with
+// the indices and are selected; other dtypes load a weight only behind its spike test.
+template <typename W, bool HOMO, int N>
+__device__ __forceinline__ void gather_add(uint32_t onm, const be_nt_v4u* wv, const W* __restrict__ weights, int64_t pos0,
+                                           int64_t stride, typename WTraits<W>::acc& acc, int& cnt) {
+  using ACC = typename WTraits<W>::acc;
+  constexpr bool VECW = std::is_same<W, float>::value && !HOMO;
+#pragma unroll
+  for (int u = 0; u < N / 4; ++u)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool on = (onm >> (4 * u + e)) & 1u;
+      if (HOMO) cnt += on ? 1 : 0;
+      else if (VECW) acc += on ? (ACC)__uint_as_float(wv[u][e]) : ACC(0);
+      else if (on) acc += (ACC)WTraits<W>::load(weights, pos0 + u * stride + e);
+    }
+}
+// a row's partial sums over its WIDTH consecutive lanes (valid in the first): the count times w0 (HOMO) or the sum
+template <bool HOMO, int WIDTH, typename ACC>
+__device__ __forceinline__ ACC gather_reduce(ACC acc, int cnt, ACC w0) {
+  if (WIDTH == 64) return HOMO ? (ACC)wave_sum(cnt) * w0 : wave_sum(acc);
+  if (HOMO) {
+#pragma unroll
+    for (int off = WIDTH / 2; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, WIDTH);
+    return (ACC)cnt * w0;
+  }
+#pragma unroll
+  for (int off = WIDTH / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, WIDTH);
+  return acc;
+}
+// Entries [from, len) of the row starting at b, by the whole wave: 2 x 256 entries per trip, 4 consecutive entries per lane
+// and load, through range-checked descriptors of at most 2^30 entries (no tail branch: what lies past the row reads as 0 and
+// is masked).  The rest of a long row in k_csrmv_nt_wave, the rows longer than two passes in k_csrmv_nt_vec (whose tail used
+// guarded 16-byte loads with a scalar fallback at the arrays' end: through descriptors its 32-lane instances no longer spill
+// and rows with a long tail run 3 ... 13 % faster; 5e7 entries, 3 ... 10 % of the rows 3 ... 12 times the average).
+template <typename W, bool HOMO, bool IN_LDS, bool AT0>
+__device__ __forceinline__ void gather_row_walk(const W* __restrict__ weights, const int32_t* __restrict__ indices, int64_t b,
+                                                int64_t len, int64_t from, const uint32_t* __restrict__ bits_s,
+                                                const uint32_t* __restrict__ bits_g, int g_shift, int lane,
+                                                typename WTraits<W>::acc& acc, int& cnt) {
+  constexpr bool VECW = std::is_same<W, float>::value && !HOMO;
+  for (int64_t p0 = (from >> 30) << 30; p0 < len; p0 += (1ll << 30)) {
+    const int64_t plen = len - p0 < (1ll << 30) ? len - p0 : (1ll << 30);
+    auto ri = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(indices + b + p0), 0, (int)(plen * 4), 0x00020000);
+    auto rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<W*>(VECW ? weights + b + p0 : weights), 0,
+                                                VECW ? (int)(plen * 4) : 0, 0x00020000);
+    for (int64_t j0 = (p0 == ((from >> 30) << 30)) ? (from - p0) : 0; j0 < plen; j0 += 512) {
+      be_nt_v4u c[2], wv[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int off = (int)(j0 + 256 * u + 4 * lane) * 4;
+        c[u] = __builtin_amdgcn_raw_buffer_load_b128(ri, off, 0, BE_GATHER_AUX);
+        if (VECW) wv[u] = __builtin_amdgcn_raw_buffer_load_b128(rw, off, 0, BE_GATHER_AUX);
+      }
+      uint32_t cols[8], valid = 0;
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          cols[4 * u + q] = c[u][q];
+          valid |= (j0 + 256 * u + 4 * lane + q < plen ? 1u : 0u) << (4 * u + q);
+        }
+      const uint32_t onm = spike_mask<IN_LDS, 8, AT0>(bits_s, bits_g, cols, valid, g_shift);
+      gather_add<W, HOMO, 8>(onm, wv, weights, b + p0 + j0 + 4 * lane, 256, acc, cnt);
+    }
+  }
+}
+// entries [j, j + 4) of the row of `len` entries that starts at b: one 16-byte load where that stays inside the arrays (they
+// end at nnz_end; a row's last piece may read into the next row), entry by entry within four entries of their end, zeros for
+// what is not loaded (j >= len loads nothing).  (Stated on (pos, entries left) the compiler saw that the fallback never loads a
+// fourth entry, merged the pieces' registers differently and put two copies and a wait behind every 16-byte load: the next
+// group's loads no longer overlapped the mask gathers, +7 % at 100 entries per row and 8 columns.)
+template <typename W, bool VECW>
+__device__ __forceinline__ void gather_ld4_guarded(const int32_t* __restrict__ indices, const W* __restrict__ weights, int64_t b,
+                                                   int32_t j, int32_t len, int64_t nnz_end, be_nt_v4u& c, be_nt_v4u& wv) {
+  c = be_nt_v4u{0u, 0u, 0u, 0u};
+  wv = be_nt_v4u{0u, 0u, 0u, 0u};
+  if (j + 4 <= len || (j < len && b + j + 4 <= nnz_end)) {
+    const uint4 t = gather_ld16(indices + b + j);
+    c = be_nt_v4u{t.x, t.y, t.z, t.w};
+    if (VECW) {
+      const uint4 tw = gather_ld16(reinterpret_cast<const float*>(weights) + b + j);
+      wv = be_nt_v4u{tw.x, tw.y, tw.z, tw.w};
+    }
+  } else if (j < len) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (j + e < len) {
+        c[e] = (uint32_t)indices[b + j + e];
+        if (VECW) wv[e] = __float_as_uint(reinterpret_cast<const float*>(weights)[b + j + e]);
+      }
+  }
+}
+// lane src's 64-bit value, wave-uniform (src is; the casts keep a low word >= 2^31 from sign-extending over the high word)
+__device__ __forceinline__ int64_t lane_i64(int64_t v, int src) {
+  return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)((uint64_t)v >> 32), src) << 32) |
+                   (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)v, src));
+}
+// 64 CONSECUTIVE rows per wave batch (coalesced row pointers and results): lane l holds row r0 + l
+struct RowBatch {
+  int64_t my_r, rb, rl;      // the lane's row, its start and its length (0 past the matrix)
+  bool valid;
+};
+__device__ __forceinline__ RowBatch row_batch(const RowPtr& rp, int64_t r0, int lane, int64_t m) {
+  RowBatch t;
+  t.my_r = r0 + lane;
+  t.valid = t.my_r < m;
+  const int64_t rc = t.valid ? t.my_r : m - 1;
+  t.rb = rp.at(rc);
+  t.rl = t.valid ? rp.at(rc + 1) - t.rb : 0;
+  return t;
+}
 
+// (waves_per_eu: the workgroup's 16 waves are all a CU runs, so nothing is gained below 128 registers — where an instance came
+//  to 62, the scheduler held it under 64 for an eighth wave per SIMD and serialised the walk's LDS reads: +1 ... 2 % on rows of
+//  500 and 1000)
 template <typename W, bool HOMO, bool BITS_IN_LDS>
-__global__ void __launch_bounds__(1024) k_csrmv_nt_wave(const W* __restrict__ weights, const int32_t* __restrict__ indices,
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) k_csrmv_nt_wave(const W* __restrict__ weights, const int32_t* __restrict__ indices,
                                                         RowPtr rp, const uint32_t* __restrict__ bits_g, int64_t n_words,
                                                         W* __restrict__ out, int64_t m, const uint32_t* __restrict__ coarse_g,
                                                         int64_t n_cwords, int g_shift) {
   bits_g += (int64_t)blockIdx.y * n_words;
   out += (int64_t)blockIdx.y * m;
   extern __shared__ uint32_t bits_s[];
-  {   // the exact bitmap (BITS_IN_LDS) or the coarse one (spike_on)
-    const uint32_t* src = BITS_IN_LDS ? bits_g : coarse_g + (int64_t)blockIdx.y * n_cwords;
-    const int64_t nw = BITS_IN_LDS ? n_words : n_cwords;
-    for (int64_t i = threadIdx.x; i < nw; i += blockDim.x) bits_s[i] = src[i];
-    __syncthreads();
-  }
+  stage_bitmap<BITS_IN_LDS>(bits_s, bits_g, n_words, coarse_g, n_cwords);
   using ACC = typename WTraits<W>::acc;
   constexpr bool VECW = std::is_same<W, float>::value && !HOMO;
   const int lane = lane_id();
@@ -385,47 +507,8 @@ __global__ void __launch_bounds__(1024) k_csrmv_nt_wave(const W* __restrict__ we
   ACC w0 = ACC(0);
   if (HOMO) w0 = (ACC)WTraits<W>::load(weights, 0);
 
-  // one row: entries [j_begin, len) of the row starting at b, through descriptors of at most 2^30 entries
-  auto row_tail = [&](int64_t b, int64_t len, int64_t j_begin, ACC& acc, int& cnt) {
-    for (int64_t p0 = (j_begin >> 30) << 30; p0 < len; p0 += (1ll << 30)) {
-      const int64_t plen = len - p0 < (1ll << 30) ? len - p0 : (1ll << 30);
-      auto ri = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(indices + b + p0), 0, (int)(plen * 4), 0x00020000);
-      auto rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<W*>(VECW ? weights + b + p0 : weights), 0,
-                                                  VECW ? (int)(plen * 4) : 0, 0x00020000);
-      for (int64_t j0 = (p0 == ((j_begin >> 30) << 30)) ? (j_begin - p0) : 0; j0 < plen; j0 += 512) {
-        be_nt_v4u c[2], wv[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int off = (int)(j0 + 256 * u + 4 * lane) * 4;
-          c[u] = __builtin_amdgcn_raw_buffer_load_b128(ri, off, 0, BE_GATHER_AUX);
-          if (VECW) wv[u] = __builtin_amdgcn_raw_buffer_load_b128(rw, off, 0, BE_GATHER_AUX);
-        }
-        uint32_t cols[8], valid = 0;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            cols[4 * u + q] = c[u][q];
-            valid |= (j0 + 256 * u + 4 * lane + q < plen ? 1u : 0u) << (4 * u + q);
-          }
-        const uint32_t onm = spike_mask<BITS_IN_LDS, 8>(bits_s, bits_g, cols, valid, g_shift);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int64_t j = j0 + 256 * u + 4 * lane + q;
-            const bool on = (onm >> (4 * u + q)) & 1u;
-            if (HOMO) cnt += on ? 1 : 0;
-            else if (VECW) acc += on ? (ACC)__uint_as_float(wv[u][q]) : ACC(0);
-            else if (on) acc += (ACC)WTraits<W>::load(weights, b + p0 + j);
-          }
-        }
-      }
-    }
-  };
-
   // rows of this wave: wave, wave + n_waves, ...; their bounds are fetched 64 at a time (lane l -> l-th next row) and
-  // four rows' first 256 entries are in flight together; longer rows continue in row_tail
+  // four rows' first 256 entries are in flight together; longer rows continue in gather_row_walk
   for (int64_t t0 = 0;; t0 += 64) {
     const int64_t my_r = wave + n_waves * (t0 + lane);
     const bool valid = my_r < m;
@@ -475,23 +558,10 @@ __global__ void __launch_bounds__(1024) k_csrmv_nt_wave(const W* __restrict__ we
           valid |= ((4 * lane + e < gl[q] && 4 * lane + e < 256) ? 1u : 0u) << e;
         }
         const uint32_t onm = spike_mask<BITS_IN_LDS, 4>(bits_s, bits_g, cols, valid, g_shift);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int64_t j = 4 * lane + e;
-          const bool on = (onm >> e) & 1u;
-          if (HOMO) cnt += on ? 1 : 0;
-          else if (VECW) acc += on ? (ACC)__uint_as_float(wv[q][e]) : ACC(0);
-          else if (on) acc += (ACC)WTraits<W>::load(weights, gb[q] + j);
-        }
-        if (gl[q] > 256) row_tail(gb[q], gl[q], 256, acc, cnt);   // uniform
-        if (HOMO) {
-#pragma unroll
-          for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-          acc = (ACC)cnt * w0;
-        } else {
-#pragma unroll
-          for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-        }
+        gather_add<W, HOMO, 4>(onm, &wv[q], weights, gb[q] + 4 * lane, 0, acc, cnt);
+        if (gl[q] > 256)                                          // uniform
+          gather_row_walk<W, HOMO, BITS_IN_LDS, false>(weights, indices, gb[q], gl[q], 256, bits_s, bits_g, g_shift, lane, acc, cnt);
+        acc = gather_reduce<HOMO, 64>(acc, cnt, w0);
         if (lane == 0) WTraits<W>::store(out, wave + n_waves * (t0 + i + q), acc);
       }
     }
@@ -516,12 +586,7 @@ __global__ void __launch_bounds__(1024) k_csrmv_nt_vec(const W* __restrict__ wei
   bits_g += (int64_t)blockIdx.y * n_words;
   out += (int64_t)blockIdx.y * m;
   extern __shared__ uint32_t bits_s[];
-  {   // the exact bitmap (BITS_IN_LDS) or the coarse one (spike_mask)
-    const uint32_t* src = BITS_IN_LDS ? bits_g : coarse_g + (int64_t)blockIdx.y * n_cwords;
-    const int64_t nw = BITS_IN_LDS ? n_words : n_cwords;
-    for (int64_t i = threadIdx.x; i < nw; i += blockDim.x) bits_s[i] = src[i];
-    __syncthreads();
-  }
+  stage_bitmap<BITS_IN_LDS>(bits_s, bits_g, n_words, coarse_g, n_cwords);
   using ACC = typename WTraits<W>::acc;
   constexpr bool VECW = std::is_same<W, float>::value && !HOMO;
   constexpr int RPW = 64 / LPR;                  // rows per group (one load instruction)
@@ -546,11 +611,8 @@ __global__ void __launch_bounds__(1024) k_csrmv_nt_vec(const W* __restrict__ wei
   };
   // a batch = 64 CONSECUTIVE rows (coalesced row pointers and results); batches are dealt to the waves round-robin
   for (int64_t r0 = wave * 64; r0 < m; r0 += n_waves * 64) {
-    const int64_t my_r = r0 + lane;
-    const bool valid = my_r < m;
-    const int64_t rc = valid ? my_r : m - 1;
-    const int64_t rb = rp.at(rc);
-    const int64_t rl = valid ? rp.at(rc + 1) - rb : 0;
+    const RowBatch t = row_batch(rp, r0, lane, m);
+    const int64_t rb = t.rb, rl = t.rl;
     // The batch's entries are read through ONE descriptor over [first row's start, +2^29 entries) with 32-bit offsets
     // relative to it: loads past the arrays' end return zeros (no end-of-array special case), a piece a row does not reach
     // gets an out-of-range offset instead of a branch, and the address arithmetic is one add-shift per piece.  A batch that
@@ -593,29 +655,16 @@ __global__ void __launch_bounds__(1024) k_csrmv_nt_vec(const W* __restrict__ wei
       const uint32_t onm = spike_mask<BITS_IN_LDS, 8, true>(bits_s, bits_g, cols, vmask, g_shift);
       ACC acc = ACC(0);
       int cnt = HOMO ? __popc(onm) : 0;
-      if (!HOMO) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const bool on = (onm >> (4 * u + e)) & 1u;
-            if (VECW) acc += on ? (ACC)__uint_as_float(g.wv[u][e]) : ACC(0);
-            else if (on) acc += (ACC)WTraits<W>::load(weights, b_first + g.rel + (int64_t)u * PASS + 4 * sub + e);
-          }
-      }
-      if (HOMO) {
-#pragma unroll
-        for (int off = LPR / 2; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, LPR);
-        acc = (ACC)cnt;
-      } else {
-#pragma unroll
-        for (int off = LPR / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, LPR);
-      }
+      if (!HOMO) gather_add<W, HOMO, 8>(onm, g.wv, weights, b_first + g.rel + 4 * sub, PASS, acc, cnt);
+      acc = gather_reduce<HOMO, LPR>(acc, cnt, ACC(1));      // (counts stay counts until the batch's store applies w0)
       if (sub == 0) res_s[wv_id][q * RPW + slot] = acc;
     };
     Grp g[NGRP];
 #pragma unroll
     for (int q = 0; q < DEPTH; ++q) issue(g[q], q);
+    // (nothing of consume() moves up between these loads: in some instances the scheduler started on group 0 after its two
+    //  loads and issued group 1's only once they had arrived — counted, 2 lanes per row: +7 % at 4 and 8 entries per row)
+    if (HOMO) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int q = 0; q < NGRP; ++q) {
       if (q + DEPTH < NGRP) issue(g[q + DEPTH], q + DEPTH);
@@ -627,64 +676,18 @@ __global__ void __launch_bounds__(1024) k_csrmv_nt_vec(const W* __restrict__ wei
     while (longm) {
       const int src = __ffsll((long long)longm) - 1;
       longm &= longm - 1;
-      const int64_t b = __shfl(rb, src, 64), len = __shfl(rl, src, 64);
+      const int64_t b = lane_i64(rb, src), len = lane_i64(rl, src);     // (in scalar registers: the walk's descriptors)
       ACC acc = ACC(0);
       int cnt = 0;
-      for (int64_t j0 = tail_from; j0 < len; j0 += 2 * 256) {
-        be_nt_v4u c[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}}, wv[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int64_t j = j0 + (int64_t)u * 256 + 4 * lane;
-          if (j + 4 <= len || (j < len && b + j + 4 <= nnz_end)) {
-            const uint4 t = gather_ld16(indices + b + j);
-            c[u] = be_nt_v4u{t.x, t.y, t.z, t.w};
-            if (VECW) {
-              const uint4 tw = gather_ld16(reinterpret_cast<const float*>(weights) + b + j);
-              wv[u] = be_nt_v4u{tw.x, tw.y, tw.z, tw.w};
-            }
-          } else if (j < len) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (j + e < len) {
-                c[u][e] = (uint32_t)indices[b + j + e];
-                if (VECW) wv[u][e] = __float_as_uint(reinterpret_cast<const float*>(weights)[b + j + e]);
-              }
-          }
-        }
-        uint32_t cols[8], vmask = 0;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            cols[4 * u + e] = c[u][e];
-            vmask |= (j0 + (int64_t)u * 256 + 4 * lane + e < len ? 1u : 0u) << (4 * u + e);
-          }
-        const uint32_t onm = spike_mask<BITS_IN_LDS, 8, true>(bits_s, bits_g, cols, vmask, g_shift);
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const bool on = (onm >> (4 * u + e)) & 1u;
-            if (HOMO) cnt += on ? 1 : 0;
-            else if (VECW) acc += on ? (ACC)__uint_as_float(wv[u][e]) : ACC(0);
-            else if (on) acc += (ACC)WTraits<W>::load(weights, b + j0 + (int64_t)u * 256 + 4 * lane + e);
-          }
-      }
-      if (HOMO) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-        acc = (ACC)cnt;
-      } else {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-      }
+      gather_row_walk<W, HOMO, BITS_IN_LDS, true>(weights, indices, b, len, tail_from, bits_s, bits_g, g_shift, lane, acc, cnt);
+      acc = gather_reduce<HOMO, 64>(acc, cnt, ACC(1));
       if (lane == 0) res_s[wv_id][src] += acc;        // (same wave wrote the slot: program order)
     }
     // one coalesced store of the batch's 64 results (LDS traffic of one wave needs no barrier, only the wait below)
     __builtin_amdgcn_s_waitcnt(0xc07f);               // lgkmcnt(0)
-    if (valid) {
+    if (t.valid) {
       const ACC r = res_s[wv_id][lane];
-      WTraits<W>::store(out, my_r, HOMO ? r * w0 : r);
+      WTraits<W>::store(out, t.my_r, HOMO ? r * w0 : r);
     }
   }
 }
@@ -715,6 +718,38 @@ __global__ void __launch_bounds__(256) k_batch_masks(const typename SP::type* __
 
 constexpr int kFusedSlots = 33;      // 32 columns + 1 pad word: lane l's slots start at bank l
 
+// ---- the parts the two fused kernels share, each stated once
+// visit the set bits of one entry's mask: w (HOMO: 1, as uint32 counts) into the slots of those columns
+template <bool HOMO>
+__device__ __forceinline__ void fused_add(uint32_t bits, float w, float* slots) {
+  while (bits) {
+    const int b = __ffs(bits) - 1;
+    bits &= bits - 1;
+    if (HOMO) reinterpret_cast<uint32_t*>(slots)[b] += 1u;
+    else slots[b] += w;
+  }
+}
+// one entry of the streamed pieces: its weight (wbits: the streamed f32; other dtypes load weights[pos]) only if any column fired
+template <typename W, bool HOMO>
+__device__ __forceinline__ void fused_entry(uint32_t bits, uint32_t wbits, const W* __restrict__ weights, int64_t pos, float* slots) {
+  constexpr bool VECW = std::is_same<W, float>::value && !HOMO;
+  if (bits) {
+    float w = 0.0f;
+    if (!HOMO) w = VECW ? __uint_as_float(wbits) : (float)WTraits<W>::load(weights, pos);
+    fused_add<HOMO>(bits, w, slots);
+  }
+}
+__device__ __forceinline__ void fused_clear(float* slots) {
+#pragma unroll
+  for (int b = 0; b < 32; ++b) slots[b] = 0.0f;
+}
+// the wave's slot writes before, its slot reads after: LDS traffic of one wave needs no s_barrier, only this ordering
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 template <typename W, bool HOMO>
 __global__ void __launch_bounds__(1024) k_csrmm_nt_fused(const W* __restrict__ weights, const int32_t* __restrict__ indices,
                                                          RowPtr rp, const uint32_t* __restrict__ mask, int nc,
@@ -722,9 +757,7 @@ __global__ void __launch_bounds__(1024) k_csrmm_nt_fused(const W* __restrict__ w
   extern __shared__ float fused_s[];                 // [1024][kFusedSlots]; uint32 counts when HOMO
   constexpr bool VECW = std::is_same<W, float>::value && !HOMO;
   float* my = fused_s + threadIdx.x * kFusedSlots;
-  uint32_t* my_u = reinterpret_cast<uint32_t*>(my);
-#pragma unroll
-  for (int b = 0; b < 32; ++b) my[b] = 0.0f;
+  fused_clear(my);
   const int lane = lane_id();
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -756,22 +789,13 @@ __global__ void __launch_bounds__(1024) k_csrmm_nt_fused(const W* __restrict__ w
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int64_t j = j0 + 256 * u + 4 * lane + q;
-            uint32_t bits = j < plen ? mk[4 * u + q] : 0u;
-            if (bits) {
-              float w = 0.0f;
-              if (!HOMO) w = VECW ? __uint_as_float(wv[u][q]) : (float)WTraits<W>::load(weights, rb + p0 + j);
-              do {
-                const int b = __ffs(bits) - 1;
-                bits &= bits - 1;
-                if (HOMO) my_u[b] += 1u;
-                else my[b] += w;
-              } while (bits);
-            }
+            fused_entry<W, HOMO>(j < plen ? mk[4 * u + q] : 0u, VECW ? wv[u][q] : 0u, weights, rb + p0 + j, my);
           }
         }
       }
     }
-    // fold the wave's 64 x 32 slots: lane l sums column (l & 31) over lanes [32 * (l >> 5), +32)
+    // fold the wave's 64 x 32 slots: lane l sums column (l & 31) over lanes [32 * (l >> 5), +32).  (wave_lds_sync in halves:
+    // release + barrier in front of the fold, acquire + barrier behind it)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     {
@@ -794,8 +818,7 @@ __global__ void __launch_bounds__(1024) k_csrmm_nt_fused(const W* __restrict__ w
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int b = 0; b < 32; ++b) my[b] = 0.0f;
+    fused_clear(my);
   }
 }
 
@@ -812,9 +835,7 @@ __global__ void __launch_bounds__(1024) k_csrmm_nt_fused_vec(const W* __restrict
   constexpr bool VECW = std::is_same<W, float>::value && !HOMO;
   constexpr int RPW = 64 / LPR, NGRP = 64 / RPW, PASS = 4 * LPR;
   float* my = fused_s + threadIdx.x * kFusedSlots;
-  uint32_t* my_u = reinterpret_cast<uint32_t*>(my);
-#pragma unroll
-  for (int b = 0; b < 32; ++b) my[b] = 0.0f;
+  fused_clear(my);
   const int lane = lane_id(), sub = lane % LPR, slot = lane / LPR;
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -828,24 +849,9 @@ __global__ void __launch_bounds__(1024) k_csrmm_nt_fused_vec(const W* __restrict
     int64_t b;
     int32_t len;               // clamped to two passes
   };
-  auto add_entry = [&](uint32_t bits, uint32_t wbits, int64_t pos) {          // visit the set bits of one entry's mask
-    if (bits) {
-      float w = 0.0f;
-      if (!HOMO) w = VECW ? __uint_as_float(wbits) : (float)WTraits<W>::load(weights, pos);
-      do {
-        const int b = __ffs(bits) - 1;
-        bits &= bits - 1;
-        if (HOMO) my_u[b] += 1u;
-        else my[b] += w;
-      } while (bits);
-    }
-  };
   for (int64_t r0 = wave * 64; r0 < m; r0 += n_waves * 64) {
-    const int64_t my_r = r0 + lane;
-    const bool valid = my_r < m;
-    const int64_t rc = valid ? my_r : m - 1;
-    const int64_t rb = rp.at(rc);
-    const int64_t rl = valid ? rp.at(rc + 1) - rb : 0;
+    const RowBatch t = row_batch(rp, r0, lane, m);
+    const int64_t rb = t.rb, rl = t.rl;
     auto issue = [&](Grp& g, int q) {
       const int src = q * RPW + slot;
       g.b = __shfl(rb, src, 64);
@@ -855,24 +861,8 @@ __global__ void __launch_bounds__(1024) k_csrmm_nt_fused_vec(const W* __restrict
       }
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        g.c[u] = be_nt_v4u{0u, 0u, 0u, 0u};
-        g.wv[u] = be_nt_v4u{0u, 0u, 0u, 0u};
         const int32_t j = u * PASS + 4 * sub;
-        if (j + 4 <= g.len || (j < g.len && g.b + j + 4 <= nnz_end)) {
-          const uint4 t = gather_ld16(indices + g.b + j);
-          g.c[u] = be_nt_v4u{t.x, t.y, t.z, t.w};
-          if (VECW) {
-            const uint4 tw = gather_ld16(reinterpret_cast<const float*>(weights) + g.b + j);
-            g.wv[u] = be_nt_v4u{tw.x, tw.y, tw.z, tw.w};
-          }
-        } else if (j < g.len) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (j + e < g.len) {
-              g.c[u][e] = (uint32_t)indices[g.b + j + e];
-              if (VECW) g.wv[u][e] = __float_as_uint(reinterpret_cast<const float*>(weights)[g.b + j + e]);
-            }
-        }
+        gather_ld4_guarded<W, VECW>(indices, weights, g.b, j, g.len, nnz_end, g.c[u], g.wv[u]);
       }
     };
     // One group at a time, in a real loop (the body — tails, fold — is too long to unroll 8 ... 32 times): the mask gathers
@@ -893,7 +883,7 @@ __global__ void __launch_bounds__(1024) k_csrmm_nt_fused_vec(const W* __restrict
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int32_t j = u * PASS + 4 * sub + e;
-          add_entry(j < g.len ? mk[4 * u + e] : 0u, g.wv[u][e], g.b + j);
+          fused_entry<W, HOMO>(j < g.len ? mk[4 * u + e] : 0u, g.wv[u][e], weights, g.b + j, my);
         }
       // rows of this group longer than two passes: the whole wave takes the rest of each (the slots of ALL its lanes are
       // folded into that row below, so the tail entries go to the slots of the row's own lanes: lane l -> slot lane l % LPR)
@@ -905,7 +895,6 @@ __global__ void __launch_bounds__(1024) k_csrmm_nt_fused_vec(const W* __restrict
         const int src = q * RPW + src_lane / LPR;
         const int64_t b = __shfl(rb, src, 64), len = __shfl(rl, src, 64);
         float* tgt = wave_slots + (src_lane + sub) * kFusedSlots;                // a slot row of that group, by this lane's sub index
-        uint32_t* tgt_u = reinterpret_cast<uint32_t*>(tgt);
         for (int64_t j0 = 2 * PASS; j0 < len; j0 += 64) {
           const int64_t j = j0 + lane;
           uint32_t bits = 0;
@@ -917,25 +906,13 @@ __global__ void __launch_bounds__(1024) k_csrmm_nt_fused_vec(const W* __restrict
           // lanes with the same sub index share a slot row here: serialise them by their slot number (RPW rounds)
 #pragma unroll
           for (int turn = 0; turn < RPW; ++turn) {
-            if (slot == turn) {
-              uint32_t bb = bits;
-              while (bb) {
-                const int bi = __ffs(bb) - 1;
-                bb &= bb - 1;
-                if (HOMO) tgt_u[bi] += 1u;
-                else tgt[bi] += w;
-              }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (slot == turn) fused_add<HOMO>(bits, w, tgt);
+            wave_lds_sync();
           }
         }
       }
       // fold the group's rows: lane (slot, sub) sums columns sub, sub + LPR, ... over the LPR lanes of its row
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       {
         const int64_t row = r0 + q * RPW + slot;
         const float* src = wave_slots + (slot * LPR) * kFusedSlots;
@@ -951,11 +928,8 @@ __global__ void __launch_bounds__(1024) k_csrmm_nt_fused_vec(const W* __restrict
           if (col < nc && row < m) WTraits<W>::store(out_bm, (int64_t)col * m + row, sum);
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-      for (int b = 0; b < 32; ++b) my[b] = 0.0f;
+      wave_lds_sync();
+      fused_clear(my);
       g = gn;
     }
   }
@@ -1089,6 +1063,56 @@ static inline int gather_g_shift(int64_t k) {
 }
 static inline int64_t gather_cwords(int64_t k, int g_shift) { return g_shift ? (((k + ((int64_t)1 << g_shift) - 1) >> g_shift) + 31) / 32 : 0; }
 
+// Lanes per row by the average row length: two passes of a row (8 x LPR entries) should hold nearly every row.
+constexpr int64_t kGatherVecMaxRow = 200;   // average row length up to which the lanes-per-row vector kernels are used (32 lanes: 256 entries in two passes)
+constexpr int64_t kGatherLpr2MaxRow = 8, kGatherLpr4MaxRow = 20, kGatherLpr8MaxRow = 45, kGatherLpr16MaxRow = 100;
+// Rows of one known length (no indptr: FixedNumConn) have no long tail to provide for: 8 / 16 lanes up to exactly
+// two passes (64 / 128 entries; measured +5 % at 48 ... 64 per row).  Fewer lanes with both passes in use lose
+// (12 ... 32 per row on 2 / 4 lanes instead of 4 / 8: 0.30-0.33 -> 0.36 ms at 2e8 weighted entries).
+constexpr int64_t kGatherLpr8MaxFixed = 64, kGatherLpr16MaxFixed = 128;
+constexpr int64_t kFusedLpr8MaxRow = 45, kFusedLpr16MaxRow = 100;
+// k_csrmv_nt_vec's lanes per row; 0: a wave per row (k_csrmv_nt_wave)
+static inline int gather_lpr_of(int64_t avg, bool fixed) {
+  if (avg <= kGatherLpr2MaxRow) return 2;
+  if (avg <= kGatherLpr4MaxRow) return 4;
+  if (avg <= (fixed ? kGatherLpr8MaxFixed : kGatherLpr8MaxRow)) return 8;
+  if (avg <= (fixed ? kGatherLpr16MaxFixed : kGatherLpr16MaxRow)) return 16;
+  return avg <= kGatherVecMaxRow ? 32 : 0;
+}
+// k_csrmm_nt_fused_vec's lanes per row; 0: a wave per row (k_csrmm_nt_fused)
+static inline int fused_lpr_of(int64_t avg) {
+  if (avg <= kFusedLpr8MaxRow) return 8;
+  if (avg <= kFusedLpr16MaxRow) return 16;
+  return avg <= kGatherVecMaxRow ? 32 : 0;
+}
+
+// one launch of the bit-vector gather: k_csrmv_nt_vec with LPR lanes per row, k_csrmv_nt_wave for LPR = 0 (same arguments)
+template <typename W, bool HOMO, int LPR, bool IN_LDS>
+int launch_gather(const W* weights, const int32_t* indices, RowPtr rp, const uint32_t* bits, int64_t n_words, W* out, int64_t m,
+                  int64_t nb, const uint32_t* coarse, int64_t n_cwords, int g_shift, hipStream_t st) {
+  auto kern = k_csrmv_nt_wave<W, HOMO, IN_LDS>;
+  const int64_t nw = IN_LDS ? n_words : n_cwords;
+  size_t lds = (size_t)nw * 4;
+  if constexpr (LPR != 0) {
+    kern = k_csrmv_nt_vec<W, HOMO, LPR, IN_LDS>;
+    // bitmap (rounded to 16 bytes) + the 16 waves' result rows
+    lds = (size_t)(((nw + 3) & ~(int64_t)3) * 4) + 16 * 64 * sizeof(typename WTraits<W>::acc);
+    // the kernel addresses the bitmap from LDS address 0 (spike_mask AT0): true while the very instantiation that is launched
+    // declares no static LDS (checked once per kernel; a static __shared__ added later fails here, loudly, instead of
+    // testing the wrong bits)
+    BE_REQUIRE(be_static_lds_bytes(reinterpret_cast<const void*>(kern)) == 0, BE_ERR_UNSUPPORTED,
+               "k_csrmv_nt_vec: static LDS in front of the bitmap (spike_mask AT0 addresses it from 0)");
+  }
+  BE_HIP(be_allow_lds(reinterpret_cast<const void*>(kern), (int)lds));
+  const int grid = grid_for(m, LPR != 0 ? 16 * 64 : 16, nb >= 8 ? 256 : 512);      // 16 waves: 64 rows each, or one
+  const int prof = be_prof_begin(st);
+  hipLaunchKernelGGL(kern, dim3(grid, (unsigned)nb), dim3(1024), lds, st, weights, indices, rp, bits, n_words, out, m, coarse,
+                     n_cwords, g_shift);
+  be_prof_end(prof, st);
+  BE_LAUNCH_CHECK();
+  return BE_OK;
+}
+
 template <typename W, bool HOMO>
 int csrmv_nt(const void* weights, const int32_t* indices, RowPtr rp, int64_t nnz_hint, const void* spikes, int sd,
              void* out, int64_t m, int64_t k, int64_t nb, void* ws, hipStream_t st) {
@@ -1102,11 +1126,11 @@ int csrmv_nt(const void* weights, const int32_t* indices, RowPtr rp, int64_t nnz
     uint32_t* mask = static_cast<uint32_t*>(ws);
     const size_t lds = (size_t)1024 * kFusedSlots * 4;
     auto kern = k_csrmm_nt_fused<W, HOMO>;
-    const int64_t avg_row = nnz_hint / m;
-    const int grid_rows = avg_row <= kGatherVecMaxRow ? 16 * 64 : 16;      // rows a workgroup takes per round
-    if (avg_row <= 45) kern = k_csrmm_nt_fused_vec<W, HOMO, 8>;
-    else if (avg_row <= 100) kern = k_csrmm_nt_fused_vec<W, HOMO, 16>;
-    else if (avg_row <= kGatherVecMaxRow) kern = k_csrmm_nt_fused_vec<W, HOMO, 32>;
+    const int lpr = fused_lpr_of(nnz_hint / m);
+    const int grid_rows = lpr != 0 ? 16 * 64 : 16;      // rows a workgroup takes per round
+    if (lpr == 8) kern = k_csrmm_nt_fused_vec<W, HOMO, 8>;
+    else if (lpr == 16) kern = k_csrmm_nt_fused_vec<W, HOMO, 16>;
+    else if (lpr == 32) kern = k_csrmm_nt_fused_vec<W, HOMO, 32>;
     BE_HIP(be_allow_lds(reinterpret_cast<const void*>(kern), (int)lds));
     const size_t ssz = sd == BE_SPIKE_FLOAT ? 4 : 1;
     for (int64_t c0 = 0; c0 < nb; c0 += 32) {
@@ -1145,73 +1169,13 @@ int csrmv_nt(const void* weights, const int32_t* indices, RowPtr rp, int64_t nnz
     coarse = cw;
   }
   const bool in_lds = g_shift == 0;
-  const size_t lds = (size_t)(in_lds ? n_words : n_cwords) * 4;
-  const int64_t avg = nnz_hint / (m > 0 ? m : 1);
-  if (avg <= kGatherVecMaxRow) {      // short and medium rows: 2 ... 32 lanes per row, four entries per lane and load
-    const int prof = be_prof_begin(st);
-    // bitmap (rounded to 16 bytes) + the 16 waves' result rows
-    const size_t vlds = (size_t)((((in_lds ? n_words : n_cwords) + 3) & ~(int64_t)3) * 4) + 16 * 64 * sizeof(typename WTraits<W>::acc);
-    // the kernels address the bitmap from LDS address 0 (spike_mask AT0): true while the very instantiation that is launched
-    // declares no static LDS (checked once per kernel; a static __shared__ added later fails here, loudly, instead of
-    // testing the wrong bits)
-#define BE_NT_VEC_AT0(KERN)                                                                                                 \
-    do {                                                                                                                    \
-      if (be_static_lds_bytes(reinterpret_cast<const void*>(KERN)) != 0) {                                                  \
-        be_set_error("k_csrmv_nt_vec: static LDS in front of the bitmap (spike_mask AT0 addresses it from 0)");             \
-        return BE_ERR_UNSUPPORTED;                                                                                          \
-      }                                                                                                                     \
-    } while (0)
-#define BE_NT_VEC(LPR_)                                                                                                     \
-    do {                                                                                                                    \
-      const int grid = grid_for(m, 16 * 64, nb >= 8 ? 256 : 512);                                                   \
-      if (in_lds) {                                                                                                          \
-        auto kern = k_csrmv_nt_vec<W, HOMO, LPR_, true>;                                                                    \
-        BE_NT_VEC_AT0(kern);                                                                                                 \
-        BE_HIP(be_allow_lds(reinterpret_cast<const void*>(kern), (int)vlds));                                               \
-        hipLaunchKernelGGL(kern, dim3(grid, (unsigned)nb), dim3(1024), vlds, st, static_cast<const W*>(weights), indices, rp, \
-                           bits, n_words, static_cast<W*>(out), m, coarse, n_cwords, g_shift);                              \
-      } else {                                                                                                               \
-        auto kern = k_csrmv_nt_vec<W, HOMO, LPR_, false>;                                                                   \
-        BE_NT_VEC_AT0(kern);                                                                                                 \
-        BE_HIP(be_allow_lds(reinterpret_cast<const void*>(kern), (int)vlds));                                               \
-        hipLaunchKernelGGL(kern, dim3(grid, (unsigned)nb), dim3(1024), vlds, st, static_cast<const W*>(weights), indices, rp, \
-                           bits, n_words, static_cast<W*>(out), m, coarse, n_cwords, g_shift);                              \
-      }                                                                                                                      \
-    } while (0)
-    // two passes of a row (8 x LPR entries) should hold nearly every row: LPR by the average length
-    // — rows of one known length (no indptr: FixedNumConn) have no long tail to provide for: 8 / 16 lanes up to exactly
-    // two passes (64 / 128 entries; measured +5 % at 48 ... 64 per row).  Fewer lanes with both passes in use lose
-    // (12 ... 32 per row on 2 / 4 lanes instead of 4 / 8: 0.30-0.33 -> 0.36 ms at 2e8 weighted entries).
-    const bool fixed = rp.p == nullptr;
-    if (avg <= 8) BE_NT_VEC(2);
-    else if (avg <= 20) BE_NT_VEC(4);
-    else if (avg <= (fixed ? 64 : 45)) BE_NT_VEC(8);
-    else if (avg <= (fixed ? 128 : 100)) BE_NT_VEC(16);
-    else BE_NT_VEC(32);
-#undef BE_NT_VEC
-#undef BE_NT_VEC_AT0
-    be_prof_end(prof, st);
-    BE_LAUNCH_CHECK();
-    return BE_OK;
-  }
-  {
-    const int grid = grid_for(m, 16, nb >= 8 ? 256 : 512);
-    const int prof = be_prof_begin(st);
-    if (in_lds) {
-      auto kern = k_csrmv_nt_wave<W, HOMO, true>;
-      BE_HIP(be_allow_lds(reinterpret_cast<const void*>(kern), (int)lds));
-      hipLaunchKernelGGL(kern, dim3(grid, (unsigned)nb), dim3(1024), lds, st, static_cast<const W*>(weights), indices, rp,
-                         bits, n_words, static_cast<W*>(out), m, coarse, n_cwords, g_shift);
-    } else {
-      auto kern = k_csrmv_nt_wave<W, HOMO, false>;
-      BE_HIP(be_allow_lds(reinterpret_cast<const void*>(kern), (int)lds));
-      hipLaunchKernelGGL(kern, dim3(grid, (unsigned)nb), dim3(1024), lds, st, static_cast<const W*>(weights), indices, rp,
-                         bits, n_words, static_cast<W*>(out), m, coarse, n_cwords, g_shift);
-    }
-    be_prof_end(prof, st);
-    BE_LAUNCH_CHECK();
-    return BE_OK;
-  }
+  const int lpr = gather_lpr_of(nnz_hint / m, rp.p == nullptr);
+  return be_dispatch_int<0, 2, 4, 8, 16, 32>(lpr, [&](auto l) {
+    return be_dispatch_bool(in_lds, [&](auto b) {
+      return launch_gather<W, HOMO, decltype(l)::value, decltype(b)::value>(static_cast<const W*>(weights), indices, rp, bits, n_words,
+                                                                            static_cast<W*>(out), m, nb, coarse, n_cwords, g_shift, st);
+    });
+  });
 }
 
 
