@@ -10,7 +10,8 @@ The JIT-connectivity products are differentiable in their parameters (``weight``
 their operand: both parameter gradients of a call come out of one walk of the generated edges (``jit_param_sums``).
 ``CSR.solve`` / ``CSC.solve`` / ``csr_solve`` solve ``A x = b`` by Jacobi-preconditioned BiCGSTAB on the device (``_solve``).
 ``SpikeRing @ DelayedCSR`` gives every synapse a conduction delay: a bit-packed spike history and the matrix split by delay, one
-ordinary scatter per step (``_delay``).
+ordinary scatter per step (``_delay``).  Delayed synapses learn: ``DelayedCSR.update_on_pre`` / ``update_on_post`` (the pre-side
+value of a synapse comes from a ``ValueRing``, read by age), and ``ring @ D`` is differentiable in the weights.
 """
 from ._version import __version__
 __version_info__ = tuple(int(p) for p in __version__.split('.')[:3] if p.isdigit())
@@ -38,7 +39,7 @@ from ._slice import (csr_slice_rows, csr_slice_rows_p, csr_slice_rows_p_call, cs
 from ._arith import ArithmeticMixin, entries_dense_op_p
 from ._diag import csr_diag_position, csr_diag_add
 from ._solve import csr_solve, csr_solve_p, csr_solve_p_call
-from ._delay import SpikeRing, DelayedCSR
+from ._delay import SpikeRing, ValueRing, DelayedCSR
 from ._graph import GraphedStep, capture_step
 from ._tuning import (ScatterTuning, DEFAULT_SCATTER_TUNING, get_scatter_tuning, save_scatter_tuning, apply_scatter_tuning,
                       tune_scatter_routes)

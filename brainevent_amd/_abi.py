@@ -61,7 +61,8 @@ _SIGNATURES = dict(
     be_binary_jitmv_rows='i:iddilupipllllplp', be_binary_jitmm_workspace_bytes='l:lllli', be_binary_jitmm='i:iddilupiplllliplp',
     be_jit_edge_weights='i:iddupplpp', be_jitc_csr_count='i:lulllipp', be_jitc_csr_fill='i:iddlulllippppp',
     be_jitc_fill_sorted='i:iddlulllippippp',
-    be_plasticity_workspace_bytes='l:l', be_plasticity_rows='i:pippillpipilpididplp', be_plasticity_dense='i:ipillpipididplp',
+    be_plasticity_workspace_bytes='l:l', be_plasticity_rows='i:pippillpipilpididplp',
+    be_plasticity_rows_aged='i:pippilpipilppliiididplp', be_plasticity_dense='i:ipillpipididplp',
     be_grad_mask_bytes='l:ll', be_grad_pack_activity='i:pillpp', be_grad_rows_workspace_bytes='l:l',
     be_grad_rows='i:ipiippilllplpllplp', be_grad_dense_workspace_bytes='l:ll', be_grad_dense='i:ipillplpllp',
     be_sddmm_rows='i:pippilplllpplp',
@@ -70,7 +71,7 @@ _SIGNATURES = dict(
     be_solve_workspace_bytes='l:li', be_solve_setup='i:pippillplp', be_solve_residual='i:pippillppplp',
     be_solve_diagonal='i:ilppplp', be_solve_iterate='i:pippillpidplp',
     be_delay_split_workspace_bytes='l:li', be_delay_split_count='i:pilplipiplp', be_delay_split_fill='i:pilpplipipppp',
-    be_spike_ring_push='i:pilipppp', be_spike_ring_compact='i:ppliipppp',
+    be_spike_ring_push='i:pilipppp', be_spike_ring_compact='i:ppliipppp', be_value_ring_push='i:pilipippp',
 )
 
 # be_binary_jit{s,u,n}{mv,mm}_{notrans,trans}_{w}: BE_FOR_JIT_VARIANTS over BE_DECL_JIT_VARIANT (BE_JIT_MV_ARGS / BE_JIT_MM_ARGS)

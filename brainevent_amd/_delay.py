@@ -6,6 +6,12 @@ The last ``depth`` spike vectors are kept bit-packed (:class:`SpikeRing`); every
 ring is compacted into that id list (``csrc/be_delay.hip``) and the list goes through the scatter routes that exist (planned,
 binned, direct) as an :class:`~brainevent_amd._array.ActiveIds` operand.  The reference has no delays.
 
+Delayed synapses learn: ``D.update_on_pre(ring, post_trace)`` is the row-driven update of the stacked matrix over
+the same id list; ``D.update_on_post(hist, post_spike)`` reads the pre-side value each synapse saw arrive from a
+:class:`ValueRing` — the history of a per-neuron quantity beside the history of spikes — by age, inside the update kernel; and
+``ring @ D`` is differentiable in the weights (``D.stacked.data`` is the leaf, :meth:`DelayedCSR.stacked_to_original` moves its
+gradient to the order the synapses were given in).  The delays are axonal: they sit between the pre neuron and the synapse.
+
 Everything that can be refused is refused before the first device call (shapes, dtypes, the ``depth`` range), so the validation
 runs without a GPU."""
 from typing import Optional
@@ -17,7 +23,7 @@ from . import _array as A
 from ._event import BinaryArray, BitPackedBinary, CompactBinary
 from ._lib import call, fn
 
-__all__ = ['SpikeRing', 'DelayedCSR', 'MAX_DELAY_DEPTH', 'check_ring_matches']
+__all__ = ['SpikeRing', 'ValueRing', 'DelayedCSR', 'MAX_DELAY_DEPTH', 'check_ring_matches']
 
 #: largest ``depth`` of a :class:`DelayedCSR` (the split kernels keep one LDS counter per delay and wave: kMaxDepth)
 MAX_DELAY_DEPTH = 256
@@ -149,6 +155,86 @@ class SpikeRing:
         return f"SpikeRing(n={self.n}, depth={self.depth})"
 
 
+_VALUE_DTYPES = (torch.float32, torch.float64, torch.float16, torch.bfloat16)
+
+
+def _float_dtype_of(x):
+    """The torch float dtype of a tensor or numpy array, ``None`` for anything else (no device call)."""
+    if isinstance(x, torch.Tensor):
+        return x.dtype if x.dtype in _VALUE_DTYPES else None
+    dt = np.asarray(x).dtype
+    return {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.float16): torch.float16}.get(dt)
+
+
+class ValueRing:
+    """The last ``depth`` value vectors of ``n`` neurons on the device — the history of a per-neuron quantity (a presynaptic
+    trace) beside the history of spikes, for the updates of delayed synapses.
+
+    ``values`` is ``[depth, n]`` in ``dtype`` (f32, f64, f16 or bf16), ``head`` a device int32 ``[1]`` with :class:`SpikeRing`'s
+    convention: :meth:`push` writes slot ``head`` and advances ``head`` on the device (one launch, no host read, so a captured step
+    replays correctly), and the vector of *age* ``a`` (0: just pushed) lies in slot ``(head - 1 - a) mod depth``.  History before the
+    first push is zero.  One vector per step (no batch).  Results are device tensors."""
+
+    def __init__(self, n: int, depth: int, dtype=torch.float32, device=None):
+        n, depth = int(n), int(depth)
+        if n < 1:
+            raise ValueError(f"ValueRing: n must be >= 1; got {n}.")
+        if depth < 1:
+            raise ValueError(f"ValueRing: depth must be >= 1; got {depth}.")
+        if depth * n >= _ID_LIMIT:
+            raise ValueError(f"ValueRing: depth * n = {depth * n} must stay below 2^31 (the ids of the stacked rows are int32).")
+        if dtype not in _VALUE_DTYPES:
+            raise TypeError(f"ValueRing: dtype must be torch.float32, float64, float16 or bfloat16; got {dtype}.")
+        self.n, self.depth, self.dtype = n, depth, dtype
+        dev = torch.device(device) if device is not None else A.device()
+        self.values = torch.zeros((depth, n), dtype=dtype, device=dev)
+        self._state = torch.zeros(2, dtype=torch.int32, device=dev)       # head, and the push kernel's arrival ticket
+        self.head = self._state[:1]
+        self._ages = None       # 0 .. depth - 1 on the device: built by the first by_age()
+
+    def push(self, x) -> 'ValueRing':
+        """Store the values of the current step: a 1-D tensor or numpy array of ``n`` elements in any float dtype, converted to
+        the ring's dtype as a cast does.  One launch, no host read."""
+        shape = _shape_of(x)
+        if len(shape) != 1:
+            raise NotImplementedError(f"ValueRing.push takes one 1-D value vector; got shape {shape} (batched rings are not built).")
+        if shape[0] != self.n:
+            raise ValueError(f"ValueRing.push: {shape[0]} values for a ring of {self.n} neurons.")
+        if _float_dtype_of(x) is None:
+            raise TypeError(f"ValueRing.push takes a float tensor or numpy array; got {getattr(x, 'dtype', type(x).__name__)}.")
+        buf = A.to_device(x)
+        call('be_value_ring_push', A.ptr(buf), A.wcode(buf), self.n, self.depth, A.ptr(self.values), A.wcode(self.values),
+             A.ptr(self.head), A.ptr(self._state[1:]), A.stream_ptr())
+        return self
+
+    def reset(self) -> 'ValueRing':
+        """Forget the history (``values`` and ``head`` back to zero)."""
+        self.values.zero_()
+        self._state.zero_()
+        return self
+
+    def value(self, age: int = 0) -> torch.Tensor:
+        """The vector of ``age`` steps ago (a copy of that slot).  The slot is picked by a device-side index, so the call
+        captures."""
+        age = int(age)
+        if not 0 <= age < self.depth:
+            raise ValueError(f"ValueRing.value: age must lie in [0, {self.depth}); got {age}.")
+        slot = torch.remainder(self.head - (1 + age), self.depth)
+        return self.values.index_select(0, slot).reshape(-1)
+
+    def by_age(self) -> torch.Tensor:
+        """``[depth, n]`` with row ``a`` = the vector of age ``a``: a gather with a device-side index (capturable), a copy of
+        the whole history."""
+        if self._ages is None:
+            self._ages = torch.arange(1, self.depth + 1, dtype=torch.int32, device=self.values.device)
+        return self.values.index_select(0, torch.remainder(self.head - self._ages, self.depth))
+
+    shape = property(lambda self: (self.depth, self.n))
+
+    def __repr__(self):
+        return f"ValueRing(n={self.n}, depth={self.depth}, dtype={self.dtype})"
+
+
 def _as_int32_delays(delays, nnz: int):
     """``delays`` checked without touching a device: an integer array (numpy or torch) with one element per stored entry."""
     if not isinstance(delays, torch.Tensor):
@@ -178,8 +264,10 @@ class DelayedCSR:
 
     ``stacked`` is a plain :class:`~brainevent_amd.CSR` of shape ``(depth * n_pre, n_post)`` whose row ``d * n_pre + i`` holds the
     entries of row ``i`` with delay ``d`` in their original order; ``perm`` maps a stacked position to the original one;
-    ``row_mask`` (int32 ``[depth, ceil(n_pre / 32)]``) marks the non-empty stacked rows.  Gradients, STDP on delayed synapses, CSC
-    and JIT-connectivity inputs and batched rings are not built."""
+    ``row_mask`` (int32 ``[depth, ceil(n_pre / 32)]``) marks the non-empty stacked rows.  ``update_on_pre`` / ``update_on_post`` are
+    the spike-triggered updates; ``ring @ D`` is differentiable in the weights, with ``stacked.data`` as the leaf
+    (no spike gradient: the ring holds bits).  Dendritic delays, CSC and JIT-connectivity inputs and batched rings are not
+    built."""
 
     def __init__(self, args, *, shape, depth: int, backend: Optional[str] = None):
         if len(args) != 4:
@@ -286,21 +374,102 @@ class DelayedCSR:
         self.stacked.data.copy_(self._stacked_order(new_data).reshape(self.stacked.data.shape))
         return self
 
+    @property
+    def plastic_state(self):
+        """``stacked.plastic_state``: ``None`` unless ``prepare(plastic=(w_min, w_max))`` armed plastic mode."""
+        return self.stacked.plastic_state
+
+    def stacked_to_original(self, t) -> torch.Tensor:
+        """One value per stored entry in the order of ``stacked.data`` (``stacked.data.grad``, say) moved to the ORIGINAL order
+        through ``perm``, in the shape the weights were given in — what :attr:`data` does for the weights."""
+        t = A.to_device(t)
+        if int(t.numel()) != int(self.stacked.data.numel()):
+            raise ValueError(f"DelayedCSR.stacked_to_original: {int(t.numel())} values for {int(self.stacked.data.numel())} "
+                             "stacked weights.")
+        if int(np.prod(self._data_shape)) == 1:
+            return t.reshape(self._data_shape)
+        out = torch.empty_like(t.reshape(-1))
+        out[self._gather] = t.reshape(-1)
+        return out.reshape(self._data_shape)
+
+    # -- plasticity (DESIGN.md 2.16) ------------------------------------------------------------------------------------
+    def _check_plastic(self, vec, vec_name: str) -> None:
+        """What both updates refuse before the first device call: one shared weight, a spike / trace vector of the wrong shape."""
+        from ._plasticity import _HOMO_MSG, _check_vec
+        if int(np.prod(self._data_shape)) == 1 and self.nse > 1:
+            raise ValueError(_HOMO_MSG)
+        _check_vec(vec, self.shape[1], vec_name)
+
+    def _updated(self, st, inplace: bool) -> 'DelayedCSR':
+        if inplace:
+            return self
+        obj = object.__new__(DelayedCSR)
+        obj.__dict__.update(self.__dict__)
+        # over the stacked structure itself, as with_data (CSR.with_data would narrow an int64 indptr into a new array); the
+        # clip certificate and the transposed structure of the update travel along
+        obj.stacked = _stacked_csr(st.data, self.stacked.indices, self.stacked.indptr, self.stacked.shape, self.backend,
+                                   self._numpy_result)
+        obj.stacked.buffers.update(st.buffers)
+        return obj
+
+    def update_on_pre(self, ring: SpikeRing, post_trace, w_min=None, w_max=None, *, inplace: bool = False) -> 'DelayedCSR':
+        """The update at a spike's ARRIVAL: every stored entry ``e`` whose pre neuron fired ``delays[e]`` steps ago (``ring``, as in
+        ``ring @ D``) gets ``w_e += post_trace[col(e)]`` — one rounding to the weight dtype, then ``clip(W, w_min, w_max)`` over
+        the whole array, as ``CSR.update_on_pre``.  ``inplace=False`` returns a new ``DelayedCSR`` sharing ``perm``, ``delays``,
+        ``row_mask`` and the stacked structure; ``inplace=True`` updates ``stacked.data`` and returns ``self``, with the clip
+        certificate and the plastic-mode upkeep of ``CSR.update_on_pre(inplace=True)``."""
+        from ._plasticity import _bounds, container_update
+        if not isinstance(ring, SpikeRing):
+            raise TypeError("DelayedCSR.update_on_pre takes the SpikeRing of the pre population (the spikes by age).")
+        check_ring_matches(ring.n, ring.depth, self.shape, self.depth)
+        self._check_plastic(post_trace, 'post_trace')
+        _bounds(w_min, w_max)
+        ids = ring.ids(ages=self.depth, row_mask=self.row_mask)
+        return self._updated(container_update(self.stacked, True, ids, post_trace, w_min, w_max, inplace), inplace)
+
+    def update_on_post(self, pre_history, post_spike, w_min=None, w_max=None, *, inplace: bool = False) -> 'DelayedCSR':
+        """The update at a POST spike: every stored entry ``e`` of an active post neuron (``post_spike``: any encoding
+        ``CSR.update_on_post`` takes, any non-zero float is a spike) gets ``w_e +=`` the pre-side value of ``row(e)`` at age
+        ``delays[e]`` — what that synapse saw arrive —, then the whole-array clip; ``inplace`` as in :meth:`update_on_pre`.
+
+        ``pre_history`` is a :class:`ValueRing` over the pre population (``n == n_pre``, ``depth >= self.depth``, the weights'
+        dtype: a whole history is never converted per step), read by age inside the update kernel; or a plain ``[self.depth,
+        n_pre]`` array by age (``hist.by_age()[:self.depth]``), which is the stacked matrix's pre-trace as it is."""
+        from ._plasticity import _bounds, container_update
+        if isinstance(pre_history, ValueRing):
+            if pre_history.n != self.shape[0]:
+                raise ValueError(f"DelayedCSR.update_on_post: the history holds {pre_history.n} neurons, the matrix has "
+                                 f"{self.shape[0]} rows.")
+            if pre_history.depth < self.depth:
+                raise ValueError(f"DelayedCSR.update_on_post: the history remembers {pre_history.depth} steps, the matrix needs "
+                                 f"depth {self.depth}.")
+            if pre_history.dtype != self.dtype:
+                raise TypeError(f"DelayedCSR.update_on_post: the history holds {pre_history.dtype}, the weights are {self.dtype}: "
+                                "build the ValueRing in the weights' dtype (push converts one vector per step).")
+            trace, aged = None, (pre_history, self.depth)
+        else:
+            if _shape_of(pre_history) != (self.depth, self.shape[0]):
+                raise ValueError(f"DelayedCSR.update_on_post: a history by age must have shape ({self.depth}, {self.shape[0]}); got "
+                                 f"{_shape_of(pre_history)}.")
+            trace = (pre_history if isinstance(pre_history, torch.Tensor) else np.asarray(pre_history)).reshape(-1)
+            aged = None
+        self._check_plastic(post_spike, 'post_spike')
+        _bounds(w_min, w_max)
+        return self._updated(container_update(self.stacked, False, post_spike, trace, w_min, w_max, inplace, aged=aged), inplace)
+
     # -- product --------------------------------------------------------------------------------------------------------
     def __rmatmul__(self, ring):
         if not isinstance(ring, SpikeRing):
             raise NotImplementedError("x @ DelayedCSR is defined for a SpikeRing (one vector per step); a 2-D or batched "
                                       "history is not built.")
         check_ring_matches(ring.n, ring.depth, self.shape, self.depth)
-        if torch.is_grad_enabled() and self.stacked.data.requires_grad:
-            raise NotImplementedError("gradients through the delayed product are not built: detach the weights.")
         from ._csr import _csr_p_call, binary_csrmv_p
         ids = ring.ids(ages=self.depth, row_mask=self.row_mask)
         st = self.stacked
         rows = st._stored_rows()
         r = _csr_p_call(binary_csrmv_p, st.data, rows.indices, rows.indptr, ids, st._scatter_workspace(), (rows.m, rows.k), True,
                         self.backend)[0]
-        return A.to_result(r, self._numpy_result and ring._numpy)
+        return A.to_result(r, self._numpy_result and ring._numpy and not r.requires_grad)
 
     def __matmul__(self, other):
         raise NotImplementedError("DelayedCSR @ x is not defined: the delays live on the presynaptic side (ring @ D).")

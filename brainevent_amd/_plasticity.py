@@ -10,8 +10,9 @@ Rule (the reference's order of operations):
 A spike is any nonzero value.  The trace is cast to the weight dtype first; f16 / bf16 add in f32 and round once.
 
 The hot path is ``csrc/be_plasticity.hip``: ``be_plasticity_rows`` (row-driven, or through a slot -> weight permutation for the
-unfavourable direction) and ``be_plasticity_dense``.  The functional API copies the weights, runs the kernel unclipped and clamps
-the whole copy.  The methods also take ``inplace=True``: the container's own ``data`` is updated and, once the container has
+unfavourable direction), ``be_plasticity_rows_aged`` (the permuted walk with the trace read by age from a ring of values: the
+post-spike update of delayed synapses, ``DelayedCSR.update_on_post``) and ``be_plasticity_dense``.  The functional API copies
+the weights, runs the kernel unclipped and clamps the whole copy.  The methods also take ``inplace=True``: the container's own ``data`` is updated and, once the container has
 established that every weight lies in ``[w_min, w_max]`` (a *clip certificate* kept in ``buffers``), the kernel clips the
 touched entries only, which gives the same result without a pass over the whole array.
 
@@ -138,6 +139,19 @@ def _run_rows(w: torch.Tensor, col, indptr, row_len: int, perm, spikes, n_rows: 
     check(f(A.ptr(w), A.wcode(w), A.ptr(col), A.ptr(indptr), int(indptr is not None and indptr.dtype == torch.int64),
             int(row_len), int(col.numel()), A.ptr(perm), int(perm is not None and perm.dtype == torch.int64), A.ptr(sp), sd,
             int(n_rows), A.ptr(tr), lo_on, lo, hi_on, hi, A.ptr(ws), ws.numel(), A.stream_ptr()), 'be_plasticity_rows')
+
+
+def _run_rows_aged(w: torch.Tensor, t_rows, t_indptr, perm, spikes, n_post: int, hist, ages: int, clip=(None, None)) -> None:
+    """``be_plasticity_rows_aged`` on ``w`` in place: the permuted walk over the transposed structure of a matrix stacked by
+    delay, the trace read by age from ``hist`` (a :class:`~brainevent_amd.ValueRing` of ``w``'s dtype over the pre neurons)."""
+    sp, sd = _spikes(spikes)
+    ws = _workspace(n_post)
+    f = fn('be_plasticity_rows_aged')
+    lo_on, lo, hi_on, hi = _clip_args(w, *clip)
+    check(f(A.ptr(w), A.wcode(w), A.ptr(t_rows), A.ptr(t_indptr), int(t_indptr.dtype == torch.int64), int(t_rows.numel()),
+            A.ptr(perm), int(perm.dtype == torch.int64), A.ptr(sp), sd, int(n_post), A.ptr(hist.values), A.ptr(hist.head),
+            int(hist.n), int(hist.depth), int(ages), lo_on, lo, hi_on, hi, A.ptr(ws), ws.numel(), A.stream_ptr()),
+          'be_plasticity_rows_aged')
 
 
 def _run_dense(w: torch.Tensor, pre: bool, spikes, trace, clip=(None, None)) -> None:
@@ -568,8 +582,10 @@ def _plan_patch_entries(plan, w, index, sp, sd) -> None:
             ws.numel(), A.stream_ptr()), 'be_scatter_plan_patch_entries')
 
 
-def container_update(M, pre: bool, spikes, trace, w_min, w_max, inplace: bool):
-    """Shared body of the ``update_on_pre`` / ``update_on_post`` methods."""
+def container_update(M, pre: bool, spikes, trace, w_min, w_max, inplace: bool, aged=None):
+    """Shared body of the ``update_on_pre`` / ``update_on_post`` methods.  ``aged=(hist, ages)`` (``DelayedCSR.update_on_post`` on
+    its stacked matrix, in place of ``trace``): the trace of stacked row ``d * n + i`` is ``hist``'s value of neuron ``i`` at age
+    ``d`` — the same walk, certificate and plan upkeep, with ``be_plasticity_rows_aged`` as the update kernel."""
     from ._dense import Dense
     n_pre, n_post = int(M.shape[0]), int(M.shape[1])
     n_spk, n_tr = (n_pre, n_post) if pre else (n_post, n_pre)
@@ -580,7 +596,10 @@ def container_update(M, pre: bool, spikes, trace, w_min, w_max, inplace: bool):
     if M.data.numel() == 1 and n_syn > 1:
         raise ValueError(_HOMO_MSG)
     _check_vec(spikes, n_spk, 'pre_spike' if pre else 'post_spike')
-    _check_vec(trace, n_tr, 'post_trace' if pre else 'pre_trace')
+    if aged is None:
+        _check_vec(trace, n_tr, 'post_trace' if pre else 'pre_trace')
+    else:
+        assert not pre and trace is None and not isinstance(M, Dense) and not M._scatter_side(pre)
     lo, hi = _bounds(w_min, w_max)
 
     # which kernel: row-driven over the stored rows (the spikes are on the scatter side: pre spikes are the left operand of
@@ -594,7 +613,10 @@ def container_update(M, pre: bool, spikes, trace, w_min, w_max, inplace: bool):
             _run_rows(w.reshape(-1), rows.indices.reshape(-1), rows.indptr, rows.row_len, None, spikes, n_spk, trace, clip)
         else:
             t_ptr, t_rows, perm = plasticity_index(M)
-            _run_rows(w.reshape(-1), t_rows, t_ptr, -1, perm, spikes, n_spk, trace, clip)
+            if aged is not None:
+                _run_rows_aged(w.reshape(-1), t_rows, t_ptr, perm, spikes, n_spk, aged[0], aged[1], clip)
+            else:
+                _run_rows(w.reshape(-1), t_rows, t_ptr, -1, perm, spikes, n_spk, trace, clip)
 
     if inplace:
         # plastic mode (prepare(plastic=...)): the cached scatter workspace is kept current by launches of its own after the

@@ -1,5 +1,6 @@
 // be_delay.hip — synaptic delays on the presynaptic side: the device-side split of a matrix's stored rows by
-// delay, the bit-packed spike-history ring, and the compaction of the ring into the active-row list of the *stacked* matrix.
+// delay, the bit-packed spike-history ring, and the compaction of the ring into the active-row list of the *stacked* matrix; and
+// the push of the value-history ring that the plasticity of delayed synapses reads by age (be_plasticity.hip).
 //
 // Stored row d * m + i of the stacked matrix holds the entries of row i whose delay is d; a delayed step is then one ordinary
 // scatter over the stacked rows {d * m + i : neuron i fired d steps ago} — a BE_SPIKE_IDS operand of the scatter entry points
@@ -7,7 +8,7 @@
 //
 // No float atomics here; the integer ones are the error word of the count pass, one reservation per workgroup in the
 // compaction (as k_compact_bits, be_csr.hip) and one arrival ticket per workgroup in the push.
-#include "be_common.h"
+#include "be_pbits.h"
 
 namespace {
 
@@ -196,6 +197,74 @@ __global__ void __launch_bounds__(kRingThreads) k_ring_compact(const uint32_t* _
   }
 }
 
+// =================================================================================================
+// value-history ring: values[depth][n] in one of the four float dtypes, head[1]
+// =================================================================================================
+// one workgroup converts and copies kValueTile elements of the pushed vector; a lane moves 16 bytes of the ring's dtype at a time
+constexpr int kValueThreads = 256, kValuePer = 16;
+constexpr int kValueTile = kValueThreads * kValuePer;
+
+template <typename T, int E>
+struct alignas(sizeof(T) * E < 16 ? sizeof(T) * E : 16) ValuePack {
+  T v[E];
+};
+
+// S -> D as torch's .to(): through the accumulation type of the narrower side (f64 -> f16 / bf16 rounds through f32); the same
+// dtype is a copy of the bits
+template <typename S, typename D>
+__device__ __forceinline__ typename PB<D>::bits value_convert(typename PB<S>::bits b) {
+  if constexpr (std::is_same<S, D>::value) return b;
+  else return PB<D>::put((typename PB<D>::acc)PB<S>::get(b));
+}
+
+// Writes x[n], converted to the ring's dtype, into slot `head`, then advances head: k_ring_push's protocol (every workgroup
+// reads head before it takes its ticket; the last ticket writes head and re-arms the ticket word).  A lane takes E = 16 bytes'
+// worth of ring elements per step; where the slot and x are 16-byte aligned — the slot's address depends on head, so this is
+// decided here — full groups of E move as one vector load (or 16-byte pieces of it) and one 16-byte store, the rest one by one.
+template <typename S, typename D>
+__global__ void __launch_bounds__(kValueThreads) k_value_ring_push(const typename PB<S>::bits* __restrict__ x, int64_t n, int depth,
+                                                                   typename PB<D>::bits* __restrict__ values, int32_t* head,
+                                                                   uint32_t* arrivals) {
+  using SB = typename PB<S>::bits;
+  using DB = typename PB<D>::bits;
+  constexpr int E = 16 / (int)sizeof(DB);
+  static_assert(kValuePer % E == 0, "a lane's share of the tile is a whole number of 16-byte groups");
+  __shared__ int h_sh;
+  if (threadIdx.x == 0) h_sh = ring_head(head, depth);
+  __syncthreads();
+  const int h = h_sh;
+  DB* __restrict__ row = values + (int64_t)h * n;
+  const int64_t tile = (int64_t)blockIdx.x * kValueTile;
+  const int64_t tile_end = tile + kValueTile < n ? tile + kValueTile : n;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(row) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
+  for (int64_t i = tile + (int64_t)threadIdx.x * E; i < tile_end; i += (int64_t)kValueThreads * E) {
+    if (aligned && i + E <= tile_end) {
+      const ValuePack<SB, E> in = *reinterpret_cast<const ValuePack<SB, E>*>(x + i);
+      ValuePack<DB, E> out;
+#pragma unroll
+      for (int u = 0; u < E; ++u) out.v[u] = value_convert<S, D>(in.v[u]);
+      *reinterpret_cast<ValuePack<DB, E>*>(row + i) = out;
+    } else {
+      for (int u = 0; u < E && i + u < tile_end; ++u) row[i + u] = value_convert<S, D>(x[i + u]);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t t = atomicAdd(arrivals, 1u);
+    if (t == gridDim.x - 1) {
+      *arrivals = 0u;
+      *head = (h + 1 == depth) ? 0 : h + 1;
+    }
+  }
+}
+
+template <typename S, typename D>
+void launch_value_push(const void* x, int64_t n, int depth, void* values, int32_t* head, uint32_t* arrivals, hipStream_t st) {
+  hipLaunchKernelGGL((k_value_ring_push<S, D>), dim3((unsigned)((n + kValueTile - 1) / kValueTile)), dim3(kValueThreads), 0, st,
+                     static_cast<const typename PB<S>::bits*>(x), n, depth, static_cast<typename PB<D>::bits*>(values), head,
+                     arrivals);
+}
+
 int ceil_log2(int depth) {
   int nbits = 0;
   while ((1 << nbits) < depth) ++nbits;
@@ -288,6 +357,22 @@ extern "C" int be_spike_ring_push(const void* spikes, int spike_dtype, int64_t n
     hipLaunchKernelGGL(k_ring_push<SpikeWords>, grid, block, 0, st, static_cast<const uint32_t*>(spikes), n, depth, bits, head, arrivals);
   else
     BE_REQUIRE(false, BE_ERR_UNSUPPORTED, "spike dtype must be BE_SPIKE_BOOL, BE_SPIKE_FLOAT or BE_SPIKE_BITS");
+  BE_LAUNCH_CHECK();
+  return BE_OK;
+}
+
+extern "C" int be_value_ring_push(const void* x, int x_dtype, int64_t n, int depth, void* values, int wdtype, int32_t* head,
+                                  uint32_t* arrivals, be_stream_t stream) {
+  BE_REQUIRE(n >= 1 && depth >= 1 && (int64_t)depth * n < (1ll << 31), BE_ERR_INVALID, "need n >= 1, depth >= 1, depth * n < 2^31");
+  BE_REQUIRE(x && values && head && arrivals, BE_ERR_INVALID, "null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rc = be_dispatch_wdtype(x_dtype, [&](auto s) {
+    return be_dispatch_wdtype(wdtype, [&](auto d) {
+      launch_value_push<typename decltype(s)::type, typename decltype(d)::type>(x, n, depth, values, head, arrivals, st);
+      return (int)BE_OK;
+    });
+  });
+  if (rc != BE_OK) return rc;
   BE_LAUNCH_CHECK();
   return BE_OK;
 }

@@ -14,6 +14,9 @@
 // kTile entries (a thread binary-searches the row of its first entry, then walks forward).  Each entry is read and written
 // by exactly one lane: no atomics (a duplicated column is two entries, each updated once).  The index and weight streams
 // are read once (non-temporal); the trace vector is gathered through the caches.
+//
+// Delayed synapses: be_plasticity_rows_aged is the same permuted walk over the transposed structure of a matrix
+// stacked by delay, with the trace looked up by age in a ring of per-neuron values (the TraceAged policy of k_plast_rows).
 #include "be_csr_shared.h"
 #include "be_pbits.h"
 
@@ -104,15 +107,53 @@ __global__ void __launch_bounds__(kScanThreads) k_plast_offsets(RowPtr rp, const
 // trace[col[k]] (random read-modify-write, one per slot, each weight owned by one slot).
 constexpr int kRowThreads = 256, kRowPer = 8, kTile = kRowThreads * kRowPer;
 
-template <typename W, typename PT, bool PERM, bool CLIP>
+// What an entry adds, given its secondary id j = col[e]: the trace lookup of k_plast_rows, a policy of two kinds.
+// Plain: trace[j].
+template <typename B>
+struct TracePlain {
+  const B* __restrict__ trace;
+  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ B at(int32_t j) const { return trace[j]; }
+};
+
+// Aged (delayed synapses): j is a row id d * n + i of a matrix stacked by delay (be_delay.hip) and the value is
+// the one neuron i had d pushes ago in a ring of per-neuron values, values[depth][n] with age a in slot (head - 1 - a) mod depth.
+// head is read once per workgroup (thread 0, broadcast through LDS).  d < depth is the caller's contract (be_plasticity_rows_aged
+// checks ages <= depth), so one conditional add is the whole modulo.  The division is a 32-bit unsigned one: j < 2^31.
+template <typename B>
+struct TraceAged {
+  const B* __restrict__ values;
+  const int32_t* __restrict__ head;
+  uint32_t n;
+  int depth;
+  int h;
+  __device__ __forceinline__ void begin() {
+    __shared__ int h_sh;
+    if (threadIdx.x == 0) {
+      const int v = *head;
+      h_sh = ((unsigned)v < (unsigned)depth) ? v : 0;
+    }
+    __syncthreads();
+    h = h_sh;
+  }
+  __device__ __forceinline__ B at(int32_t j) const {
+    const uint32_t d = (uint32_t)j / n;
+    const uint32_t i = (uint32_t)j - d * n;
+    int slot = h - 1 - (int)(d < (uint32_t)depth ? d : (uint32_t)depth - 1u);   // (the clamp only keeps a broken id in bounds)
+    if (slot < 0) slot += depth;
+    return values[(int64_t)slot * n + i];
+  }
+};
+
+template <typename W, typename PT, bool PERM, bool CLIP, typename TR>
 __global__ void __launch_bounds__(kRowThreads) k_plast_rows(typename PB<W>::bits* __restrict__ w,
                                                             const int32_t* __restrict__ col, RowPtr rp,
-                                                            const PT* __restrict__ perm,
-                                                            const typename PB<W>::bits* __restrict__ trace,
+                                                            const PT* __restrict__ perm, TR tr,
                                                             const uint32_t* __restrict__ active,
                                                             const uint32_t* __restrict__ n_active_p,
                                                             const int64_t* __restrict__ offs, ClipArgs c) {
   using B = typename PB<W>::bits;
+  tr.begin();
   const int64_t n_active = *n_active_p;
   const int64_t total = offs[n_active];
   for (int64_t tile = (int64_t)blockIdx.x * kTile; tile < total; tile += (int64_t)gridDim.x * kTile) {
@@ -137,7 +178,7 @@ __global__ void __launch_bounds__(kRowThreads) k_plast_rows(typename PB<W>::bits
       }
       const int64_t e = row_start + p;
       const int32_t j = __builtin_nontemporal_load(col + e);
-      const B t = trace[j];
+      const B t = tr.at(j);
       if (PERM) {
         const int64_t we = (int64_t)__builtin_nontemporal_load(perm + e);
         w[we] = plast_add<W, CLIP>(w[we], t, c);
@@ -230,30 +271,70 @@ int plast_active(const void* spikes, int sd, int64_t n, const PlastWs& ws, hipSt
   return be_resolve_active(spikes, sd, n, 1, ws.active, active_stride_of(n), ws.count, st, true, al);
 }
 
-template <typename W, typename PT, bool PERM>
-void launch_rows(void* weights, const int32_t* col, RowPtr rp, const void* perm, const void* trace, const ActiveList& al,
+template <typename W, typename PT, bool PERM, typename TR>
+void launch_rows(void* weights, const int32_t* col, RowPtr rp, const void* perm, TR tr, const ActiveList& al,
                  const int64_t* offs, ClipArgs c, int grid, hipStream_t st) {
   using B = typename PB<W>::bits;
   if (c.lo_on || c.hi_on)
-    hipLaunchKernelGGL((k_plast_rows<W, PT, PERM, true>), dim3(grid), dim3(kRowThreads), 0, st, static_cast<B*>(weights), col,
-                       rp, static_cast<const PT*>(perm), static_cast<const B*>(trace), al.ids, al.count, offs, c);
+    hipLaunchKernelGGL((k_plast_rows<W, PT, PERM, true, TR>), dim3(grid), dim3(kRowThreads), 0, st, static_cast<B*>(weights), col,
+                       rp, static_cast<const PT*>(perm), tr, al.ids, al.count, offs, c);
   else
-    hipLaunchKernelGGL((k_plast_rows<W, PT, PERM, false>), dim3(grid), dim3(kRowThreads), 0, st, static_cast<B*>(weights), col,
-                       rp, static_cast<const PT*>(perm), static_cast<const B*>(trace), al.ids, al.count, offs, c);
+    hipLaunchKernelGGL((k_plast_rows<W, PT, PERM, false, TR>), dim3(grid), dim3(kRowThreads), 0, st, static_cast<B*>(weights), col,
+                       rp, static_cast<const PT*>(perm), tr, al.ids, al.count, offs, c);
 }
 
-template <typename W>
-int plast_rows_t(void* weights, const int32_t* col, RowPtr rp, const void* perm, int perm64, const void* trace,
+// the trace operand as the host hands it in: make<W>() is the kernel's lookup policy; `permuted_only` leaves the row-driven
+// instantiations of a policy that has no row-driven caller out of the library
+struct PlainOperand {
+  static constexpr bool permuted_only = false;
+  const void* trace;
+  template <typename W> TracePlain<typename PB<W>::bits> make() const {
+    return {static_cast<const typename PB<W>::bits*>(trace)};
+  }
+};
+
+struct AgedOperand {
+  static constexpr bool permuted_only = true;
+  const void* values;
+  const int32_t* head;
+  uint32_t n;
+  int depth;
+  template <typename W> TraceAged<typename PB<W>::bits> make() const {
+    return {static_cast<const typename PB<W>::bits*>(values), head, n, depth, 0};
+  }
+};
+
+template <typename W, typename OP>
+int plast_rows_t(void* weights, const int32_t* col, RowPtr rp, const void* perm, int perm64, const OP& operand,
                  const ActiveList& al, const int64_t* offs, ClipArgs c, int64_t nnz_hint, hipStream_t st) {
   // enough tiles to fill the chip at the largest update, never more workgroups than tiles of the whole structure
   const int grid = grid_for(nnz_hint, kTile, 4096);
+  const auto tr = operand.template make<W>();
   const int prof = be_prof_begin(st);
-  if (perm == nullptr) launch_rows<W, int32_t, false>(weights, col, rp, nullptr, trace, al, offs, c, grid, st);
-  else if (perm64) launch_rows<W, int64_t, true>(weights, col, rp, perm, trace, al, offs, c, grid, st);
-  else launch_rows<W, int32_t, true>(weights, col, rp, perm, trace, al, offs, c, grid, st);
+  if (perm == nullptr) {
+    if constexpr (!OP::permuted_only) launch_rows<W, int32_t, false>(weights, col, rp, nullptr, tr, al, offs, c, grid, st);
+  } else if (perm64) launch_rows<W, int64_t, true>(weights, col, rp, perm, tr, al, offs, c, grid, st);
+  else launch_rows<W, int32_t, true>(weights, col, rp, perm, tr, al, offs, c, grid, st);
   be_prof_end(prof, st);
   BE_LAUNCH_CHECK();
   return BE_OK;
+}
+
+// the shared body of be_plasticity_rows and be_plasticity_rows_aged: compaction of the spikes, offsets scan, update
+template <typename OP>
+int plast_rows_run(void* weights, int wdtype, const int32_t* indices, RowPtr rp, int64_t nnz, const void* perm, int perm64,
+                   const void* spikes, int spike_dtype, int64_t n_rows, const OP& operand, ClipArgs c, void* workspace,
+                   hipStream_t st) {
+  const PlastWs ws = plast_ws(workspace, n_rows);
+  ActiveList al;
+  int rc = plast_active(spikes, spike_dtype, n_rows, ws, st, &al);
+  if (rc != BE_OK) return rc;
+  hipLaunchKernelGGL(k_plast_offsets, dim3(1), dim3(kScanThreads), 0, st, rp, al.ids, al.count, ws.offs);
+  BE_LAUNCH_CHECK();
+  return be_dispatch_wdtype(wdtype, [&](auto w) {
+    using W = typename decltype(w)::type;
+    return plast_rows_t<W>(weights, indices, rp, perm, perm64, operand, al, ws.offs, c, nnz, st);
+  });
 }
 
 template <typename W>
@@ -318,19 +399,25 @@ int be_plasticity_rows(void* weights, int wdtype, const int32_t* indices, const 
   BE_REQUIRE(workspace_bytes >= plast_ws_bytes(n_rows) && workspace != nullptr, BE_ERR_WORKSPACE, "workspace too small");
   if (n_rows == 0 || nnz == 0) return BE_OK;
   BE_REQUIRE(weights && indices && trace && spikes, BE_ERR_INVALID, "null pointer");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const PlastWs ws = plast_ws(workspace, n_rows);
-  ActiveList al;
-  int rc = plast_active(spikes, spike_dtype, n_rows, ws, st, &al);
-  if (rc != BE_OK) return rc;
-  const RowPtr rp{indptr, indptr_is_i64, row_len};
-  hipLaunchKernelGGL(k_plast_offsets, dim3(1), dim3(kScanThreads), 0, st, rp, al.ids, al.count, ws.offs);
-  BE_LAUNCH_CHECK();
-  const ClipArgs c{clip_lo, clip_hi, w_lo, w_hi};
-  return be_dispatch_wdtype(wdtype, [&](auto w) {
-    using W = typename decltype(w)::type;
-    return plast_rows_t<W>(weights, indices, rp, perm, perm_is_i64, trace, al, ws.offs, c, nnz, st);
-  });
+  return plast_rows_run(weights, wdtype, indices, RowPtr{indptr, indptr_is_i64, row_len}, nnz, perm, perm_is_i64, spikes,
+                        spike_dtype, n_rows, PlainOperand{trace}, ClipArgs{clip_lo, clip_hi, w_lo, w_hi}, workspace,
+                        static_cast<hipStream_t>(stream));
+}
+
+int be_plasticity_rows_aged(void* weights, int wdtype, const int32_t* t_rows, const void* t_indptr, int indptr_is_i64,
+                            int64_t nnz, const void* perm, int perm_is_i64, const void* spikes, int spike_dtype,
+                            int64_t n_post, const void* values, const int32_t* head, int64_t n_pre, int ring_depth, int ages,
+                            int clip_lo, double w_lo, int clip_hi, double w_hi, void* workspace, int64_t workspace_bytes,
+                            be_stream_t stream) {
+  BE_REQUIRE(n_post >= 0 && n_post <= 0xffffffffll && nnz >= 0, BE_ERR_INVALID, "n_post / nnz out of range");
+  BE_REQUIRE(n_pre >= 1 && ages >= 1 && ages <= ring_depth && (int64_t)ring_depth * n_pre < (1ll << 31), BE_ERR_INVALID,
+             "need n_pre >= 1, 1 <= ages <= ring_depth, ring_depth * n_pre < 2^31");
+  BE_REQUIRE(workspace_bytes >= plast_ws_bytes(n_post) && workspace != nullptr, BE_ERR_WORKSPACE, "workspace too small");
+  if (n_post == 0 || nnz == 0) return BE_OK;
+  BE_REQUIRE(weights && t_rows && t_indptr && perm && values && head && spikes, BE_ERR_INVALID, "null pointer");
+  return plast_rows_run(weights, wdtype, t_rows, RowPtr{t_indptr, indptr_is_i64, -1}, nnz, perm, perm_is_i64, spikes,
+                        spike_dtype, n_post, AgedOperand{values, head, (uint32_t)n_pre, ring_depth},
+                        ClipArgs{clip_lo, clip_hi, w_lo, w_hi}, workspace, static_cast<hipStream_t>(stream));
 }
 
 int be_plasticity_dense(int pre, void* weights, int wdtype, int64_t n_rows, int64_t n_cols, const void* spikes,

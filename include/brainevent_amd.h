@@ -840,6 +840,18 @@ int be_plasticity_rows(void* weights, int wdtype, const int32_t* indices, const 
                        int64_t row_len, int64_t nnz, const void* perm, int perm_is_i64, const void* spikes, int spike_dtype,
                        int64_t n_rows, const void* trace, int clip_lo, double w_lo, int clip_hi, double w_hi,
                        void* workspace, int64_t workspace_bytes, be_stream_t stream);
+/* The permuted walk with an AGED trace: the post-spike update of delayed synapses (brainevent_amd/_delay.py).
+ * t_indptr [n_post + 1] / t_rows / perm are the transposed structure of a matrix STACKED by delay (stacked row d * n_pre + i =
+ * the entries of row i with delay d, d < ages); values[ring_depth][n_pre] (the weight dtype) and head[1] are a value ring
+ * (be_value_ring_push): for slot k of every active post neuron, with r = t_rows[k], d = r / n_pre, i = r - d * n_pre,
+ *   w[perm[k]] = w[perm[k]] + values[((*head - 1 - d) mod ring_depth) * n_pre + i]
+ * with the rounding, the clip, the spike encodings and the workspace of be_plasticity_rows (n_rows = n_post).  perm is required;
+ * ages <= ring_depth, ring_depth * n_pre < 2^31.  *head is read on the device: graph-capturable. */
+int be_plasticity_rows_aged(void* weights, int wdtype, const int32_t* t_rows, const void* t_indptr, int indptr_is_i64,
+                            int64_t nnz, const void* perm, int perm_is_i64, const void* spikes, int spike_dtype,
+                            int64_t n_post, const void* values, const int32_t* head, int64_t n_pre, int ring_depth, int ages,
+                            int clip_lo, double w_lo, int clip_hi, double w_hi, void* workspace, int64_t workspace_bytes,
+                            be_stream_t stream);
 /* Dense row-major weights [n_rows, n_cols].  pre = 1: spikes [n_rows], trace [n_cols], active row i gets += trace.
  * pre = 0: spikes [n_cols], trace [n_rows], w[i, j] += trace[i] for each active column j.  Workspace: n = n_rows (pre)
  * or n_cols (post). */
@@ -993,6 +1005,11 @@ int be_solve_iterate(const void* weights, int wdtype, const int32_t* indices, co
  *     once; *count = how many.  *count is zeroed on the stream by the call itself.  {active_ids, count} is a be_spike_ids_t over
  *     ages * n positions: the BE_SPIKE_IDS operand of the scatter entry points for the stacked matrix.
  * Both are graph-capturable: head is read on the device.
+ *
+ * Value ring: values[depth][n] in one of the four float dtypes (wdtype), head[1] and arrivals[1] as above, zero to begin with.
+ *   be_value_ring_push: writes x[n] (x_dtype: any of the four; converted as a cast does, f64 -> f16 / bf16 through f32) into slot
+ *     *head, then *head = (*head + 1) % depth — one launch, no host read, arrivals as above.  The vector of age a lies in slot
+ *     (*head - 1 - a) mod depth: what be_plasticity_rows_aged reads.
  * ---------------------------------------------------------------------------------------------- */
 int64_t be_delay_split_workspace_bytes(int64_t m, int depth);
 int be_delay_split_count(const void* indptr, int indptr_is_i64, int64_t row_len, const int32_t* delays, int64_t m, int depth,
@@ -1004,6 +1021,8 @@ int be_spike_ring_push(const void* spikes, int spike_dtype, int64_t n, int depth
                        uint32_t* arrivals, be_stream_t stream);
 int be_spike_ring_compact(const uint32_t* bits, const int32_t* head, int64_t n, int depth, int ages, const uint32_t* row_mask,
                           uint32_t* active_ids, uint32_t* count, be_stream_t stream);
+int be_value_ring_push(const void* x, int x_dtype, int64_t n, int depth, void* values, int wdtype, int32_t* head,
+                       uint32_t* arrivals, be_stream_t stream);
 
 #define BE_FOR_ALL_VARIANTS(X) \
   X(f32, BE_F32, bool, BE_SPIKE_BOOL)   X(f32, BE_F32, float, BE_SPIKE_FLOAT)   \
