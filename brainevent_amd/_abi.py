@@ -72,6 +72,7 @@ _SIGNATURES = dict(
     be_solve_diagonal='i:ilppplp', be_solve_iterate='i:pippillpidplp',
     be_delay_split_workspace_bytes='l:li', be_delay_split_count='i:pilplipiplp', be_delay_split_fill='i:pilpplipipppp',
     be_spike_ring_push='i:pilipppp', be_spike_ring_compact='i:ppliipppp', be_value_ring_push='i:pilipippp',
+    be_spike_ring_push_batch='i:pililpppp', be_spike_ring_unroll='i:pplilippp',
 )
 
 # be_binary_jit{s,u,n}{mv,mm}_{notrans,trans}_{w}: BE_FOR_JIT_VARIANTS over BE_DECL_JIT_VARIANT (BE_JIT_MV_ARGS / BE_JIT_MM_ARGS)

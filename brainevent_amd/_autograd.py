@@ -91,6 +91,14 @@ def activity(operand, layout: str):
     return mask, nb
 
 
+def packed_activity(words: torch.Tensor, n: int, nb: int) -> torch.Tensor:
+    """The per-neuron mask of a bit-packed batch ``words [nb, ceil(n / 32)]`` (``BE_SPIKE_BITS`` rows over ``n`` positions): what
+    :func:`activity` builds, for an operand that exists only as packed rows (the unrolled batched ring, ``_delay``)."""
+    mask = torch.empty(max(fn('be_grad_mask_bytes')(int(n), int(nb)), 4) // 4, dtype=torch.int32, device=A.device())
+    call('be_grad_pack_activity', A.ptr(words), A.BE_SPIKE_BITS, int(n), int(nb), A.ptr(mask), A.stream_ptr())
+    return mask
+
+
 def rows_weight_grad(w_meta, indices, indptr, row_len: int, n_rows: int, transpose: bool, mask, nb: int, g_nm) -> torch.Tensor:
     """``be_grad_rows``: the gradient of the weights (``w_meta``: a tensor or ``(shape, dtype)``; one value per stored entry, or
     the scalar of a shared weight).  ``g_nm``: the output gradient neuron-major ``[out_len, nb]``."""

@@ -13,7 +13,11 @@ the same id list; ``D.update_on_post(hist, post_spike)`` reads the pre-side valu
 gradient to the order the synapses were given in).  The delays are axonal: they sit between the pre neuron and the synapse.
 
 Everything that can be refused is refused before the first device call (shapes, dtypes, the ``depth`` range), so the validation
-runs without a GPU."""
+runs without a GPU.
+
+Batched rings: ``SpikeRing(n, depth, batch=B)`` holds ``B`` histories under one ``head``; ``ring @ D`` then
+unrolls them by age into the bit-packed batch ``[B, depth * n_pre]`` (``be_spike_ring_unroll``) that the stacked matrix
+multiplies through its own scatter route, and comes back ``[B, n_post]``."""
 from typing import Optional
 
 import numpy as np
@@ -29,6 +33,9 @@ __all__ = ['SpikeRing', 'ValueRing', 'DelayedCSR', 'MAX_DELAY_DEPTH', 'check_rin
 MAX_DELAY_DEPTH = 256
 #: largest number of ages one compaction covers (its grid's second dimension)
 MAX_RING_AGES = 65535
+#: largest ``batch`` of a :class:`SpikeRing` (the batch row is the second grid dimension of the push and of the unroll; it is
+#: also the largest batch of every batched product of the library)
+MAX_RING_BATCH = 65535
 _ID_LIMIT = 1 << 31
 
 
@@ -55,29 +62,46 @@ class SpikeRing:
     ``bits`` is int32 ``[depth, ceil(n / 32)]`` (the ``BitPackedBinary`` layout per slot), ``head`` a device int32 ``[1]``.
     :meth:`push` writes the spikes of the current step into slot ``head`` and advances ``head`` on the device, so a captured step
     (``capture_step(fn, repeat=r)``) stays correct when replayed; the spikes of *age* ``a`` (0: just pushed) lie in slot
-    ``(head - 1 - a) mod depth``.  History before the first push is silent.  One vector per step (no batch)."""
+    ``(head - 1 - a) mod depth``.  History before the first push is silent.
 
-    def __init__(self, n: int, depth: int, device=None):
+    ``batch=None`` (the default): one vector per step.  ``batch=B`` (``1 <= B <= 65535``): ``B`` histories under the one
+    ``head`` — ``bits`` is ``[depth, B, ceil(n / 32)]``, :meth:`push` takes ``[B, n]`` (batch-major, the layout ``ring @ D``
+    answers in: ``[B, n_post]``), ``shape`` is ``(B, n)``; :meth:`stacked_bits` lays the histories out by age as the bit-packed
+    batch the stacked matrix of a :class:`DelayedCSR` multiplies."""
+
+    #: ``None``: one vector per step; ``B``: a batched ring
+    batch: Optional[int] = None
+
+    def __init__(self, n: int, depth: int, device=None, *, batch: Optional[int] = None):
         n, depth = int(n), int(depth)
         _check_ring_size(n, depth)
-        self.n, self.depth = n, depth
+        if batch is not None:
+            batch = int(batch)
+            if not 1 <= batch <= MAX_RING_BATCH:
+                raise ValueError(f"SpikeRing: batch must lie in [1, {MAX_RING_BATCH}]; got {batch}.")
+        self.n, self.depth, self.batch = n, depth, batch
         dev = torch.device(device) if device is not None else A.device()
         self._words = (n + 31) // 32
-        self.bits = torch.zeros((depth, self._words), dtype=torch.int32, device=dev)
+        self.bits = torch.zeros((depth, self._words) if batch is None else (depth, batch, self._words), dtype=torch.int32,
+                                device=dev)
         self._state = torch.zeros(2, dtype=torch.int32, device=dev)       # head, and the push kernel's arrival ticket
         self.head = self._state[:1]
         self._ids = None        # the id buffer (depth * n), its counter and the operands over it: built by the first ids()
         self._count = None
         self._operands = {}
+        self._stacked = {}      # ages -> the unrolled words [B, ceil(ages * n / 32)]: built by the first stacked_bits(ages)
         self._numpy = True      # numpy in -> numpy out: False once a device tensor was pushed
 
     # -- writing --------------------------------------------------------------------------------------------------------
     def push(self, spikes) -> 'SpikeRing':
         """Store the spikes of the current step.  A tensor or numpy array of ``n`` elements (bool / integer: active when ``!= 0``;
         float: active when ``> 0``), a ``BinaryArray``, or a ``BitPackedBinary`` / ``CompactBinary`` (their packed words are
-        copied, the bits past ``n`` cleared).  One launch, no host read."""
+        copied, the bits past ``n`` cleared).  A batched ring takes ``[B, n]`` — a tensor or numpy array, or a ``BinaryArray``
+        of one; packed words go through :meth:`push_packed`.  One launch, no host read."""
         if isinstance(spikes, SpikeRing):
             raise TypeError("SpikeRing.push takes one spike vector.")
+        if self.batch is not None:
+            return self._push_batch(spikes)
         if isinstance(spikes, (BitPackedBinary, CompactBinary)):
             p = spikes._packed_operand()
             v = p if p is not None else spikes.value
@@ -89,7 +113,8 @@ class SpikeRing:
             raise TypeError("SpikeRing.push takes spikes by position, not an id list.")
         shape = tuple(v.shape) if hasattr(v, 'shape') else np.shape(v)
         if len(shape) != 1:
-            raise NotImplementedError(f"SpikeRing.push takes one 1-D spike vector; got shape {shape} (batched rings are not built).")
+            raise NotImplementedError(f"SpikeRing.push takes one 1-D spike vector; got shape {shape} (a ring of B histories is "
+                                      "SpikeRing(n, depth, batch=B)).")
         if shape[0] != self.n:
             raise ValueError(f"SpikeRing.push: {shape[0]} spikes for a ring of {self.n} neurons.")
         if not A.wants_numpy(v):
@@ -99,6 +124,52 @@ class SpikeRing:
              A.ptr(self._state[1:]), A.stream_ptr())
         return self
 
+    def _push_batch(self, spikes) -> 'SpikeRing':
+        if isinstance(spikes, (BitPackedBinary, CompactBinary)):
+            raise TypeError("SpikeRing.push of a batched ring takes [batch, n] spikes (or a BinaryArray of them); hand packed "
+                            "words [batch, ceil(n / 32)] to push_packed.")
+        v = spikes.value if isinstance(spikes, BinaryArray) else spikes
+        if isinstance(v, (A.ActiveIds, A.PackedSpikes)):
+            raise TypeError("SpikeRing.push of a batched ring takes spikes by position, [batch, n].")
+        shape = _shape_of(v)
+        if len(shape) != 2 or shape != (self.batch, self.n):
+            raise ValueError(f"SpikeRing.push: a ring of batch {self.batch} over {self.n} neurons takes spikes of shape "
+                             f"({self.batch}, {self.n}); got {shape}.")
+        if not A.wants_numpy(v):
+            self._numpy = False
+        buf, sd = A.spikes_to_device(v)
+        return self._push_call(buf, sd)
+
+    def _push_call(self, buf, sd) -> 'SpikeRing':
+        call('be_spike_ring_push_batch', A.ptr(buf), sd, self.n, self.depth, self.batch, A.ptr(self.bits), A.ptr(self.head),
+             A.ptr(self._state[1:]), A.stream_ptr())
+        return self
+
+    def push_packed(self, words) -> 'SpikeRing':
+        """Store the spikes of the current step of a batched ring from already packed words: int32 ``[B, ceil(n / 32)]`` (bit
+        ``i % 32`` of word ``i // 32`` of row ``b`` = neuron ``i`` of sample ``b``).  The bits past ``n`` of every row are cleared.
+        A method of its own because a ``[B, W]`` integer array given to :meth:`push` is ``B`` vectors of ``W`` spikes.  One
+        launch, no host read.  (A ring without a batch takes its packed words as a ``BitPackedBinary``, through :meth:`push`.)"""
+        if self.batch is None:
+            raise NotImplementedError("SpikeRing.push_packed is the packed input of a batched ring; a ring without a batch takes "
+                                      "push(BitPackedBinary.from_packed(words, n)).")
+        want = (self.batch, self._words)
+        shape = _shape_of(words)
+        if shape != want:
+            raise ValueError(f"SpikeRing.push_packed: the packed words of this ring have shape {want}; got {shape}.")
+        if isinstance(words, torch.Tensor):
+            dt, ok = words.dtype, words.dtype in (torch.int32, torch.uint32)
+        else:
+            dt = np.asarray(words).dtype
+            ok = dt in (np.dtype(np.int32), np.dtype(np.uint32))
+        if not ok:
+            raise TypeError(f"SpikeRing.push_packed takes 32-bit words (int32); got {dt}.")
+        if not A.wants_numpy(words):
+            self._numpy = False
+        if not isinstance(words, torch.Tensor):
+            words = np.asarray(words).view(np.int32)
+        return self._push_call(A.to_device(words), A.BE_SPIKE_BITS)
+
     def reset(self) -> 'SpikeRing':
         """Forget the history (``bits`` and ``head`` back to zero)."""
         self.bits.zero_()
@@ -106,20 +177,31 @@ class SpikeRing:
         return self
 
     # -- reading --------------------------------------------------------------------------------------------------------
-    def events(self, age: int = 0) -> BitPackedBinary:
+    def events(self, age: int = 0):
         """The spikes of ``age`` steps ago as a ``BitPackedBinary`` (a copy of that slot): ``ring.events(3) @ csr`` is one delay
-        for a whole projection, with any container.  The slot is picked by a device-side index, so the call captures."""
+        for a whole projection, with any container.  The slot is picked by a device-side index, so the call captures.  A
+        batched ring gives a ``BinaryArray`` over a bool ``[B, n]`` tensor (unpacked with torch bit arithmetic: not a hot path);
+        ``ring.events(3) @ csr`` is then ``[B, n_post]``."""
         age = int(age)
         if not 0 <= age < self.depth:
             raise ValueError(f"SpikeRing.events: age must lie in [0, {self.depth}); got {age}.")
         slot = torch.remainder(self.head - (1 + age), self.depth)
+        if self.batch is not None:
+            words = self.bits.index_select(0, slot).reshape(self.batch, self._words, 1)
+            lanes = torch.arange(32, dtype=torch.int32, device=words.device)
+            on = torch.bitwise_and(torch.bitwise_right_shift(words, lanes), 1).ne(0)
+            return BinaryArray(on.reshape(self.batch, self._words * 32)[:, :self.n].contiguous())
         words = self.bits.index_select(0, slot).reshape(-1)
         return BitPackedBinary.from_packed(words, self.n)
 
     def ids(self, ages: Optional[int] = None, row_mask: Optional[torch.Tensor] = None) -> A.ActiveIds:
         """The ring compacted into the list ``{a * n + i : neuron i fired a steps ago, a < ages}`` (default: every age), gated by
         ``row_mask`` (int32 ``[>= ages, ceil(n / 32)]``, word for word) — an ``ActiveIds`` over ``ages * n`` positions, in no
-        particular order.  The id buffer is allocated once, by the first call; the counter is zeroed on the stream by every call."""
+        particular order.  The id buffer is allocated once, by the first call; the counter is zeroed on the stream by every call.
+        An id list is one vector: a batched ring raises ``NotImplementedError`` (its form by age is :meth:`stacked_bits`)."""
+        if self.batch is not None:
+            raise NotImplementedError("SpikeRing.ids: an id list is one vector; a batched ring is laid out by age with "
+                                      "stacked_bits().")
         ages = self.depth if ages is None else int(ages)
         if not 1 <= ages <= min(self.depth, MAX_RING_AGES):
             raise ValueError(f"SpikeRing.ids: ages must lie in [1, {min(self.depth, MAX_RING_AGES)}]; got {ages}.")
@@ -138,9 +220,33 @@ class SpikeRing:
         op.numpy_result = self._numpy
         return op
 
+    def stacked_bits(self, ages: Optional[int] = None, row_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The histories of a batched ring by age, bit-packed: int32 ``[B, ceil(ages * n / 32)]`` whose bit
+        ``a * n + i`` of row ``b`` is the spike of neuron ``i`` of sample ``b`` at age ``a < ages`` (default: every age), gated by
+        ``row_mask`` (int32 ``[>= ages, ceil(n / 32)]``); the bits past ``ages * n`` are 0.  It is the ``BE_SPIKE_BITS`` batch
+        operand over the ``ages * n`` rows of a stacked matrix.  Every word is written by each call (nothing is zeroed first);
+        the buffer is allocated by the first call for that ``ages`` and reused: the next call overwrites what this one returned.
+        A ring without a batch has :meth:`ids` instead."""
+        if self.batch is None:
+            raise NotImplementedError("SpikeRing.stacked_bits lays out a batched ring; a ring without a batch is compacted with ids().")
+        ages = self.depth if ages is None else int(ages)
+        if not 1 <= ages <= self.depth:
+            raise ValueError(f"SpikeRing.stacked_bits: ages must lie in [1, {self.depth}]; got {ages}.")
+        if row_mask is not None:
+            if not isinstance(row_mask, torch.Tensor) or row_mask.dtype != torch.int32 or row_mask.ndim != 2 \
+                    or row_mask.shape[0] < ages or row_mask.shape[1] != self._words or not row_mask.is_contiguous():
+                raise ValueError(f"SpikeRing.stacked_bits: row_mask must be a contiguous int32 [>= {ages}, {self._words}] tensor.")
+        out = self._stacked.get(ages)
+        if out is None:
+            out = self._stacked[ages] = torch.empty((self.batch, (ages * self.n + 31) // 32), dtype=torch.int32,
+                                                    device=self.bits.device)
+        call('be_spike_ring_unroll', A.ptr(self.bits), A.ptr(self.head), self.n, self.depth, self.batch, ages, A.ptr(row_mask),
+             A.ptr(out), A.stream_ptr())
+        return out
+
     # -- product --------------------------------------------------------------------------------------------------------
-    shape = property(lambda self: (self.n,))
-    ndim = property(lambda self: 1)
+    shape = property(lambda self: (self.n,) if self.batch is None else (self.batch, self.n))
+    ndim = property(lambda self: 1 if self.batch is None else 2)
 
     def __matmul__(self, other):
         if isinstance(other, DelayedCSR):
@@ -152,6 +258,8 @@ class SpikeRing:
         raise NotImplementedError("x @ SpikeRing is not defined: the delays live on the presynaptic side (ring @ D).")
 
     def __repr__(self):
+        if self.batch is not None:
+            return f"SpikeRing(n={self.n}, depth={self.depth}, batch={self.batch})"
         return f"SpikeRing(n={self.n}, depth={self.depth})"
 
 
@@ -266,8 +374,9 @@ class DelayedCSR:
     entries of row ``i`` with delay ``d`` in their original order; ``perm`` maps a stacked position to the original one;
     ``row_mask`` (int32 ``[depth, ceil(n_pre / 32)]``) marks the non-empty stacked rows.  ``update_on_pre`` / ``update_on_post`` are
     the spike-triggered updates; ``ring @ D`` is differentiable in the weights, with ``stacked.data`` as the leaf
-    (no spike gradient: the ring holds bits).  Dendritic delays, CSC and JIT-connectivity inputs and batched rings are not
-    built."""
+    (no spike gradient: the ring holds bits).  A batched ring (``SpikeRing(n_pre, depth, batch=B)``) gives ``[B, n_post]``
+    through the same stacked matrix and the same gradient, summed over the batch; the plasticity updates are
+    defined for one sample.  Dendritic delays and CSC and JIT-connectivity inputs are not built."""
 
     def __init__(self, args, *, shape, depth: int, backend: Optional[str] = None):
         if len(args) != 4:
@@ -421,6 +530,9 @@ class DelayedCSR:
         from ._plasticity import _bounds, container_update
         if not isinstance(ring, SpikeRing):
             raise TypeError("DelayedCSR.update_on_pre takes the SpikeRing of the pre population (the spikes by age).")
+        if ring.batch is not None:
+            raise NotImplementedError("DelayedCSR.update_on_pre is defined for one sample: a batched ring has no single arrival "
+                                      "per synapse (batched plasticity is not built).")
         check_ring_matches(ring.n, ring.depth, self.shape, self.depth)
         self._check_plastic(post_trace, 'post_trace')
         _bounds(w_min, w_max)
@@ -460,15 +572,43 @@ class DelayedCSR:
     # -- product --------------------------------------------------------------------------------------------------------
     def __rmatmul__(self, ring):
         if not isinstance(ring, SpikeRing):
-            raise NotImplementedError("x @ DelayedCSR is defined for a SpikeRing (one vector per step); a 2-D or batched "
-                                      "history is not built.")
+            raise NotImplementedError("x @ DelayedCSR is defined for a SpikeRing (a batch of histories: SpikeRing(n, depth, "
+                                      "batch=B)); a 2-D array of spikes carries no history.")
         check_ring_matches(ring.n, ring.depth, self.shape, self.depth)
+        if ring.batch is not None:
+            return self._batched_product(ring)
         from ._csr import _csr_p_call, binary_csrmv_p
         ids = ring.ids(ages=self.depth, row_mask=self.row_mask)
         st = self.stacked
         rows = st._stored_rows()
         r = _csr_p_call(binary_csrmv_p, st.data, rows.indices, rows.indptr, ids, st._scatter_workspace(), (rows.m, rows.k), True,
                         self.backend)[0]
+        return A.to_result(r, self._numpy_result and ring._numpy and not r.requires_grad)
+
+    def _batched_product(self, ring: SpikeRing):
+        """``ring @ D`` for a batched ring: the histories unrolled by age are the ``BE_SPIKE_BITS`` batch operand
+        ``[B, ceil(depth * n_pre / 32)]`` of the stacked matrix's scatter step, on the matrix's own workspace."""
+        from . import _autograd as _ag
+        from ._csr import binary_csrmm_p, rows_step
+        binary_csrmm_p.resolve(self.backend)                    # (an unknown backend is refused as the 1-D product refuses it)
+        st = self.stacked
+        rows = st._stored_rows()
+        ws = st._scatter_workspace()
+        words = ring.stacked_bits(ages=self.depth, row_mask=self.row_mask)
+        weights = st.data.reshape(1) if st.data.ndim == 0 else st.data
+
+        def run():
+            return rows_step(weights.detach(), rows.indices, rows.indptr, -1, words, A.BE_SPIKE_BITS, m=rows.m, k=rows.k,
+                             transpose=True, workspace=ws)
+
+        if _ag.needed(weights):
+            # the ring reuses `words` from step to step: the packed activity, not the buffer, is what backward keeps (2.16)
+            spec = _ag.RowsSpec(run, rows, True, 'bm')
+            spec.w_meta = (tuple(weights.shape), weights.dtype)
+            spec.mask, spec.nb = _ag.packed_activity(words, rows.m, ring.batch), ring.batch
+            r = _ag.RowsProduct.apply(weights, None, spec)
+        else:
+            r = run()
         return A.to_result(r, self._numpy_result and ring._numpy and not r.requires_grad)
 
     def __matmul__(self, other):

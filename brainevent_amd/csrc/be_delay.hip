@@ -1,6 +1,8 @@
 // be_delay.hip — synaptic delays on the presynaptic side: the device-side split of a matrix's stored rows by
 // delay, the bit-packed spike-history ring, and the compaction of the ring into the active-row list of the *stacked* matrix; and
-// the push of the value-history ring that the plasticity of delayed synapses reads by age (be_plasticity.hip).
+// the push of the value-history ring that the plasticity of delayed synapses reads by age (be_plasticity.hip);
+// and the batched ring: B histories under one head, and their age-ordered unroll into the bit-packed batch
+// operand [B, depth * n] of the stacked matrix (a BE_SPIKE_BITS batch of the scatter entry points).
 //
 // Stored row d * m + i of the stacked matrix holds the entries of row i whose delay is d; a delayed step is then one ordinary
 // scatter over the stacked rows {d * m + i : neuron i fired d steps ago} — a BE_SPIKE_IDS operand of the scatter entry points
@@ -22,6 +24,11 @@ constexpr int kMaskGridCap = 64;                   // row-mask kernel: 256 rows 
 constexpr int kRingThreads = 256, kRingPer = 32;
 constexpr int kRingTileBits = kRingThreads * kRingPer;
 static_assert(kRingTileBits == kRingThreads * 32, "the compaction gives every thread one 32-bit word of the push tile");
+// batched ring: the batch row is the grid's second dimension, in the push and in the unroll (no stride over it), so the batch
+// count is bounded by that dimension's limit — the n_batch bound of every batched entry point of the library
+constexpr int kRingMaxBatch = 65535;
+// unroll: one thread assembles one output word; a workgroup takes kUnrollThreads consecutive words of one batch row
+constexpr int kUnrollThreads = 256;
 
 __device__ __forceinline__ void wave_fence() { __builtin_amdgcn_wave_barrier(); }
 
@@ -113,6 +120,8 @@ struct SpikeWords { using type = uint32_t; };
 // Packs the spikes into slot `head`, then advances head.  Every workgroup reads head (thread 0, broadcast through LDS) before
 // it takes its arrival ticket, and the holder of the last ticket is the one that writes head and re-arms the ticket word: no
 // workgroup reads head after it was written in this launch; later launches are ordered behind this one by the stream.
+// The grid is (bit tiles, batch rows): workgroup (x, b) packs tile x of spikes[b] into row b of the slot, bits[head][b][.]; the
+// rule holds over the whole grid, the last of gridDim.x * gridDim.y tickets advances head.  One vector is gridDim.y == 1.
 template <typename SP>
 __global__ void __launch_bounds__(kRingThreads) k_ring_push(const typename SP::type* __restrict__ spikes, int64_t n, int depth,
                                                             uint32_t* __restrict__ bits, int32_t* head, uint32_t* arrivals) {
@@ -121,7 +130,9 @@ __global__ void __launch_bounds__(kRingThreads) k_ring_push(const typename SP::t
   __syncthreads();
   const int h = h_sh;
   const int64_t n_words = (n + 31) >> 5;
-  uint32_t* __restrict__ row = bits + (int64_t)h * n_words;
+  const int64_t b = blockIdx.y;
+  uint32_t* __restrict__ row = bits + ((int64_t)h * gridDim.y + b) * n_words;
+  spikes += b * (std::is_same<SP, SpikeWords>::value ? n_words : n);
   const int64_t tile = (int64_t)blockIdx.x * kRingTileBits;
   if constexpr (std::is_same<SP, SpikeWords>::value) {
     const int64_t w = (tile >> 5) + threadIdx.x;
@@ -145,7 +156,7 @@ __global__ void __launch_bounds__(kRingThreads) k_ring_push(const typename SP::t
   __syncthreads();
   if (threadIdx.x == 0) {
     const uint32_t t = atomicAdd(arrivals, 1u);
-    if (t == gridDim.x - 1) {
+    if (t == gridDim.x * gridDim.y - 1) {
       *arrivals = 0u;
       *head = (h + 1 == depth) ? 0 : h + 1;
     }
@@ -195,6 +206,56 @@ __global__ void __launch_bounds__(kRingThreads) k_ring_compact(const uint32_t* _
     bw &= bw - 1;
     active[pos++] = id0 + (uint32_t)b;
   }
+}
+
+// The batched ring by age: out[b][.] is the bit string of ages * n bits whose bit p = a * n + i is bit i of the slot of age a of
+// sample b — slot (head - 1 - a) mod depth, bits[slot][b][.] — ANDed with bit i of row_mask[a] (NULL: keep all); the bits from
+// ages * n to the end of the row's last word are 0.  n is in general no multiple of 32, so age a starts at bit offset a * n of
+// the row: a funnel shift, not a copy.  One thread assembles one output word, from pieces: a piece is the run of bits that
+// comes from ONE source word of ONE age — it ends where the output word, the age (at bit n) or the source word (at a multiple
+// of 32) ends.  For n >= 32 an output word spans at most two ages and at most two source words of each (at most four pieces,
+// three unless an age boundary falls inside it); for n < 32 every age is one piece and the word draws on up to 32 ages (n = 1:
+// exactly 32).  Every shift count is at most 31: `sh` is a bit position inside a source word, `filled` the number of bits
+// already placed, which is below 32 while the loop runs, and a piece of all 32 bits (n % 32 == 0, word-aligned ages) is taken
+// whole, without a mask.  The position arithmetic is one 32-bit unsigned divide per word (p < 2^31 + 32).  Lanes of a wave read
+// consecutive source words (each word is read by at most two neighbouring lanes) and write consecutive output words; every
+// output word is written once, by one lane: no atomics, nothing to zero beforehand.  head is read once per workgroup.
+__global__ void __launch_bounds__(kUnrollThreads) k_ring_unroll(const uint32_t* __restrict__ bits, const int32_t* __restrict__ head,
+                                                                 uint32_t n, int64_t n_words, int depth, uint32_t total,
+                                                                 int64_t out_words, const uint32_t* __restrict__ row_mask,
+                                                                 uint32_t* __restrict__ out) {
+  __shared__ int h_sh;
+  if (threadIdx.x == 0) h_sh = ring_head(head, depth);
+  __syncthreads();
+  const int64_t w = (int64_t)blockIdx.x * kUnrollThreads + threadIdx.x;
+  if (w >= out_words) return;
+  const int64_t b = blockIdx.y, n_batch = gridDim.y;
+  uint32_t p = (uint32_t)w << 5;
+  const uint32_t end = (total - p < 32u) ? total : p + 32u;
+  uint32_t a = p / n, i = p - a * n;
+  int slot = h_sh - 1 - (int)a;                       // a < ages <= depth, 0 <= head < depth: one conditional add is the modulo
+  if (slot < 0) slot += depth;
+  uint32_t word = 0, filled = 0;
+  while (p < end) {
+    const uint32_t sh = i & 31u;
+    uint32_t take = end - p;
+    if (n - i < take) take = n - i;
+    if (32u - sh < take) take = 32u - sh;
+    uint32_t src = bits[((int64_t)slot * n_batch + b) * n_words + (i >> 5)];
+    if (row_mask != nullptr) src &= row_mask[(int64_t)a * n_words + (i >> 5)];
+    uint32_t v = src >> sh;
+    if (take < 32u) v &= (1u << take) - 1u;
+    word |= v << filled;
+    filled += take;
+    p += take;
+    i += take;
+    if (i == n) {
+      i = 0;
+      ++a;
+      slot = (slot == 0) ? depth - 1 : slot - 1;
+    }
+  }
+  out[b * out_words + w] = word;
 }
 
 // =================================================================================================
@@ -343,12 +404,17 @@ extern "C" int be_delay_split_fill(const void* indptr, int indptr_is64, int64_t 
   return BE_OK;
 }
 
-extern "C" int be_spike_ring_push(const void* spikes, int spike_dtype, int64_t n, int depth, uint32_t* bits, int32_t* head,
-                                  uint32_t* arrivals, be_stream_t stream) {
+namespace {
+
+int ring_push_launch(const void* spikes, int spike_dtype, int64_t n, int depth, int64_t n_batch, uint32_t* bits, int32_t* head,
+                     uint32_t* arrivals, be_stream_t stream) {
   BE_REQUIRE(n >= 1 && depth >= 1 && (int64_t)depth * n < (1ll << 31), BE_ERR_INVALID, "need n >= 1, depth >= 1, depth * n < 2^31");
+  BE_REQUIRE(n_batch >= 1 && n_batch <= kRingMaxBatch, BE_ERR_INVALID, "need 1 <= n_batch <= 65535");
   BE_REQUIRE(spikes && bits && head && arrivals, BE_ERR_INVALID, "null pointer");
+  const int64_t tiles = (n + kRingTileBits - 1) / kRingTileBits;
+  BE_REQUIRE(tiles * n_batch < (1ll << 32), BE_ERR_INVALID, "more workgroups than the 32-bit ticket word counts");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)((n + kRingTileBits - 1) / kRingTileBits)), block(kRingThreads);
+  const dim3 grid((unsigned)tiles, (unsigned)n_batch), block(kRingThreads);
   if (spike_dtype == BE_SPIKE_BOOL)
     hipLaunchKernelGGL(k_ring_push<SpikeBool>, grid, block, 0, st, static_cast<const uint8_t*>(spikes), n, depth, bits, head, arrivals);
   else if (spike_dtype == BE_SPIKE_FLOAT)
@@ -357,6 +423,33 @@ extern "C" int be_spike_ring_push(const void* spikes, int spike_dtype, int64_t n
     hipLaunchKernelGGL(k_ring_push<SpikeWords>, grid, block, 0, st, static_cast<const uint32_t*>(spikes), n, depth, bits, head, arrivals);
   else
     BE_REQUIRE(false, BE_ERR_UNSUPPORTED, "spike dtype must be BE_SPIKE_BOOL, BE_SPIKE_FLOAT or BE_SPIKE_BITS");
+  BE_LAUNCH_CHECK();
+  return BE_OK;
+}
+
+}  // namespace
+
+extern "C" int be_spike_ring_push(const void* spikes, int spike_dtype, int64_t n, int depth, uint32_t* bits, int32_t* head,
+                                  uint32_t* arrivals, be_stream_t stream) {
+  return ring_push_launch(spikes, spike_dtype, n, depth, 1, bits, head, arrivals, stream);
+}
+
+extern "C" int be_spike_ring_push_batch(const void* spikes, int spike_dtype, int64_t n, int depth, int64_t n_batch, uint32_t* bits,
+                                        int32_t* head, uint32_t* arrivals, be_stream_t stream) {
+  return ring_push_launch(spikes, spike_dtype, n, depth, n_batch, bits, head, arrivals, stream);
+}
+
+extern "C" int be_spike_ring_unroll(const uint32_t* bits, const int32_t* head, int64_t n, int depth, int64_t n_batch, int ages,
+                                    const uint32_t* row_mask, uint32_t* out, be_stream_t stream) {
+  BE_REQUIRE(n >= 1 && depth >= 1 && ages >= 1 && ages <= depth && (int64_t)ages * n < (1ll << 31), BE_ERR_INVALID,
+             "need n >= 1, 1 <= ages <= depth, ages * n < 2^31");
+  BE_REQUIRE(n_batch >= 1 && n_batch <= kRingMaxBatch, BE_ERR_INVALID, "need 1 <= n_batch <= 65535");
+  BE_REQUIRE(bits && head && out, BE_ERR_INVALID, "null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t total = (int64_t)ages * n, out_words = (total + 31) / 32;
+  hipLaunchKernelGGL(k_ring_unroll, dim3((unsigned)((out_words + kUnrollThreads - 1) / kUnrollThreads), (unsigned)n_batch),
+                     dim3(kUnrollThreads), 0, st, bits, head, (uint32_t)n, (n + 31) / 32, depth, (uint32_t)total, out_words, row_mask,
+                     out);
   BE_LAUNCH_CHECK();
   return BE_OK;
 }

@@ -1006,6 +1006,19 @@ int be_solve_iterate(const void* weights, int wdtype, const int32_t* indices, co
  *     ages * n positions: the BE_SPIKE_IDS operand of the scatter entry points for the stacked matrix.
  * Both are graph-capturable: head is read on the device.
  *
+ * Batched spike ring: n_batch histories under ONE head — bits[depth][n_batch][ceil(n/32)], head[1] and
+ * arrivals[1] as above; 1 <= n_batch <= 65535 (the batch row is the second grid dimension of both kernels, not strided over).
+ *   be_spike_ring_push_batch: be_spike_ring_push for batch-major spikes[n_batch][n] (BE_SPIKE_BITS: [n_batch][ceil(n/32)] words,
+ *     bits past n of every row dropped): row b goes to bits[*head][b][.], then *head advances once.  One launch over the grid (bit
+ *     tiles, batch rows); every workgroup reads head before it takes its ticket, the last of all tickets advances it.
+ *     n_batch = 1 is be_spike_ring_push.
+ *   be_spike_ring_unroll: the histories by age as the bit-packed batch operand of the stacked matrix (BE_SPIKE_BITS rows over
+ *     ages * n positions): for a < ages <= depth and i < n, with p = a * n + i, bit p % 32 of word p / 32 of out row b (rows of
+ *     ceil(ages * n / 32) words) = bit i of slot (*head - 1 - a) mod depth of sample b, ANDed with bit i of row_mask[a] (rows of
+ *     ceil(n/32) words; NULL keeps all); the bits from ages * n to the end of a row's last word are 0.  ages * n < 2^31.  Every
+ *     output word is written exactly once, by a vector store: no atomics, nothing is zeroed beforehand, no memset node.
+ * Both are graph-capturable and synchronise nothing.
+ *
  * Value ring: values[depth][n] in one of the four float dtypes (wdtype), head[1] and arrivals[1] as above, zero to begin with.
  *   be_value_ring_push: writes x[n] (x_dtype: any of the four; converted as a cast does, f64 -> f16 / bf16 through f32) into slot
  *     *head, then *head = (*head + 1) % depth — one launch, no host read, arrivals as above.  The vector of age a lies in slot
@@ -1023,6 +1036,11 @@ int be_spike_ring_compact(const uint32_t* bits, const int32_t* head, int64_t n, 
                           uint32_t* active_ids, uint32_t* count, be_stream_t stream);
 int be_value_ring_push(const void* x, int x_dtype, int64_t n, int depth, void* values, int wdtype, int32_t* head,
                        uint32_t* arrivals, be_stream_t stream);
+int be_spike_ring_push_batch(const void* spikes, int spike_dtype, int64_t n, int depth, int64_t n_batch, uint32_t* bits,
+                             int32_t* head, uint32_t* arrivals, be_stream_t stream);
+int be_spike_ring_unroll(const uint32_t* bits, const int32_t* head, int64_t n, int depth, int64_t n_batch, int ages,
+                         const uint32_t* row_mask /* [>= ages][ceil(n/32)] or NULL */,
+                         uint32_t* out /* [n_batch][ceil(ages*n/32)] */, be_stream_t stream);
 
 #define BE_FOR_ALL_VARIANTS(X) \
   X(f32, BE_F32, bool, BE_SPIKE_BOOL)   X(f32, BE_F32, float, BE_SPIKE_FLOAT)   \
