@@ -56,6 +56,7 @@ _SIGNATURES = dict(
     be_jitmv_float='i:iddiluppllliplp',
     be_binary_csrmm_t_indexed='i:piippilpipiplllplp', be_binary_csrmm_nt_indexed='i:piippilpipiplllplp',
     be_binary_densemm_workspace_bytes='l:lllii', be_binary_densemm='i:pipipllliplp',
+    be_binary_densemm_f8_workspace_bytes='l:lllii', be_binary_densemm_f8='i:pidpipllliplp',
     be_jit_scatter_workspace_arm='i:plp', be_jit_scatter_workspace_disarm='i:p', be_binary_jitmv_workspace_bytes='l:llli',
     be_binary_jitmv='i:iddilupipllliiplp', be_jit_scatter_classes='i:lli', be_binary_jitmv_sharded='i:iddilupipllliiiplp',
     be_binary_jitmv_rows='i:iddilupipllllplp', be_binary_jitmm_workspace_bytes='l:lllli', be_binary_jitmm='i:iddilupiplllliplp',

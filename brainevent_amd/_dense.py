@@ -22,6 +22,7 @@ from ._op import OpKernel
 from ._plasticity import PlasticityMixin
 from ._arith import ArithmeticMixin, as_operand, broadcast_check, is_matrix
 from . import _autograd as _ag
+from . import _dense_f8 as _f8
 
 __all__ = ['Dense', 'binary_densemv', 'binary_densemm', 'binary_densemv_p', 'binary_densemm_p', 'binary_densemv_p_call',
            'binary_densemm_p_call']
@@ -29,6 +30,9 @@ __all__ = ['Dense', 'binary_densemv', 'binary_densemm', 'binary_densemv_p', 'bin
 
 def _dense_batched(weights: torch.Tensor, spikes_bm: torch.Tensor, sd: int, transpose: bool) -> torch.Tensor:
     """``spikes_bm [nb, k]`` -> ``[nb, out_len]`` through ``be_binary_densemm_{transpose,no_transpose}_*``."""
+    if _f8.is_fp8(weights):        # OCP FP8 codes: their own kernels (be_dense_f8.hip), scale 1, f32 out
+        _f8.check_finite(weights)
+        return _f8.dense_f8_batched(weights, 1.0, spikes_bm, sd, transpose)
     rows_w, cols_w = int(weights.shape[0]), int(weights.shape[1])
     nb = int(spikes_bm.shape[0])
     out_len = cols_w if transpose else rows_w
@@ -75,6 +79,7 @@ def binary_densemv_p_call(weights, spikes, *, transpose, backend=None):
     else:
         assert spikes.shape[0] == weights.shape[1], (
             f"spikes shape {tuple(spikes.shape)} and weights shape {tuple(weights.shape)} are not compatible")
+    _f8.refuse_grad(weights, spikes)
     if _ag.needed(weights, spikes):
         return [_ag.dense_product(lambda: binary_densemv_p(weights, spikes, transpose=transpose, backend=backend), weights, spikes,
                                   spikes, 'vec', transpose=transpose)]
@@ -94,6 +99,7 @@ def binary_densemm_p_call(weights, spikes, *, transpose, backend=None):
         assert weights.shape[1] == spikes.shape[0], (
             f"weights.shape[1] ({weights.shape[1]}) != spikes.shape[0] ({spikes.shape[0]}), "
             f"weights: {tuple(weights.shape)}, spikes: {tuple(spikes.shape)}")
+    _f8.refuse_grad(weights, spikes)
     if _ag.needed(weights, spikes):
         return [_ag.dense_product(lambda: binary_densemm_p(weights, spikes, transpose=transpose, backend=backend), weights, spikes,
                                   spikes, 'nm', transpose=transpose)]
@@ -111,6 +117,8 @@ def _float_weights(w):
     dt = w.dtype
     ok = dt.is_floating_point if isinstance(w, torch.Tensor) else np.issubdtype(dt, np.floating)
     assert ok, 'Weights must be a floating-point type.'
+    if _f8.is_fp8(w):              # non-finite codes are refused here, before any device call (once per tensor version)
+        _f8.check_finite(w)
 
 
 def binary_densemv(weights, spikes, *, transpose, backend: Optional[str] = None):
@@ -168,6 +176,12 @@ class Dense(PlasticityMixin, ArithmeticMixin, DataRepresentation):
         return out
 
     T = property(lambda self: self.transpose())
+
+    def quantize(self, fmt: str = 'e4m3', scale=None):
+        """``quantize_fp8(self.data, fmt, scale)``: the read-only ``Float8Dense`` twin of this matrix."""
+        out = _f8.quantize_fp8(self.data, fmt=fmt, scale=scale)
+        out._numpy_result = self._numpy_result
+        return out
 
     def __getitem__(self, index):
         return self.todense()[index]

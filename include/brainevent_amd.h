@@ -675,6 +675,27 @@ int be_binary_densemm(const void* weights, int wdtype, const void* spikes_bm, in
                       int64_t workspace_bytes, be_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same products with OCP FP8 weights, one byte per weight (brainevent_amd/csrc/be_dense_f8.hip; no counterpart in the
+ * reference).  f8_format: BE_F8_E4M3 (torch.float8_e4m3fn) or BE_F8_E5M2 (torch.float8_e5m2); never the fnuz forms.
+ *   weights : [rows_w, cols_w] row-major codes
+ *   transpose = 1: spikes_bm [n_batch, rows_w] -> out_f32_bm [n_batch, cols_w],  out[b, j] = fl32((sum_{i: e(s[b,i])} W[i, j]) * scale)
+ *   transpose = 0: spikes_bm [n_batch, cols_w] -> out_f32_bm [n_batch, rows_w],  out[b, i] = fl32((sum_{j: e(s[b,j])} W[i, j]) * scale)
+ *   scale   : one number per matrix, rounded to f32 once and applied to the finished f32 sum (scale = 1 leaves it bit for bit)
+ *   workspace >= be_binary_densemm_f8_workspace_bytes(rows_w, cols_w, n_batch, transpose, f8_format)
+ * The output is always f32.  spike_dtype: BE_SPIKE_BOOL, BE_SPIKE_FLOAT or BE_SPIKE_BITS.  Same contracts as be_binary_densemm
+ * (contraction dimension < 2^28; a contraction of length 0 gives zeros; empty outputs return BE_OK; asynchronous on `stream`,
+ * no host read, capturable), sums in f32 in a fixed order.
+ * PRECONDITION: every code is finite (e4m3: (c & 0x7f) != 0x7f; e5m2: (c & 0x7c) != 0x7c) — a non-finite code in a row that
+ * carries a spike makes every batch row of its MFMA tile NaN, and there is no repair pass.
+ * ---------------------------------------------------------------------------------------------- */
+#define BE_F8_E4M3 0
+#define BE_F8_E5M2 1
+int64_t be_binary_densemm_f8_workspace_bytes(int64_t rows_w, int64_t cols_w, int64_t n_batch, int transpose, int f8_format);
+int be_binary_densemm_f8(const void* weights, int f8_format, double scale, const void* spikes_bm, int spike_dtype,
+                         void* out_f32_bm, int64_t rows_w, int64_t cols_w, int64_t n_batch, int transpose, void* workspace,
+                         int64_t workspace_bytes, be_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * JIT-connectivity products (the matrix is regenerated on the fly, never stored)
  * replaces: jit_scalar_binary_jitsmv.{pack_bool,notrans_*,trans_*} (brainevent/_jit_scalar/binary_jitsmv.cu:107-321),
  *           jit_scalar_binary_jitsmm.{pack,notrans_*,trans_*} (brainevent/_jit_scalar/binary_jitsmm.cu),
