@@ -7,7 +7,11 @@ spike function is a Heaviside step in the forward pass and a fast-sigmoid deriva
 for the spikes, per-synapse for the weights.  The task is synthetic and generated here: each of two input patterns must drive
 its own readout unit.  Trained with ``torch.optim.SGD``; the loss falls.
 
-    python examples/surrogate_csr.py [--steps 60]
+    python examples/surrogate_csr.py [--steps 60] [--fused]
+
+``--fused`` replaces the hand-written neuron (about six elementwise launches forwards and twice that backwards per time step) by
+``be.lif_step`` (one launch each way; the same leak, threshold, hard reset to 0 and fast-sigmoid surrogate, the reset's gradient
+kept), trains the hand-written network from the same start next to it and prints the end points of both loss curves.
 """
 import argparse
 import os
@@ -35,12 +39,7 @@ class SpikeFn(torch.autograd.Function):
         return g / (1.0 + 10.0 * (v - 1.0).abs()) ** 2
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument('--steps', type=int, default=60)
-    ap.add_argument('--n', type=int, default=2000, help='recurrent neurons')
-    ap.add_argument('--T', type=int, default=25, help='time steps per trial')
-    args = ap.parse_args()
+def train(args, fused=False):
     dev = torch.device('cuda')
     rng = np.random.default_rng(0)
     torch.manual_seed(0)
@@ -63,8 +62,11 @@ def main():
         s = torch.zeros(batch, n, device=dev)
         acc = torch.zeros(batch, n_out, device=dev)
         for _ in range(args.T):
-            v = 0.9 * v * (1.0 - s) + drive + be.BinaryArray(s) @ rec   # reset, leak, input, recurrent events
-            s = SpikeFn.apply(v)
+            if fused:                                                   # the same step as one launch: v is the membrane after the reset
+                s, v = be.lif_step(v, drive + be.BinaryArray(s) @ rec, beta=0.9, v_th=1.0, v_reset=0.0, alpha=10.0)
+            else:
+                v = 0.9 * v * (1.0 - s) + drive + be.BinaryArray(s) @ rec   # reset, leak, input, recurrent events
+                s = SpikeFn.apply(v)
             acc = acc + be.BinaryArray(s) @ readout
         return acc / args.T
 
@@ -82,7 +84,26 @@ def main():
             print(f"step {step:3d}  loss {losses[-1]:.4f}")
     head, tail = np.mean(losses[:5]), np.mean(losses[-5:])
     print(f"loss {head:.4f} -> {tail:.4f} in {time.perf_counter() - t0:.1f} s ({'falling' if tail < head else 'NOT falling'})")
+    return head, tail
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument('--steps', type=int, default=60)
+    ap.add_argument('--n', type=int, default=2000, help='recurrent neurons')
+    ap.add_argument('--T', type=int, default=25, help='time steps per trial')
+    ap.add_argument('--fused', action='store_true', help='the neuron as one launch (be.lif_step) instead of elementwise torch ops')
+    args = ap.parse_args()
+    if not args.fused:
+        train(args)
+        return 0
+    print('fused neuron (be.lif_step):')
+    fused = train(args, fused=True)
+    print('hand-written neuron (torch elementwise ops), same start:')
+    plain = train(args)
+    print(f"end points: fused {fused[0]:.4f} -> {fused[1]:.4f}, hand-written {plain[0]:.4f} -> {plain[1]:.4f}")
+    return 0 if fused[1] < fused[0] else 1
 
 
 if __name__ == '__main__':
-    main()
+    sys.exit(main())

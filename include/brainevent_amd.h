@@ -133,6 +133,41 @@ int be_lif_step_scaled_packed(int current_based, float* v, float* g_exc, float* 
                               double v_th, double v_reset, double t_ref, double e_exc, double e_inh, double decay_exc,
                               double decay_inh, double i_ext, double syn_scale, be_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * The differentiable neuron between two products (brainevent_amd/csrc/be_neuron_sg.hip; no native counterpart in the reference,
+ * which leaves the neuron to brainstate): a leaky integrate-and-fire neuron without synapse state or refractory period, T time
+ * steps of N independent slots (a batch is more slots) in ONE launch, and its backward pass with a surrogate gradient in one
+ * more.  All arrays f32; x, s_out, v_seq, h_save, g_s, g_vseq, g_x are [T, N] row-major, v0, v_last, g_vlast, g_v0 are [N].
+ * beta, v_th, v_reset, alpha are rounded to f32 once on the host; per slot i every operation is rounded separately, in this
+ * order (so both passes reproduce the plain elementwise f32 formulation bit for bit; there is no transcendental):
+ *   forward, t = 0 .. T-1, v = v0[i] (v0 NULL: 0):
+ *     h = (beta * v) + x[t][i];   s = h >= v_th   (a NaN does not spike)
+ *     v = BE_LIF_RESET_HARD: s ? v_reset : h      BE_LIF_RESET_SOFT: s ? h - v_th : h
+ *     s_out[t][i] = s ? 1 : 0;   v_seq[t][i] = v  (v_seq may be NULL);   h_save[t][i] = h  (h_save may be NULL: no backward pass)
+ *   then v_last[i] = v.
+ *   backward, t = T-1 .. 0, carry = g_vlast[i] (NULL: 0), h = h_save[t][i], u = h - v_th, s = h >= v_th:
+ *     g_vo = carry + g_vseq[t][i]                 (the addition only if g_vseq is given)
+ *     sg   = BE_LIF_SG_FAST_SIGMOID: d = 1 + alpha * |u|;  sg = 1 / (d * d)
+ *            BE_LIF_SG_ATAN:         q = f32(pi / 2 * alpha) * u;  sg = f32(alpha / 2) / (1 + q * q)
+ *            BE_LIF_SG_TRIANGLE:     a = 1 - alpha * |u|;  sg = alpha * (a > 0 ? a : 0)
+ *     g_sp = g_s[t][i] (g_s NULL: 0);  unless detach_reset:  hard: g_sp = g_sp + g_vo * (v_reset - h)   soft: g_sp = g_sp - g_vo * v_th
+ *     g_h  = g_sp * sg + (hard ? (s ? 0 : g_vo) : g_vo);   g_x[t][i] = g_h;   carry = beta * g_h
+ *   then g_v0[i] = carry (g_v0 may be NULL).
+ * T == 0 or N == 0: BE_OK, nothing launched.  BE_ERR_INVALID: x, s_out, v_last / h_save, g_x NULL; T < 0 or N < 0; an unknown
+ * reset_mode or surrogate; alpha <= 0.  A lane owns 4 consecutive slots and moves them with 16-byte accesses when N % 4 == 0 and
+ * every given pointer is 16-byte aligned, one slot with 4-byte accesses otherwise; the results do not depend on which.
+ * ---------------------------------------------------------------------------------------------- */
+#define BE_LIF_RESET_HARD 0
+#define BE_LIF_RESET_SOFT 1
+#define BE_LIF_SG_FAST_SIGMOID 0
+#define BE_LIF_SG_ATAN 1
+#define BE_LIF_SG_TRIANGLE 2
+int be_lif_sg_forward(const float* x, const float* v0, float* s_out, float* v_seq, float* h_save, float* v_last, int64_t T,
+                      int64_t N, double beta, double v_th, double v_reset, int reset_mode, be_stream_t stream);
+int be_lif_sg_backward(const float* h_save, const float* g_s, const float* g_vseq, const float* g_vlast, float* g_x, float* g_v0,
+                       int64_t T, int64_t N, double beta, double v_th, double v_reset, int reset_mode, int surrogate, double alpha,
+                       int detach_reset, be_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * event vector helpers (replace: brainevent/_jit_scalar/binary_jitsmv.cu:107-125 `_pack_bool_kern`
  * and the active-row extraction of brainevent/_csr/binary_csrmv_hybrid.cu:275-327)
