@@ -21,6 +21,8 @@ _SIGNATURES = dict(
     be_lif_cuba_step='i:pppppppplddddddddddp', be_lif_cuba_step_packed='i:ppppppppplddddddddddp',
     be_lif_step_scaled_packed='i:ippppppddppplddddddddddddp',
     be_lif_sg_forward='i:pppppplldddip', be_lif_sg_backward='i:pppppplldddiidip',
+    be_lif_sg_forward_params='i:ppplplpppplldip', be_lif_sg_backward_params='i:pppppplplpppplldiidip',
+    be_lif_sg_reduce_slots_workspace_bytes='l:ll', be_lif_sg_reduce_slots='i:pllpplp',
     be_pack_spikes='i:pilpp', be_pack_spikes_batched='i:pillpp', be_unpack_spikes='i:plpp', be_compact_spikes='i:pilppp',
     be_compact_spikes_batched='i:pillplpp',
     be_exchange_unique_id_bytes='i:', be_exchange_get_unique_id='i:p', be_exchange_init='i:piilP', be_exchange_slice='i:piLL',

@@ -167,6 +167,39 @@ int be_lif_sg_forward(const float* x, const float* v0, float* s_out, float* v_se
 int be_lif_sg_backward(const float* h_save, const float* g_s, const float* g_vseq, const float* g_vlast, float* g_x, float* g_v0,
                        int64_t T, int64_t N, double beta, double v_th, double v_reset, int reset_mode, int surrogate, double alpha,
                        int detach_reset, be_stream_t stream);
+/* The same neuron with beta and v_th read from DEVICE memory (brainevent_amd/csrc/be_neuron_sg_param.hip): each is an f32 array
+ * with a period P >= 1 that divides N, and slot i of a step uses beta[i % beta_period], v_th[i % vth_period] (P = 1: one shared
+ * value; P = N / R: one value per neuron under R leading batch rows).  No value crosses to the host: a parameter updated in place
+ * is seen by the next call and by the next replay of a captured graph.  v_reset and alpha stay host scalars.
+ *   forward: the forward pass above with beta_i, th_i in place of the two constants — the same operations, order and roundings.
+ *   backward: the backward pass above with beta_i, th_i, and per slot two f32 accumulators a_b = a_th = +0; at step t, once
+ *   g_vo, sg, g_sp, g_h are formed:
+ *     v_prev = t > 0 ? reset(h_save[t-1][i]) : v0[i] (v0 NULL: 0)
+ *              reset(h') = hard: (h' >= th_i ? v_reset : h')   soft: (h' >= th_i ? h' - th_i : h')
+ *     a_b  = a_b + (g_h * v_prev)                                              (only if g_beta_slot is given)
+ *     d    = g_sp * sg  (the product that enters g_h);  soft only: d = d + (s ? g_vo : 0);  a_th = a_th - d
+ *                                                                              (only if g_vth_slot is given)
+ *   then g_beta_slot[i] = a_b, g_vth_slot[i] = a_th ([N] each).  The soft reset's direct term is there with and without
+ *   detach_reset (the derivative of h - s * v_th in v_th at fixed s).  g_v0, g_beta_slot, g_vth_slot may be NULL, and a NULL
+ *   output costs neither its arithmetic nor its store; v0 is read only when g_beta_slot is given.  Every operation is rounded
+ *   separately, so all outputs equal the elementwise f32 formulation bit for bit; a NaN stays in its slot.
+ * be_lif_sg_reduce_slots: out[p] = sum over r < N / P of slot[r * P + p], p < P — accumulated in f64 in an order the shape alone
+ *   fixes, rounded to f32 once, no atomics (two calls give identical bits):
+ *     |f64(out[p]) - exact| <= 2^-24 |exact| + (N / P) 2^-52 sum |slot| + 2^-149.
+ *   workspace: be_lif_sg_reduce_slots_workspace_bytes(N, P) bytes, 8-byte aligned, caller-owned (0 bytes unless P == 1: NULL then).
+ * BE_ERR_INVALID, beyond the codes above: a period < 1 or not dividing N; beta or v_th NULL; slot or out NULL; a workspace that is
+ * NULL or too small where one is needed.  The 16-byte kernels also need each period to be 1 or a multiple of 4 with a 16-byte
+ * aligned base; the results do not depend on which kernel runs. */
+int be_lif_sg_forward_params(const float* x, const float* v0, const float* beta, int64_t beta_period, const float* v_th,
+                             int64_t vth_period, float* s_out, float* v_seq, float* h_save, float* v_last, int64_t T, int64_t N,
+                             double v_reset, int reset_mode, be_stream_t stream);
+int be_lif_sg_backward_params(const float* h_save, const float* v0, const float* g_s, const float* g_vseq, const float* g_vlast,
+                              const float* beta, int64_t beta_period, const float* v_th, int64_t vth_period, float* g_x, float* g_v0,
+                              float* g_beta_slot, float* g_vth_slot, int64_t T, int64_t N, double v_reset, int reset_mode,
+                              int surrogate, double alpha, int detach_reset, be_stream_t stream);
+int64_t be_lif_sg_reduce_slots_workspace_bytes(int64_t N, int64_t P);
+int be_lif_sg_reduce_slots(const float* slot, int64_t N, int64_t P, float* out, void* workspace, int64_t workspace_bytes,
+                           be_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * event vector helpers (replace: brainevent/_jit_scalar/binary_jitsmv.cu:107-125 `_pack_bool_kern`
