@@ -7,13 +7,17 @@ spike function is a Heaviside step in the forward pass and a fast-sigmoid deriva
 for the spikes, per-synapse for the weights.  The task is synthetic and generated here: each of two input patterns must drive
 its own readout unit.  Trained with ``torch.optim.SGD``; the loss falls.
 
-    python examples/surrogate_csr.py [--steps 60] [--fused [--learn-beta]]
+    python examples/surrogate_csr.py [--steps 60] [--fused [--learn-beta | --synaptic [--adapt]]]
 
 ``--fused`` replaces the hand-written neuron (about six elementwise launches forwards and twice that backwards per time step) by
 ``be.lif_step`` (one launch each way; the same leak, threshold, hard reset to 0 and fast-sigmoid surrogate, the reset's gradient
 kept), trains the hand-written network from the same start next to it and prints the end points of both loss curves.
 ``--learn-beta`` (with ``--fused``) makes the leak a per-neuron ``torch.nn.Parameter`` that starts at 0.9 and is trained with the
 weights: ``be.lif_step`` reads it on the device and hands back its gradient, summed over the batch.
+``--synaptic`` (with ``--fused``) puts a synaptic current in front of the membrane: ``be.synaptic_lif_step`` in the recurrent loop,
+its state the tuple ``(c, v)``, and the readout becomes a feed-forward layer of non-spiking leaky integrators — all ``T`` readout
+currents through one ``be.synaptic_lif_sequence`` with ``v_th=inf``, the mean membrane as the logits.  ``--adapt`` (with
+``--synaptic``) adds the adaptive threshold (``adapt=(rho, kappa)``, state ``(c, v, a)``).
 """
 import argparse
 import os
@@ -41,7 +45,7 @@ class SpikeFn(torch.autograd.Function):
         return g / (1.0 + 10.0 * (v - 1.0).abs()) ** 2
 
 
-def train(args, fused=False, learn_beta=False):
+def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False):
     dev = torch.device('cuda')
     rng = np.random.default_rng(0)
     torch.manual_seed(0)
@@ -58,6 +62,7 @@ def train(args, fused=False, learn_beta=False):
     patterns = torch.tensor(rng.random((2, n)) < 0.5, dtype=torch.float32, device=dev) * 0.35
     # the leak: one constant, or (--learn-beta) one learnable value per neuron, read by the kernel from device memory
     beta = torch.nn.Parameter(torch.full((n,), 0.9, device=dev)) if learn_beta else 0.9
+    syn_decay = 0.8
     opt = torch.optim.SGD([w_rec, w_out] + ([beta] if learn_beta else []), lr=0.05)
 
     def trial(labels):
@@ -65,6 +70,16 @@ def train(args, fused=False, learn_beta=False):
         v = torch.zeros(batch, n, device=dev)
         s = torch.zeros(batch, n, device=dev)
         acc = torch.zeros(batch, n_out, device=dev)
+        if synaptic:                                                    # current, membrane (and spike trace): one launch per step
+            state = tuple(torch.zeros(batch, n, device=dev) for _ in range(3 if adapt else 2))
+            out = []
+            for _ in range(args.T):                                     # the drive scaled so that the filtered current settles at it
+                s, state = be.synaptic_lif_step(state, (1.0 - syn_decay) * drive + be.BinaryArray(s) @ rec, syn_decay=syn_decay,
+                                                beta=0.9, v_th=1.0, adapt=(0.95, 0.3) if adapt else None)
+                out.append(be.BinaryArray(s) @ readout)
+            # the readout layer is feed-forward: its whole input sequence in one launch, leaky integrators that never spike
+            _, v_seq, _ = be.synaptic_lif_sequence(torch.stack(out), syn_decay=syn_decay, beta=0.9, v_th=float('inf'), return_v=True)
+            return v_seq.mean(0) * (1.0 - syn_decay) * (1.0 - 0.9)
         for _ in range(args.T):
             if fused:                                                   # the same step as one launch: v is the membrane after the reset
                 s, v = be.lif_step(v, drive + be.BinaryArray(s) @ rec, beta=beta, v_th=1.0, v_reset=0.0, alpha=10.0)
@@ -103,14 +118,26 @@ def main():
     ap.add_argument('--T', type=int, default=25, help='time steps per trial')
     ap.add_argument('--fused', action='store_true', help='the neuron as one launch (be.lif_step) instead of elementwise torch ops')
     ap.add_argument('--learn-beta', action='store_true', help='with --fused: the leak as a learnable per-neuron Parameter')
+    ap.add_argument('--synaptic', action='store_true',
+                    help='with --fused: a synaptic current in front of the membrane (be.synaptic_lif_step) and a leaky-integrator readout')
+    ap.add_argument('--adapt', action='store_true', help='with --synaptic: an adaptive threshold (adapt=(rho, kappa))')
     args = ap.parse_args()
     if args.learn_beta and not args.fused:
         ap.error('--learn-beta needs --fused (the hand-written neuron keeps its constant leak)')
+    if args.synaptic and not args.fused:
+        ap.error('--synaptic needs --fused (the hand-written neuron has no synaptic current)')
+    if args.adapt and not args.synaptic:
+        ap.error('--adapt needs --synaptic')
+    if args.synaptic and args.learn_beta:
+        ap.error('--learn-beta is for be.lif_step: the synaptic neuron takes Python numbers')
     if not args.fused:
         train(args)
         return 0
-    print('fused neuron (be.lif_step' + (', learnable per-neuron beta):' if args.learn_beta else '):'))
-    fused = train(args, fused=True, learn_beta=args.learn_beta)
+    if args.synaptic:
+        print('fused neuron (be.synaptic_lif_step' + (', adaptive threshold' if args.adapt else '') + '; be.synaptic_lif_sequence readout):')
+    else:
+        print('fused neuron (be.lif_step' + (', learnable per-neuron beta):' if args.learn_beta else '):'))
+    fused = train(args, fused=True, learn_beta=args.learn_beta, synaptic=args.synaptic, adapt=args.adapt)
     print('hand-written neuron (torch elementwise ops), same start:')
     plain = train(args)
     print(f"end points: fused {fused[0]:.4f} -> {fused[1]:.4f}, hand-written {plain[0]:.4f} -> {plain[1]:.4f}")

@@ -200,6 +200,47 @@ int be_lif_sg_backward_params(const float* h_save, const float* v0, const float*
 int64_t be_lif_sg_reduce_slots_workspace_bytes(int64_t N, int64_t P);
 int be_lif_sg_reduce_slots(const float* slot, int64_t N, int64_t P, float* out, void* workspace, int64_t workspace_bytes,
                            be_stream_t stream);
+/* The differentiable neuron with a synaptic current and an optional adaptive threshold (brainevent_amd/csrc/be_neuron_sg_syn.hip):
+ * per slot a current c, a membrane v and, if adaptive, a trace a of the slot's own spikes that raises its threshold (ALIF / LSNN).
+ * T steps of N slots in ONE launch forwards and one backwards, as above.  Everything is f32; x, s_out, v_seq, h_save, th_save, g_s,
+ * g_vseq, g_x are [T, N] row-major, the others [N].  syn_decay, beta, v_th, v_reset, rho, kappa, alpha are doubles rounded to f32
+ * once on the host.  No FMA contraction (#pragma clang fp contract(off)): per slot i every operation is its own rounding, in
+ * exactly this order.
+ *   forward, t = 0 .. T-1, c = c0[i], v = v0[i], a = a0[i] (a NULL pointer means 0):
+ *     c  = (syn_decay * c) + x[t][i]
+ *     h  = (beta * v) + c
+ *     th = adaptive ? v_th + (kappa * a) : v_th
+ *     s  = h >= th                                          (a NaN does not spike)
+ *     v  = hard: s ? v_reset : h        soft: s ? h - v_th : h     (soft subtracts the BASE threshold, as Bellec et al. 2018)
+ *     a  = adaptive ? (rho * a) + (s ? 1 : 0) : unused
+ *     s_out[t][i] = s ? 1 : 0;  v_seq[t][i] = v (if given);  h_save[t][i] = h (if given);  th_save[t][i] = th (adaptive and h_save given)
+ *   after the loop  c_last[i] = c;  v_last[i] = v;  a_last[i] = a (adaptive)
+ *   backward, t = T-1 .. 0, carries cc = g_clast[i], cv = g_vlast[i], ca = g_alast[i] (NULL means 0).  Per step h = h_save[t][i],
+ *   th = adaptive ? th_save[t][i] : v_th, s = h >= th, u = h - th:
+ *     g_vo = cv + g_vseq[t][i]                              (the addition only if g_vseq is given)
+ *     sg   = the surrogate above at u (BE_LIF_SG_FAST_SIGMOID / _ATAN / _TRIANGLE: the same operations and constants)
+ *     g_sp = g_s[t][i] (NULL: 0);   adaptive: g_sp = g_sp + ca
+ *            unless detach_reset:   hard: g_sp = g_sp + g_vo * (v_reset - h)     soft: g_sp = g_sp - g_vo * v_th
+ *     g_u  = g_sp * sg
+ *     g_h  = g_u + (hard ? (s ? 0 : g_vo) : g_vo)
+ *     g_c  = cc + g_h;    g_x[t][i] = g_c
+ *     cc   = syn_decay * g_c;    cv = beta * g_h;    adaptive: ca = (rho * ca) - (kappa * g_u)
+ *   after the loop  g_c0[i] = cc;  g_v0[i] = cv;  g_a0[i] = ca   (each may be NULL)
+ * detach_reset cuts only the reset's path through the spike; the adaptation's path (+ ca) is always there.  With syn_decay = 0,
+ * adaptive = 0 and c0, g_clast zero the two passes are be_lif_sg_forward / be_lif_sg_backward (up to the sign of a zero sum).
+ * T == 0 or N == 0: BE_OK, nothing launched.  BE_ERR_INVALID: x, s_out, c_last, v_last / h_save, g_x NULL; adaptive with a_last
+ * NULL, with h_save given and th_save NULL (forward), with th_save NULL (backward); T < 0 or N < 0; an unknown reset_mode or
+ * surrogate; alpha <= 0.  With adaptive == 0 the five adaptation pointers (a0, th_save, a_last / th_save, g_alast, g_a0) are neither
+ * read nor written.  16-byte accesses when N % 4 == 0 and every given pointer is 16-byte aligned, 4-byte accesses otherwise; the
+ * results do not depend on which. */
+int be_lif_syn_sg_forward(const float* x, const float* c0, const float* v0, const float* a0, float* s_out, float* v_seq,
+                          float* h_save, float* th_save, float* c_last, float* v_last, float* a_last, int64_t T, int64_t N,
+                          double syn_decay, double beta, double v_th, double v_reset, double rho, double kappa, int reset_mode,
+                          int adaptive, be_stream_t stream);
+int be_lif_syn_sg_backward(const float* h_save, const float* th_save, const float* g_s, const float* g_vseq, const float* g_clast,
+                           const float* g_vlast, const float* g_alast, float* g_x, float* g_c0, float* g_v0, float* g_a0, int64_t T,
+                           int64_t N, double syn_decay, double beta, double v_th, double v_reset, double rho, double kappa,
+                           int reset_mode, int surrogate, double alpha, int adaptive, int detach_reset, be_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * event vector helpers (replace: brainevent/_jit_scalar/binary_jitsmv.cu:107-125 `_pack_bool_kern`
