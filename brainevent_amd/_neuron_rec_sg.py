@@ -1,0 +1,230 @@
+"""The fused recurrent spiking layer: :func:`~brainevent_amd.synaptic_lif_sequence`'s neuron with a sparse
+recurrent projection INSIDE the time loop, a whole sequence as ONE launch forwards and one backwards (``be_lif_rec_sg_forward`` /
+``be_lif_rec_sg_backward``, ``csrc/be_neuron_sg_rec.hip``) under ``torch.autograd``.
+
+    xin[t] = x[t] + s[t-1] @ rec          (s[-1] = s0, or no spike)
+    then synaptic_lif_step on xin[t]:  c' = syn_decay * c + xin;  h = beta * v + c';  th = v_th + kappa * a;  s = h >= th;  ...
+
+``rec`` is a :class:`~brainevent_amd.CSR` ``[N, N]`` whose rows are the presynaptic neurons, with one f32 weight per stored entry.
+One workgroup owns one sample and keeps its spikes on the chip between steps; the recurrent sums are 64-bit fixed-point integers
+(order independent), so the forward pass is a function of its inputs bit for bit and equals the per-step loop
+``synaptic_lif_step(state, x[t] + BinaryArray(s) @ rec)`` wherever that loop's own sums are exact.  The backward pass is that
+loop's: straight-through in the spikes for the recurrent product, the surrogate for the neuron; the weight gradient is the
+existing per-entry kernel (``be_grad_rows``) over all ``T * B`` spike rows at once.
+
+Not built: CSC / fixed-number / dense / JITC recurrences, one shared (homogeneous) weight, learnable neuron parameters, synaptic
+delays, more than 8192 neurons (one sample's sums and spike ids live in one workgroup's LDS), a sample split over several
+workgroups.  A cached scatter plan or mirror of ``rec`` is neither used nor needed: the kernels read the raw CSR arrays.
+"""
+import numbers
+from typing import Optional, Sequence, Tuple
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _array as A
+from . import _autograd
+from ._lib import call
+from ._neuron_sg import _check_device, _check_tensor, _grad_in
+from ._neuron_syn_sg import _Params, _check_state
+
+__all__ = ['recurrent_lif_sequence']
+
+#: kRecMaxN of csrc/be_neuron_sg_rec.hip
+MAX_N = 8192
+#: the exponents ``be_fixed_point_exponent`` returns
+SCALE_EXP_RANGE = (-90, 150)
+
+
+class _Rec:
+    """The CSR arrays as the kernels take them (a matrix without entries hands over one unused element: no NULL pointer)."""
+    __slots__ = ('w', 'indices', 'indptr', 'nse')
+
+    def __init__(self, w, indices, indptr):
+        self.nse = int(indices.numel())
+        self.w = w.reshape(-1) if self.nse else torch.zeros(1, dtype=torch.float32, device=indptr.device)
+        self.indices = indices if self.nse else torch.zeros(1, dtype=torch.int32, device=indptr.device)
+        self.indptr = indptr
+
+
+def _forward(x, r: _Rec, s0, c0, v0, a0, T: int, B: int, N: int, p: _Params, e: int, want_v: bool, want_h: bool):
+    """``be_lif_rec_sg_forward`` on contiguous ``x [T, B, N]``: ``(s, v_seq, h, th, c_last, v_last, a_last)``; what was not asked
+    for (and, without adaptation, ``th`` / ``a_last``) is None and neither allocated nor written."""
+    new = lambda: torch.empty((B, N), dtype=x.dtype, device=x.device)
+    s = torch.empty_like(x)
+    v_seq = torch.empty_like(x) if want_v else None
+    h = torch.empty_like(x) if want_h else None
+    th = torch.empty_like(x) if want_h and p.adaptive else None
+    c_last, v_last, a_last = new(), new(), (new() if p.adaptive else None)
+    if T == 0:                                # no step: the state passes through
+        for out, start in ((c_last, c0), (v_last, v0), (a_last, a0)):
+            if out is not None:
+                out.zero_() if start is None else out.copy_(start)
+    else:
+        call('be_lif_rec_sg_forward', A.ptr(x), A.ptr(r.w), A.ptr(r.indices), A.ptr(r.indptr), A.ptr(s0), A.ptr(c0), A.ptr(v0),
+             A.ptr(a0), A.ptr(s), A.ptr(v_seq), A.ptr(h), A.ptr(th), A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N,
+             p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.adaptive, e, A.stream_ptr())
+    return s, v_seq, h, th, c_last, v_last, a_last
+
+
+def _backward(h, th, r: _Rec, g_s, g_vseq, g_last, T: int, B: int, N: int, p: _Params, want):
+    """``be_lif_rec_sg_backward``: ``(g_x, g_c0, g_v0, g_a0, g_s0)``.  A gradient that is None goes in as NULL; a state or ``s0``
+    gradient is None unless ``want`` asks for it."""
+    g_x = torch.empty_like(h)
+    g_state = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in want]
+    if T == 0:
+        for out, g in zip(g_state[:3], g_last):
+            if out is not None:
+                out.zero_() if g is None else out.copy_(g)
+        if g_state[3] is not None:
+            g_state[3].zero_()
+    else:
+        call('be_lif_rec_sg_backward', A.ptr(h), A.ptr(th), A.ptr(r.w), A.ptr(r.indices), A.ptr(r.indptr), A.ptr(g_s), A.ptr(g_vseq),
+             A.ptr(g_last[0]), A.ptr(g_last[1]), A.ptr(g_last[2]), A.ptr(g_x), A.ptr(g_state[0]), A.ptr(g_state[1]), A.ptr(g_state[2]),
+             A.ptr(g_state[3]), T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.surrogate, p.alpha,
+             p.adaptive, p.detach_reset, A.stream_ptr())
+    return (g_x,) + tuple(g_state)
+
+
+def _weight_grad(w, r: _Rec, s, s0, g_x, T: int, B: int, N: int) -> torch.Tensor:
+    """``g_w[k] = sum over t, b of sp[t][b][row k] * g_x[t][b][col k]`` with ``sp = cat(s0, s[:-1])``: ``be_grad_rows`` (the
+    ``transpose=True`` side) over ``T * B`` batch rows — ``(T - 1) * B`` without ``s0`` — in ascending order; ``g_x`` is read
+    batch-major through the stride arguments, nothing is transposed."""
+    if T == 0 or r.nse == 0:
+        return torch.zeros_like(w)
+    if s0 is None:
+        sp, g = s[:T - 1], g_x[1:]
+    else:
+        sp, g = torch.cat(((s0 != 0).to(s.dtype)[None], s[:T - 1])), g_x
+    nb = int(sp.shape[0]) * B
+    if nb == 0:
+        return torch.zeros_like(w)
+    mask, _ = _autograd.activity(sp.reshape(nb, N), 'bm')
+    dw = torch.empty(r.nse, dtype=w.dtype, device=w.device)
+    g = g.contiguous()
+    call('be_grad_rows', 1, A.ptr(dw), 0, A.wcode(dw), A.ptr(r.indices), A.ptr(r.indptr), 0, -1, N, r.nse, A.ptr(mask), nb, A.ptr(g),
+         1, N, A.ptr(None), 0, A.stream_ptr())
+    return dw.reshape(w.shape)
+
+
+class RecurrentLifSequence(torch.autograd.Function):
+    """Outputs ``s, [v_seq,] c_last, v_last [, a_last]``.  Saved: ``h``, ``th`` when adaptive, ``s`` (the weight gradient's
+    activity), the weights and ``s0``.  The gradient of an output nobody used arrives as None (``set_materialize_grads(False)``)
+    and goes in as NULL."""
+
+    @staticmethod
+    def forward(ctx, x, c0, v0, a0, s0, w, r: _Rec, dims, p: _Params, e: int, return_v: bool):
+        ctx.set_materialize_grads(False)
+        T, B, N = dims
+        s, v_seq, h, th, c_last, v_last, a_last = _forward(x, r, s0, c0, v0, a0, T, B, N, p, e, return_v, True)
+        ctx.save_for_backward(h, th, s, w, s0)
+        ctx.meta = (r, dims, p, return_v)
+        return tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_s, *rest):
+        r, (T, B, N), p, return_v = ctx.meta
+        g_vseq = rest[0] if return_v else None
+        g_last = list(rest[1:] if return_v else rest) + [None] * (3 - p.entries)
+        if g_s is None and g_vseq is None and all(g is None for g in g_last):
+            return (None,) * 11
+        h, th, s, w, s0 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = [need[1], need[2], bool(p.adaptive) and need[3], need[4]]
+        g_x, g_c0, g_v0, g_a0, g_s0 = _backward(h, th, r, _grad_in(g_s), _grad_in(g_vseq), [_grad_in(g) for g in g_last], T, B, N, p,
+                                                want)
+        g_w = _weight_grad(w, r, s, s0, g_x, T, B, N) if need[5] else None
+        return (g_x if need[0] else None), g_c0, g_v0, g_a0, g_s0, g_w, None, None, None, None, None
+
+
+def _check_rec(who, rec, n: int):
+    from ._csr import CSR
+    if not isinstance(rec, CSR):
+        raise TypeError(f"{who}: rec must be a CSR matrix (rows = presynaptic neurons), not {type(rec).__name__}; CSC, fixed-number, "
+                        f"dense, JITC and planned matrices are not built.")
+    if rec.shape[0] != rec.shape[1]:
+        raise ValueError(f"{who}: rec {tuple(rec.shape)} must be square (a recurrent projection).")
+    if rec.shape[0] != n:
+        raise ValueError(f"{who}: rec {tuple(rec.shape)} must have the size of x's last axis, {n}.")
+    if rec.data.dtype != torch.float32:
+        raise TypeError(f"{who}: the weights of rec must be float32, not {rec.data.dtype}.")
+    nse = int(rec.indices.numel())
+    if rec.data.numel() != nse:
+        raise ValueError(f"{who}: rec must hold one weight per stored entry ({nse}), not {rec.data.numel()} (one shared weight is not "
+                         f"built).")
+    if rec.indptr.dtype != torch.int32:
+        raise TypeError(f"{who}: the indptr of rec must be int32, not {rec.indptr.dtype}.")
+    if n > MAX_N:
+        raise ValueError(f"{who}: {n} neurons; the limit is {MAX_N} (one sample's sums and spike ids live in one workgroup's LDS).")
+
+
+def _scale_exp(who, scale_exp, rec, n: int) -> int:
+    if scale_exp is None:
+        if rec.indices.numel() == 0 or n == 0:
+            return 0
+        from ._csr import fixed_point_exponent
+        return fixed_point_exponent(rec.data.detach(), rec.indices, n)
+    if isinstance(scale_exp, bool) or not isinstance(scale_exp, numbers.Integral):
+        raise TypeError(f"{who}: scale_exp must be None or an int, not {type(scale_exp).__name__}.")
+    if not SCALE_EXP_RANGE[0] <= scale_exp <= SCALE_EXP_RANGE[1]:
+        raise ValueError(f"{who}: scale_exp {scale_exp} is outside {SCALE_EXP_RANGE[0]} .. {SCALE_EXP_RANGE[1]}, the exponents "
+                         f"fixed_point_exponent returns.")
+    return int(scale_exp)
+
+
+def recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                           s0: Optional[torch.Tensor] = None, *, syn_decay: float = 0.0, beta: float, v_th: float = 1.0,
+                           v_reset: float = 0.0, reset: str = 'hard', surrogate: str = 'fast_sigmoid', alpha: float = 10.0,
+                           detach_reset: bool = False, adapt: Optional[Tuple[float, float]] = None, return_v: bool = False,
+                           scale_exp: Optional[int] = None):
+    """A recurrent layer of current-based leaky integrate-and-fire neurons over a whole input sequence, one launch forwards and
+    one backwards: at every step the input of :func:`synaptic_lif_step` is ``x[t] + s[t-1] @ rec`` — the previous step's spikes
+    through the sparse recurrent projection ``rec`` (a :class:`CSR` ``[N, N]``, rows = presynaptic neurons, one f32 weight per
+    stored entry; duplicate columns, self-loops and empty rows are allowed).  ``x`` is ``[T, B, N]`` (or ``[T, N]``: one sample);
+    ``state0`` (None, or a None entry: zeros) and the returned state are ``(c, v)``, or ``(c, v, a)`` with ``adapt=(rho, kappa)``,
+    each ``[B, N]``; ``s0 [B, N]`` (f32, active where ``!= 0``; None: no spike) are the spikes before step 0.  Returns
+    ``(s [T, B, N], state_last)``, or ``(s, v_seq, state_last)`` with ``return_v``.  ``syn_decay=0`` is the plain LIF.  The neuron's
+    parameters, surrogates and ``detach_reset`` are :func:`synaptic_lif_sequence`'s; ``detach_reset`` does not cut the recurrent path.
+
+    The recurrent sums are 64-bit fixed-point integers at the exponent ``scale_exp``, so the forward pass is a function of its
+    inputs bit for bit.  ``scale_exp=None`` asks :func:`~brainevent_amd._csr.fixed_point_exponent` for it on every call — its
+    bound, every row active, is exactly this kernel's worst case — which costs ONE HOST SYNCHRONISATION per call and cannot run
+    under graph capture.  An ``int`` (for instance that function's answer, computed once; still valid while no column's sum of
+    ``|w|`` grows past the next power of two) is used as given: no synchronisation, usable under ``capture_step``.
+
+    Differentiable, once, in ``x``, every given state entry, ``s0`` and ``rec.data`` through ``s``, ``v_seq`` and the returned
+    state: straight-through in the spikes for the recurrent product (as ``BinaryArray(s) @ rec``), the surrogate for the neuron.
+    ``rec.data`` is read from device memory on every call: an in-place update is seen by the next call.
+
+    Not built: CSC / fixed-number / dense / JITC recurrences, one shared weight, learnable neuron parameters, delays, ``N > 8192``,
+    a sample split over several workgroups (only ``B`` of the chip's compute units work)."""
+    who = 'recurrent_lif_sequence'
+    p = _Params(who, syn_decay, beta, v_th, v_reset, reset, surrogate, alpha, detach_reset, adapt)
+    _check_tensor(who, 'x', x)
+    if x.ndim not in (2, 3):
+        raise ValueError(f"{who}: x must be [T, B, N] or [T, N], not {x.ndim}-dimensional.")
+    slots = tuple(x.shape[1:])
+    T, N = int(x.shape[0]), int(x.shape[-1])
+    B = int(x.shape[1]) if x.ndim == 3 else 1
+    _check_rec(who, rec, N)
+    state = _check_state(who, 'state0', state0, p, slots, allow_none=True)
+    if s0 is not None:
+        _check_tensor(who, 's0', s0)
+        if tuple(s0.shape) != slots:
+            raise ValueError(f"{who}: s0 {tuple(s0.shape)} must have the shape of a step of x, {slots}.")
+    _check_device(who, x=x, s0=s0, **{f'state0 entry {k}': t for k, t in zip('cva', state)})
+    e = _scale_exp(who, scale_exp, rec, N)
+
+    w = rec.data
+    r = _Rec(w.detach(), rec.indices, rec.indptr)
+    x3 = x.contiguous().reshape(T, B, N)
+    c0, v0, a0, sp = (None if t is None else t.contiguous().reshape(B, N) for t in state + (s0,))
+    return_v = bool(return_v)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x3, c0, v0, a0, sp, w)):
+        outs = RecurrentLifSequence.apply(x3, c0, v0, a0, sp, w, r, (T, B, N), p, e, return_v)
+    else:                                     # no backward pass: h / th are not kept
+        s, v_seq, _, _, c_last, v_last, a_last = _forward(x3, r, sp, c0, v0, a0, T, B, N, p, e, return_v, False)
+        outs = tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
+    k = 2 if return_v else 1
+    return tuple(o.reshape(x.shape) for o in outs[:k]) + (tuple(o.reshape(slots) for o in outs[k:]),)

@@ -7,7 +7,7 @@ spike function is a Heaviside step in the forward pass and a fast-sigmoid deriva
 for the spikes, per-synapse for the weights.  The task is synthetic and generated here: each of two input patterns must drive
 its own readout unit.  Trained with ``torch.optim.SGD``; the loss falls.
 
-    python examples/surrogate_csr.py [--steps 60] [--fused [--learn-beta | --synaptic [--adapt]]]
+    python examples/surrogate_csr.py [--steps 60] [--fused [--learn-beta | --synaptic [--adapt] [--fused-recurrent]]]
 
 ``--fused`` replaces the hand-written neuron (about six elementwise launches forwards and twice that backwards per time step) by
 ``be.lif_step`` (one launch each way; the same leak, threshold, hard reset to 0 and fast-sigmoid surrogate, the reset's gradient
@@ -17,7 +17,9 @@ weights: ``be.lif_step`` reads it on the device and hands back its gradient, sum
 ``--synaptic`` (with ``--fused``) puts a synaptic current in front of the membrane: ``be.synaptic_lif_step`` in the recurrent loop,
 its state the tuple ``(c, v)``, and the readout becomes a feed-forward layer of non-spiking leaky integrators — all ``T`` readout
 currents through one ``be.synaptic_lif_sequence`` with ``v_th=inf``, the mean membrane as the logits.  ``--adapt`` (with
-``--synaptic``) adds the adaptive threshold (``adapt=(rho, kappa)``, state ``(c, v, a)``).
+``--synaptic``) adds the adaptive threshold (``adapt=(rho, kappa)``, state ``(c, v, a)``).  ``--fused-recurrent`` (with ``--synaptic``)
+runs the whole recurrent layer — all ``T`` steps, the recurrent product included — as ONE ``be.recurrent_lif_sequence`` call and
+the readout product once over all ``T * batch`` spike rows.
 """
 import argparse
 import os
@@ -45,7 +47,7 @@ class SpikeFn(torch.autograd.Function):
         return g / (1.0 + 10.0 * (v - 1.0).abs()) ** 2
 
 
-def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False):
+def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False, fused_recurrent=False):
     dev = torch.device('cuda')
     rng = np.random.default_rng(0)
     torch.manual_seed(0)
@@ -70,6 +72,12 @@ def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False):
         v = torch.zeros(batch, n, device=dev)
         s = torch.zeros(batch, n, device=dev)
         acc = torch.zeros(batch, n_out, device=dev)
+        if fused_recurrent:                                             # the recurrent layer as one launch each way
+            x = ((1.0 - syn_decay) * drive).expand(args.T, batch, n)
+            s_all, _ = be.recurrent_lif_sequence(x, rec, syn_decay=syn_decay, beta=0.9, v_th=1.0, adapt=(0.95, 0.3) if adapt else None)
+            out = (be.BinaryArray(s_all.reshape(args.T * batch, n)) @ readout).reshape(args.T, batch, n_out)
+            _, v_seq, _ = be.synaptic_lif_sequence(out, syn_decay=syn_decay, beta=0.9, v_th=float('inf'), return_v=True)
+            return v_seq.mean(0) * (1.0 - syn_decay) * (1.0 - 0.9)
         if synaptic:                                                    # current, membrane (and spike trace): one launch per step
             state = tuple(torch.zeros(batch, n, device=dev) for _ in range(3 if adapt else 2))
             out = []
@@ -121,7 +129,11 @@ def main():
     ap.add_argument('--synaptic', action='store_true',
                     help='with --fused: a synaptic current in front of the membrane (be.synaptic_lif_step) and a leaky-integrator readout')
     ap.add_argument('--adapt', action='store_true', help='with --synaptic: an adaptive threshold (adapt=(rho, kappa))')
+    ap.add_argument('--fused-recurrent', action='store_true',
+                    help='with --synaptic: the whole recurrent layer as one launch (be.recurrent_lif_sequence)')
     args = ap.parse_args()
+    if args.fused_recurrent and not args.synaptic:
+        ap.error('--fused-recurrent needs --fused --synaptic (it is the synaptic neuron with the recurrence inside)')
     if args.learn_beta and not args.fused:
         ap.error('--learn-beta needs --fused (the hand-written neuron keeps its constant leak)')
     if args.synaptic and not args.fused:
@@ -134,10 +146,12 @@ def main():
         train(args)
         return 0
     if args.synaptic:
-        print('fused neuron (be.synaptic_lif_step' + (', adaptive threshold' if args.adapt else '') + '; be.synaptic_lif_sequence readout):')
+        print('fused neuron (' + ('be.recurrent_lif_sequence' if args.fused_recurrent else 'be.synaptic_lif_step') +
+              (', adaptive threshold' if args.adapt else '') + '; be.synaptic_lif_sequence readout):')
     else:
         print('fused neuron (be.lif_step' + (', learnable per-neuron beta):' if args.learn_beta else '):'))
-    fused = train(args, fused=True, learn_beta=args.learn_beta, synaptic=args.synaptic, adapt=args.adapt)
+    fused = train(args, fused=True, learn_beta=args.learn_beta, synaptic=args.synaptic, adapt=args.adapt,
+                  fused_recurrent=args.fused_recurrent)
     print('hand-written neuron (torch elementwise ops), same start:')
     plain = train(args)
     print(f"end points: fused {fused[0]:.4f} -> {fused[1]:.4f}, hand-written {plain[0]:.4f} -> {plain[1]:.4f}")

@@ -241,6 +241,43 @@ int be_lif_syn_sg_backward(const float* h_save, const float* th_save, const floa
                            const float* g_vlast, const float* g_alast, float* g_x, float* g_c0, float* g_v0, float* g_a0, int64_t T,
                            int64_t N, double syn_decay, double beta, double v_th, double v_reset, double rho, double kappa,
                            int reset_mode, int surrogate, double alpha, int adaptive, int detach_reset, be_stream_t stream);
+/* The recurrent spiking layer (brainevent_amd/csrc/be_neuron_sg_rec.hip): the neuron above with a CSR recurrence INSIDE the time
+ * loop — step t's input is x[t] + s[t-1] @ W_rec.  One launch forwards, one backwards; one workgroup per sample.  x, s_out, v_seq,
+ * h_save, th_save, g_s, g_vseq, g_x are [T, B, N] row-major; s0, c0, v0, a0, the *_last, g_c0, g_v0, g_a0, g_s0 are [B, N].  The
+ * matrix is CSR [N, N], rows = presynaptic neurons: w (f32, one per stored entry), indices (int32 columns), indptr (int32 [N + 1]);
+ * duplicate columns in a row, self-loops and empty rows are allowed.  scale_exp = e is the fixed-point exponent of the sums
+ * (be_fixed_point_exponent's bound — every row active — is this kernel's worst case): scale = ldexpf(1, e - 32), inv = ldexp(1.0, -e).
+ *   forward, for every sample b independently, t = 0 .. T-1, sp = s0[b] (NULL: no spike) before step 0 and s_out[t-1][b] after it:
+ *     R[j] = sum over the stored entries k whose row i has sp[i] != 0 and whose column is j of fixed(w[k])
+ *            fixed(w): t = w * scale;  hf = floor(t);  ((int64)(int32)hf << 32) | (uint32)((t - hf) * 2^32)
+ *            (a 64-bit wrapping integer sum: order independent)
+ *     r[j] = (float)((double)(int64)R[j] * inv)
+ *     xin  = x[t][b][j] + r[j]              (one rounded f32 addition; when no row is active r = +0 and the addition is still made)
+ *     then the forward step above, verbatim, with xin in the place of x[t][i]
+ *   The forward pass is therefore a function of its inputs, bit for bit.
+ *   backward, t = T-1 .. 0, the carries cc, cv, ca as above; G[.] = g_x[t+1][b][.], which the previous iteration produced:
+ *     g_rec = t < T-1 ? sum over the entries k of row i of w[k] * G[indices[k]] : not used
+ *             (each product rounded, then summed in f32 in an order the row's length alone fixes: lane j of 16 takes the entries
+ *             j, j + 16, ... in order, then a butterfly over the 16 partial sums)
+ *     g_sp  = g_s[t][b][i] (NULL: 0);   if t < T-1: g_sp = g_sp + g_rec;   then the backward step above continues unchanged
+ *             (adaptive: + ca; the reset term unless detach_reset; g_u, g_h, g_c; g_x[t][b][i] = g_c; the three carries)
+ *   after the loop g_c0, g_v0, g_a0 as above;  g_s0[b][i] = sum over row i of w[k] * g_x[0][b][indices[k]]   (if given)
+ *   g_x[t] is the gradient of x[t] and of r[t] alike (straight-through in the spikes, as the event-driven products); detach_reset
+ *   does not cut the recurrent path.  The weight gradient is be_grad_rows (transpose = 1) over the T * B batch rows
+ *   sp[t][b] / g_x[t][b], with g_sn = 1, g_sb = N.
+ * T == 0, B == 0 or N == 0: BE_OK, nothing launched.  BE_ERR_RANGE: N > 8192 (one sample's sums and spike ids live in one
+ * workgroup's LDS).  BE_ERR_INVALID: the codes above; B < 0; w, indices or indptr NULL; scale_exp outside -90 .. 150 (what
+ * be_fixed_point_exponent returns).  Every index must lie in [0, N).  No global atomics; never synchronises the host. */
+int be_lif_rec_sg_forward(const float* x, const float* w, const int32_t* indices, const int32_t* indptr, const float* s0,
+                          const float* c0, const float* v0, const float* a0, float* s_out, float* v_seq, float* h_save,
+                          float* th_save, float* c_last, float* v_last, float* a_last, int64_t T, int64_t B, int64_t N,
+                          double syn_decay, double beta, double v_th, double v_reset, double rho, double kappa, int reset_mode,
+                          int adaptive, int scale_exp, be_stream_t stream);
+int be_lif_rec_sg_backward(const float* h_save, const float* th_save, const float* w, const int32_t* indices, const int32_t* indptr,
+                           const float* g_s, const float* g_vseq, const float* g_clast, const float* g_vlast, const float* g_alast,
+                           float* g_x, float* g_c0, float* g_v0, float* g_a0, float* g_s0, int64_t T, int64_t B, int64_t N,
+                           double syn_decay, double beta, double v_th, double v_reset, double rho, double kappa, int reset_mode,
+                           int surrogate, double alpha, int adaptive, int detach_reset, be_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * event vector helpers (replace: brainevent/_jit_scalar/binary_jitsmv.cu:107-125 `_pack_bool_kern`
