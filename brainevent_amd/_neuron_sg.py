@@ -11,7 +11,7 @@ The reset carries a gradient through the spike too unless ``detach_reset``.  Eve
 rounded f32 operation in the order the header states, so the results equal the elementwise formulation bit for bit.
 
 ``beta`` and ``v_th`` are Python numbers (one constant for the population: the entry points above) or f32 device tensors
-(``be_lif_sg_forward_params`` / ``be_lif_sg_backward_params``, ``csrc/be_neuron_sg_param.hip``): one element for a
+(``be_lif_sg_forward_params`` / ``be_lif_sg_backward_params``, the same ``csrc/be_neuron_sg.hip``): one element for a
 shared value, or the shape of the last dimensions of a step for a value per neuron, broadcast over the leading (batch)
 dimensions.  The kernels read them from device memory — no value crosses to the host, so an optimiser's in-place update is seen
 by the next call and by the next replay of a captured graph — and a tensor that requires grad gets its gradient: per-slot sums

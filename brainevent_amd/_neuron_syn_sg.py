@@ -1,6 +1,6 @@
 """The differentiable neuron with a synaptic current and an optional adaptive threshold: a current-based leaky
 integrate-and-fire step, and a whole input sequence of them, as ONE launch forwards and one backwards (``be_lif_syn_sg_forward`` /
-``be_lif_syn_sg_backward``, ``csrc/be_neuron_sg_syn.hip``), under ``torch.autograd`` with a surrogate gradient for the spike.
+``be_lif_syn_sg_backward``, ``csrc/be_neuron_sg.hip``), under ``torch.autograd`` with a surrogate gradient for the spike.
 
     c' = syn_decay * c + x;   h = beta * v + c';   th = v_th + kappa * a  (no adaptation: v_th);   s = h >= th
     v' = v_reset if s else h   (reset='soft': h - v_th if s else h — the BASE threshold);   a' = rho * a + s

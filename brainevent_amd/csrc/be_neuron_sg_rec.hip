@@ -1,6 +1,7 @@
-// be_neuron_sg_rec.hip — the differentiable recurrent spiking layer: §2.21's neuron (be_neuron_sg_syn.hip) with
-// a CSR recurrence INSIDE the time loop.  Step t's input is x[t] + s[t-1] @ W_rec, so the T steps of a sample are one dependent
-// chain through all of its N neurons: one workgroup owns one sample for the whole launch and keeps its spikes on the chip.
+// be_neuron_sg_rec.hip — the differentiable recurrent spiking layer: §2.21's neuron (the step of be_sg_lane.h,
+// as be_neuron_sg.hip runs it per slot) with a CSR recurrence INSIDE the time loop.  Step t's input is x[t] + s[t-1] @ W_rec, so
+// the T steps of a sample are one dependent chain through all of its N neurons: one workgroup owns one sample for the whole
+// launch and keeps its spikes on the chip.
 //
 // Forwards (k_lif_rec_forward), per step: the previous step's spikes — one bit per owned neuron, in registers — are compacted into
 // an id list in LDS (ballot / popcount, as k_compact_spikes); the listed rows are walked kRecRowLanes lanes per row and scattered
@@ -37,11 +38,6 @@ __device__ __forceinline__ RowSpan row_span(const int32_t* __restrict__ indptr, 
   return RowSpan{indptr[row], indptr[row + 1]};
 }
 
-struct LifRecP {
-  float syn_decay, beta, v_th, v_reset, rho, kappa;
-  lane::Surrogate sur;
-};
-
 // Forward.  x, s_out, v_seq, h_save, th_save are [T, B, N]; s0, c0, v0, a0 and the *_last [B, N].  s0 / c0 / v0 / a0 NULL = 0;
 // v_seq / h_save / th_save may be NULL.  Dynamic LDS: N 64-bit sums, then N ids.
 template <bool HARD, bool ADAPT>
@@ -50,7 +46,7 @@ k_lif_rec_forward(const float* __restrict__ x, const float* __restrict__ w, cons
                   const int32_t* __restrict__ indptr, const float* __restrict__ s0, const float* __restrict__ c0,
                   const float* __restrict__ v0, const float* __restrict__ a0, float* __restrict__ s_out, float* __restrict__ v_seq,
                   float* __restrict__ h_save, float* __restrict__ th_save, float* __restrict__ c_last, float* __restrict__ v_last,
-                  float* __restrict__ a_last, int64_t T, int64_t B, int N, float scale, double inv, LifRecP p) {
+                  float* __restrict__ a_last, int64_t T, int64_t B, int N, float scale, double inv, lane::LifP p) {
 #pragma clang fp contract(off)
   extern __shared__ __align__(16) unsigned char smem_raw[];
   unsigned long long* acc = reinterpret_cast<unsigned long long*>(smem_raw);
@@ -139,19 +135,13 @@ k_lif_rec_forward(const float* __restrict__ x, const float* __restrict__ w, cons
         const unsigned long long R = acc[i];
         acc[i] = 0ull;                                   // read and cleared by its owner only: no barrier in between
         const float r = (float)((double)(long long)R * inv);
-        const float xin = xv[k] + r;
-        c[k] = (p.syn_decay * c[k]) + xin;
-        const float h = (p.beta * v[k]) + c[k];
-        const float th = ADAPT ? p.v_th + (p.kappa * a[k]) : p.v_th;
-        const bool s = h >= th;
-        v[k] = HARD ? (s ? p.v_reset : h) : (s ? h - p.v_th : h);
-        if (ADAPT) a[k] = (p.rho * a[k]) + (s ? 1.0f : 0.0f);
-        if (s) sbits |= 1u << k;
-        s_out[at + i] = s ? 1.0f : 0.0f;
+        const lane::Fired f = lane::forward_step<HARD, true, ADAPT>(xv[k] + r, c[k], v[k], a[k], p.beta, p.v_th, p);
+        if (f.s) sbits |= 1u << k;
+        s_out[at + i] = f.s ? 1.0f : 0.0f;
         if (v_seq != nullptr) v_seq[at + i] = v[k];
         if (h_save != nullptr) {
-          h_save[at + i] = h;
-          if (ADAPT) th_save[at + i] = th;
+          h_save[at + i] = f.h;
+          if (ADAPT) th_save[at + i] = f.th;
         }
       }
     }
@@ -210,7 +200,7 @@ k_lif_rec_backward(const float* __restrict__ h_save, const float* __restrict__ t
                    const int32_t* __restrict__ indices, const int32_t* __restrict__ indptr, const float* __restrict__ g_s,
                    const float* __restrict__ g_vseq, const float* __restrict__ g_clast, const float* __restrict__ g_vlast,
                    const float* __restrict__ g_alast, float* __restrict__ g_x, float* __restrict__ g_c0, float* __restrict__ g_v0,
-                   float* __restrict__ g_a0, float* __restrict__ g_s0, int64_t T, int64_t B, int N, int detach_reset, LifRecP p) {
+                   float* __restrict__ g_a0, float* __restrict__ g_s0, int64_t T, int64_t B, int N, int detach_reset, lane::LifP p) {
 #pragma clang fp contract(off)
   extern __shared__ __align__(16) unsigned char smem_raw[];
   float* G = reinterpret_cast<float*>(smem_raw);
@@ -252,25 +242,14 @@ k_lif_rec_backward(const float* __restrict__ h_save, const float* __restrict__ t
     for (int k = 0; k < kRecPerThread; ++k) {
       const int i = tid + k * kRecThreads;
       if (i < N) {
-        const float h = hv[k];
-        const float th = ADAPT ? tv[k] : p.v_th;
-        const bool s = h >= th;
-        const float u = h - th;
         float g_vo = cv[k];
         if (g_vseq != nullptr) g_vo = g_vo + gvv[k];
-        const float sg = lane::derivative<SG>(u, p.sur);
         float g_sp = gsv[k];                             // 0 when g_s is NULL
         if (rec) g_sp = g_sp + grec[i];
-        if (ADAPT) g_sp = g_sp + ca[k];
-        if (!detach_reset) g_sp = HARD ? g_sp + g_vo * (p.v_reset - h) : g_sp - g_vo * p.v_th;
-        const float g_u = g_sp * sg;
-        const float g_h = g_u + (HARD ? (s ? 0.0f : g_vo) : g_vo);
-        const float g_c = cc[k] + g_h;
+        const lane::Grad d = lane::backward_step<HARD, SG, ADAPT>(hv[k], ADAPT ? tv[k] : p.v_th, p.v_th, g_sp, g_vo, ca[k], detach_reset, p);
+        const float g_c = lane::backward_carry<true, ADAPT>(d, cc[k], cv[k], ca[k], p.beta, p);
         g_x[at + i] = g_c;
         G[i] = g_c;
-        cc[k] = p.syn_decay * g_c;
-        cv[k] = p.beta * g_h;
-        if (ADAPT) ca[k] = (p.rho * ca[k]) - (p.kappa * g_u);
       }
     }
     __syncthreads();
@@ -321,7 +300,7 @@ int be_lif_rec_sg_forward(const float* x, const float* w, const int32_t* indices
   const bool adapt = adaptive != 0;
   BE_REQUIRE(!adapt || a_last, BE_ERR_INVALID, "null pointer (adaptive: a_last is required)");
   BE_REQUIRE(!adapt || !h_save || th_save, BE_ERR_INVALID, "null pointer (adaptive: th_save is required where h_save is given)");
-  const LifRecP p{(float)syn_decay, (float)beta, (float)v_th, (float)v_reset, (float)rho, (float)kappa, lane::make_surrogate(1.0)};
+  const lane::LifP p = lane::make_params(syn_decay, beta, v_th, v_reset, rho, kappa, 1.);
   const bool hard = reset_mode == BE_LIF_RESET_HARD;
   if (!adapt) a0 = nullptr, th_save = nullptr, a_last = nullptr;          // neither read nor written, whatever was passed
   const float scale = ldexpf(1.0f, scale_exp - 32);   // see fixed_from_f32
@@ -350,16 +329,13 @@ int be_lif_rec_sg_backward(const float* h_save, const float* th_save, const floa
                            double syn_decay, double beta, double v_th, double v_reset, double rho, double kappa, int reset_mode,
                            int surrogate, double alpha, int adaptive, int detach_reset, be_stream_t stream) {
   if (const int rc = rec_check_common(__func__, T, B, N, reset_mode)) return rc;
-  BE_REQUIRE(surrogate == BE_LIF_SG_FAST_SIGMOID || surrogate == BE_LIF_SG_ATAN || surrogate == BE_LIF_SG_TRIANGLE, BE_ERR_INVALID,
-             "unknown surrogate");
-  BE_REQUIRE(alpha > 0., BE_ERR_INVALID, "alpha must be positive");
+  if (const int rc = lane::check_surrogate(__func__, surrogate, alpha)) return rc;
   if (T == 0 || B == 0 || N == 0) return BE_OK;
   BE_REQUIRE(h_save && g_x, BE_ERR_INVALID, "null pointer (h_save and g_x are required)");
   BE_REQUIRE(w && indices && indptr, BE_ERR_INVALID, "null pointer (w, indices and indptr are required)");
   const bool adapt = adaptive != 0;
   BE_REQUIRE(!adapt || th_save, BE_ERR_INVALID, "null pointer (adaptive: th_save is required)");
-  // derived constants in double, rounded to f32 once
-  const LifRecP p{(float)syn_decay, (float)beta, (float)v_th, (float)v_reset, (float)rho, (float)kappa, lane::make_surrogate(alpha)};
+  const lane::LifP p = lane::make_params(syn_decay, beta, v_th, v_reset, rho, kappa, alpha);
   const bool hard = reset_mode == BE_LIF_RESET_HARD;
   if (!adapt) th_save = nullptr, g_alast = nullptr, g_a0 = nullptr;       // neither read nor written, whatever was passed
   const int lds = (int)be_align_up(N * 8, 16);

@@ -167,8 +167,8 @@ int be_lif_sg_forward(const float* x, const float* v0, float* s_out, float* v_se
 int be_lif_sg_backward(const float* h_save, const float* g_s, const float* g_vseq, const float* g_vlast, float* g_x, float* g_v0,
                        int64_t T, int64_t N, double beta, double v_th, double v_reset, int reset_mode, int surrogate, double alpha,
                        int detach_reset, be_stream_t stream);
-/* The same neuron with beta and v_th read from DEVICE memory (brainevent_amd/csrc/be_neuron_sg_param.hip): each is an f32 array
- * with a period P >= 1 that divides N, and slot i of a step uses beta[i % beta_period], v_th[i % vth_period] (P = 1: one shared
+/* The same neuron with beta and v_th read from DEVICE memory (brainevent_amd/csrc/be_neuron_sg.hip; the reduce:
+ * be_neuron_sg_reduce.hip): each is an f32 array with a period P >= 1 that divides N, and slot i of a step uses beta[i % beta_period], v_th[i % vth_period] (P = 1: one shared
  * value; P = N / R: one value per neuron under R leading batch rows).  No value crosses to the host: a parameter updated in place
  * is seen by the next call and by the next replay of a captured graph.  v_reset and alpha stay host scalars.
  *   forward: the forward pass above with beta_i, th_i in place of the two constants — the same operations, order and roundings.
@@ -200,7 +200,7 @@ int be_lif_sg_backward_params(const float* h_save, const float* v0, const float*
 int64_t be_lif_sg_reduce_slots_workspace_bytes(int64_t N, int64_t P);
 int be_lif_sg_reduce_slots(const float* slot, int64_t N, int64_t P, float* out, void* workspace, int64_t workspace_bytes,
                            be_stream_t stream);
-/* The differentiable neuron with a synaptic current and an optional adaptive threshold (brainevent_amd/csrc/be_neuron_sg_syn.hip):
+/* The differentiable neuron with a synaptic current and an optional adaptive threshold (brainevent_amd/csrc/be_neuron_sg.hip):
  * per slot a current c, a membrane v and, if adaptive, a trace a of the slot's own spikes that raises its threshold (ALIF / LSNN).
  * T steps of N slots in ONE launch forwards and one backwards, as above.  Everything is f32; x, s_out, v_seq, h_save, th_save, g_s,
  * g_vseq, g_x are [T, N] row-major, the others [N].  syn_decay, beta, v_th, v_reset, rho, kappa, alpha are doubles rounded to f32

@@ -1,7 +1,7 @@
 """Shared by tests/test_lif_sg_param_cpu.py and tests/test_lif_sg_param_gpu.py: the numpy restatement of the differentiable LIF
 neuron with ``beta`` and ``v_th`` as periodic per-slot arrays (include/brainevent_amd.h, be_lif_sg_forward_params /
-be_lif_sg_backward_params / be_lif_sg_reduce_slots; csrc/be_neuron_sg_param.hip), the CONSTS table the GPU sizes are taken from
-(the CPU test holds it against the source text), and the bounds the comparisons use.
+be_lif_sg_backward_params / be_lif_sg_reduce_slots; csrc/be_neuron_sg.hip, be_neuron_sg_reduce.hip), the CONSTS table the GPU sizes
+are taken from (the CPU test holds it against the source text), and the bounds the comparisons use.
 
 It builds on tests/lif_sg_cases.py (``Params`` for the host scalars, ``surrogate``, ``same_bits``, ``inputs``) and adds the periods,
 the two per-slot accumulators of the parameters' gradients and the reduce's reference.  As there, every constant is an
@@ -14,16 +14,16 @@ import numpy as np
 import lif_sg_cases as C
 from lif_sg_cases import F
 
-#: the constants of csrc/be_neuron_sg_param.hip that the GPU sizes below are derived from
-CONSTS = {'kSgpThreads': 256, 'kSgpGridCap': 2048, 'kSgpVec': 4, 'kSgpPrefetch': 4,
+#: the constants of csrc/be_neuron_sg.hip (the lane's) and csrc/be_neuron_sg_reduce.hip (kSgpRed*) the GPU sizes are derived from
+CONSTS = {'kSgThreads': 256, 'kSgGridCap': 2048, 'kSgVec': 4, 'kSgPrefetch': 4,
           'kSgpRedThreads': 256, 'kSgpRedTile': 4096, 'kSgpRedGridCap': 256, 'kSgpRedCols': 64}
 
-FULL_PASS_SCALAR = CONSTS['kSgpThreads'] * CONSTS['kSgpGridCap']
-FULL_PASS_VECTOR = FULL_PASS_SCALAR * CONSTS['kSgpVec']
+FULL_PASS_SCALAR = CONSTS['kSgThreads'] * CONSTS['kSgGridCap']
+FULL_PASS_VECTOR = FULL_PASS_SCALAR * CONSTS['kSgVec']
 N_SIZES = (1, 63, 64, 65)
 #: one slot past a full pass of the capped grid of the 4-byte kernel, one lane past it of the 16-byte kernel
-N_PAST_ONE_PASS = (FULL_PASS_SCALAR + 1, FULL_PASS_VECTOR + CONSTS['kSgpVec'])
-T_SIZES = (1, 2, 25, CONSTS['kSgpPrefetch'] - 1, CONSTS['kSgpPrefetch'], CONSTS['kSgpPrefetch'] + 1)
+N_PAST_ONE_PASS = (FULL_PASS_SCALAR + 1, FULL_PASS_VECTOR + CONSTS['kSgVec'])
+T_SIZES = (1, 2, 25, CONSTS['kSgPrefetch'] - 1, CONSTS['kSgPrefetch'], CONSTS['kSgPrefetch'] + 1)
 #: the reduce with period 1: past one block's tile, and past one pass of the first stage's capped grid
 REDUCE_N_SHARED = (1, CONSTS['kSgpRedThreads'] + 1, CONSTS['kSgpRedTile'] + 1, CONSTS['kSgpRedTile'] * CONSTS['kSgpRedGridCap'] + 1)
 #: the reduce with a longer period: under, at and past one block's columns; rows under, at and past the row lanes of a block

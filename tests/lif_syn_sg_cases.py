@@ -1,6 +1,6 @@
 """Shared by tests/test_lif_syn_sg_cpu.py and tests/test_lif_syn_sg_gpu.py: a numpy restatement of the two passes of the
 differentiable LIF neuron with a synaptic current and an optional adaptive threshold (include/brainevent_amd.h,
-be_lif_syn_sg_forward / be_lif_syn_sg_backward; csrc/be_neuron_sg_syn.hip), the CONSTS table the GPU sizes are taken from (the CPU
+be_lif_syn_sg_forward / be_lif_syn_sg_backward; csrc/be_neuron_sg.hip), the CONSTS table the GPU sizes are taken from (the CPU
 test holds it against the source text), seeded inputs, the crafted on-threshold cases and the mode list.
 
 As tests/lif_sg_cases.py: ``np.float32`` arrays and constants, one operation per statement in the header's order, each of them
@@ -13,10 +13,10 @@ import numpy as np
 
 from lif_sg_cases import F, same_bits, surrogate  # noqa: F401  (same_bits, F: for the tests that import this module)
 
-#: the constants of csrc/be_neuron_sg_syn.hip that the GPU sizes below are derived from
-CONSTS = {'kSynThreads': 256, 'kSynGridCap': 2048, 'kSynVec': 4, 'kSynPrefetch': 4}
+#: the constants of csrc/be_neuron_sg.hip that the GPU sizes below are derived from
+CONSTS = {'kSgThreads': 256, 'kSgGridCap': 2048, 'kSgVec': 4, 'kSgPrefetch': 4}
 #: every ring depth a kernel of the file has (one: the adaptive 16-byte backward kernel stays within 128 VGPRs at it)
-PREFETCH_DEPTHS = (CONSTS['kSynPrefetch'],)
+PREFETCH_DEPTHS = (CONSTS['kSgPrefetch'],)
 RESETS = ('hard', 'soft')
 SURROGATES = ('fast_sigmoid', 'atan', 'triangle')
 #: every reset x surrogate x detach_reset x adaptive
@@ -27,10 +27,10 @@ GRADS = ('g_s', 'g_vseq', 'g_clast', 'g_vlast', 'g_alast')
 GRAD_SETS = {**{name: tuple(g == name for g in GRADS) for name in GRADS}, 'all': (True,) * 5}
 
 #: one slot more than a full pass of the capped grid: of the 4-byte kernel, and (one lane more: N % 4 stays 0) of the 16-byte one
-FULL_PASS_SCALAR = CONSTS['kSynThreads'] * CONSTS['kSynGridCap']
-FULL_PASS_VECTOR = FULL_PASS_SCALAR * CONSTS['kSynVec']
+FULL_PASS_SCALAR = CONSTS['kSgThreads'] * CONSTS['kSgGridCap']
+FULL_PASS_VECTOR = FULL_PASS_SCALAR * CONSTS['kSgVec']
 N_SIZES = (1, 63, 64, 65)
-N_PAST_ONE_PASS = (FULL_PASS_SCALAR + 1, FULL_PASS_VECTOR + CONSTS['kSynVec'])
+N_PAST_ONE_PASS = (FULL_PASS_SCALAR + 1, FULL_PASS_VECTOR + CONSTS['kSgVec'])
 T_SIZES = tuple(sorted({1, 2, 25} | {d + k for d in PREFETCH_DEPTHS for k in (-1, 0, 1)}))
 SHAPES = ((65,), (3, 65), (2, 3, 5))
 

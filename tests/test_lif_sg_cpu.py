@@ -124,18 +124,29 @@ PATTERNS = {
 
 SOURCE_TEXT = [
     # which kernel a call takes, and how many blocks
-    ('const bool vec = (N % kSgVec == 0) && sg_aligned16(x) && sg_aligned16(v0) && sg_aligned16(s_out) && sg_aligned16(v_seq) &&', 1),
-    ('const bool vec = (N % kSgVec == 0) && sg_aligned16(h_save) && sg_aligned16(g_s) && sg_aligned16(g_vseq) && sg_aligned16(g_vlast) &&', 1),
-    ('const int grid = sg_grid(N, vec ? kSgVec : 1);', 2),
+    ('const bool vec = (N % kSgVec == 0) && lane::all_aligned16(x, v0, s_out, v_seq, h_save, v_last);', 1),
+    ('const bool vec = (N % kSgVec == 0) && lane::all_aligned16(h_save, g_s, g_vseq, g_vlast, g_x, g_v0);', 1),
+    ('constexpr int S = decltype(V)::value ? kSgVec : 1;', 2),
+    ('dim3(lane_grid(N, S)),', 2),
     ('return (int)std::min<int64_t>((groups + kSgThreads - 1) / kSgThreads, kSgGridCap);', 1),
     ('__launch_bounds__(kSgThreads)', 2),
     # the ring: filled kSgPrefetch steps ahead, walked in blocks of kSgPrefetch
     ('for (int64_t t0 = 0; t0 < T; t0 += kSgPrefetch) {', 1),
     ('for (int64_t k0 = 0; k0 < T; k0 += kSgPrefetch) {', 1),
-    ('if (t + kSgPrefetch < T) ring[r] = sg_load<S>(x + (t + kSgPrefetch) * N + i);', 1),
+    ('if (t + kSgPrefetch < T) ring[r] = lane::load<S>(x + (t + kSgPrefetch) * N + i);', 1),
     ('if (k + kSgPrefetch < T) {', 1),
-    ('#pragma clang fp contract(off)', 3),
+    ('#pragma clang fp contract(off)', 2),            # the two kernels; the arithmetic's are be_sg_lane.h's (test_lif_syn_sg_cpu.py)
 ]
+
+#: the six entry points of the one file, and what must be stated in exactly one file under csrc/
+ENTRY_POINTS = ('be_lif_sg_forward', 'be_lif_sg_backward', 'be_lif_sg_forward_params', 'be_lif_sg_backward_params',
+                'be_lif_syn_sg_forward', 'be_lif_syn_sg_backward')
+STATED_ONCE = {
+    "the surrogate's derivative": r'1\.0f / \(d \* d\)',
+    'the 16-byte pack': r'struct \w*Pack<4> \{ using type = float4; \};',
+    "the backward pass's reset term": r'g_vo \* \(p\.v_reset - h\)',
+    "the forward pass's soft reset": r's \? h - \w+ : h',
+}
 
 
 @pytest.mark.parametrize('key', sorted(PATTERNS))
@@ -159,6 +170,19 @@ def test_sizes_follow_the_constants():
     assert any(n % k['kSgVec'] for n in C.N_SIZES) and any(n % k['kSgVec'] == 0 for n in C.N_SIZES)
     # plain stores: no atomic read-modify-write, no LDS
     assert 'atomicAdd' not in text and '__hip_atomic' not in text and '__shared__' not in text
+
+
+def test_the_lane_is_stated_once():
+    """One file defines the six feed-forward entry points, each once, and the lane's arithmetic exists in one file under csrc/."""
+    text = SOURCE.read_text()
+    for name in ENTRY_POINTS:
+        assert len(re.findall(rf'^int {name}\(', text, flags=re.M)) == 1, name
+    sources = [p for p in sorted(SOURCE.parent.iterdir()) if p.suffix in ('.hip', '.h')]
+    assert SOURCE in sources and len(sources) > 10
+    for what, pattern in STATED_ONCE.items():
+        holders = {p.name: len(re.findall(pattern, p.read_text())) for p in sources}
+        holders = {name: n for name, n in holders.items() if n}
+        assert holders == {'be_sg_lane.h': 1}, f'{what}: {holders}'
 
 
 def test_abi_and_codes():

@@ -1,7 +1,7 @@
 """The LIF neuron with learnable, per-neuron ``beta`` / ``v_th`` without a device: the numpy restatement the GPU tests compare with
 (tests/lif_sg_param_cases.py) is held to torch's CPU autograd of the plain formula with the two parameters as leaf tensors, the
-reduce's reference to ``math.fsum``, the constants the GPU sizes come from to the text of csrc/be_neuron_sg_param.hip, and the
-refusals that need no device are raised.
+reduce's reference to ``math.fsum``, the constants the GPU sizes come from to the text of csrc/be_neuron_sg.hip (the lane kernels) and
+csrc/be_neuron_sg_reduce.hip (the reduce), and the refusals that need no device are raised.
 
 Forward values must be equal.  ``g_x`` / ``g_v0`` are compared within the bound of tests/lif_sg_cases.py.  A parameter's gradient
 is a sum of ``n = T * N / P`` terms that autograd forms and adds in an order that is not ours to fix; it is compared within
@@ -21,8 +21,8 @@ import lif_sg_param_cases as PC
 from lif_sg_cases import F
 
 ROOT = Path(__file__).resolve().parent.parent
-SOURCE = ROOT / 'brainevent_amd' / 'csrc' / 'be_neuron_sg_param.hip'
-OLD_SOURCE = ROOT / 'brainevent_amd' / 'csrc' / 'be_neuron_sg.hip'
+SOURCE = ROOT / 'brainevent_amd' / 'csrc' / 'be_neuron_sg.hip'
+REDUCE = ROOT / 'brainevent_amd' / 'csrc' / 'be_neuron_sg_reduce.hip'
 HEADER = ROOT / 'include' / 'brainevent_amd.h'
 
 
@@ -210,21 +210,26 @@ PATTERNS = {key: rf'constexpr int {key} = (\d+);' for key in PC.CONSTS}
 
 SOURCE_TEXT = [
     # which kernel a call takes, and how many blocks
-    ('const bool vec = (N % kSgpVec == 0) && sgp_aligned16(x) && sgp_aligned16(v0) && sgp_aligned16(s_out) && sgp_aligned16(v_seq) &&', 1),
-    ('sgp_aligned16(h_save) && sgp_aligned16(v_last) && sgp_param_vec(beta, beta_period) && sgp_param_vec(v_th, vth_period);', 1),
-    ('sgp_aligned16(g_vth_slot) && sgp_param_vec(beta, beta_period) && sgp_param_vec(v_th, vth_period);', 1),
-    ('return period == 1 || (period % kSgpVec == 0 && sgp_aligned16(p));', 1),
-    ('const int grid = sgp_grid(N, vec ? kSgpVec : 1);', 2),
-    ('return (int)std::min<int64_t>((groups + kSgpThreads - 1) / kSgpThreads, kSgpGridCap);', 1),
-    ('__launch_bounds__(kSgpThreads)', 2),
+    ('const bool vec = (N % kSgVec == 0) && lane::all_aligned16(x, v0, s_out, v_seq, h_save, v_last) && param_vec(beta, beta_period) &&\n'
+     '                   param_vec(v_th, vth_period);', 1),
+    ('const float* v0_read = g_beta_slot != nullptr ? v0 : nullptr;', 1),
+    ('const bool vec = (N % kSgVec == 0) && lane::all_aligned16(h_save, v0_read, g_s, g_vseq, g_vlast, g_x, g_v0, g_beta_slot, g_vth_slot) &&\n'
+     '                   param_vec(beta, beta_period) && param_vec(v_th, vth_period);', 1),
+    ('return period == 1 || (period % kSgVec == 0 && lane::aligned16(p));', 1),
+    ('constexpr int S = decltype(V)::value ? kSgVec : 1;', 2),
+    ('dim3(lane_grid(N, S)),', 2),
+    ('return (int)std::min<int64_t>((groups + kSgThreads - 1) / kSgThreads, kSgGridCap);', 1),
+    ('__launch_bounds__(kSgThreads)', 2),
     # the ring
-    ('for (int64_t t0 = 0; t0 < T; t0 += kSgpPrefetch) {', 1),
-    ('for (int64_t k0 = 0; k0 < T; k0 += kSgpPrefetch) {', 1),
-    ('if (t + kSgpPrefetch < T) ring[r] = sgp_load<S>(x + (t + kSgpPrefetch) * N + i);', 1),
-    ('if (k + kSgpPrefetch < T) {', 1),
-    ('const SgpVals<S> hp = ring_h[(r + 1) % kSgpPrefetch];', 1),
-    ('#pragma clang fp contract(off)', 4),
-    # the reduce
+    ('for (int64_t t0 = 0; t0 < T; t0 += kSgPrefetch) {', 1),
+    ('for (int64_t k0 = 0; k0 < T; k0 += kSgPrefetch) {', 1),
+    ('if (t + kSgPrefetch < T) ring[r] = lane::load<S>(x + (t + kSgPrefetch) * N + i);', 1),
+    ('if (k + kSgPrefetch < T) {', 1),
+    ('const V hp = ring_h[(r + 1) % kSgPrefetch];', 1),
+    ('#pragma clang fp contract(off)', 2),
+]
+
+REDUCE_TEXT = [
     ('return (int)std::min<int64_t>((N + kSgpRedTile - 1) / kSgpRedTile, kSgpRedGridCap);', 1),
     ('for (int64_t base = (int64_t)blockIdx.x * kSgpRedTile; base < N; base += (int64_t)gridDim.x * kSgpRedTile) {', 1),
     ('const int64_t blocks = (P + kSgpRedCols - 1) / kSgpRedCols;', 1),
@@ -235,28 +240,32 @@ SOURCE_TEXT = [
 
 @pytest.mark.parametrize('key', sorted(PATTERNS))
 def test_constant_matches_the_source(key):
-    found = re.findall(PATTERNS[key], SOURCE.read_text())
-    assert len(found) == 1 and int(found[0]) == PC.CONSTS[key], (f'{key}: be_neuron_sg_param.hip says {found}, '
+    source = REDUCE if key.startswith('kSgpRed') else SOURCE
+    found = re.findall(PATTERNS[key], source.read_text())
+    assert len(found) == 1 and int(found[0]) == PC.CONSTS[key], (f'{key}: {source.name} says {found}, '
                                                                 f'tests/lif_sg_param_cases.py assumes {PC.CONSTS[key]}')
 
 
 def test_sizes_follow_the_constants():
-    text = SOURCE.read_text()
-    for line, times in SOURCE_TEXT:
-        assert text.count(line) == times, f'be_neuron_sg_param.hip holds {line!r} {text.count(line)} times, not {times}'
+    text, reduce = SOURCE.read_text(), REDUCE.read_text()
+    for source, held, lines in ((SOURCE, text, SOURCE_TEXT), (REDUCE, reduce, REDUCE_TEXT)):
+        for line, times in lines:
+            assert held.count(line) == times, f'{source.name} holds {line!r} {held.count(line)} times, not {times}'
     k = PC.CONSTS
     scalar, vector = PC.N_PAST_ONE_PASS
-    assert scalar % k['kSgpVec'] != 0 and scalar == k['kSgpThreads'] * k['kSgpGridCap'] + 1
-    assert vector % k['kSgpVec'] == 0 and vector // k['kSgpVec'] == k['kSgpThreads'] * k['kSgpGridCap'] + 1
-    assert {k['kSgpPrefetch'] - 1, k['kSgpPrefetch'], k['kSgpPrefetch'] + 1, 1, 2, 25} == set(PC.T_SIZES)
-    assert any(n % k['kSgpVec'] for n in PC.N_SIZES) and any(n % k['kSgpVec'] == 0 for n in PC.N_SIZES)
+    assert scalar % k['kSgVec'] != 0 and scalar == k['kSgThreads'] * k['kSgGridCap'] + 1
+    assert vector % k['kSgVec'] == 0 and vector // k['kSgVec'] == k['kSgThreads'] * k['kSgGridCap'] + 1
+    assert {k['kSgPrefetch'] - 1, k['kSgPrefetch'], k['kSgPrefetch'] + 1, 1, 2, 25} == set(PC.T_SIZES)
+    assert any(n % k['kSgVec'] for n in PC.N_SIZES) and any(n % k['kSgVec'] == 0 for n in PC.N_SIZES)
     assert max(PC.REDUCE_N_SHARED) == k['kSgpRedTile'] * k['kSgpRedGridCap'] + 1 and k['kSgpRedTile'] + 1 in PC.REDUCE_N_SHARED
     assert k['kSgpRedThreads'] + 1 in PC.REDUCE_N_SHARED and k['kSgpRedGridCap'] <= k['kSgpRedThreads']
     rows = k['kSgpRedThreads'] // k['kSgpRedCols']
     assert {k['kSgpRedCols'], k['kSgpRedCols'] + 1} <= set(PC.REDUCE_PERIODS) and min(PC.REDUCE_PERIODS) < k['kSgpRedCols']
     assert min(PC.REDUCE_ROWS) < rows < max(PC.REDUCE_ROWS) and max(PC.REDUCE_ROWS) % rows != 0
-    # deterministic sums: no atomic read-modify-write
-    assert 'atomicAdd' not in text and '__hip_atomic' not in text and 'atomic_' not in text
+    # deterministic sums: no atomic read-modify-write in the lane kernels or in the reduce; LDS in the reduce alone
+    for held in (text, reduce):
+        assert 'atomicAdd' not in held and '__hip_atomic' not in held and 'atomic_' not in held
+    assert '__shared__' not in text and '__shared__' in reduce
 
 
 def test_abi_and_codes():
@@ -351,5 +360,8 @@ def test_two_floats_take_the_unchanged_path(be, monkeypatch):
     (name, args), = calls
     assert name == 'be_lif_sg_forward_params' and len(args) == 15
     assert (args[3], args[5]) == (4, 1) and args[10:12] == (5, 12) and args[8].value is None      # periods, T, N; no h_save
-    text = OLD_SOURCE.read_text()
-    assert 'be_lif_sg_forward_params' not in text and 'Sgp' not in text                   # the float path's file is not involved
+    # one file defines both entry points, each once; two floats allocate and copy nothing on their way to the kernel
+    text = SOURCE.read_text()
+    for entry in ('be_lif_sg_forward', 'be_lif_sg_forward_params'):
+        assert len(re.findall(rf'^int {entry}\(', text, flags=re.M)) == 1, entry
+    assert 'hipMalloc' not in text and 'hipMemcpy' not in text

@@ -1,4 +1,4 @@
-"""The LIF neuron with ``beta`` / ``v_th`` read from device memory (csrc/be_neuron_sg_param.hip, brainevent_amd/_neuron_sg.py) on the
+"""The LIF neuron with ``beta`` / ``v_th`` read from device memory (csrc/be_neuron_sg.hip, brainevent_amd/_neuron_sg.py) on the
 device.  The two passes are compared with the numpy restatement of tests/lif_sg_param_cases.py as EQUALITIES, bit for bit
 (``same_bits``), the per-slot gradient partials included; the reduce is compared with ``math.fsum`` within
 
@@ -133,7 +133,7 @@ def test_sizes_and_periods(N):
     """One slot, a wave less one, a wave, a wave and one; 84 and 96 for R = 2 and 3 with periods that are (28, 48, 32) and are not
     (42) a multiple of 4: the latter falls to the 4-byte kernel although N % 4 == 0.  One step, two, the ring's depth and its
     neighbours, and 25."""
-    k = PC.CONSTS['kSgpVec']
+    k = PC.CONSTS['kSgVec']
     assert N != 84 or {(42 % k == 0), (28 % k == 0)} == {False, True}
     for T in PC.T_SIZES:
         for (Pb, Pt), p in zip(period_cases(N), itertools.cycle((Params(), Params(reset='soft', surrogate='atan', v_reset=-0.25)))):
@@ -145,7 +145,7 @@ def test_sizes_and_periods(N):
 def test_past_one_pass_of_the_capped_grid(N):
     """A second trip of the grid-stride loop at T = 2: of the 4-byte kernel (one slot) and of the 16-byte kernel (one lane), with a
     per-neuron beta under three rows (both N are multiples of 3) and a shared v_th."""
-    k = PC.CONSTS['kSgpVec']
+    k = PC.CONSTS['kSgVec']
     assert N % 3 == 0 and (N % k == 0) == ((N // 3) % k == 0)
     check_direct(2, N, N // 3, 1, Params(surrogate='triangle', alpha=2.0), seed=3)
 

@@ -1,7 +1,7 @@
 """The differentiable neuron with a synaptic current and an adaptive threshold without a device: the numpy restatement the GPU
 tests compare with (tests/lif_syn_sg_cases.py) is held to torch's CPU autograd of the plain formula and, where the two coincide,
 to the restatement of the plain LIF neuron (tests/lif_sg_cases.py); the constants the GPU sizes come from are held to the text of
-csrc/be_neuron_sg_syn.hip, the prototypes to the header, and the refusals that need no device are raised.
+csrc/be_neuron_sg.hip and csrc/be_sg_lane.h, the prototypes to the header, and the refusals that need no device are raised.
 
 Forward values must be equal.  Gradients are compared within the propagated bound of ``lif_syn_sg_cases.backward(with_bound=True)``:
 ``4 * 2**-24 * sum |terms of g_c|`` per step, carried through the three coupled carries — autograd sums the same terms in an
@@ -19,7 +19,7 @@ import lif_syn_sg_cases as C
 from lif_syn_sg_cases import F
 
 ROOT = Path(__file__).resolve().parent.parent
-SOURCE = ROOT / 'brainevent_amd' / 'csrc' / 'be_neuron_sg_syn.hip'
+SOURCE = ROOT / 'brainevent_amd' / 'csrc' / 'be_neuron_sg.hip'
 LANE = ROOT / 'brainevent_amd' / 'csrc' / 'be_sg_lane.h'
 HEADER = ROOT / 'include' / 'brainevent_amd.h'
 
@@ -203,25 +203,26 @@ def test_restatement_edges():
 
 # ------------------------------------------------------------------------------------------------ the constants and the source
 PATTERNS = {
-    'kSynThreads': (r'constexpr int kSynThreads = (\d+);', 'N_PAST_ONE_PASS'),
-    'kSynGridCap': (r'constexpr int kSynGridCap = (\d+);', 'N_PAST_ONE_PASS'),
-    'kSynVec': (r'constexpr int kSynVec = (\d+);', 'N_PAST_ONE_PASS and the scalar-path cases'),
-    'kSynPrefetch': (r'constexpr int kSynPrefetch = (\d+);', 'T_SIZES'),
+    'kSgThreads': (r'constexpr int kSgThreads = (\d+);', 'N_PAST_ONE_PASS'),
+    'kSgGridCap': (r'constexpr int kSgGridCap = (\d+);', 'N_PAST_ONE_PASS'),
+    'kSgVec': (r'constexpr int kSgVec = (\d+);', 'N_PAST_ONE_PASS and the scalar-path cases'),
+    'kSgPrefetch': (r'constexpr int kSgPrefetch = (\d+);', 'T_SIZES'),
 }
 
 SOURCE_TEXT = [
     # which kernel a call takes, and how many blocks
-    ('const bool vec = (N % kSynVec == 0) && syn_all_aligned16(x, c0, v0, a0, s_out, v_seq, h_save, th_save, c_last, v_last, a_last);', 1),
-    ('const bool vec = (N % kSynVec == 0) && syn_all_aligned16(h_save, th_save, g_s, g_vseq, g_clast, g_vlast, g_alast, g_x, g_c0, g_v0, g_a0);', 1),
-    ('const int grid = syn_grid(N, vec ? kSynVec : 1);', 2),
-    ('return (int)std::min<int64_t>((groups + kSynThreads - 1) / kSynThreads, kSynGridCap);', 1),
-    ('__launch_bounds__(kSynThreads)', 2),
+    ('const bool vec = (N % kSgVec == 0) && lane::all_aligned16(x, c0, v0, a0, s_out, v_seq, h_save, th_save, c_last, v_last, a_last);', 1),
+    ('const bool vec = (N % kSgVec == 0) && lane::all_aligned16(h_save, th_save, g_s, g_vseq, g_clast, g_vlast, g_alast, g_x, g_c0, g_v0, g_a0);', 1),
+    ('constexpr int S = decltype(V)::value ? kSgVec : 1;', 2),
+    ('dim3(lane_grid(N, S)),', 2),
+    ('return (int)std::min<int64_t>((groups + kSgThreads - 1) / kSgThreads, kSgGridCap);', 1),
+    ('__launch_bounds__(kSgThreads)', 2),
     # the rings: filled a depth ahead, walked in blocks of the depth
-    ('for (int64_t t0 = 0; t0 < T; t0 += kSynPrefetch) {', 1),
-    ('if (t + kSynPrefetch < T) ring[r] = lane::load<S>(x + (t + kSynPrefetch) * N + i);', 1),
-    ('constexpr int P = kSynPrefetch;', 1),
-    ('for (int64_t k0 = 0; k0 < T; k0 += P) {', 1),
-    ('if (k + P < T) {', 1),
+    ('for (int64_t t0 = 0; t0 < T; t0 += kSgPrefetch) {', 1),
+    ('if (t + kSgPrefetch < T) ring[r] = lane::load<S>(x + (t + kSgPrefetch) * N + i);', 1),
+    ('for (int64_t k0 = 0; k0 < T; k0 += kSgPrefetch) {', 1),
+    ('if (k + kSgPrefetch < T) {', 1),
+    ('V ring_h[kSgPrefetch], ring_t[M::ADAPT ? kSgPrefetch : 1], ring_s[kSgPrefetch], ring_v[kSgPrefetch];', 1),
     ('#pragma clang fp contract(off)', 2),
 ]
 
@@ -230,7 +231,7 @@ SOURCE_TEXT = [
 def test_constant_matches_the_source(key):
     pattern, cases = PATTERNS[key]
     found = re.findall(pattern, SOURCE.read_text())
-    assert len(found) == 1 and int(found[0]) == C.CONSTS[key], (f'{key}: be_neuron_sg_syn.hip says {found}, '
+    assert len(found) == 1 and int(found[0]) == C.CONSTS[key], (f'{key}: be_neuron_sg.hip says {found}, '
                                                                f'tests/lif_syn_sg_cases.py assumes {C.CONSTS[key]}: re-size {cases}')
 
 
@@ -238,20 +239,21 @@ def test_sizes_follow_the_constants():
     assert set(PATTERNS) == set(C.CONSTS)
     text = SOURCE.read_text()
     for line, times in SOURCE_TEXT:
-        assert text.count(line) == times, f'be_neuron_sg_syn.hip holds {line!r} {text.count(line)} times, not {times}'
-    assert len(re.findall(r'constexpr int kSyn\w+ = ', text)) == len(C.CONSTS)                  # no depth the table does not know
+        assert text.count(line) == times, f'be_neuron_sg.hip holds {line!r} {text.count(line)} times, not {times}'
+    assert len(re.findall(r'constexpr int kSg\w+ = ', text)) == len(C.CONSTS)                  # no depth the table does not know
     k = C.CONSTS
     scalar, vector = C.N_PAST_ONE_PASS
-    assert scalar % k['kSynVec'] != 0 and scalar == k['kSynThreads'] * k['kSynGridCap'] + 1     # 4-byte kernel, second trip: one slot
-    assert vector % k['kSynVec'] == 0 and vector // k['kSynVec'] == k['kSynThreads'] * k['kSynGridCap'] + 1   # 16-byte kernel: one lane
-    assert C.PREFETCH_DEPTHS == (k['kSynPrefetch'],)
+    assert scalar % k['kSgVec'] != 0 and scalar == k['kSgThreads'] * k['kSgGridCap'] + 1     # 4-byte kernel, second trip: one slot
+    assert vector % k['kSgVec'] == 0 and vector // k['kSgVec'] == k['kSgThreads'] * k['kSgGridCap'] + 1   # 16-byte kernel: one lane
+    assert C.PREFETCH_DEPTHS == (k['kSgPrefetch'],)
     assert {1, 2, 25} | {d + j for d in C.PREFETCH_DEPTHS for j in (-1, 0, 1)} == set(C.T_SIZES)
-    assert any(n % k['kSynVec'] for n in C.N_SIZES) and any(n % k['kSynVec'] == 0 for n in C.N_SIZES)
-    # plain stores: no atomic read-modify-write, no LDS — here and in the lane helpers, which hold the third contract(off)
+    assert any(n % k['kSgVec'] for n in C.N_SIZES) and any(n % k['kSgVec'] == 0 for n in C.N_SIZES)
+    # plain stores: no atomic read-modify-write, no LDS — here and in the lane helpers, which hold the arithmetic: the derivative,
+    # the reset, the forward step, the backward step and its carries, each under a contract(off) of its own
     lane = LANE.read_text()
     for t in (text, lane):
         assert 'atomicAdd' not in t and '__hip_atomic' not in t and '__shared__' not in t
-    assert '#include "be_sg_lane.h"' in text and lane.count('#pragma clang fp contract(off)') == 1
+    assert '#include "be_sg_lane.h"' in text and lane.count('#pragma clang fp contract(off)') == 5
 
 
 def test_prototypes_against_the_header():

@@ -1,4 +1,4 @@
-"""The differentiable neuron with a synaptic current and an adaptive threshold (csrc/be_neuron_sg_syn.hip,
+"""The differentiable neuron with a synaptic current and an adaptive threshold (csrc/be_neuron_sg.hip,
 brainevent_amd/_neuron_syn_sg.py) on the device, compared with the numpy restatement of tests/lif_syn_sg_cases.py as EQUALITIES,
 bit for bit (``lif_sg_cases.same_bits``): every operation of both passes is an individually rounded IEEE f32 add, multiply,
 divide, abs or compare.  Nothing here is compared with torch's device kernels.  tests/test_lif_syn_sg_cpu.py holds the

@@ -1,4 +1,4 @@
-"""The price of learnable, per-neuron ``beta`` / ``v_th`` in the fused differentiable neuron (csrc/be_neuron_sg_param.hip,
+"""The price of learnable, per-neuron ``beta`` / ``v_th`` in the fused differentiable neuron (csrc/be_neuron_sg.hip,
 DESIGN.md §2.20), and what the only other route to them costs.
 
 One training step = forward + ``torch.autograd.grad`` over ``--T`` 25 steps, hard reset to 0, fast sigmoid.  For each shape

@@ -1,4 +1,4 @@
-"""What the synaptic current and the adaptive threshold cost in the fused differentiable neuron (csrc/be_neuron_sg_syn.hip,
+"""What the synaptic current and the adaptive threshold cost in the fused differentiable neuron (csrc/be_neuron_sg.hip,
 DESIGN.md §2.21), next to the one-state neuron of §2.19 and to the only other route to them.
 
 One training step = forward + ``torch.autograd.grad`` over ``--T`` 25 steps, hard reset to 0, fast sigmoid.  For each shape
