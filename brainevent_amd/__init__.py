@@ -16,7 +16,8 @@ The dense products also take OCP FP8 weights (``float8_e4m3fn`` / ``float8_e5m2`
 ``_dense_f8``): a byte per weight, f32 sums, f32 out.
 ``lif_step`` / ``lif_sequence`` are the spiking neuron between two products, with its surrogate gradient: one launch forwards and
 one backwards for a step or a whole input sequence (``_neuron_sg``); ``synaptic_lif_step`` / ``synaptic_lif_sequence`` are the same
-with a synaptic current in front of the membrane and an optional adaptive threshold (``_neuron_syn_sg``); ``recurrent_lif_sequence``
+with a synaptic current in front of the membrane and an optional adaptive threshold, ``parametric_synaptic_lif_step`` /
+``parametric_synaptic_lif_sequence`` that neuron with learnable, per-neuron parameters (``_neuron_syn_sg``); ``recurrent_lif_sequence``
 runs that neuron with a sparse recurrent projection inside the time loop, a whole sequence per launch (``_neuron_rec_sg``).
 """
 from ._version import __version__
@@ -52,7 +53,8 @@ from ._tuning import (ScatterTuning, DEFAULT_SCATTER_TUNING, get_scatter_tuning,
                       tune_scatter_routes)
 from ._neuron import lif_coba_step, lif_cuba_step
 from ._neuron_sg import lif_step, lif_sequence
-from ._neuron_syn_sg import synaptic_lif_step, synaptic_lif_sequence
+from ._neuron_syn_sg import (synaptic_lif_step, synaptic_lif_sequence, parametric_synaptic_lif_step,
+                             parametric_synaptic_lif_sequence)
 from ._neuron_rec_sg import recurrent_lif_sequence
 from ._plasticity import (update_csr_on_binary_pre, update_csr_on_binary_post, update_csc_on_binary_pre,
                           update_csc_on_binary_post, update_dense_on_binary_pre, update_dense_on_binary_post,

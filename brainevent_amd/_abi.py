@@ -24,6 +24,8 @@ _SIGNATURES = dict(
     be_lif_sg_forward_params='i:ppplplpppplldip', be_lif_sg_backward_params='i:pppppplplpppplldiidip',
     be_lif_sg_reduce_slots_workspace_bytes='l:ll', be_lif_sg_reduce_slots='i:pllpplp',
     be_lif_syn_sg_forward='i:pppppppppppllddddddiip', be_lif_syn_sg_backward='i:pppppppppppllddddddiidiip',
+    be_lif_syn_sg_forward_params='i:ppppplplplplplpppppppplldiip',
+    be_lif_syn_sg_backward_params='i:ppppppppppplplplplplppppppppplldiidiip',
     be_lif_rec_sg_forward='i:ppppppppppppppplllddddddiiip', be_lif_rec_sg_backward='i:ppppppppppppppplllddddddiidiip',
     be_pack_spikes='i:pilpp', be_pack_spikes_batched='i:pillpp', be_unpack_spikes='i:plpp', be_compact_spikes='i:pilppp',
     be_compact_spikes_batched='i:pillplpp',

@@ -179,11 +179,16 @@ inline bool all_aligned16(Ptr... ptrs) {
 
 // the checks the entry points share (BE_REQUIRE would name these functions, not the entry point); the periods are those of per-slot
 // parameters, where the entry point has them
-inline int check_common(const char* who, int64_t T, int64_t N, int reset_mode, int64_t beta_period = 1, int64_t vth_period = 1) {
+inline int check_common(const char* who, int64_t T, int64_t N, int reset_mode, int64_t beta_period = 1, int64_t vth_period = 1,
+                        int64_t sd_period = 1, int64_t rho_period = 1, int64_t kappa_period = 1) {
+  const int64_t periods[] = {beta_period, vth_period, sd_period, rho_period, kappa_period};
+  bool small = false, split = false;
+  for (const int64_t period : periods) small = small || period < 1;
+  for (const int64_t period : periods) split = split || (!small && N % period != 0);
   const char* msg = (T < 0 || N < 0) ? ": T < 0 or N < 0"
                     : (reset_mode != BE_LIF_RESET_HARD && reset_mode != BE_LIF_RESET_SOFT) ? ": unknown reset_mode"
-                    : (beta_period < 1 || vth_period < 1) ? ": a period must be >= 1"
-                    : (N % beta_period != 0 || N % vth_period != 0) ? ": a period must divide N" : nullptr;
+                    : small ? ": a period must be >= 1"
+                    : split ? ": a period must divide N" : nullptr;
   if (msg == nullptr) return BE_OK;
   be_set_error(std::string(who) + msg);
   return BE_ERR_INVALID;

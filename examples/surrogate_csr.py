@@ -7,7 +7,7 @@ spike function is a Heaviside step in the forward pass and a fast-sigmoid deriva
 for the spikes, per-synapse for the weights.  The task is synthetic and generated here: each of two input patterns must drive
 its own readout unit.  Trained with ``torch.optim.SGD``; the loss falls.
 
-    python examples/surrogate_csr.py [--steps 60] [--fused [--learn-beta | --synaptic [--adapt] [--fused-recurrent]]]
+    python examples/surrogate_csr.py [--steps 60] [--fused [--learn-beta | --synaptic [--adapt] [--learn-neuron | --fused-recurrent]]]
 
 ``--fused`` replaces the hand-written neuron (about six elementwise launches forwards and twice that backwards per time step) by
 ``be.lif_step`` (one launch each way; the same leak, threshold, hard reset to 0 and fast-sigmoid surrogate, the reset's gradient
@@ -19,7 +19,9 @@ its state the tuple ``(c, v)``, and the readout becomes a feed-forward layer of 
 currents through one ``be.synaptic_lif_sequence`` with ``v_th=inf``, the mean membrane as the logits.  ``--adapt`` (with
 ``--synaptic``) adds the adaptive threshold (``adapt=(rho, kappa)``, state ``(c, v, a)``).  ``--fused-recurrent`` (with ``--synaptic``)
 runs the whole recurrent layer — all ``T`` steps, the recurrent product included — as ONE ``be.recurrent_lif_sequence`` call and
-the readout product once over all ``T * batch`` spike rows.
+the readout product once over all ``T * batch`` spike rows.  ``--learn-neuron`` (with ``--synaptic``, not ``--fused-recurrent``) makes
+``syn_decay``, ``beta``, ``v_th`` and, with ``--adapt``, ``rho`` and ``kappa`` per-neuron ``torch.nn.Parameter``s that start at the constants
+and are trained with the weights: ``be.parametric_synaptic_lif_step`` reads them on the device and hands back their gradients.
 """
 import argparse
 import os
@@ -47,7 +49,7 @@ class SpikeFn(torch.autograd.Function):
         return g / (1.0 + 10.0 * (v - 1.0).abs()) ** 2
 
 
-def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False, fused_recurrent=False):
+def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False, fused_recurrent=False, learn_neuron=False):
     dev = torch.device('cuda')
     rng = np.random.default_rng(0)
     torch.manual_seed(0)
@@ -65,7 +67,11 @@ def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False, fuse
     # the leak: one constant, or (--learn-beta) one learnable value per neuron, read by the kernel from device memory
     beta = torch.nn.Parameter(torch.full((n,), 0.9, device=dev)) if learn_beta else 0.9
     syn_decay = 0.8
-    opt = torch.optim.SGD([w_rec, w_out] + ([beta] if learn_beta else []), lr=0.05)
+    # --learn-neuron: the synaptic neuron's constants as per-neuron Parameters (the readout layer keeps the numbers)
+    start = dict(syn_decay=syn_decay, beta=0.9, v_th=1.0, **(dict(rho=0.95, kappa=0.3) if adapt else {}))
+    neuron = {k: torch.nn.Parameter(torch.full((n,), c, device=dev)) for k, c in start.items()} if learn_neuron else {}
+    limits = dict(syn_decay=(0.0, 1.0), beta=(0.0, 1.0), v_th=(0.1, 10.0), rho=(0.0, 1.0), kappa=(0.0, 10.0))
+    opt = torch.optim.SGD([w_rec, w_out] + ([beta] if learn_beta else []) + list(neuron.values()), lr=0.05)
 
     def trial(labels):
         drive = patterns[labels]                                        # [batch, n]
@@ -82,6 +88,13 @@ def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False, fuse
             state = tuple(torch.zeros(batch, n, device=dev) for _ in range(3 if adapt else 2))
             out = []
             for _ in range(args.T):                                     # the drive scaled so that the filtered current settles at it
+                if learn_neuron:
+                    q = neuron
+                    s, state = be.parametric_synaptic_lif_step(state, (1.0 - syn_decay) * drive + be.BinaryArray(s) @ rec,
+                                                               syn_decay=q['syn_decay'], beta=q['beta'], v_th=q['v_th'],
+                                                               adapt=(q['rho'], q['kappa']) if adapt else None)
+                    out.append(be.BinaryArray(s) @ readout)
+                    continue
                 s, state = be.synaptic_lif_step(state, (1.0 - syn_decay) * drive + be.BinaryArray(s) @ rec, syn_decay=syn_decay,
                                                 beta=0.9, v_th=1.0, adapt=(0.95, 0.3) if adapt else None)
                 out.append(be.BinaryArray(s) @ readout)
@@ -108,6 +121,8 @@ def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False, fuse
         opt.step()
         if learn_beta:
             beta.data.clamp_(0.0, 1.0)
+        for k, t in neuron.items():
+            t.data.clamp_(*limits[k])
         losses.append(loss.item())
         if step % 10 == 0 or step == args.steps - 1:
             print(f"step {step:3d}  loss {losses[-1]:.4f}")
@@ -116,6 +131,9 @@ def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False, fuse
     if learn_beta:
         b = beta.detach()
         print(f"beta: started at 0.9 everywhere, now {b.min().item():.4f} .. {b.max().item():.4f} (mean {b.mean().item():.4f})")
+    for k, t in neuron.items():
+        t = t.detach()
+        print(f"{k}: started at {start[k]} everywhere, now {t.min().item():.4f} .. {t.max().item():.4f} (mean {t.mean().item():.4f})")
     return head, tail
 
 
@@ -131,7 +149,12 @@ def main():
     ap.add_argument('--adapt', action='store_true', help='with --synaptic: an adaptive threshold (adapt=(rho, kappa))')
     ap.add_argument('--fused-recurrent', action='store_true',
                     help='with --synaptic: the whole recurrent layer as one launch (be.recurrent_lif_sequence)')
+    ap.add_argument('--learn-neuron', action='store_true',
+                    help='with --synaptic: syn_decay, beta, v_th (and rho, kappa) as learnable per-neuron Parameters '
+                         '(be.parametric_synaptic_lif_step)')
     args = ap.parse_args()
+    if args.learn_neuron and (not args.synaptic or args.fused_recurrent):
+        ap.error('--learn-neuron needs --fused --synaptic and excludes --fused-recurrent (the recurrent layer takes Python numbers)')
     if args.fused_recurrent and not args.synaptic:
         ap.error('--fused-recurrent needs --fused --synaptic (it is the synaptic neuron with the recurrence inside)')
     if args.learn_beta and not args.fused:
@@ -141,17 +164,19 @@ def main():
     if args.adapt and not args.synaptic:
         ap.error('--adapt needs --synaptic')
     if args.synaptic and args.learn_beta:
-        ap.error('--learn-beta is for be.lif_step: the synaptic neuron takes Python numbers')
+        ap.error('--learn-beta is for be.lif_step: the synaptic neuron has --learn-neuron')
     if not args.fused:
         train(args)
         return 0
     if args.synaptic:
-        print('fused neuron (' + ('be.recurrent_lif_sequence' if args.fused_recurrent else 'be.synaptic_lif_step') +
+        print('fused neuron (' + ('be.recurrent_lif_sequence' if args.fused_recurrent else
+                                  'be.parametric_synaptic_lif_step, learnable per-neuron parameters' if args.learn_neuron else
+                                  'be.synaptic_lif_step') +
               (', adaptive threshold' if args.adapt else '') + '; be.synaptic_lif_sequence readout):')
     else:
         print('fused neuron (be.lif_step' + (', learnable per-neuron beta):' if args.learn_beta else '):'))
     fused = train(args, fused=True, learn_beta=args.learn_beta, synaptic=args.synaptic, adapt=args.adapt,
-                  fused_recurrent=args.fused_recurrent)
+                  fused_recurrent=args.fused_recurrent, learn_neuron=args.learn_neuron)
     print('hand-written neuron (torch elementwise ops), same start:')
     plain = train(args)
     print(f"end points: fused {fused[0]:.4f} -> {fused[1]:.4f}, hand-written {plain[0]:.4f} -> {plain[1]:.4f}")

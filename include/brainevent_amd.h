@@ -241,6 +241,57 @@ int be_lif_syn_sg_backward(const float* h_save, const float* th_save, const floa
                            const float* g_vlast, const float* g_alast, float* g_x, float* g_c0, float* g_v0, float* g_a0, int64_t T,
                            int64_t N, double syn_decay, double beta, double v_th, double v_reset, double rho, double kappa,
                            int reset_mode, int surrogate, double alpha, int adaptive, int detach_reset, be_stream_t stream);
+/* The same neuron with syn_decay, beta, v_th, rho and kappa read from DEVICE memory (brainevent_amd/csrc/be_neuron_sg.hip; the reduce
+ * is be_lif_sg_reduce_slots above, called once per parameter that needs a gradient).  Each of the five is an f32 array with a period
+ * P >= 1 of its own that divides N; slot i of a step uses param[i % P] — write sd_i, beta_i, vth_i, rho_i, kappa_i.  v_reset and
+ * alpha stay host scalars.  Every operation is rounded on its own, in this order and with these parentheses.
+ *   forward, t = 0 .. T-1, c = c0[i], v = v0[i], a = a0[i] (a NULL pointer means 0):
+ *     a_in = a                                                        (adaptive)
+ *     c  = (sd_i * c) + x[t][i]
+ *     h  = (beta_i * v) + c
+ *     th = adaptive ? vth_i + (kappa_i * a_in) : vth_i
+ *     s  = h >= th
+ *     v  = hard: s ? v_reset : h        soft: s ? h - vth_i : h       (the BASE threshold, as above)
+ *     a  = adaptive ? (rho_i * a_in) + (s ? 1 : 0)
+ *     s_out, v_seq, h_save as above;   c_save[t][i] = c (if given);   a_save[t][i] = a_in (adaptive and h_save given)
+ *   after the loop c_last, v_last, a_last
+ *   a_save takes the place of th_save: the backward pass forms th = vth_i + (kappa_i * a_save[t][i]) with the same two operations,
+ *   so it has the same bits.  c_save is needed for g_sd_slot alone and may be NULL otherwise.
+ *   backward, t = T-1 .. 0: the step above verbatim with the slot's own five values and the recomputed th, and up to five f32
+ *   accumulators per slot, each +0 at the start and each kept only if its output pointer is given.  With a_in = a_save[t][i], ca_in
+ *   the trace's carry BEFORE this step updates it, and g_c = g_x[t][i]:
+ *     th_prev = adaptive ? vth_i + (kappa_i * a_save[t-1][i]) : vth_i
+ *     v_prev  = t > 0 ? membrane_after(h_save[t-1][i], th_prev, vth_i, v_reset) : v0[i]   (NULL: 0)
+ *               membrane_after(h', th', vth, v_reset) = hard: (h' >= th' ? v_reset : h')   soft: (h' >= th' ? h' - vth : h')
+ *     c_prev  = t > 0 ? c_save[t-1][i] : c0[i]                                            (NULL: 0)
+ *     acc_sd    = acc_sd    + (g_c * c_prev)
+ *     acc_beta  = acc_beta  + (g_h * v_prev)
+ *     d = g_u;  soft only: d = d + (s ? g_vo : 0);      acc_vth = acc_vth - d             (with and without detach_reset)
+ *     acc_kappa = acc_kappa - (g_u * a_in)                                                (adaptive)
+ *     acc_rho   = acc_rho   + (ca_in * a_in)                                              (adaptive)
+ *   after the loop: g_sd_slot[i], g_beta_slot[i], g_vth_slot[i], g_rho_slot[i], g_kappa_slot[i]   ([N] each; each may be NULL)
+ *   v_prev is decided with the ADAPTIVE threshold of step t - 1; acc_rho uses the carry that ARRIVES at step t.  c0 is read only
+ *   when g_sd_slot is given, v0 only when g_beta_slot is.
+ * T == 0 or N == 0: BE_OK, nothing launched.  BE_ERR_INVALID: everything be_lif_syn_sg_forward / _backward refuse (a_save in
+ * th_save's place); a period < 1 or not dividing N; syn_decay, beta or v_th NULL; adaptive with rho or kappa NULL; c_save NULL
+ * while g_sd_slot is given.  With adaptive == 0 the adaptation's pointers and periods (a0, rho, kappa, a_save, a_last / a_save,
+ * g_alast, g_a0, g_rho_slot, g_kappa_slot) are neither read nor written.  16-byte accesses when N % 4 == 0, every given pointer is
+ * 16-byte aligned and every period is 1 or a multiple of 4 with a 16-byte aligned base, 4-byte accesses otherwise; the results do
+ * not depend on which. */
+int be_lif_syn_sg_forward_params(const float* x, const float* c0, const float* v0, const float* a0, const float* syn_decay,
+                                 int64_t sd_period, const float* beta, int64_t beta_period, const float* v_th, int64_t vth_period,
+                                 const float* rho, int64_t rho_period, const float* kappa, int64_t kappa_period, float* s_out,
+                                 float* v_seq, float* h_save, float* c_save, float* a_save, float* c_last, float* v_last,
+                                 float* a_last, int64_t T, int64_t N, double v_reset, int reset_mode, int adaptive,
+                                 be_stream_t stream);
+int be_lif_syn_sg_backward_params(const float* h_save, const float* c_save, const float* a_save, const float* c0, const float* v0,
+                                  const float* g_s, const float* g_vseq, const float* g_clast, const float* g_vlast,
+                                  const float* g_alast, const float* syn_decay, int64_t sd_period, const float* beta,
+                                  int64_t beta_period, const float* v_th, int64_t vth_period, const float* rho, int64_t rho_period,
+                                  const float* kappa, int64_t kappa_period, float* g_x, float* g_c0, float* g_v0, float* g_a0,
+                                  float* g_sd_slot, float* g_beta_slot, float* g_vth_slot, float* g_rho_slot, float* g_kappa_slot,
+                                  int64_t T, int64_t N, double v_reset, int reset_mode, int surrogate, double alpha, int adaptive,
+                                  int detach_reset, be_stream_t stream);
 /* The recurrent spiking layer (brainevent_amd/csrc/be_neuron_sg_rec.hip): the neuron above with a CSR recurrence INSIDE the time
  * loop — step t's input is x[t] + s[t-1] @ W_rec.  One launch forwards, one backwards; one workgroup per sample.  x, s_out, v_seq,
  * h_save, th_save, g_s, g_vseq, g_x are [T, B, N] row-major; s0, c0, v0, a0, the *_last, g_c0, g_v0, g_a0, g_s0 are [B, N].  The
