@@ -18,7 +18,8 @@ The dense products also take OCP FP8 weights (``float8_e4m3fn`` / ``float8_e5m2`
 one backwards for a step or a whole input sequence (``_neuron_sg``); ``synaptic_lif_step`` / ``synaptic_lif_sequence`` are the same
 with a synaptic current in front of the membrane and an optional adaptive threshold, ``parametric_synaptic_lif_step`` /
 ``parametric_synaptic_lif_sequence`` that neuron with learnable, per-neuron parameters (``_neuron_syn_sg``); ``recurrent_lif_sequence``
-runs that neuron with a sparse recurrent projection inside the time loop, a whole sequence per launch (``_neuron_rec_sg``).
+runs that neuron with a sparse recurrent projection inside the time loop, a whole sequence per launch, and
+``parametric_recurrent_lif_sequence`` that layer with learnable, per-neuron parameters (``_neuron_rec_sg``).
 """
 from ._version import __version__
 __version_info__ = tuple(int(p) for p in __version__.split('.')[:3] if p.isdigit())
@@ -55,7 +56,7 @@ from ._neuron import lif_coba_step, lif_cuba_step
 from ._neuron_sg import lif_step, lif_sequence
 from ._neuron_syn_sg import (synaptic_lif_step, synaptic_lif_sequence, parametric_synaptic_lif_step,
                              parametric_synaptic_lif_sequence)
-from ._neuron_rec_sg import recurrent_lif_sequence
+from ._neuron_rec_sg import recurrent_lif_sequence, parametric_recurrent_lif_sequence
 from ._plasticity import (update_csr_on_binary_pre, update_csr_on_binary_post, update_csc_on_binary_pre,
                           update_csc_on_binary_post, update_dense_on_binary_pre, update_dense_on_binary_post,
                           update_fixed_post_conn_on_binary_pre, update_fixed_pre_conn_on_binary_post)

@@ -27,6 +27,8 @@ _SIGNATURES = dict(
     be_lif_syn_sg_forward_params='i:ppppplplplplplpppppppplldiip',
     be_lif_syn_sg_backward_params='i:ppppppppppplplplplplppppppppplldiidiip',
     be_lif_rec_sg_forward='i:ppppppppppppppplllddddddiiip', be_lif_rec_sg_backward='i:ppppppppppppppplllddddddiidiip',
+    be_lif_rec_sg_forward_params='i:ppppppppplplplplplppppppppllldiiip',
+    be_lif_rec_sg_backward_params='i:pppppppppppppplplplplplppppppppppllldiidiip',
     be_pack_spikes='i:pilpp', be_pack_spikes_batched='i:pillpp', be_unpack_spikes='i:plpp', be_compact_spikes='i:pilppp',
     be_compact_spikes_batched='i:pillplpp',
     be_exchange_unique_id_bytes='i:', be_exchange_get_unique_id='i:p', be_exchange_init='i:piilP', be_exchange_slice='i:piLL',

@@ -12,9 +12,16 @@ One workgroup owns one sample and keeps its spikes on the chip between steps; th
 loop's: straight-through in the spikes for the recurrent product, the surrogate for the neuron; the weight gradient is the
 existing per-entry kernel (``be_grad_rows``) over all ``T * B`` spike rows at once.
 
-Not built: CSC / fixed-number / dense / JITC recurrences, one shared (homogeneous) weight, learnable neuron parameters, synaptic
-delays, more than 8192 neurons (one sample's sums and spike ids live in one workgroup's LDS), a sample split over several
-workgroups.  A cached scatter plan or mirror of ``rec`` is neither used nor needed: the kernels read the raw CSR arrays.
+``recurrent_lif_sequence`` takes Python numbers.  :func:`parametric_recurrent_lif_sequence` (DESIGN.md §2.25;
+``be_lif_rec_sg_forward_params`` / ``be_lif_rec_sg_backward_params``, the same kernels) takes each of ``syn_decay``, ``beta``, ``v_th``,
+``rho`` and ``kappa`` as a number or an f32 device tensor — one element, or ``[N]`` for a value per neuron — read on the device and,
+where it requires grad, differentiated: per-(sample, neuron) sums over time from the backward launch, then
+``be_lif_sg_reduce_slots`` over the batch.
+
+Not built: CSC / fixed-number / dense / JITC recurrences, one shared (homogeneous) weight, learnable ``v_reset`` / ``alpha``,
+per-sample (``[B, N]``) parameters, synaptic delays, more than 8192 neurons (one sample's sums and spike ids live in one workgroup's
+LDS), a sample split over several workgroups.  A cached scatter plan or mirror of ``rec`` is neither used nor needed: the kernels
+read the raw CSR arrays.
 """
 import numbers
 from typing import Optional, Sequence, Tuple
@@ -25,10 +32,10 @@ from torch.autograd.function import once_differentiable
 from . import _array as A
 from . import _autograd
 from ._lib import call
-from ._neuron_sg import _check_device, _check_tensor, _grad_in
-from ._neuron_syn_sg import _Params, _check_state
+from ._neuron_sg import _check_device, _check_tensor, _grad_in, _reduce_slots
+from ._neuron_syn_sg import FIVE_TENSORS, _Params, _check_state, _device_params, _split_params
 
-__all__ = ['recurrent_lif_sequence']
+__all__ = ['recurrent_lif_sequence', 'parametric_recurrent_lif_sequence']
 
 #: kRecMaxN of csrc/be_neuron_sg_rec.hip
 MAX_N = 8192
@@ -197,10 +204,28 @@ def recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Sequence[Optio
     state: straight-through in the spikes for the recurrent product (as ``BinaryArray(s) @ rec``), the surrogate for the neuron.
     ``rec.data`` is read from device memory on every call: an in-place update is seen by the next call.
 
-    Not built: CSC / fixed-number / dense / JITC recurrences, one shared weight, learnable neuron parameters, delays, ``N > 8192``,
-    a sample split over several workgroups (only ``B`` of the chip's compute units work)."""
+    The neuron's parameters are Python numbers here; :func:`parametric_recurrent_lif_sequence` takes them as device tensors, shared
+    or per neuron, and differentiates them.
+
+    Not built: CSC / fixed-number / dense / JITC recurrences, one shared weight, delays, ``N > 8192``, a sample split over several
+    workgroups (only ``B`` of the chip's compute units work)."""
     who = 'recurrent_lif_sequence'
     p = _Params(who, syn_decay, beta, v_th, v_reset, reset, surrogate, alpha, detach_reset, adapt)
+    (T, B, N), slots, x3, (c0, v0, a0, sp), e = _prepare(who, x, rec, state0, s0, p, scale_exp)
+    w = rec.data
+    r = _Rec(w.detach(), rec.indices, rec.indptr)
+    return_v = bool(return_v)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x3, c0, v0, a0, sp, w)):
+        outs = RecurrentLifSequence.apply(x3, c0, v0, a0, sp, w, r, (T, B, N), p, e, return_v)
+    else:                                     # no backward pass: h / th are not kept
+        s, v_seq, _, _, c_last, v_last, a_last = _forward(x3, r, sp, c0, v0, a0, T, B, N, p, e, return_v, False)
+        outs = tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
+    return _shaped(outs, x, slots, return_v)
+
+
+def _prepare(who, x, rec, state0, s0, p: _Params, scale_exp):
+    """The checks and layouts both functions share: ``(T, B, N)``, the shape of a step, contiguous ``x [T, B, N]``, the state entries
+    and ``s0`` as ``[B, N]`` (or None), and the exponent."""
     _check_tensor(who, 'x', x)
     if x.ndim not in (2, 3):
         raise ValueError(f"{who}: x must be [T, B, N] or [T, N], not {x.ndim}-dimensional.")
@@ -215,16 +240,144 @@ def recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Sequence[Optio
             raise ValueError(f"{who}: s0 {tuple(s0.shape)} must have the shape of a step of x, {slots}.")
     _check_device(who, x=x, s0=s0, **{f'state0 entry {k}': t for k, t in zip('cva', state)})
     e = _scale_exp(who, scale_exp, rec, N)
-
-    w = rec.data
-    r = _Rec(w.detach(), rec.indices, rec.indptr)
     x3 = x.contiguous().reshape(T, B, N)
-    c0, v0, a0, sp = (None if t is None else t.contiguous().reshape(B, N) for t in state + (s0,))
-    return_v = bool(return_v)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x3, c0, v0, a0, sp, w)):
-        outs = RecurrentLifSequence.apply(x3, c0, v0, a0, sp, w, r, (T, B, N), p, e, return_v)
-    else:                                     # no backward pass: h / th are not kept
-        s, v_seq, _, _, c_last, v_last, a_last = _forward(x3, r, sp, c0, v0, a0, T, B, N, p, e, return_v, False)
-        outs = tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
+    start = tuple(None if t is None else t.contiguous().reshape(B, N) for t in state + (s0,))
+    return (T, B, N), slots, x3, start, e
+
+
+def _shaped(outs, x, slots, return_v: bool):
     k = 2 if return_v else 1
     return tuple(o.reshape(x.shape) for o in outs[:k]) + (tuple(o.reshape(slots) for o in outs[k:]),)
+
+
+# ------------------------------------------------------------------------------------------------ the five parameters on the device
+def _forward_params(x, r: _Rec, s0, c0, v0, a0, params, T: int, B: int, N: int, p: _Params, e: int, want_v: bool, want_h: bool,
+                    want_c: bool):
+    """``be_lif_rec_sg_forward_params``: :func:`_forward` with the five parameters contiguous f32 device tensors (``rho`` / ``kappa``
+    None without adaptation; a period is the element count): ``(s, v_seq, h, c_save, a_save, c_last, v_last, a_last)``.  ``a_save`` —
+    the trace every step started from — is kept beside ``h`` when adaptive, ``c_save`` only when asked for."""
+    new = lambda: torch.empty((B, N), dtype=x.dtype, device=x.device)
+    s = torch.empty_like(x)
+    v_seq = torch.empty_like(x) if want_v else None
+    h = torch.empty_like(x) if want_h else None
+    c_save = torch.empty_like(x) if want_c else None
+    a_save = torch.empty_like(x) if want_h and p.adaptive else None
+    c_last, v_last, a_last = new(), new(), (new() if p.adaptive else None)
+    if T == 0:                                # no step: the state passes through
+        for out, start in ((c_last, c0), (v_last, v0), (a_last, a0)):
+            if out is not None:
+                out.zero_() if start is None else out.copy_(start)
+    elif B * N > 0:
+        call('be_lif_rec_sg_forward_params', A.ptr(x), A.ptr(r.w), A.ptr(r.indices), A.ptr(r.indptr), A.ptr(s0), A.ptr(c0), A.ptr(v0),
+             A.ptr(a0), *(v for t in params for v in (A.ptr(t), 1 if t is None else t.numel())), A.ptr(s), A.ptr(v_seq), A.ptr(h),
+             A.ptr(c_save), A.ptr(a_save), A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N, p.v_reset, p.reset, p.adaptive, e,
+             A.stream_ptr())
+    return s, v_seq, h, c_save, a_save, c_last, v_last, a_last
+
+
+class RecurrentLifSequenceParams(torch.autograd.Function):
+    """:class:`RecurrentLifSequence` with the five parameters as device tensors that may require grad.  Saved: ``h``, ``a_save``
+    in ``th``'s place when adaptive, ``s``, the weights, ``s0``, the parameters, ``c_save`` only if ``syn_decay`` needs a gradient,
+    and ``c0`` / ``v0`` only for the gradient of ``syn_decay`` / ``beta`` (what the first step started from).  A parameter that does
+    not need a gradient has its ``[B, N]`` accumulator go in as NULL."""
+
+    @staticmethod
+    def forward(ctx, x, c0, v0, a0, s0, w, syn_decay, beta, v_th, rho, kappa, r: _Rec, dims, p: _Params, e: int, return_v: bool):
+        ctx.set_materialize_grads(False)
+        T, B, N = dims
+        params = (syn_decay, beta, v_th, rho, kappa)
+        need_sd, need_b = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
+        s, v_seq, h, c_save, a_save, c_last, v_last, a_last = _forward_params(x, r, s0, c0, v0, a0, params, T, B, N, p, e, return_v,
+                                                                              True, need_sd)
+        ctx.save_for_backward(h, a_save, s, w, s0, c_save, *params, c0 if need_sd else None, v0 if need_b else None)
+        ctx.meta = (r, dims, p, return_v)
+        return tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_s, *rest):
+        r, (T, B, N), p, return_v = ctx.meta
+        g_vseq = rest[0] if return_v else None
+        g_last = list(rest[1:] if return_v else rest) + [None] * (3 - p.entries)
+        if g_s is None and g_vseq is None and all(g is None for g in g_last):
+            return (None,) * 16
+        h, a_save, s, w, s0, c_save, *params, c0, v0 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = [need[1], need[2], bool(p.adaptive) and need[3], need[4]]
+        need_p = [need[6 + k] and params[k] is not None for k in range(5)]
+        g_s, g_vseq, g_last = _grad_in(g_s), _grad_in(g_vseq), [_grad_in(g) for g in g_last]
+        g_x = torch.empty_like(h)
+        g_state = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in want]
+        if T == 0 or B * N == 0:              # no step: the state's gradient passes through, the parameters were not used
+            for out, g in zip(g_state[:3], g_last):
+                if out is not None:
+                    out.zero_() if g is None else out.copy_(g)
+            if g_state[3] is not None:
+                g_state[3].zero_()
+            g_params = [torch.zeros_like(t) if k else None for t, k in zip(params, need_p)]
+        else:
+            slot = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in need_p]
+            call('be_lif_rec_sg_backward_params', A.ptr(h), A.ptr(c_save), A.ptr(a_save), A.ptr(c0), A.ptr(v0), A.ptr(r.w),
+                 A.ptr(r.indices), A.ptr(r.indptr), A.ptr(g_s), A.ptr(g_vseq), A.ptr(g_last[0]), A.ptr(g_last[1]), A.ptr(g_last[2]),
+                 *(v for t in params for v in (A.ptr(t), 1 if t is None else t.numel())), A.ptr(g_x), A.ptr(g_state[0]),
+                 A.ptr(g_state[1]), A.ptr(g_state[2]), A.ptr(g_state[3]), *(A.ptr(t) for t in slot), T, B, N, p.v_reset, p.reset,
+                 p.surrogate, p.alpha, p.adaptive, p.detach_reset, A.stream_ptr())
+            g_params = [_reduce_slots(sl.reshape(-1), t) if k else None for sl, t, k in zip(slot, params, need_p)]
+        g_w = _weight_grad(w, r, s, s0, g_x, T, B, N) if need[5] else None
+        return ((g_x if need[0] else None), *g_state, g_w, *g_params, None, None, None, None, None)
+
+
+def _layer_params(who, given, like, N: int, adaptive):
+    """The five parameters as contiguous device tensors (a number: one element).  The rule of this layer, beyond
+    :func:`~brainevent_amd._neuron_syn_sg._device_params`': a tensor has one element or is ``[N]`` — the shape of a step is
+    ``[B, N]``, but a value per sample and neuron is refused: the layer's neurons are the same neurons in every sample, as the rows
+    of ``rec`` are."""
+    labels = ('syn_decay', 'beta', 'v_th', 'adapt[0] (rho)', 'adapt[1] (kappa)')
+    for label, v in zip(labels, given):
+        if isinstance(v, torch.Tensor) and v.ndim >= 2 and v.numel() != 1:
+            raise ValueError(f"{who}: {label} {tuple(v.shape)} must have one element or be [N] = ({N},): the layer's neurons are the "
+                             f"same neurons in every sample, as rec is, so a parameter has no batch dimension ([B, N] parameters "
+                             f"are not built).")
+    return _device_params(who, given, like, (N,), adaptive)
+
+
+def parametric_recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                                      s0: Optional[torch.Tensor] = None, *, syn_decay=0.0, beta, v_th=1.0, v_reset: float = 0.0,
+                                      reset: str = 'hard', surrogate: str = 'fast_sigmoid', alpha: float = 10.0,
+                                      detach_reset: bool = False, adapt=None, return_v: bool = False,
+                                      scale_exp: Optional[int] = None):
+    """:func:`recurrent_lif_sequence` with each of ``syn_decay``, ``beta``, ``v_th`` and the two entries of ``adapt = (rho, kappa)``
+    independently a Python number or an f32 device tensor: one element (0-d or ``[1]``) for a value the layer shares, or ``[N]`` for a
+    value per neuron, shared by the samples of the batch (a ``[B, N]`` tensor is refused: the layer's neurons are the same neurons in
+    every sample, as ``rec`` is).  The LSNN with heterogeneous, learned time constants and thresholds as two launches.
+
+    A tensor is read on the device (never copied to the host: an optimiser's in-place update is seen by the next call and the next
+    replay of a captured graph — with ``scale_exp`` given the function runs under ``capture_step``) and, if it requires grad, gets
+    its gradient in its own shape: per (sample, neuron) the sum over time from the backward launch, in f32 in descending ``t``, then
+    the sum over the samples — and, for one element, the neurons — in f64 in a fixed order (``be_lif_sg_reduce_slots``).  A number
+    beside a tensor becomes a one-element device tensor; all numbers is :func:`recurrent_lif_sequence` itself.  ``v_reset`` and
+    ``alpha`` stay numbers.  ``x``, ``rec``, ``state0``, ``s0``, ``scale_exp``, the outputs, the limit ``N <= 8192``, the refusals and
+    the bit-for-bit forward contract are :func:`recurrent_lif_sequence`'s (``be_lif_rec_sg_forward_params``); differentiable, once,
+    in ``x``, the state entries, ``s0``, ``rec.data`` and the five parameters.
+
+    Not built: learnable ``v_reset`` / ``alpha``, ``[B, N]`` parameters, and what :func:`recurrent_lif_sequence` does not build."""
+    who = 'parametric_recurrent_lif_sequence'
+    given, stand_in, any_tensor = _split_params(who, syn_decay, beta, v_th, adapt)
+    if not any_tensor:
+        return recurrent_lif_sequence(x, rec, state0, s0, syn_decay=syn_decay, beta=beta, v_th=v_th, v_reset=v_reset, reset=reset,
+                                      surrogate=surrogate, alpha=alpha, detach_reset=detach_reset, adapt=adapt, return_v=return_v,
+                                      scale_exp=scale_exp)
+    p = _Params(who, stand_in[0], stand_in[1], stand_in[2], v_reset, reset, surrogate, alpha, detach_reset,
+                None if adapt is None else (stand_in[3], stand_in[4]), FIVE_TENSORS)
+    (T, B, N), slots, x3, (c0, v0, a0, sp), e = _prepare(who, x, rec, state0, s0, p, scale_exp)
+    params = _layer_params(who, given, x, N, p.adaptive)
+    w = rec.data
+    r = _Rec(w.detach(), rec.indices, rec.indptr)
+    return_v = bool(return_v)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x3, c0, v0, a0, sp, w, *params)):
+        outs = RecurrentLifSequenceParams.apply(x3, c0, v0, a0, sp, w, *params, r, (T, B, N), p, e, return_v)
+    else:                                     # no backward pass: nothing is kept
+        s, v_seq, _, _, _, c_last, v_last, a_last = _forward_params(x3, r, sp, c0, v0, a0, params, T, B, N, p, e, return_v, False,
+                                                                    False)
+        outs = tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
+    return _shaped(outs, x, slots, return_v)

@@ -12,6 +12,15 @@
 // order), and §2.21's backward step follows.  A thread owns neurons tid, tid + kRecThreads, ... — at most kRecPerThread of them,
 // their state in registers whose indices are compile-time constants (no scratch).  Everything is f32, every operation rounded on
 // its own (no FMA contraction).  Global traffic is plain vector loads and stores; no global atomics.
+//
+// PARAMS (be_lif_rec_sg_forward_params / _backward_params) is the same kernel pair with syn_decay, beta, v_th, rho and
+// kappa read from DEVICE memory, one value for the layer (period 1) or one per neuron (period N), and with the per-(sample, neuron)
+// accumulators of their gradients.  A 1024-thread workgroup leaves a lane 128 registers, and five values plus five accumulators
+// for each of a thread's kRecPerThread neurons would be 80 of them: so a neuron's values are loaded where its step needs them
+// ([N] arrays, at most 32 KB each: they stay in L2), and the accumulators live in the [B, N] output arrays themselves — an entry
+// belongs to ONE thread, which at every step reads it (t = T-1: starts from +0 instead), adds the step's term and writes it back
+// with plain 4-byte vector loads and stores, in program order: the additions are the ones a register accumulator would make, in
+// the same order, so the bits are the same.  Without PARAMS none of this exists in the instantiation.
 #include "be_sg_lane.h"
 
 namespace {
@@ -38,15 +47,48 @@ __device__ __forceinline__ RowSpan row_span(const int32_t* __restrict__ indptr, 
   return RowSpan{indptr[row], indptr[row + 1]};
 }
 
-// Forward.  x, s_out, v_seq, h_save, th_save are [T, B, N]; s0, c0, v0, a0 and the *_last [B, N].  s0 / c0 / v0 / a0 NULL = 0;
-// v_seq / h_save / th_save may be NULL.  Dynamic LDS: N 64-bit sums, then N ids.
-template <bool HARD, bool ADAPT>
+// PARAMS: the five parameter arrays, each with a period of 1 or N (the entry points check it)
+struct RecParams {
+  lane::ParamArr sd, beta, vth, rho, kappa;
+};
+constexpr RecParams kRecNoParams{{nullptr, 1}, {nullptr, 1}, {nullptr, 1}, {nullptr, 1}, {nullptr, 1}};
+
+// PARAMS reaches every array it adds through a block-uniform base pointer plus a 32-bit byte offset, `off`, that a thread's arrays
+// share (neuron i of the thread: off = 4 * i).  Addresses that do not change over the time loop — the five parameters, the five
+// accumulators — would otherwise each be a 64-bit register pair per array and owned neuron, kept across the whole loop: 160
+// registers where a lane has 128.  rec_fresh() makes the offset a new value at every step, so nothing derived from it is hoisted
+// out of the loop; it emits no instruction.
+__device__ __forceinline__ uint32_t rec_fresh(uint32_t off) {
+  asm volatile("" : "+v"(off));
+  return off;
+}
+
+__device__ __forceinline__ float rec_load(const float* base, uint32_t off) {
+  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + off);
+}
+
+__device__ __forceinline__ void rec_store(float* base, uint32_t off, float value) {
+  *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) = value;
+}
+
+// the neuron at `off`'s value of a parameter (no remainder is needed: the period is 1 or N)
+__device__ __forceinline__ float rec_param(const lane::ParamArr& a, uint32_t off) {
+  return rec_load(a.p, a.period == 1 ? 0u : off);
+}
+
+// Forward.  x, s_out, v_seq, h_save, th_save, c_save are [T, B, N]; s0, c0, v0, a0 and the *_last [B, N].  s0 / c0 / v0 / a0 NULL = 0;
+// v_seq / h_save / th_save / c_save may be NULL.  Dynamic LDS: N 64-bit sums, then N ids.  With PARAMS q's arrays are read in the
+// place of p's syn_decay, beta, v_th, rho and kappa, c_save (if given) takes the current after every step, and with ADAPT th_save
+// takes the trace a the step STARTED from (the entry point's a_save), as in be_neuron_sg.hip; without PARAMS q and c_save are not
+// touched.
+template <bool HARD, bool ADAPT, bool PARAMS>
 __global__ void __launch_bounds__(kRecThreads)
 k_lif_rec_forward(const float* __restrict__ x, const float* __restrict__ w, const int32_t* __restrict__ indices,
                   const int32_t* __restrict__ indptr, const float* __restrict__ s0, const float* __restrict__ c0,
-                  const float* __restrict__ v0, const float* __restrict__ a0, float* __restrict__ s_out, float* __restrict__ v_seq,
-                  float* __restrict__ h_save, float* __restrict__ th_save, float* __restrict__ c_last, float* __restrict__ v_last,
-                  float* __restrict__ a_last, int64_t T, int64_t B, int N, float scale, double inv, lane::LifP p) {
+                  const float* __restrict__ v0, const float* __restrict__ a0, RecParams q, float* __restrict__ s_out,
+                  float* __restrict__ v_seq, float* __restrict__ h_save, float* __restrict__ th_save, float* __restrict__ c_save,
+                  float* __restrict__ c_last, float* __restrict__ v_last, float* __restrict__ a_last, int64_t T, int64_t B, int N,
+                  float scale, double inv, lane::LifP p) {
 #pragma clang fp contract(off)
   extern __shared__ __align__(16) unsigned char smem_raw[];
   unsigned long long* acc = reinterpret_cast<unsigned long long*>(smem_raw);
@@ -128,6 +170,7 @@ k_lif_rec_forward(const float* __restrict__ x, const float* __restrict__ w, cons
     }
     __syncthreads();
     sbits = 0;
+    const uint32_t off0 = PARAMS ? rec_fresh((uint32_t)tid * 4u) : 0u;
 #pragma unroll
     for (int k = 0; k < kRecPerThread; ++k) {
       const int i = tid + k * kRecThreads;
@@ -135,14 +178,22 @@ k_lif_rec_forward(const float* __restrict__ x, const float* __restrict__ w, cons
         const unsigned long long R = acc[i];
         acc[i] = 0ull;                                   // read and cleared by its owner only: no barrier in between
         const float r = (float)((double)(long long)R * inv);
-        const lane::Fired f = lane::forward_step<HARD, true, ADAPT>(xv[k] + r, c[k], v[k], a[k], p.beta, p.v_th, p);
+        lane::LifP pi = p;                               // the step's constants: the kernel's, or the neuron's own
+        if (PARAMS) {
+          const uint32_t off = off0 + (uint32_t)k * (kRecThreads * 4u);
+          pi.syn_decay = rec_param(q.sd, off), pi.beta = rec_param(q.beta, off), pi.v_th = rec_param(q.vth, off);
+          if (ADAPT) pi.rho = rec_param(q.rho, off), pi.kappa = rec_param(q.kappa, off);
+        }
+        const float a_in = a[k];
+        const lane::Fired f = lane::forward_step<HARD, true, ADAPT>(xv[k] + r, c[k], v[k], a[k], pi.beta, pi.v_th, pi);
         if (f.s) sbits |= 1u << k;
         s_out[at + i] = f.s ? 1.0f : 0.0f;
         if (v_seq != nullptr) v_seq[at + i] = v[k];
         if (h_save != nullptr) {
           h_save[at + i] = f.h;
-          if (ADAPT) th_save[at + i] = f.th;
+          if (ADAPT) th_save[at + i] = PARAMS ? a_in : f.th;
         }
+        if (PARAMS && c_save != nullptr) c_save[at + i] = c[k];
       }
     }
   }
@@ -194,13 +245,22 @@ __device__ __forceinline__ void rec_gather(const float* __restrict__ w, const in
 
 // Backward.  h_save, th_save, g_s, g_vseq, g_x are [T, B, N]; the others [B, N].  g_s / g_vseq / g_clast / g_vlast / g_alast
 // NULL = 0; g_c0 / g_v0 / g_a0 / g_s0 may be NULL.  Dynamic LDS: g_x[t+1] of the sample, then g_rec (N floats each).
-template <bool HARD, int SG, bool ADAPT>
+// With PARAMS q's arrays are the parameters, th_save holds the trace a_in every step started from (th = vth_i + (kappa_i * a_in) is
+// formed as forwards) and each of the five slot arrays [B, N] that is given is the accumulator of its parameter's gradient, kept
+// in memory by the entry's owner (see the top of the file):  a_sd += g_c * c_prev,  a_b += g_h * v_prev,  a_th -= g_u (+ the soft
+// reset's direct term),  a_k -= g_u * a_in,  a_r += ca_in * a_in with the carry that ARRIVES at the step.  v_prev is recomputed
+// from h_save[t-1] and its own threshold (v0 at t = 0, NULL = 0), c_prev is c_save[t-1] (c0 at t = 0, NULL = 0); c_save, c0 and
+// v0 are read for g_sd_slot / g_beta_slot alone.  Without PARAMS none of these arguments is touched.
+template <bool HARD, int SG, bool ADAPT, bool PARAMS>
 __global__ void __launch_bounds__(kRecThreads)
-k_lif_rec_backward(const float* __restrict__ h_save, const float* __restrict__ th_save, const float* __restrict__ w,
+k_lif_rec_backward(const float* __restrict__ h_save, const float* __restrict__ th_save, const float* __restrict__ c_save,
+                   const float* __restrict__ c0, const float* __restrict__ v0, const float* __restrict__ w,
                    const int32_t* __restrict__ indices, const int32_t* __restrict__ indptr, const float* __restrict__ g_s,
                    const float* __restrict__ g_vseq, const float* __restrict__ g_clast, const float* __restrict__ g_vlast,
-                   const float* __restrict__ g_alast, float* __restrict__ g_x, float* __restrict__ g_c0, float* __restrict__ g_v0,
-                   float* __restrict__ g_a0, float* __restrict__ g_s0, int64_t T, int64_t B, int N, int detach_reset, lane::LifP p) {
+                   const float* __restrict__ g_alast, RecParams q, float* __restrict__ g_x, float* __restrict__ g_c0,
+                   float* __restrict__ g_v0, float* __restrict__ g_a0, float* __restrict__ g_s0, float* __restrict__ g_sd_slot,
+                   float* __restrict__ g_beta_slot, float* __restrict__ g_vth_slot, float* __restrict__ g_rho_slot,
+                   float* __restrict__ g_kappa_slot, int64_t T, int64_t B, int N, int detach_reset, lane::LifP p) {
 #pragma clang fp contract(off)
   extern __shared__ __align__(16) unsigned char smem_raw[];
   float* G = reinterpret_cast<float*>(smem_raw);
@@ -238,6 +298,7 @@ k_lif_rec_backward(const float* __restrict__ h_save, const float* __restrict__ t
       rec_gather(w, indices, indptr, G, N, grec);
       __syncthreads();
     }
+    const uint32_t off0 = PARAMS ? rec_fresh((uint32_t)tid * 4u) : 0u;
 #pragma unroll
     for (int k = 0; k < kRecPerThread; ++k) {
       const int i = tid + k * kRecThreads;
@@ -246,10 +307,56 @@ k_lif_rec_backward(const float* __restrict__ h_save, const float* __restrict__ t
         if (g_vseq != nullptr) g_vo = g_vo + gvv[k];
         float g_sp = gsv[k];                             // 0 when g_s is NULL
         if (rec) g_sp = g_sp + grec[i];
-        const lane::Grad d = lane::backward_step<HARD, SG, ADAPT>(hv[k], ADAPT ? tv[k] : p.v_th, p.v_th, g_sp, g_vo, ca[k], detach_reset, p);
-        const float g_c = lane::backward_carry<true, ADAPT>(d, cc[k], cv[k], ca[k], p.beta, p);
+        lane::LifP pi = p;                               // the step's constants: the kernel's, or the neuron's own
+        float th = ADAPT ? tv[k] : p.v_th;               // the threshold h was compared with
+        const uint32_t off = off0 + (uint32_t)k * (kRecThreads * 4u);
+        if (PARAMS) {
+          pi.syn_decay = rec_param(q.sd, off), pi.beta = rec_param(q.beta, off), pi.v_th = rec_param(q.vth, off);
+          if (ADAPT) pi.rho = rec_param(q.rho, off), pi.kappa = rec_param(q.kappa, off);
+          th = ADAPT ? pi.v_th + (pi.kappa * tv[k]) : pi.v_th;
+        }
+        const float ca_in = ca[k];
+        const lane::Grad d = lane::backward_step<HARD, SG, ADAPT>(hv[k], th, pi.v_th, g_sp, g_vo, ca[k], detach_reset, pi);
+        const float g_c = lane::backward_carry<true, ADAPT>(d, cc[k], cv[k], ca[k], pi.beta, pi);
         g_x[at + i] = g_c;
         G[i] = g_c;
+        if (PARAMS) {
+          // the accumulators, in memory: this thread alone reads and writes the entry at `off` of the sample's row, in program order
+          const bool first = t == T - 1;
+          if (g_sd_slot != nullptr) {
+            float c_prev = 0.f;                          // the current the step started from
+            if (t > 0) c_prev = rec_load(c_save + (at - step), off);
+            else if (c0 != nullptr) c_prev = rec_load(c0 + base, off);
+            const float sum = first ? 0.f : rec_load(g_sd_slot + base, off);
+            rec_store(g_sd_slot + base, off, sum + (g_c * c_prev));
+          }
+          if (g_beta_slot != nullptr) {
+            float v_prev = 0.f;                          // the membrane the step started from
+            if (t > 0) {
+              const float hp = rec_load(h_save + (at - step), off);
+              const float tp = ADAPT ? pi.v_th + (pi.kappa * rec_load(th_save + (at - step), off)) : pi.v_th;
+              v_prev = lane::membrane_after<HARD>(hp, tp, pi.v_th, p.v_reset);
+            } else if (v0 != nullptr) {
+              v_prev = rec_load(v0 + base, off);
+            }
+            const float sum = first ? 0.f : rec_load(g_beta_slot + base, off);
+            rec_store(g_beta_slot + base, off, sum + (d.g_h * v_prev));
+          }
+          if (g_vth_slot != nullptr) {
+            float direct = d.g_u;
+            if (!HARD) direct = direct + (d.s ? g_vo : 0.0f);
+            const float sum = first ? 0.f : rec_load(g_vth_slot + base, off);
+            rec_store(g_vth_slot + base, off, sum - direct);
+          }
+          if (ADAPT && g_kappa_slot != nullptr) {
+            const float sum = first ? 0.f : rec_load(g_kappa_slot + base, off);
+            rec_store(g_kappa_slot + base, off, sum - (d.g_u * tv[k]));
+          }
+          if (ADAPT && g_rho_slot != nullptr) {
+            const float sum = first ? 0.f : rec_load(g_rho_slot + base, off);
+            rec_store(g_rho_slot + base, off, sum + (ca_in * tv[k]));
+          }
+        }
       }
     }
     __syncthreads();
@@ -282,6 +389,73 @@ inline int rec_check_common(const char* who, int64_t T, int64_t B, int64_t N, in
   return BE_OK;
 }
 
+// a parameter's period: one value for the layer, or one per neuron
+inline int rec_check_periods(const char* who, int64_t N, std::initializer_list<int64_t> periods) {
+  for (const int64_t period : periods) {
+    if (period == 1 || (period == N && N >= 1)) continue;
+    be_set_error(std::string(who) + ": a period of " + std::to_string(period) + " (a parameter has period 1, one value for the layer, " +
+                 "or period N = " + std::to_string(N) + ", one per neuron: the neurons are the same in every sample)");
+    return BE_ERR_INVALID;
+  }
+  return BE_OK;
+}
+
+// the forward launch of both entry points (params: q holds the five arrays, th_save is a_save); the checks are the callers'
+hipError_t rec_launch_forward(bool params, const float* x, const float* w, const int32_t* indices, const int32_t* indptr, const float* s0,
+                              const float* c0, const float* v0, const float* a0, const RecParams& q, float* s_out, float* v_seq,
+                              float* h_save, float* th_save, float* c_save, float* c_last, float* v_last, float* a_last, int64_t T,
+                              int64_t B, int64_t N, const lane::LifP& p, bool hard, bool adapt, int scale_exp, be_stream_t stream) {
+  const float scale = ldexpf(1.0f, scale_exp - 32);   // see fixed_from_f32
+  const double inv = ldexp(1.0, -scale_exp);
+  const int lds = (int)be_align_up(N * 12, 16);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  hipError_t allowed = hipSuccess;
+  be_dispatch_bool(hard, [&](auto H) {
+    return be_dispatch_bool(adapt, [&](auto A) {
+      return be_dispatch_bool(params, [&](auto P) {
+        auto kern = k_lif_rec_forward<decltype(H)::value, decltype(A)::value, decltype(P)::value>;
+        allowed = be_allow_lds(reinterpret_cast<const void*>(kern), lds);
+        if (allowed == hipSuccess)
+          hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kRecThreads), lds, st, x, w, indices, indptr, s0, c0, v0, a0, q, s_out,
+                             v_seq, h_save, th_save, c_save, c_last, v_last, a_last, T, B, (int)N, scale, inv, p);
+        return BE_OK;
+      });
+    });
+  });
+  return allowed;
+}
+
+// the backward launch of both entry points
+hipError_t rec_launch_backward(bool params, const float* h_save, const float* th_save, const float* c_save, const float* c0,
+                               const float* v0, const float* w, const int32_t* indices, const int32_t* indptr, const float* g_s,
+                               const float* g_vseq, const float* g_clast, const float* g_vlast, const float* g_alast,
+                               const RecParams& q, float* g_x, float* g_c0, float* g_v0, float* g_a0, float* g_s0, float* g_sd_slot,
+                               float* g_beta_slot, float* g_vth_slot, float* g_rho_slot, float* g_kappa_slot, int64_t T, int64_t B,
+                               int64_t N, const lane::LifP& p, bool hard, bool adapt, int surrogate, int detach, be_stream_t stream) {
+  const int lds = (int)be_align_up(N * 8, 16);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  hipError_t allowed = hipSuccess;
+  be_dispatch_bool(hard, [&](auto H) {
+    return be_dispatch_bool(adapt, [&](auto A) {
+      return be_dispatch_int<BE_LIF_SG_FAST_SIGMOID, BE_LIF_SG_ATAN, BE_LIF_SG_TRIANGLE>(surrogate, [&](auto SG) {
+        return be_dispatch_bool(params, [&](auto P) {
+          auto kern = k_lif_rec_backward<decltype(H)::value, decltype(SG)::value, decltype(A)::value, decltype(P)::value>;
+          allowed = be_allow_lds(reinterpret_cast<const void*>(kern), lds);
+          if (allowed == hipSuccess)
+            hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kRecThreads), lds, st, h_save, th_save, c_save, c0, v0, w, indices, indptr,
+                               g_s, g_vseq, g_clast, g_vlast, g_alast, q, g_x, g_c0, g_v0, g_a0, g_s0, g_sd_slot, g_beta_slot,
+                               g_vth_slot, g_rho_slot, g_kappa_slot, T, B, (int)N, detach, p);
+          return BE_OK;
+        });
+      });
+    });
+  });
+  return allowed;
+}
+
+constexpr const float* kNoIn = nullptr;
+constexpr float* kNoOut = nullptr;
+
 }  // namespace
 
 extern "C" {
@@ -301,23 +475,9 @@ int be_lif_rec_sg_forward(const float* x, const float* w, const int32_t* indices
   BE_REQUIRE(!adapt || a_last, BE_ERR_INVALID, "null pointer (adaptive: a_last is required)");
   BE_REQUIRE(!adapt || !h_save || th_save, BE_ERR_INVALID, "null pointer (adaptive: th_save is required where h_save is given)");
   const lane::LifP p = lane::make_params(syn_decay, beta, v_th, v_reset, rho, kappa, 1.);
-  const bool hard = reset_mode == BE_LIF_RESET_HARD;
   if (!adapt) a0 = nullptr, th_save = nullptr, a_last = nullptr;          // neither read nor written, whatever was passed
-  const float scale = ldexpf(1.0f, scale_exp - 32);   // see fixed_from_f32
-  const double inv = ldexp(1.0, -scale_exp);
-  const int lds = (int)be_align_up(N * 12, 16);
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t allowed = hipSuccess;
-  be_dispatch_bool(hard, [&](auto H) {
-    return be_dispatch_bool(adapt, [&](auto A) {
-      auto kern = k_lif_rec_forward<decltype(H)::value, decltype(A)::value>;
-      allowed = be_allow_lds(reinterpret_cast<const void*>(kern), lds);
-      if (allowed == hipSuccess)
-        hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kRecThreads), lds, st, x, w, indices, indptr, s0, c0, v0, a0, s_out, v_seq,
-                           h_save, th_save, c_last, v_last, a_last, T, B, (int)N, scale, inv, p);
-      return BE_OK;
-    });
-  });
+  const hipError_t allowed = rec_launch_forward(false, x, w, indices, indptr, s0, c0, v0, a0, kRecNoParams, s_out, v_seq, h_save, th_save, kNoOut, c_last,
+                            v_last, a_last, T, B, N, p, reset_mode == BE_LIF_RESET_HARD, adapt, scale_exp, stream);
   BE_HIP(allowed);
   BE_LAUNCH_CHECK();
   return BE_OK;
@@ -336,24 +496,73 @@ int be_lif_rec_sg_backward(const float* h_save, const float* th_save, const floa
   const bool adapt = adaptive != 0;
   BE_REQUIRE(!adapt || th_save, BE_ERR_INVALID, "null pointer (adaptive: th_save is required)");
   const lane::LifP p = lane::make_params(syn_decay, beta, v_th, v_reset, rho, kappa, alpha);
-  const bool hard = reset_mode == BE_LIF_RESET_HARD;
   if (!adapt) th_save = nullptr, g_alast = nullptr, g_a0 = nullptr;       // neither read nor written, whatever was passed
-  const int lds = (int)be_align_up(N * 8, 16);
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int detach = detach_reset != 0;
-  hipError_t allowed = hipSuccess;
-  be_dispatch_bool(hard, [&](auto H) {
-    return be_dispatch_bool(adapt, [&](auto A) {
-      return be_dispatch_int<BE_LIF_SG_FAST_SIGMOID, BE_LIF_SG_ATAN, BE_LIF_SG_TRIANGLE>(surrogate, [&](auto SG) {
-        auto kern = k_lif_rec_backward<decltype(H)::value, decltype(SG)::value, decltype(A)::value>;
-        allowed = be_allow_lds(reinterpret_cast<const void*>(kern), lds);
-        if (allowed == hipSuccess)
-          hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kRecThreads), lds, st, h_save, th_save, w, indices, indptr, g_s, g_vseq,
-                             g_clast, g_vlast, g_alast, g_x, g_c0, g_v0, g_a0, g_s0, T, B, (int)N, detach, p);
-        return BE_OK;
-      });
-    });
-  });
+  const hipError_t allowed = rec_launch_backward(false, h_save, th_save, kNoIn, kNoIn, kNoIn, w, indices, indptr, g_s, g_vseq, g_clast, g_vlast, g_alast,
+                             kRecNoParams, g_x, g_c0, g_v0, g_a0, g_s0, kNoOut, kNoOut, kNoOut, kNoOut, kNoOut, T, B, N, p,
+                             reset_mode == BE_LIF_RESET_HARD, adapt, surrogate, (int)(detach_reset != 0), stream);
+  BE_HIP(allowed);
+  BE_LAUNCH_CHECK();
+  return BE_OK;
+}
+
+int be_lif_rec_sg_forward_params(const float* x, const float* w, const int32_t* indices, const int32_t* indptr, const float* s0,
+                                 const float* c0, const float* v0, const float* a0, const float* syn_decay, int64_t sd_period,
+                                 const float* beta, int64_t beta_period, const float* v_th, int64_t vth_period, const float* rho,
+                                 int64_t rho_period, const float* kappa, int64_t kappa_period, float* s_out, float* v_seq,
+                                 float* h_save, float* c_save, float* a_save, float* c_last, float* v_last, float* a_last, int64_t T,
+                                 int64_t B, int64_t N, double v_reset, int reset_mode, int adaptive, int scale_exp,
+                                 be_stream_t stream) {
+  const bool adapt = adaptive != 0;
+  if (!adapt) rho_period = 1, kappa_period = 1;                            // the adaptation's arguments are not looked at
+  if (const int rc = rec_check_common(__func__, T, B, N, reset_mode)) return rc;
+  if (const int rc = rec_check_periods(__func__, N, {sd_period, beta_period, vth_period, rho_period, kappa_period})) return rc;
+  BE_REQUIRE(scale_exp >= kRecMinExp && scale_exp <= kRecMaxExp, BE_ERR_INVALID,
+             "scale_exp outside the exponents be_fixed_point_exponent returns (-90 .. 150)");
+  if (T == 0 || B == 0 || N == 0) return BE_OK;
+  BE_REQUIRE(x && s_out && c_last && v_last, BE_ERR_INVALID, "null pointer (x, s_out, c_last and v_last are required)");
+  BE_REQUIRE(w && indices && indptr, BE_ERR_INVALID, "null pointer (w, indices and indptr are required)");
+  BE_REQUIRE(syn_decay && beta && v_th, BE_ERR_INVALID, "null pointer (syn_decay, beta and v_th are required)");
+  BE_REQUIRE(!adapt || (rho && kappa), BE_ERR_INVALID, "null pointer (adaptive: rho and kappa are required)");
+  BE_REQUIRE(!adapt || a_last, BE_ERR_INVALID, "null pointer (adaptive: a_last is required)");
+  BE_REQUIRE(!adapt || !h_save || a_save, BE_ERR_INVALID, "null pointer (adaptive: a_save is required where h_save is given)");
+  const lane::LifP p = lane::make_params(0., 0., 0., v_reset, 0., 0., 1.);
+  if (!adapt) a0 = nullptr, a_save = nullptr, a_last = nullptr, rho = nullptr, kappa = nullptr;   // neither read nor written
+  const RecParams q{{syn_decay, sd_period}, {beta, beta_period}, {v_th, vth_period}, {rho, rho_period}, {kappa, kappa_period}};
+  const hipError_t allowed = rec_launch_forward(true, x, w, indices, indptr, s0, c0, v0, a0, q, s_out, v_seq, h_save, a_save, c_save, c_last, v_last,
+                            a_last, T, B, N, p, reset_mode == BE_LIF_RESET_HARD, adapt, scale_exp, stream);
+  BE_HIP(allowed);
+  BE_LAUNCH_CHECK();
+  return BE_OK;
+}
+
+int be_lif_rec_sg_backward_params(const float* h_save, const float* c_save, const float* a_save, const float* c0, const float* v0,
+                                  const float* w, const int32_t* indices, const int32_t* indptr, const float* g_s,
+                                  const float* g_vseq, const float* g_clast, const float* g_vlast, const float* g_alast,
+                                  const float* syn_decay, int64_t sd_period, const float* beta, int64_t beta_period,
+                                  const float* v_th, int64_t vth_period, const float* rho, int64_t rho_period, const float* kappa,
+                                  int64_t kappa_period, float* g_x, float* g_c0, float* g_v0, float* g_a0, float* g_s0,
+                                  float* g_sd_slot, float* g_beta_slot, float* g_vth_slot, float* g_rho_slot, float* g_kappa_slot,
+                                  int64_t T, int64_t B, int64_t N, double v_reset, int reset_mode, int surrogate, double alpha,
+                                  int adaptive, int detach_reset, be_stream_t stream) {
+  const bool adapt = adaptive != 0;
+  if (!adapt) rho_period = 1, kappa_period = 1;                            // the adaptation's arguments are not looked at
+  if (const int rc = rec_check_common(__func__, T, B, N, reset_mode)) return rc;
+  if (const int rc = rec_check_periods(__func__, N, {sd_period, beta_period, vth_period, rho_period, kappa_period})) return rc;
+  if (const int rc = lane::check_surrogate(__func__, surrogate, alpha)) return rc;
+  if (T == 0 || B == 0 || N == 0) return BE_OK;
+  BE_REQUIRE(h_save && g_x, BE_ERR_INVALID, "null pointer (h_save and g_x are required)");
+  BE_REQUIRE(w && indices && indptr, BE_ERR_INVALID, "null pointer (w, indices and indptr are required)");
+  BE_REQUIRE(syn_decay && beta && v_th, BE_ERR_INVALID, "null pointer (syn_decay, beta and v_th are required)");
+  BE_REQUIRE(!adapt || (rho && kappa), BE_ERR_INVALID, "null pointer (adaptive: rho and kappa are required)");
+  BE_REQUIRE(!adapt || a_save, BE_ERR_INVALID, "null pointer (adaptive: a_save is required)");
+  BE_REQUIRE(!g_sd_slot || c_save, BE_ERR_INVALID, "null pointer (c_save is required where g_sd_slot is given)");
+  const lane::LifP p = lane::make_params(0., 0., 0., v_reset, 0., 0., alpha);
+  if (!adapt)                                                              // neither read nor written, whatever was passed
+    a_save = nullptr, g_alast = nullptr, g_a0 = nullptr, rho = nullptr, kappa = nullptr, g_rho_slot = nullptr, g_kappa_slot = nullptr;
+  const RecParams q{{syn_decay, sd_period}, {beta, beta_period}, {v_th, vth_period}, {rho, rho_period}, {kappa, kappa_period}};
+  const hipError_t allowed = rec_launch_backward(true, h_save, a_save, c_save, c0, v0, w, indices, indptr, g_s, g_vseq, g_clast, g_vlast, g_alast, q, g_x,
+                             g_c0, g_v0, g_a0, g_s0, g_sd_slot, g_beta_slot, g_vth_slot, g_rho_slot, g_kappa_slot, T, B, N, p,
+                             reset_mode == BE_LIF_RESET_HARD, adapt, surrogate, (int)(detach_reset != 0), stream);
   BE_HIP(allowed);
   BE_LAUNCH_CHECK();
   return BE_OK;

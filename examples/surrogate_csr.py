@@ -7,7 +7,7 @@ spike function is a Heaviside step in the forward pass and a fast-sigmoid deriva
 for the spikes, per-synapse for the weights.  The task is synthetic and generated here: each of two input patterns must drive
 its own readout unit.  Trained with ``torch.optim.SGD``; the loss falls.
 
-    python examples/surrogate_csr.py [--steps 60] [--fused [--learn-beta | --synaptic [--adapt] [--learn-neuron | --fused-recurrent]]]
+    python examples/surrogate_csr.py [--steps 60] [--fused [--learn-beta | --synaptic [--adapt] [--learn-neuron] [--fused-recurrent]]]
 
 ``--fused`` replaces the hand-written neuron (about six elementwise launches forwards and twice that backwards per time step) by
 ``be.lif_step`` (one launch each way; the same leak, threshold, hard reset to 0 and fast-sigmoid surrogate, the reset's gradient
@@ -19,9 +19,10 @@ its state the tuple ``(c, v)``, and the readout becomes a feed-forward layer of 
 currents through one ``be.synaptic_lif_sequence`` with ``v_th=inf``, the mean membrane as the logits.  ``--adapt`` (with
 ``--synaptic``) adds the adaptive threshold (``adapt=(rho, kappa)``, state ``(c, v, a)``).  ``--fused-recurrent`` (with ``--synaptic``)
 runs the whole recurrent layer — all ``T`` steps, the recurrent product included — as ONE ``be.recurrent_lif_sequence`` call and
-the readout product once over all ``T * batch`` spike rows.  ``--learn-neuron`` (with ``--synaptic``, not ``--fused-recurrent``) makes
-``syn_decay``, ``beta``, ``v_th`` and, with ``--adapt``, ``rho`` and ``kappa`` per-neuron ``torch.nn.Parameter``s that start at the constants
-and are trained with the weights: ``be.parametric_synaptic_lif_step`` reads them on the device and hands back their gradients.
+the readout product once over all ``T * batch`` spike rows.  ``--learn-neuron`` (with ``--synaptic``) makes ``syn_decay``, ``beta``,
+``v_th`` and, with ``--adapt``, ``rho`` and ``kappa`` per-neuron ``torch.nn.Parameter``s that start at the constants and are trained with
+the weights: ``be.parametric_synaptic_lif_step`` reads them on the device and hands back their gradients — or, together with
+``--fused-recurrent``, ``be.parametric_recurrent_lif_sequence`` does, still as one launch each way.
 """
 import argparse
 import os
@@ -80,7 +81,13 @@ def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False, fuse
         acc = torch.zeros(batch, n_out, device=dev)
         if fused_recurrent:                                             # the recurrent layer as one launch each way
             x = ((1.0 - syn_decay) * drive).expand(args.T, batch, n)
-            s_all, _ = be.recurrent_lif_sequence(x, rec, syn_decay=syn_decay, beta=0.9, v_th=1.0, adapt=(0.95, 0.3) if adapt else None)
+            if learn_neuron:                                            # the same call with the neuron's Parameters
+                q = neuron
+                s_all, _ = be.parametric_recurrent_lif_sequence(x, rec, syn_decay=q['syn_decay'], beta=q['beta'], v_th=q['v_th'],
+                                                                adapt=(q['rho'], q['kappa']) if adapt else None)
+            else:
+                s_all, _ = be.recurrent_lif_sequence(x, rec, syn_decay=syn_decay, beta=0.9, v_th=1.0,
+                                                     adapt=(0.95, 0.3) if adapt else None)
             out = (be.BinaryArray(s_all.reshape(args.T * batch, n)) @ readout).reshape(args.T, batch, n_out)
             _, v_seq, _ = be.synaptic_lif_sequence(out, syn_decay=syn_decay, beta=0.9, v_th=float('inf'), return_v=True)
             return v_seq.mean(0) * (1.0 - syn_decay) * (1.0 - 0.9)
@@ -151,10 +158,10 @@ def main():
                     help='with --synaptic: the whole recurrent layer as one launch (be.recurrent_lif_sequence)')
     ap.add_argument('--learn-neuron', action='store_true',
                     help='with --synaptic: syn_decay, beta, v_th (and rho, kappa) as learnable per-neuron Parameters '
-                         '(be.parametric_synaptic_lif_step)')
+                         '(be.parametric_synaptic_lif_step; with --fused-recurrent be.parametric_recurrent_lif_sequence)')
     args = ap.parse_args()
-    if args.learn_neuron and (not args.synaptic or args.fused_recurrent):
-        ap.error('--learn-neuron needs --fused --synaptic and excludes --fused-recurrent (the recurrent layer takes Python numbers)')
+    if args.learn_neuron and not args.synaptic:
+        ap.error('--learn-neuron needs --fused --synaptic')
     if args.fused_recurrent and not args.synaptic:
         ap.error('--fused-recurrent needs --fused --synaptic (it is the synaptic neuron with the recurrence inside)')
     if args.learn_beta and not args.fused:
@@ -169,7 +176,9 @@ def main():
         train(args)
         return 0
     if args.synaptic:
-        print('fused neuron (' + ('be.recurrent_lif_sequence' if args.fused_recurrent else
+        print('fused neuron (' + ('be.parametric_recurrent_lif_sequence, learnable per-neuron parameters'
+                                  if args.fused_recurrent and args.learn_neuron else
+                                  'be.recurrent_lif_sequence' if args.fused_recurrent else
                                   'be.parametric_synaptic_lif_step, learnable per-neuron parameters' if args.learn_neuron else
                                   'be.synaptic_lif_step') +
               (', adaptive threshold' if args.adapt else '') + '; be.synaptic_lif_sequence readout):')

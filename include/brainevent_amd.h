@@ -329,6 +329,51 @@ int be_lif_rec_sg_backward(const float* h_save, const float* th_save, const floa
                            float* g_x, float* g_c0, float* g_v0, float* g_a0, float* g_s0, int64_t T, int64_t B, int64_t N,
                            double syn_decay, double beta, double v_th, double v_reset, double rho, double kappa, int reset_mode,
                            int surrogate, double alpha, int adaptive, int detach_reset, be_stream_t stream);
+/* The recurrent layer with syn_decay, beta, v_th, rho and kappa read from DEVICE memory (the same kernels, csrc/be_neuron_sg_rec.hip;
+ * the reduce is be_lif_sg_reduce_slots above, called once per parameter that needs a gradient, with N' = B * N and P = N or 1).  Each
+ * of the five is an f32 array with a period of its own, which is 1 (one value for the layer) or N (one per neuron, shared by the
+ * samples of the batch: the layer's neurons are the same neurons in every sample, as the matrix is); neuron i uses
+ * param[period == 1 ? 0 : i] — write sd_i, beta_i, vth_i, rho_i, kappa_i.  v_reset and alpha stay host scalars.  Arrays and shapes
+ * as be_lif_rec_sg_forward / _backward; c_save and a_save are [T, B, N], the five slot arrays [B, N].
+ *   forward, for every sample b, t = 0 .. T-1: R[j], r[j] and xin = x[t][b][j] + r[j] exactly as be_lif_rec_sg_forward (the wrapping
+ *   64-bit fixed-point sum, r = (float)((double)(int64)R * inv), one rounded addition), then the step of
+ *   be_lif_syn_sg_forward_params, verbatim, with neuron i's own five values and xin in the place of x[t][i]:
+ *     a_in = a;  c = (sd_i * c) + xin;  h = (beta_i * v) + c;  th = adaptive ? vth_i + (kappa_i * a_in) : vth_i;  s = h >= th;
+ *     v = hard: s ? v_reset : h   soft: s ? h - vth_i : h;   a = adaptive ? (rho_i * a_in) + (s ? 1 : 0)
+ *     s_out, v_seq, h_save as there;  c_save[t][b][i] = c (if given);  a_save[t][b][i] = a_in (adaptive and h_save given)
+ *   a_save takes the place of th_save and c_save is needed for g_sd_slot alone, as there.
+ *   backward, t = T-1 .. 0: g_rec, g_sp = g_s[t][b][i] (+ g_rec if t < T-1), g_x and g_s0 exactly as be_lif_rec_sg_backward, the
+ *   step that of be_lif_syn_sg_backward_params with the recomputed th, and its five accumulators per (sample, neuron), each +0 at
+ *   t = T-1, added to in descending t, every operation rounded on its own, each kept only if its output pointer is given:
+ *     acc_sd    = acc_sd    + (g_c * c_prev)          c_prev = t > 0 ? c_save[t-1][b][i] : c0[b][i]   (NULL: 0)
+ *     acc_beta  = acc_beta  + (g_h * v_prev)          v_prev = t > 0 ? membrane_after(h_save[t-1][b][i], th_prev, vth_i, v_reset)
+ *                                                              : v0[b][i]   (NULL: 0),  th_prev from a_save[t-1][b][i]
+ *     d = g_u;  soft only: d = d + (s ? g_vo : 0);    acc_vth = acc_vth - d
+ *     acc_kappa = acc_kappa - (g_u * a_in)            (adaptive)
+ *     acc_rho   = acc_rho   + (ca_in * a_in)          (adaptive; ca_in: the trace's carry BEFORE this step updates it)
+ *   after the loop g_sd_slot[b][i], g_beta_slot[b][i], g_vth_slot[b][i], g_rho_slot[b][i], g_kappa_slot[b][i] hold them.  The
+ *   kernel keeps each accumulator IN its output entry (read, add, write by the one thread that owns the entry, plain vector loads
+ *   and stores, no atomics): the additions and their order are the ones written here, so the bits are a register accumulator's.
+ *   c0 and c_save are read only when g_sd_slot is given, v0 only when g_beta_slot is.
+ * T == 0, B == 0 or N == 0: BE_OK, nothing launched.  BE_ERR_RANGE: N > 8192.  BE_ERR_INVALID: everything be_lif_rec_sg_forward /
+ * _backward and be_lif_syn_sg_forward_params / _backward_params refuse, and a period that is neither 1 nor N.  With adaptive == 0 the
+ * adaptation's pointers and periods are neither read nor written.  No global atomics; never synchronises the host. */
+int be_lif_rec_sg_forward_params(const float* x, const float* w, const int32_t* indices, const int32_t* indptr, const float* s0,
+                                 const float* c0, const float* v0, const float* a0, const float* syn_decay, int64_t sd_period,
+                                 const float* beta, int64_t beta_period, const float* v_th, int64_t vth_period, const float* rho,
+                                 int64_t rho_period, const float* kappa, int64_t kappa_period, float* s_out, float* v_seq,
+                                 float* h_save, float* c_save, float* a_save, float* c_last, float* v_last, float* a_last, int64_t T,
+                                 int64_t B, int64_t N, double v_reset, int reset_mode, int adaptive, int scale_exp,
+                                 be_stream_t stream);
+int be_lif_rec_sg_backward_params(const float* h_save, const float* c_save, const float* a_save, const float* c0, const float* v0,
+                                  const float* w, const int32_t* indices, const int32_t* indptr, const float* g_s,
+                                  const float* g_vseq, const float* g_clast, const float* g_vlast, const float* g_alast,
+                                  const float* syn_decay, int64_t sd_period, const float* beta, int64_t beta_period,
+                                  const float* v_th, int64_t vth_period, const float* rho, int64_t rho_period, const float* kappa,
+                                  int64_t kappa_period, float* g_x, float* g_c0, float* g_v0, float* g_a0, float* g_s0,
+                                  float* g_sd_slot, float* g_beta_slot, float* g_vth_slot, float* g_rho_slot, float* g_kappa_slot,
+                                  int64_t T, int64_t B, int64_t N, double v_reset, int reset_mode, int surrogate, double alpha,
+                                  int adaptive, int detach_reset, be_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * event vector helpers (replace: brainevent/_jit_scalar/binary_jitsmv.cu:107-125 `_pack_bool_kern`
