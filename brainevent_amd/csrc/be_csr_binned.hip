@@ -211,10 +211,14 @@ __device__ __forceinline__ void stream_flush_list(const StreamLds<HOMO, CB>& S, 
         const uint16_t* bi = reinterpret_cast<const uint16_t*>(blk);
         const float* bw = reinterpret_cast<const float*>(blk);
         const uint32_t vb = sid >> kRingLog, bb = vb / (uint32_t)n_bins_b;          // (batch row, bin) of the virtual bin
-        float* dst = out + (int64_t)bb * k + (int64_t)(vb - bb * (uint32_t)n_bins_b) * width;
+        const int64_t c0 = (int64_t)(vb - bb * (uint32_t)n_bins_b) * width;
+        float* dst = out + (int64_t)bb * k + c0;
+        // the bin's columns that are outputs: a partial last bin also takes columns >= k (the caller's error, dropped like every
+        // such entry) — past the batch row's image, where pass C would never clear them and the next batch row's image begins
+        const uint32_t lim = k - c0 < (int64_t)width ? (uint32_t)(k - c0) : width;
         for (int j = lane; j < CB; j += 64) {
           const uint32_t c = bi[B::col_hw(j)];          // (< width by construction; the test keeps a float atomic inside the bin's slice whatever LDS holds)
-          if (c < width) atomicAdd(dst + c, HOMO ? w0 : bw[B::w_dw(j)]);
+          if (c < lim) atomicAdd(dst + c, HOMO ? w0 : bw[B::w_dw(j)]);
         }
         if (lane == 0) S.ovf[sid >> kRingLog] = 1u;
       }
@@ -620,10 +624,12 @@ __global__ void __launch_bounds__(1024) k_bin_stream(const W* __restrict__ weigh
       const uint16_t* bi = reinterpret_cast<const uint16_t*>(bp);
       const float* bw = reinterpret_cast<const float*>(bp);
       const uint32_t bb = (uint32_t)bin / (uint32_t)n_bins_b;
-      float* dst = out + (int64_t)bb * k + (int64_t)((uint32_t)bin - bb * (uint32_t)n_bins_b) * width;
+      const int64_t c0 = (int64_t)((uint32_t)bin - bb * (uint32_t)n_bins_b) * width;
+      float* dst = out + (int64_t)bb * k + c0;
+      const uint32_t lim = k - c0 < (int64_t)width ? (uint32_t)(k - c0) : width;       // (as in stream_flush_list: outputs only)
       for (uint32_t j = 0; j < d; ++j) {
         const uint32_t c = bi[B::col_hw(j)];
-        if (c < width) atomicAdd(dst + c, HOMO ? w0 : bw[B::w_dw(j)]);
+        if (c < lim) atomicAdd(dst + c, HOMO ? w0 : bw[B::w_dw(j)]);
       }
       o = 1u;
     }
