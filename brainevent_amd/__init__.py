@@ -19,7 +19,9 @@ one backwards for a step or a whole input sequence (``_neuron_sg``); ``synaptic_
 with a synaptic current in front of the membrane and an optional adaptive threshold, ``parametric_synaptic_lif_step`` /
 ``parametric_synaptic_lif_sequence`` that neuron with learnable, per-neuron parameters (``_neuron_syn_sg``); ``recurrent_lif_sequence``
 runs that neuron with a sparse recurrent projection inside the time loop, a whole sequence per launch, and
-``parametric_recurrent_lif_sequence`` that layer with learnable, per-neuron parameters (``_neuron_rec_sg``).
+``parametric_recurrent_lif_sequence`` that layer with learnable, per-neuron parameters (``_neuron_rec_sg``); given a ``DelayedCSR``
+as the recurrence, ``recurrent_lif_sequence`` runs the layer with a conduction delay per synapse — a sample's spike history stays on
+the chip —, still one launch each way and differentiable through the spikes, the history and ``stacked.data``.
 """
 from ._version import __version__
 __version_info__ = tuple(int(p) for p in __version__.split('.')[:3] if p.isdigit())

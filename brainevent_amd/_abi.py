@@ -29,6 +29,8 @@ _SIGNATURES = dict(
     be_lif_rec_sg_forward='i:ppppppppppppppplllddddddiiip', be_lif_rec_sg_backward='i:ppppppppppppppplllddddddiidiip',
     be_lif_rec_sg_forward_params='i:ppppppppplplplplplppppppppllldiiip',
     be_lif_rec_sg_backward_params='i:pppppppppppppplplplplplppppppppppllldiidiip',
+    be_lif_rec_delay_sg_forward='i:pppppipipppppppppplllddddddiiip',
+    be_lif_rec_delay_sg_backward='i:ppppppippppppppppilllddddddiidiip',
     be_pack_spikes='i:pilpp', be_pack_spikes_batched='i:pillpp', be_unpack_spikes='i:plpp', be_compact_spikes='i:pilppp',
     be_compact_spikes_batched='i:pillplpp',
     be_exchange_unique_id_bytes='i:', be_exchange_get_unique_id='i:p', be_exchange_init='i:piilP', be_exchange_slice='i:piLL',
@@ -73,7 +75,8 @@ _SIGNATURES = dict(
     be_jitc_fill_sorted='i:iddlulllippippp',
     be_plasticity_workspace_bytes='l:l', be_plasticity_rows='i:pippillpipilpididplp',
     be_plasticity_rows_aged='i:pippilpipilppliiididplp', be_plasticity_dense='i:ipillpipididplp',
-    be_grad_mask_bytes='l:ll', be_grad_pack_activity='i:pillpp', be_grad_rows_workspace_bytes='l:l',
+    be_grad_mask_bytes='l:ll', be_grad_pack_activity='i:pillpp', be_grad_pack_activity_aged='i:ppllliipp',
+    be_grad_rows_workspace_bytes='l:l',
     be_grad_rows='i:ipiippilllplpllplp', be_grad_dense_workspace_bytes='l:ll', be_grad_dense='i:ipillplpllp',
     be_sddmm_rows='i:pippilplllpplp',
     be_entries_dense_op='i:ppiippillllpillip', be_diag_scan='i:ppilllpp', be_diag_move='i:piippillpplpppip',

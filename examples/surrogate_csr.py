@@ -7,7 +7,7 @@ spike function is a Heaviside step in the forward pass and a fast-sigmoid deriva
 for the spikes, per-synapse for the weights.  The task is synthetic and generated here: each of two input patterns must drive
 its own readout unit.  Trained with ``torch.optim.SGD``; the loss falls.
 
-    python examples/surrogate_csr.py [--steps 60] [--fused [--learn-beta | --synaptic [--adapt] [--learn-neuron] [--fused-recurrent]]]
+    python examples/surrogate_csr.py [--steps 60] [--fused [--learn-beta | --synaptic [--adapt] [--learn-neuron] [--fused-recurrent [--rec-delays DEPTH]]]]
 
 ``--fused`` replaces the hand-written neuron (about six elementwise launches forwards and twice that backwards per time step) by
 ``be.lif_step`` (one launch each way; the same leak, threshold, hard reset to 0 and fast-sigmoid surrogate, the reset's gradient
@@ -22,7 +22,10 @@ runs the whole recurrent layer — all ``T`` steps, the recurrent product includ
 the readout product once over all ``T * batch`` spike rows.  ``--learn-neuron`` (with ``--synaptic``) makes ``syn_decay``, ``beta``,
 ``v_th`` and, with ``--adapt``, ``rho`` and ``kappa`` per-neuron ``torch.nn.Parameter``s that start at the constants and are trained with
 the weights: ``be.parametric_synaptic_lif_step`` reads them on the device and hands back their gradients — or, together with
-``--fused-recurrent``, ``be.parametric_recurrent_lif_sequence`` does, still as one launch each way.
+``--fused-recurrent``, ``be.parametric_recurrent_lif_sequence`` does, still as one launch each way.  ``--rec-delays DEPTH`` (with
+``--fused-recurrent``, without ``--learn-neuron``) gives every recurrent synapse a conduction delay drawn uniformly from ``[0, DEPTH)``
+steps: ``rec.with_delays(delays, DEPTH)`` goes into the same ``be.recurrent_lif_sequence`` call, and the trained leaf is the
+``DelayedCSR``'s ``stacked.data``.
 """
 import argparse
 import os
@@ -50,7 +53,8 @@ class SpikeFn(torch.autograd.Function):
         return g / (1.0 + 10.0 * (v - 1.0).abs()) ** 2
 
 
-def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False, fused_recurrent=False, learn_neuron=False):
+def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False, fused_recurrent=False, learn_neuron=False,
+          rec_delays=0):
     dev = torch.device('cuda')
     rng = np.random.default_rng(0)
     torch.manual_seed(0)
@@ -61,6 +65,10 @@ def train(args, fused=False, learn_beta=False, synaptic=False, adapt=False, fuse
     indices = torch.tensor(rng.integers(0, n, n * n_conn).astype(np.int32), device=dev)
     w_rec = torch.nn.Parameter(torch.tensor(rng.normal(0.0, 0.05, n * n_conn), dtype=torch.float32, device=dev))
     rec = be.CSR((w_rec, indices, indptr), shape=(n, n))
+    if rec_delays:                                                      # a delay per synapse: the stacked weights are the leaf
+        delays = torch.tensor(rng.integers(0, rec_delays, n * n_conn).astype(np.int32), device=dev)
+        rec = be.CSR((w_rec.detach(), indices, indptr), shape=(n, n)).with_delays(delays, rec_delays)
+        w_rec = rec.stacked.data.requires_grad_()
     w_out = torch.nn.Parameter(torch.tensor(rng.normal(0.0, 0.05, (n, n_out)), dtype=torch.float32, device=dev))
     readout = be.Dense(w_out)
     # two input patterns: each drives a different random half of the neurons
@@ -156,6 +164,9 @@ def main():
     ap.add_argument('--adapt', action='store_true', help='with --synaptic: an adaptive threshold (adapt=(rho, kappa))')
     ap.add_argument('--fused-recurrent', action='store_true',
                     help='with --synaptic: the whole recurrent layer as one launch (be.recurrent_lif_sequence)')
+    ap.add_argument('--rec-delays', type=int, default=0, metavar='DEPTH',
+                    help='with --fused-recurrent: a conduction delay per recurrent synapse, uniform in [0, DEPTH) steps '
+                         '(be.recurrent_lif_sequence on rec.with_delays(delays, DEPTH))')
     ap.add_argument('--learn-neuron', action='store_true',
                     help='with --synaptic: syn_decay, beta, v_th (and rho, kappa) as learnable per-neuron Parameters '
                          '(be.parametric_synaptic_lif_step; with --fused-recurrent be.parametric_recurrent_lif_sequence)')
@@ -164,6 +175,10 @@ def main():
         ap.error('--learn-neuron needs --fused --synaptic')
     if args.fused_recurrent and not args.synaptic:
         ap.error('--fused-recurrent needs --fused --synaptic (it is the synaptic neuron with the recurrence inside)')
+    if args.rec_delays and (not args.fused_recurrent or args.learn_neuron):
+        ap.error('--rec-delays needs --fused-recurrent and no --learn-neuron (learnable neuron parameters with delays are not built)')
+    if not 0 <= args.rec_delays <= 256:
+        ap.error('--rec-delays takes a depth of 1 .. 256 (0: no delays)')
     if args.learn_beta and not args.fused:
         ap.error('--learn-beta needs --fused (the hand-written neuron keeps its constant leak)')
     if args.synaptic and not args.fused:
@@ -178,6 +193,7 @@ def main():
     if args.synaptic:
         print('fused neuron (' + ('be.parametric_recurrent_lif_sequence, learnable per-neuron parameters'
                                   if args.fused_recurrent and args.learn_neuron else
+                                  f'be.recurrent_lif_sequence, synaptic delays below {args.rec_delays} steps' if args.rec_delays else
                                   'be.recurrent_lif_sequence' if args.fused_recurrent else
                                   'be.parametric_synaptic_lif_step, learnable per-neuron parameters' if args.learn_neuron else
                                   'be.synaptic_lif_step') +
@@ -185,7 +201,7 @@ def main():
     else:
         print('fused neuron (be.lif_step' + (', learnable per-neuron beta):' if args.learn_beta else '):'))
     fused = train(args, fused=True, learn_beta=args.learn_beta, synaptic=args.synaptic, adapt=args.adapt,
-                  fused_recurrent=args.fused_recurrent, learn_neuron=args.learn_neuron)
+                  fused_recurrent=args.fused_recurrent, learn_neuron=args.learn_neuron, rec_delays=args.rec_delays)
     print('hand-written neuron (torch elementwise ops), same start:')
     plain = train(args)
     print(f"end points: fused {fused[0]:.4f} -> {fused[1]:.4f}, hand-written {plain[0]:.4f} -> {plain[1]:.4f}")

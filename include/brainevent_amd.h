@@ -374,6 +374,52 @@ int be_lif_rec_sg_backward_params(const float* h_save, const float* c_save, cons
                                   float* g_sd_slot, float* g_beta_slot, float* g_vth_slot, float* g_rho_slot, float* g_kappa_slot,
                                   int64_t T, int64_t B, int64_t N, double v_reset, int reset_mode, int surrogate, double alpha,
                                   int adaptive, int detach_reset, be_stream_t stream);
+/* The recurrent layer with SYNAPTIC DELAYS (brainevent_amd/csrc/be_neuron_sg_rec_delay.hip): be_lif_rec_sg_forward / _backward with
+ * the stacked matrix of a delay split in the place of the CSR matrix.  w, indices (int32 columns in [0, N)) and indptr (int32
+ * [depth * N + 1]) are the STACKED arrays: stacked row d * N + i holds the stored entries of presynaptic neuron i whose conduction
+ * delay is d steps, 0 <= d < depth <= 256 (be_delay_split_count / _fill produce them).  row_mask (uint32 [depth, ceil(N / 32)], bit
+ * i % 32 of word i / 32 of row d set where stacked row d * N + i is NOT empty; NULL keeps every row) lets both passes skip empty
+ * stacked rows; it must not clear the bit of a row that has entries, and the results do not depend on whether it is given.
+ * s_hist / g_s_hist are [hist_ages, B, N], 0 <= hist_ages <= depth: s_hist[a] are the spikes emitted a + 1 steps before step 0
+ * (active where != 0); ages from hist_ages on are silent.  Every other array, shape and scalar is be_lif_rec_sg_forward /
+ * _backward's.  Write sp(tau)[b][i] = s_out[tau][b][i] != 0 for tau >= 0, s_hist[-1 - tau][b][i] != 0 for -hist_ages <= tau < 0,
+ * false below.
+ *   forward, for every sample b independently, t = 0 .. T-1:
+ *     R[j] = sum over the stored entries k of every ACTIVE stacked row whose column is j of fixed(w[k]);  stacked row d * N + i is
+ *            active when sp(t - 1 - d)[b][i]     (fixed() and the 64-bit wrapping integer sum as be_lif_rec_sg_forward: order
+ *            independent)
+ *     r[j] = (float)((double)(int64)R[j] * inv);   xin = x[t][b][j] + r[j]   (one rounded f32 addition, made even when r = +0)
+ *     then the forward step of be_lif_syn_sg_forward, verbatim, with xin in the place of x[t][i]
+ *   The forward pass is therefore a function of its inputs, bit for bit; depth = 1 is be_lif_rec_sg_forward with s0 = s_hist[0].
+ *   backward, t = T-1 .. 0, the carries cc, cv, ca as there; g_x[t + 1 ..] are what the earlier iterations produced:
+ *     g_rec = +0;  for d = 0, 1, .. ascending while d < depth and t + 1 + d <= T-1:
+ *               g_rec = g_rec + (sum over the entries k of stacked row d * N + i of w[k] * g_x[t + 1 + d][b][indices[k]])
+ *             (each product rounded; the row sum in f32 in an order the row's length alone fixes: lane j of 2 takes the entries
+ *             j, j + 2, ... in order from +0, then the two partial sums are added; an empty row adds +0)
+ *     g_sp  = g_s[t][b][i] (NULL: 0);   if t < T-1: g_sp = g_sp + g_rec;   then the backward step continues unchanged
+ *   after the loop g_c0, g_v0, g_a0 as there, and, if g_s_hist is given, for a < hist_ages:
+ *     g_s_hist[a][b][i] = +0, then for d = a, a + 1, .. ascending while d < depth and d - a <= T-1:
+ *               + (sum over the entries k of stacked row d * N + i of w[k] * g_x[d - a][b][indices[k]])     (the same row sum)
+ *   g_x is a REQUIRED output: it is the history the gathers read back (the workgroup's own stores, ordered by workgroup barriers).
+ *   Two calls on the same inputs give identical bits.  The weight gradient is be_grad_rows (transpose = 1) over the stacked matrix
+ *   (n_rows = depth * N) and the T * B batch rows (t, b) of g_x, g_sn = 1, g_sb = N, with the activity mask of
+ *   be_grad_pack_activity_aged below: g_w[k] = sum over (t, b) ascending of sp(t - 1 - d)[b][i] * g_x[t][b][indices[k]].
+ * LIMITS: N <= 8192 and 8 * N + 8 * depth * ceil(N / 64) + 16384 <= 162816 bytes (one sample's sums, its spike history and a list
+ * of at least 4096 active rows live in one workgroup's LDS): every N <= 8192 with depth <= 16 and every N <= 2048 with depth <= 256
+ * fit.  BE_ERR_RANGE beyond them, by both calls.  T == 0, B == 0 or N == 0: BE_OK, nothing launched.  BE_ERR_INVALID: depth outside
+ * 1 .. 256; hist_ages outside 0 .. depth; hist_ages > 0 with s_hist NULL (forward); g_x NULL; everything be_lif_rec_sg_forward /
+ * _backward list.  No global atomics, no workspace; never synchronises the host. */
+int be_lif_rec_delay_sg_forward(const float* x, const float* w, const int32_t* indices, const int32_t* indptr, const uint32_t* row_mask,
+                                int depth, const float* s_hist, int hist_ages, const float* c0, const float* v0, const float* a0,
+                                float* s_out, float* v_seq, float* h_save, float* th_save, float* c_last, float* v_last, float* a_last,
+                                int64_t T, int64_t B, int64_t N, double syn_decay, double beta, double v_th, double v_reset, double rho,
+                                double kappa, int reset_mode, int adaptive, int scale_exp, be_stream_t stream);
+int be_lif_rec_delay_sg_backward(const float* h_save, const float* th_save, const float* w, const int32_t* indices,
+                                 const int32_t* indptr, const uint32_t* row_mask, int depth, const float* g_s, const float* g_vseq,
+                                 const float* g_clast, const float* g_vlast, const float* g_alast, float* g_x, float* g_c0, float* g_v0,
+                                 float* g_a0, float* g_s_hist, int hist_ages, int64_t T, int64_t B, int64_t N, double syn_decay,
+                                 double beta, double v_th, double v_reset, double rho, double kappa, int reset_mode, int surrogate,
+                                 double alpha, int adaptive, int detach_reset, be_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * event vector helpers (replace: brainevent/_jit_scalar/binary_jitsmv.cu:107-125 `_pack_bool_kern`
@@ -1136,6 +1182,12 @@ int be_plasticity_dense(int pre, void* weights, int wdtype, int64_t n_rows, int6
  * be_grad_pack_activity: the activity of a batch-major spike buffer [n_batch, n] (BE_SPIKE_BOOL / BE_SPIKE_FLOAT; BE_SPIKE_BITS:
  * [n_batch, ceil(n/32)] words; BE_SPIKE_IDS: one vector) as the per-neuron bit mask mask[n][ceil(n_batch/32)] (bit b % 32 of
  * word b / 32), be_grad_mask_bytes(n, n_batch) bytes.
+ * be_grad_pack_activity_aged (csrc/be_neuron_sg_rec_delay.hip; ONE launch): the activity of the stacked rows of a delay split over
+ * the T * B batch rows (t, b) of be_lif_rec_delay_sg_backward's g_x, from the layer's f32 spikes s [T, B, N] and s_hist
+ * [hist_ages, B, N] (active where != 0): mask[depth * N][ceil(T * B / 32)], bit p % 32 of word p / 32 of row d * N + i, p = t * B + b,
+ * = sp(t - 1 - d)[b][i] — neuron i's spike train shifted by d steps, history included, silence before it;
+ * be_grad_mask_bytes(depth * N, T * B) bytes, every word written.  BE_ERR_INVALID: B < 1, T < 1, T * B > 65535, depth outside
+ * 1 .. 256, hist_ages outside 0 .. depth, a NULL pointer that is needed.
  * be_grad_rows: CSR rows (indptr int32 / int64) or fixed-length rows (indptr = NULL, row_len = num_conn, nse = n_rows *
  * row_len).  mask has one row per stored row (transpose = 1) or per column id (transpose = 0).  g is the weight dtype; its
  * element (batch b, neuron x) is g[x * g_sn + b * g_sb], x a column id (transpose = 1) or a row (transpose = 0).
@@ -1144,6 +1196,8 @@ int be_plasticity_dense(int pre, void* weights, int wdtype, int64_t n_rows, int6
  * ---------------------------------------------------------------------------------------------- */
 int64_t be_grad_mask_bytes(int64_t n, int64_t n_batch);
 int be_grad_pack_activity(const void* spikes, int spike_dtype, int64_t n, int64_t n_batch, uint32_t* mask, be_stream_t stream);
+int be_grad_pack_activity_aged(const float* s, const float* s_hist, int64_t N, int64_t B, int64_t T, int depth, int hist_ages,
+                               uint32_t* mask, be_stream_t stream);
 int64_t be_grad_rows_workspace_bytes(int64_t nse);
 int be_grad_rows(int transpose, void* dw, int homo, int wdtype, const int32_t* indices, const void* indptr, int indptr_is_i64,
                  int64_t row_len, int64_t n_rows, int64_t nse, const uint32_t* mask, int64_t n_batch, const void* g,
