@@ -26,8 +26,9 @@ def _check_state(who, v, g_exc, g_inh, refractory, in_exc, in_inh, spikes, spike
     if spike_bits is not None and (spike_bits.dtype != torch.int32 or spike_bits.numel() < (n + 31) // 32 or not spike_bits.is_cuda
                                    or not spike_bits.is_contiguous()):
         raise ValueError(f'{who}: spike_bits must be a contiguous int32 device tensor of ceil(n / 32) words.')
-    if spike_count is not None and (spike_count.dtype != torch.float32 or spike_count.numel() != n or not spike_count.is_cuda):
-        raise ValueError(f'{who}: spike_count must be an f32 device tensor of the same length.')
+    if spike_count is not None and (spike_count.dtype != torch.float32 or spike_count.numel() != n or not spike_count.is_cuda
+                                    or not spike_count.is_contiguous()):
+        raise ValueError(f'{who}: spike_count must be a contiguous f32 device tensor of the same length.')
     return n
 
 
@@ -38,7 +39,8 @@ def lif_coba_step(v: torch.Tensor, g_exc: torch.Tensor, g_inh: torch.Tensor, ref
                   t_ref: float = 5.0, e_exc: float = 0.0, e_inh: float = -80.0, tau_exc: float = 5.0, tau_inh: float = 10.0,
                   i_ext: float = 20.0, syn_scale: float = 1e-3, in_scale_exc: float = 1.0, in_scale_inh: float = 1.0) -> None:
     """Advance ``v``, ``g_exc``, ``g_inh``, ``refractory`` (f32 device tensors of one length) by one step **in place**, write
-    this step's spikes (``bool`` / ``uint8``) to ``spikes`` and add them to ``spike_count`` if given.  ``in_exc`` / ``in_inh``
+    this step's spikes (``bool`` / ``uint8``) to ``spikes`` and add them to ``spike_count`` (contiguous f32 of the same length; a
+    strided view such as ``counts[:, 0]`` is refused, the kernel would add into other elements) if given.  ``in_exc`` / ``in_inh``
     are this step's synaptic inputs (the outputs of ``BinaryArray(spikes) @ W_exc`` / ``@ W_inh``).  Defaults: the COBA
     benchmark network (Vogels & Abbott 2005).  Every operation is rounded separately, in the order the header states, so the
     result equals the same formulas written as elementwise tensor ops bit for bit.

@@ -51,23 +51,32 @@ __global__ void __launch_bounds__(256) k_lif_coba_step(float* __restrict__ V, fl
   }
 }
 
+// the five entry points share this function: it reports under `who`, the name of the entry point that was called (BE_REQUIRE
+// and BE_LAUNCH_CHECK would name this template)
 template <bool CUBA>
-int lif_step(float* v, float* g_exc, float* g_inh, float* refractory, const float* in_exc, const float* in_inh,
+int lif_step(const char* who, float* v, float* g_exc, float* g_inh, float* refractory, const float* in_exc, const float* in_inh,
              uint8_t* spikes_out, uint32_t* spike_bits_out, float* spike_count, int64_t n, double dt, double tau_m,
              double v_rest, double v_th, double v_reset, double t_ref, double e_exc, double e_inh,
              double decay_exc, double decay_inh, double i_ext, double syn_scale, double in_scale_exc, double in_scale_inh,
              be_stream_t stream) {
-  BE_REQUIRE(n >= 0, BE_ERR_INVALID, "n < 0");
+  const auto refuse = [who](const char* msg) {
+    be_set_error(std::string(who) + ": " + msg);
+    return BE_ERR_INVALID;
+  };
+  if (n < 0) return refuse("n < 0");
   if (n == 0) return BE_OK;
-  BE_REQUIRE(v && g_exc && g_inh && refractory && in_exc && in_inh && (spikes_out || spike_bits_out), BE_ERR_INVALID, "null pointer");
-  BE_REQUIRE(tau_m > 0. && dt > 0., BE_ERR_INVALID, "dt and tau_m must be positive");
+  if (!(v && g_exc && g_inh && refractory && in_exc && in_inh && (spikes_out || spike_bits_out))) return refuse("null pointer");
+  if (!(tau_m > 0. && dt > 0.)) return refuse("dt and tau_m must be positive");
   // derived constants in double, rounded to f32 once (what a host formulation with Python / C doubles hands to f32 arrays)
   const LifCobaP p{(float)dt, (float)(dt / tau_m), (float)v_rest, (float)v_th, (float)v_reset, (float)t_ref, (float)e_exc, (float)e_inh,
                    (float)decay_exc, (float)decay_inh, (float)i_ext, (float)syn_scale, (float)in_scale_exc, (float)in_scale_inh};
   const int grid = (int)std::min<int64_t>((n + 255) / 256, 2048);
   hipLaunchKernelGGL(k_lif_coba_step<CUBA>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), v, g_exc,
                      g_inh, refractory, in_exc, in_inh, spikes_out, spike_bits_out, spike_count, n, p);
-  BE_LAUNCH_CHECK();
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
+    be_set_error(std::string(who) + ": hipGetLastError() -> " + hipGetErrorString(e));
+    return BE_ERR_HIP;
+  }
   return BE_OK;
 }
 
@@ -79,7 +88,7 @@ int be_lif_coba_step_packed(float* v, float* g_exc, float* g_inh, float* refract
                             uint8_t* spikes_out, uint32_t* spike_bits_out, float* spike_count, int64_t n, double dt, double tau_m,
                             double v_rest, double v_th, double v_reset, double t_ref, double e_exc, double e_inh,
                             double decay_exc, double decay_inh, double i_ext, double syn_scale, be_stream_t stream) {
-  return lif_step<false>(v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, spike_bits_out, spike_count, n, dt, tau_m, v_rest,
+  return lif_step<false>(__func__, v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, spike_bits_out, spike_count, n, dt, tau_m, v_rest,
                          v_th, v_reset, t_ref, e_exc, e_inh, decay_exc, decay_inh, i_ext, syn_scale, 1.0, 1.0, stream);
 }
 
@@ -89,9 +98,9 @@ int be_lif_step_scaled_packed(int current_based, float* v, float* g_exc, float* 
                               double v_th, double v_reset, double t_ref, double e_exc, double e_inh, double decay_exc,
                               double decay_inh, double i_ext, double syn_scale, be_stream_t stream) {
   if (current_based)
-    return lif_step<true>(v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, spike_bits_out, spike_count, n, dt, tau_m, v_rest,
+    return lif_step<true>(__func__, v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, spike_bits_out, spike_count, n, dt, tau_m, v_rest,
                           v_th, v_reset, t_ref, 0., 0., decay_exc, decay_inh, i_ext, syn_scale, in_scale_exc, in_scale_inh, stream);
-  return lif_step<false>(v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, spike_bits_out, spike_count, n, dt, tau_m, v_rest,
+  return lif_step<false>(__func__, v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, spike_bits_out, spike_count, n, dt, tau_m, v_rest,
                          v_th, v_reset, t_ref, e_exc, e_inh, decay_exc, decay_inh, i_ext, syn_scale, in_scale_exc, in_scale_inh, stream);
 }
 
@@ -99,7 +108,7 @@ int be_lif_cuba_step_packed(float* v, float* g_exc, float* g_inh, float* refract
                             uint8_t* spikes_out, uint32_t* spike_bits_out, float* spike_count, int64_t n, double dt, double tau_m,
                             double v_rest, double v_th, double v_reset, double t_ref, double decay_exc, double decay_inh, double i_ext,
                             double syn_scale, be_stream_t stream) {
-  return lif_step<true>(v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, spike_bits_out, spike_count, n, dt, tau_m, v_rest,
+  return lif_step<true>(__func__, v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, spike_bits_out, spike_count, n, dt, tau_m, v_rest,
                         v_th, v_reset, t_ref, 0., 0., decay_exc, decay_inh, i_ext, syn_scale, 1.0, 1.0, stream);
 }
 
@@ -107,18 +116,16 @@ int be_lif_cuba_step(float* v, float* g_exc, float* g_inh, float* refractory, co
                      uint8_t* spikes_out, float* spike_count, int64_t n, double dt, double tau_m, double v_rest, double v_th,
                      double v_reset, double t_ref, double decay_exc, double decay_inh, double i_ext, double syn_scale,
                      be_stream_t stream) {
-  BE_REQUIRE(n == 0 || spikes_out, BE_ERR_INVALID, "null pointer");
-  return be_lif_cuba_step_packed(v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, nullptr, spike_count, n, dt, tau_m, v_rest,
-                                 v_th, v_reset, t_ref, decay_exc, decay_inh, i_ext, syn_scale, stream);
+  return lif_step<true>(__func__, v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, nullptr, spike_count, n, dt, tau_m, v_rest,
+                        v_th, v_reset, t_ref, 0., 0., decay_exc, decay_inh, i_ext, syn_scale, 1.0, 1.0, stream);
 }
 
 int be_lif_coba_step(float* v, float* g_exc, float* g_inh, float* refractory, const float* in_exc, const float* in_inh,
                      uint8_t* spikes_out, float* spike_count, int64_t n, double dt, double tau_m, double v_rest, double v_th,
                      double v_reset, double t_ref, double e_exc, double e_inh, double decay_exc, double decay_inh, double i_ext,
                      double syn_scale, be_stream_t stream) {
-  BE_REQUIRE(n == 0 || spikes_out, BE_ERR_INVALID, "null pointer");
-  return be_lif_coba_step_packed(v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, nullptr, spike_count, n, dt, tau_m, v_rest,
-                                 v_th, v_reset, t_ref, e_exc, e_inh, decay_exc, decay_inh, i_ext, syn_scale, stream);
+  return lif_step<false>(__func__, v, g_exc, g_inh, refractory, in_exc, in_inh, spikes_out, nullptr, spike_count, n, dt, tau_m, v_rest,
+                         v_th, v_reset, t_ref, e_exc, e_inh, decay_exc, decay_inh, i_ext, syn_scale, 1.0, 1.0, stream);
 }
 
 }  // extern "C"
