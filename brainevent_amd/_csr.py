@@ -753,12 +753,12 @@ class BinnedScatter:
         ids = torch.arange(m, dtype=torch.int32, device=dev)
         colsum = torch.zeros(k, dtype=torch.float32, device=dev)
         count = torch.zeros(k, dtype=torch.float32, device=dev)
-        out = torch.empty(k, dtype=torch.float32, device=dev)
+        out = torch.empty(k, dtype=torch.float32, device=dev)      # f32 for f16 / bf16 weights too: BE_BINNED_OUT_F32 (16)
         wcode = A.wcode(flat)
         for lo in range(0, m, chunk):
             n_act = torch.tensor([min(chunk, m - lo)], dtype=torch.int32, device=dev)
             ev = A.ActiveIds(ids[lo:lo + chunk], n_act, m)
-            for kind, w_arg, code, acc in ((4, flat, wcode, colsum), (1, one, A.BE_F32, count)):
+            for kind, w_arg, code, acc in ((4 | 16, flat, wcode, colsum), (1, one, A.BE_F32, count)):
                 call('be_binary_csrmv_t_binned', A.ptr(w_arg), kind, code, A.ptr(indices), A.ptr(indptr), is64, row_len, A.ptr(ev),
                      A.BE_SPIKE_IDS, A.ptr(out), m, k, self.slice_shift, cap, e0, A.ptr(ws), ws.numel(), A.stream_ptr())
                 acc += out
@@ -775,7 +775,9 @@ class BinnedScatter:
             self._stats = self._column_stats_by_steps(weights, indices)
             self._stats_stamp = weights_stamp(weights)
         colsum_max, mean_min, wmax, wmin = self._stats
-        need = 62 - (math.frexp(colsum_max * 1.001)[1] if colsum_max > 0 else 0)
+        # (a column sum that f32 cannot hold reads inf, and frexp(inf) says 0: the bound without the structure is always valid)
+        bound = colsum_max * 1.001 if math.isfinite(colsum_max) else wmax * (self.nnz + 1.0)
+        need = 62 - (math.frexp(bound)[1] if bound > 0 else 0)
         need = max(-90, min(150, need))
         for e in ([keep] if keep is not None and keep <= need else []) + [need]:
             thr = math.ldexp(1.0, min_bits - e)

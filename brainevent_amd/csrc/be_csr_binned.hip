@@ -1126,7 +1126,9 @@ int be_binary_csrmm_t_binned(const void* weights, int homo, int wdtype, const in
   // wasted issue (one post slice of an 8-way cut of C4, rows of ~125: 92.0 -> 84.8 us per step; C4 itself, rows of 1000,
   // loses with it: 0.592 -> 0.619 ms; tools/ab_binned_knobs.sh).  Any value gives the same bits.
   const bool short_rows = indptr == nullptr ? (row_len > 0 && row_len <= kShortRow) : (homo & 8) != 0;
-  homo &= ~(4 | 8);
+  // BE_BINNED_OUT_F32 (bit 4): `out_bm` is f32 whatever the weight dtype (the sums are f32 either way: no rounding to f16 / bf16)
+  const bool out_f32 = wdtype == BE_F32 || (homo & 16) != 0;
+  homo &= ~(4 | 8 | 16);
   BE_REQUIRE(homo >= 0 && homo <= 2, BE_ERR_INVALID, "homo must be 0 (per-entry weights), 1 (one weight) or 2 (BE_BINNED_ACC32)");
   const int kind = homo;
   const bool acc32 = kind == 2;
@@ -1154,7 +1156,7 @@ int be_binary_csrmm_t_binned(const void* weights, int homo, int wdtype, const in
   float* ovf_img = reinterpret_cast<float*>(wsb + wl.ovf_off);
   float* out32 = reinterpret_cast<float*>(wsb + wl.out32_off);
   void* out_user = out_bm;
-  float* out = wdtype != BE_F32 ? out32 : static_cast<float*>(out_bm);       // accumulate in f32, round once at the end
+  float* out = out_f32 ? static_cast<float*>(out_bm) : out32;                // accumulate in f32, round once at the end
   RowPtr rp{indptr, indptr_is_i64, row_len};
   const size_t spk_sz = spike_dtype == BE_SPIKE_FLOAT ? 4 : 1;
   const int64_t row_stride = spike_dtype == BE_SPIKE_BITS ? (m + 31) / 32 : m;            // elements per batch row of spikes
@@ -1274,6 +1276,7 @@ int be_binary_csrmm_t_binned(const void* weights, int homo, int wdtype, const in
   }
   be_prof_end(prof, st);
   const int64_t total = n_batch * k;
+  if (out_f32) return BE_OK;
   if (wdtype == BE_F16)
     hipLaunchKernelGGL(k_bin_round<__half>, dim3(grid_for(total, 256, 2048)), dim3(256), 0, st, out32, static_cast<__half*>(out_user), total);
   else if (wdtype == BE_BF16)

@@ -2351,8 +2351,10 @@ int be_scatter_plan_patch_entries(const void* weights, int wdtype, const void* t
   return BE_OK;
 }
 
-// The fixed-point exponent of a weighted plan from the plan itself (k_plan_colstats): same bound, same gate and same keep_exp rule
-// as be_fixed_point_exponent, whose global-atomic passes over the raw entries it replaces for matrices that have a plan.
+// The fixed-point exponent of a weighted plan from the plan itself (k_plan_colstats): same gate and same keep_exp rule as
+// be_fixed_point_exponent, whose global-atomic passes over the raw entries it replaces for matrices that have a plan.  The bound is
+// the integer column sum itself (addends rounded up), without that pass's 1.001 margin: the same exponent, or one ABOVE it where the
+// sum lies within 0.1 % under a power of two — never below (tests/exponent_cases.py).
 // maxabs_bits: what the fill left (max |w| bits, smallest non-zero |w| bits).  scratch >= 256 bytes.  SYNCHRONOUS.
 int be_scatter_plan_exponent(const void* blob, const void* seg, int64_t m, int64_t k, int slice_shift, int slice_width, int layout,
                              int64_t nnz, const uint32_t* maxabs_bits, int min_weight_bits, int keep_exp, void* scratch,

@@ -141,7 +141,10 @@ int be_fixed_point_exponent(const void* weights, int wdtype, const int32_t* indi
   const float wmax = bits_to_float(h[0]);
   // bound on any output with every row active: the largest column sum of |w| (a row may list a column several times,
   // so "rows x max |w|" is not a bound); without the structure, all the weights there are
-  double bound = indices ? (double)bits_to_float(h[2]) * 1.001 : (double)wmax * (double)(nnz + 1);
+  // (a column sum that f32 cannot hold reads inf, which frexp leaves alone: such weights take the bound without the structure,
+  // which is always valid — they are not refused: the planned route serves them)
+  const bool sum_ok = indices && h[2] < 0x7f800000u;
+  double bound = sum_ok ? (double)bits_to_float(h[2]) * 1.001 : (double)wmax * (double)(nnz + 1);
   int eb = 0;
   if (bound > 0) (void)frexp(bound, &eb);                                  // bound < 2^eb
   int need = 62 - eb;

@@ -566,6 +566,9 @@ int be_binary_csrmm_t(const void* weights, int homo, int wdtype, const int32_t* 
 #define BE_BINNED_SHORT_ROWS 8 /* ... OR-ed to any kind, a performance hint for matrices WITH an indptr: the stored rows average at
                                  most 256 entries (pass B keeps one step of loads in flight instead of two; rows of one length —
                                  indptr NULL — are classified by row_len).  Results do not depend on it. */
+#define BE_BINNED_OUT_F32 16 /* ... OR-ed to any kind: `out` is f32 [n_batch, k] whatever the weight dtype.  The sums are accumulated
+                                 in f32 and, without this flag, rounded once to f16 / bf16 weights' own dtype; column statistics
+                                 (BE_BINNED_ABS) need them unrounded — 8 significant bits lose more than the exponent's 1.001 margin. */
 #define BE_PLAN_U16 0 /* uint16 local columns (both weight kinds) */
 #define BE_PLAN_D8 1  /* sorted columns as uint8 deltas (heterogeneous weights) */
 #define BE_PLAN_H8 2  /* sorted columns as uint8 advance codes (one homogeneous weight) */
@@ -659,8 +662,17 @@ int be_scatter_plan_patch_entries(const void* weights, int wdtype, const void* t
  *   keep_exp       : an exponent to keep when it still cannot overflow (weights refreshed under a captured graph, where
  *                    scale_exp is a recorded launch argument), or INT_MIN.
  * SYNCHRONOUS (reads statistics back).  Returns BE_ERR_RANGE — use the direct route — for inf / nan weights or a dynamic
- * range 64-bit sums cannot resolve.  scratch >= be_fixed_point_scratch_bytes(k).  No reference counterpart: its GPU kernels
- * add floats with global atomics (brainevent/_csr/binary_csrmv_hybrid.cu:199-234). */
+ * range 64-bit sums cannot resolve.  scratch >= be_fixed_point_scratch_bytes(k).  Every index must lie in [0, k): the passes
+ * address colsum[indices[j]] unchecked.  No reference counterpart: its GPU kernels add floats with global atomics
+ * (brainevent/_csr/binary_csrmv_hybrid.cu:199-234).
+ *   the bound      : 1.001 x the largest f32 column sum S', summed with float atomics.  Every add rounds by at most half an ulp,
+ *                    i.e. 2^-24 of the running sum, which never exceeds S' (the addends are non-negative): the true sum S of a
+ *                    column of n entries obeys S <= S' (1 + n 2^-24).  The step wraps at 2^63, the rule keeps 1.001 S' 2^e below
+ *                    2^62: that spare bit covers S <= 2.002 S', i.e. any column of up to n = 2^24 entries (1.68e7), whatever its
+ *                    weights.  (Equal weights are the worst case: their sum stops growing at 2^24 addends, the next one being
+ *                    exactly half an ulp, so such a column stays safe up to 1.001 x 2^25 entries and wraps beyond.)  Past that
+ *                    in-degree take the plan's exponent, whose sums are integers.  A column sum beyond the f32 range (inf) is
+ *                    replaced by max|w| * (nnz + 1) in f64, always valid: such weights are not refused. */
 int64_t be_fixed_point_scratch_bytes(int64_t k);
 /* max |w| and the smallest non-zero |w| of a weight array as f32 bit patterns (0 / 0xffffffff when there is none; a max at or
  * above 0x7f800000 means inf / nan): one streaming pass.  scratch >= 256 bytes.  SYNCHRONOUS. */
@@ -669,11 +681,13 @@ int be_weight_stats(const void* weights, int wdtype, int64_t n, uint32_t* max_bi
 int be_fixed_point_exponent(const void* weights, int wdtype, const int32_t* indices, int64_t nnz, int64_t k,
                             int min_weight_bits, int keep_exp, void* scratch, int64_t scratch_bytes, int* scale_exp_host,
                             be_stream_t stream);
-/* The same exponent — same bound, gate and keep_exp rule — for a matrix that has a WEIGHTED plan (BE_PLAN_U16 with per-entry
+/* The same exponent — same gate and keep_exp rule — for a matrix that has a WEIGHTED plan (BE_PLAN_U16 with per-entry
  * weights, BE_PLAN_D8), computed from the plan's own blocks: one workgroup per slice sums |w| of every row's block in LDS
  * (64-bit fixed point, addends rounded up: the bound never falls short) — a planned step with all rows active — instead of two
- * passes of global float atomics over the raw entries (1e10 entries: 0.47 s -> tens of ms).  maxabs_bits: what
- * be_scatter_plan_fill left.  scratch >= 256 bytes.  SYNCHRONOUS. */
+ * passes of global float atomics over the raw entries (1e10 entries: 0.47 s -> tens of ms).  Its bound is the sum itself, without
+ * the entry pass's 1.001 margin: the result equals be_fixed_point_exponent's or is ONE ABOVE it (largest column sum within 0.1 %
+ * under a power of two); away from the clamps it is never below.  Both are safe.  maxabs_bits: what be_scatter_plan_fill left.
+ * min_weight_bits: 0 ... 40.  scratch >= 256 bytes.  SYNCHRONOUS. */
 int be_scatter_plan_exponent(const void* blob, const void* seg, int64_t m, int64_t k, int slice_shift, int slice_width, int layout,
                              int64_t nnz, const uint32_t* maxabs_bits, int min_weight_bits, int keep_exp, void* scratch,
                              int64_t scratch_bytes, int* scale_exp_host, be_stream_t stream);
