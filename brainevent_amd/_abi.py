@@ -68,6 +68,12 @@ _SIGNATURES = dict(
     be_binary_csrmm_t_indexed='i:piippilpipiplllplp', be_binary_csrmm_nt_indexed='i:piippilpipiplllplp',
     be_binary_densemm_workspace_bytes='l:lllii', be_binary_densemm='i:pipipllliplp',
     be_binary_densemm_f8_workspace_bytes='l:lllii', be_binary_densemm_f8='i:pidpipllliplp',
+    be_binary_csrmv_t_f8_workspace_bytes='l:ll', be_binary_csrmm_t_f8_workspace_bytes='l:lll',
+    be_binary_csrmv_t_f8='i:pidppillpipllplp', be_binary_csrmm_t_f8='i:pidppillpiplllplp',
+    be_scatter_plan_q8_scratch_bytes='l:llii', be_scatter_plan_q8_count='i:ppillliipplLpp',
+    be_scatter_plan_q8_fill='i:pppillliipppp', be_binary_csrmv_t_plan_f8_workspace_bytes='l:lliiii',
+    be_binary_csrmm_t_plan_f8_workspace_bytes='l:llliiii', be_binary_csrmv_t_plan_f8='i:ppidpiplliiiiplp',
+    be_binary_csrmm_t_plan_f8='i:ppidpipllliiiiplp',
     be_jit_scatter_workspace_arm='i:plp', be_jit_scatter_workspace_disarm='i:p', be_binary_jitmv_workspace_bytes='l:llli',
     be_binary_jitmv='i:iddilupipllliiplp', be_jit_scatter_classes='i:lli', be_binary_jitmv_sharded='i:iddilupipllliiiplp',
     be_binary_jitmv_rows='i:iddilupipllllplp', be_binary_jitmm_workspace_bytes='l:lllli', be_binary_jitmm='i:iddilupiplllliplp',

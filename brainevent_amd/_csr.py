@@ -1973,6 +1973,12 @@ class CSR(CompressedSparseData):
     def tocsr(self):
         return self
 
+    def quantize_fp8(self, fmt: str = 'e4m3', scale: Optional[float] = None):
+        """This matrix with OCP FP8 weights (``fmt``: ``'e4m3'`` / ``'e5m2'``): a read-only :class:`~brainevent_amd.Float8CSR` over
+        the same ``indices`` / ``indptr``, quantised by ``quantize_fp8``'s formula (``_csr_f8.csr_quantize_fp8``)."""
+        from ._csr_f8 import csr_quantize_fp8
+        return csr_quantize_fp8(self, fmt, scale)
+
     def with_delays(self, delays, depth: int):
         """This matrix with one conduction delay per stored entry (integer steps in ``[0, depth)``, in the order of ``data``): a
         :class:`~brainevent_amd.DelayedCSR`, multiplied from the left by a :class:`~brainevent_amd.SpikeRing`."""

@@ -1,6 +1,6 @@
 // be_csr_plan.hip — the post-sliced scatter plan behind `spk @ CSR` / `spk @ FixedNumPerPre` on gfx950: build kernels
-// (count -> scan -> fill, the uint16 / d8 / h8 block layouts), the LDS-accumulating step kernels, the reduce and the
-// single-launch kernel for small matrices.  Semantics as in be_csr.hip (reference brainevent/_csr/binary.py:387-489,
+// (count -> scan -> fill, the uint16 / d8 / h8 block layouts and q8, the layout of FP8 codes), the LDS-accumulating step kernels,
+// the reduce and the single-launch kernel for small matrices.  Semantics as in be_csr.hip (reference brainevent/_csr/binary.py:387-489,
 // transpose=True); the role of the reference's per-matrix task workspace (brainevent/_csr/main.py:58-88).
 #include "be_csr_shared.h"
 #include <climits>
@@ -515,7 +515,7 @@ __device__ __forceinline__ void sub_tails(uint32_t st_v, uint32_t n4_v, int nval
 }
 
 #ifndef BE_PARTIAL_NT
-#define BE_PARTIAL_NT 1     // bit 0: the d8 kernel's partial sums leave with non-temporal stores, bit 1: the u16 kernels',
+#define BE_PARTIAL_NT 1     // bit 0: the d8 and q8 kernels' partial sums leave with non-temporal stores, bit 1: the u16 kernels',
                             // bit 2: the h8 kernel's (nobody reads them before the reduce launch; C2: 754-761 -> 777-781 Geff/s)
 #endif
 // a task's accumulators, LDS -> its partial sums (n16 pieces of 16 bytes)
@@ -1021,7 +1021,7 @@ __device__ __forceinline__ D8Item d8_item(const unsigned long long* keys, int i,
 }
 __host__ __device__ __forceinline__ uint32_t h8_block_units(uint32_t ng) { return (ng * 8u + 127u) >> 7; }
 
-template <bool H8>
+template <bool H8, bool Q8 = false /* q8: d8's items, one byte of weight each (8 bytes per lane-group, as h8) */>
 __global__ void __launch_bounds__(1024) k_plan_d8_count(const int32_t* __restrict__ indices, RowPtr rp, int64_t m,
                                                         uint32_t slice_width, int n_slices, uint2* __restrict__ seg,
                                                         unsigned long long* __restrict__ too_long,
@@ -1044,7 +1044,7 @@ __global__ void __launch_bounds__(1024) k_plan_d8_count(const int32_t* __restric
     for (int s = threadIdx.x; s < n_slices; s += blockDim.x) {
       // ng < 2^16: a row has at most kD8MaxRow entries + W/255 escapes
       const uint32_t ng = H8 ? (tot[s] + 7u) >> 3 : (tot[s] + 3u) >> 2;
-      seg[r * n_slices + s] = make_uint2(H8 ? h8_block_units(ng) : d8_block_units(ng), ng | (base_s[s] << 16));
+      seg[r * n_slices + s] = make_uint2(H8 || Q8 ? h8_block_units(ng) : d8_block_units(ng), ng | (base_s[s] << 16));
     }
     __syncthreads();
   }
@@ -1552,6 +1552,276 @@ __global__ void __launch_bounds__(1024) k_plan_accumulate_h8(const unsigned char
 }
 
 // =================================================================================================
+// "q8" layout of the scatter plan (FP8 weights, one code per entry): 2 bytes per entry instead of d8's 5.
+//   block(r, s) = [ uint8 FP8 code x 4*ng ][ uint8 delta x 4*ng ]   (8 * ng bytes, padded to 128);   seg[r][s] as for d8
+// Sorted columns and d8's delta / escape / pad rules: an escape is (code 0x00, delta 255), a tail pad (code 0, delta 0) — both
+// add the integer 0 to an accumulator of the slice.  The count pass is d8's (k_plan_d8_count<false, true>: the same items, 8 bytes
+// per lane-group), the fill is d8's with the weight array a byte array.  The step adds Q(code) = decode(code) * 2^E — an exact
+// integer at the format's fixed exponent (f8_fixed, be_csr_shared.h) — to the 64-bit LDS accumulators: no per-matrix exponent,
+// no rounding, the same bits whatever the geometry, the parts or the order.  k_plan_reduce<float, false> finishes the step
+// with inv_scale = scale * 2^-E.
+// =================================================================================================
+__global__ void __launch_bounds__(1024) k_plan_q8_fill(const uint8_t* __restrict__ codes, const int32_t* __restrict__ indices, RowPtr rp,
+                                                       int64_t m, uint32_t slice_width, int n_slices, const uint2* __restrict__ seg,
+                                                       unsigned char* __restrict__ blob, const uint16_t* __restrict__ order) {
+  const uint32_t wmagic = d8_magic(slice_width);
+  extern __shared__ unsigned long long d8_keys[];
+  __shared__ uint32_t first_idx[kD8MaxSlices], e_first[kD8MaxSlices], seg_start[kD8MaxSlices], seg_ng[kD8MaxSlices],
+      tot[kD8MaxSlices];
+  __shared__ uint32_t wtot[16];
+  for (int64_t r = blockIdx.x; r < m; r += gridDim.x) {
+    for (int s = threadIdx.x; s < n_slices; s += blockDim.x) {
+      const uint2 sg = seg[r * n_slices + s];
+      seg_start[s] = sg.x;
+      seg_ng[s] = sg.y & 0xffffu;
+      tot[s] = 0;
+    }
+    const int64_t rb = rp.at(r);
+    const int len = d8_sort_row(d8_keys, indices, rb, rp.at(r + 1), order, nullptr, slice_width * (uint32_t)n_slices);
+    const int per = (len + 1023) >> 10;
+    const int i0 = threadIdx.x * per, i1 = (i0 + per < len) ? i0 + per : len;
+    uint32_t mine = 0;
+    for (int i = i0; i < i1; ++i) mine += d8_item(d8_keys, i, slice_width, wmagic).esc;
+    const uint32_t excl = block_scan_1024(mine, wtot) - mine;
+    uint32_t run = excl;
+    for (int i = i0; i < i1; ++i) {
+      const D8Item it = d8_item(d8_keys, i, slice_width, wmagic);
+      run += it.esc;
+      if (it.first) { first_idx[it.s] = (uint32_t)i; e_first[it.s] = run; }
+    }
+    __syncthreads();
+    run = excl;
+    for (int i = i0; i < i1; ++i) {
+      const D8Item it = d8_item(d8_keys, i, slice_width, wmagic);
+      run += it.esc;
+      const uint32_t pos = ((uint32_t)i - first_idx[it.s]) + (run - e_first[it.s]);
+      unsigned char* cp = blob + ((int64_t)seg_start[it.s] << 7);
+      unsigned char* dp = cp + (size_t)seg_ng[it.s] * 4;
+      for (uint32_t q = pos - it.esc; q < pos; ++q) { cp[q] = 0; dp[q] = 255; }
+      cp[pos] = codes[rb + (int64_t)(d8_keys[i] & 0xffffull)];
+      dp[pos] = (unsigned char)it.rem;
+      atomicMax(&tot[it.s], pos + 1u);
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < n_slices; s += blockDim.x) {   // tail pads
+      unsigned char* cp = blob + ((int64_t)seg_start[s] << 7);
+      for (uint32_t q = tot[s]; q < seg_ng[s] * 4u; ++q) {
+        cp[q] = 0;
+        (cp + (size_t)seg_ng[s] * 4)[q] = 0;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+#ifndef BE_Q8_DECODE
+#define BE_Q8_DECODE 1      // the step's decoder of four codes: 1 = v_cvt_pk_f32_fp8 / _bf8 and an exact float -> integer conversion,
+                            // 0 = integer operations only (f8_fixed).  Both give Q bit for bit (the GPU tests pass on either build);
+                            // the step is bound by its vector ALU work and the converts are fewer instructions (1M x 1M, 1 % firing, us
+                            // per step e4m3 / e5m2: 10 000 per row 83 / 93 against 109 / 108; 1000 per row 102 / 118 against 137 / 136).
+#endif
+// Q of the four codes of one dword
+template <int FMT>
+__device__ __forceinline__ void q8_fixed4(uint32_t cw, unsigned long long (&v)[4]) {
+  if constexpr (BE_Q8_DECODE == 0) {
+    v[0] = f8_fixed<FMT>(cw & 0xffu), v[1] = f8_fixed<FMT>((cw >> 8) & 0xffu), v[2] = f8_fixed<FMT>((cw >> 16) & 0xffu),
+    v[3] = f8_fixed<FMT>(cw >> 24);
+  } else {
+    typedef float q8_v2f __attribute__((ext_vector_type(2)));
+    q8_v2f lo, hi;
+    if constexpr (FMT == BE_F8_E4M3) lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)cw, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)cw, true);
+    else lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)cw, false), hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)cw, true);
+    const float f[4] = {lo.x, lo.y, hi.x, hi.y};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if constexpr (FMT == BE_F8_E4M3) {
+        v[i] = (unsigned long long)(long long)(int)(f[i] * 512.0f);                  // |Q| <= 229 376: an int32, sign-extended
+      } else {
+        const unsigned long long mag = (unsigned long long)(uint32_t)(fabsf(f[i]) * 65536.0f);     // |Q| <= 3 758 096 384: a uint32
+        v[i] = f[i] < 0.f ? 0ull - mag : mag;
+      }
+    }
+  }
+}
+// one lane-group: 4 deltas (one dword) + 4 codes (one dword); `before` = column of the entry preceding this lane-group
+template <int FMT>
+__device__ __forceinline__ void q8_add4(unsigned long long* acc, uint32_t before, uint32_t d, uint32_t cw) {
+  const uint32_t c0 = before + (d & 0xffu), c1 = c0 + ((d >> 8) & 0xffu), c2 = c1 + ((d >> 16) & 0xffu), c3 = c2 + (d >> 24);
+  unsigned long long v[4];
+  q8_fixed4<FMT>(cw, v);
+  atomicAdd(&acc[c0], v[0]);
+  atomicAdd(&acc[c1], v[1]);
+  atomicAdd(&acc[c2], v[2]);
+  atomicAdd(&acc[c3], v[3]);
+}
+
+struct SegGroupQ8 {
+  uint32_t start[4], ng[4], base[4];
+  uint32_t dv[4], cv[4];
+};
+
+__device__ __forceinline__ void q8_issue(SegGroupQ8& g, int i, int nvalid, uint32_t st_v, uint32_t n4_v, int lane,
+                                         const unsigned char* __restrict__ blob) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int src = (i + q) & 63;
+    g.start[q] = __builtin_amdgcn_readlane(st_v, src);
+    const uint32_t y = (i + q < nvalid) ? __builtin_amdgcn_readlane(n4_v, src) : 0u;
+    g.ng[q] = y & 0xffffu;
+    g.base[q] = y >> 16;
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    unsigned char* blk = const_cast<unsigned char*>(blob) + ((uint64_t)g.start[q] << 7);
+    auto rc = __builtin_amdgcn_make_buffer_rsrc(blk, 0, (int)(g.ng[q] * 4u), kBufFlags);
+    g.cv[q] = __builtin_amdgcn_raw_buffer_load_b32(rc, lane * 4, 0, 0);
+    auto rd = __builtin_amdgcn_make_buffer_rsrc(blk + (uint64_t)g.ng[q] * 4u, 0, (int)(g.ng[q] * 4u), kBufFlags);
+    g.dv[q] = __builtin_amdgcn_raw_buffer_load_b32(rd, lane * 4, 0, 0);     // lanes past the block read 0
+  }
+}
+
+// lane-groups [o_begin, ng) of a q8 block, a wave per block (64 lane-groups per pass), from `carry` = the column reached before
+// lane-group o_begin: what the decoder's one pass left of a long block (q8_consume, q8q_tails)
+template <int FMT>
+__device__ __forceinline__ void q8_walk(unsigned long long* acc, const unsigned char* blk, uint32_t ng, uint32_t o_begin, uint32_t carry,
+                                        int lane) {
+  for (uint32_t o0 = o_begin; o0 < ng; o0 += 64) {
+    const uint32_t o = o0 + lane;
+    const bool in = o < ng;
+    const uint32_t d = in ? reinterpret_cast<const uint32_t*>(blk + (uint64_t)ng * 4u)[o] : 0u;
+    const uint32_t cw = in ? reinterpret_cast<const uint32_t*>(blk)[o] : 0u;
+    const uint32_t t = d8_sum4(d);
+    const uint32_t incl = wave_incl_scan_u32(t);
+    if (in) q8_add4<FMT>(acc, carry + incl - t, d, cw);
+    carry += __builtin_amdgcn_readlane(incl, 63);
+  }
+}
+
+template <int FMT>
+__device__ __forceinline__ void q8_consume(const SegGroupQ8& g, unsigned long long* acc, int lane, const unsigned char* __restrict__ blob) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    // the prefix sum runs on all 64 lanes (out-of-range lanes hold delta 0: range-checked loads); only the adds are masked
+    const uint32_t t = d8_sum4(g.dv[q]);
+    const uint32_t before = g.base[q] + wave_incl_scan_u32(t) - t;
+    if ((uint32_t)lane < g.ng[q]) q8_add4<FMT>(acc, before, g.dv[q], g.cv[q]);
+  }
+  if ((g.ng[0] | g.ng[1] | g.ng[2] | g.ng[3]) > 64u) {      // long blocks: remaining chunks of 64 lane-groups
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (g.ng[q] <= 64u) continue;
+      const uint32_t t0 = d8_sum4(g.dv[q]);
+      q8_walk<FMT>(acc, blob + ((uint64_t)g.start[q] << 7), g.ng[q], 64u,
+                   g.base[q] + __builtin_amdgcn_readlane(wave_incl_scan_u32(t0), 63), lane);
+    }
+  }
+}
+
+// ---- short blocks: LPB (8 / 16) lanes per block, as d8q_* does for d8
+struct QGroupQ8 {
+  uint32_t ng, base, d, c;
+  const unsigned char* blk;
+};
+
+template <int LPB>
+__device__ __forceinline__ void q8q_issue(QGroupQ8& g, int i, int nvalid, uint32_t st_v, uint32_t n4_v, int lane,
+                                          const unsigned char* __restrict__ blob) {
+  const int row = i + lane / LPB;
+  const uint32_t st = (uint32_t)__shfl((int)st_v, row & 63, 64);
+  const uint32_t y = (uint32_t)__shfl((int)n4_v, row & 63, 64);
+  g.ng = row < nvalid ? (y & 0xffffu) : 0u;
+  g.base = y >> 16;
+  g.blk = g.ng ? blob + ((uint64_t)st << 7) : blob;          // nothing to do: read the head of the blob (in bounds, cached)
+  const uint32_t l = (uint32_t)(lane % LPB);
+  const uint32_t o = l < g.ng ? l : 0u;                       // clamped: loads stay unconditional (counted vmcnt waits)
+  g.c = *(reinterpret_cast<const uint32_t*>(g.blk) + o);
+  g.d = *(reinterpret_cast<const uint32_t*>(g.blk + (uint64_t)g.ng * 4u) + o);
+}
+
+template <int FMT, int LPB>
+__device__ __forceinline__ void q8q_consume(QGroupQ8& g, unsigned long long* acc, int lane) {
+  asm volatile("" : "+v"(g.c), "+v"(g.d));                    // an opaque use in straight-line code: see d8q_consume
+  const uint32_t l = (uint32_t)(lane % LPB);
+  const uint32_t d0 = l < g.ng ? g.d : 0u;
+  const uint32_t t0 = d8_sum4(d0);
+  const uint32_t incl0 = sub_incl_scan_u32<LPB>(t0, l);
+  if (l < g.ng) q8_add4<FMT>(acc, g.base + incl0 - t0, d0, g.c);
+}
+
+// the rare blocks longer than one sub-wave pass (ng > LPB lane-groups), a wave per block (see d8q_tails)
+template <int FMT, int LPB>
+__device__ __forceinline__ void q8q_tails(uint32_t st_v, uint32_t n4_v, int nvalid, unsigned long long* acc, int lane,
+                                          const unsigned char* __restrict__ blob) {
+  unsigned long long longm = __ballot(lane < nvalid && (n4_v & 0xffffu) > (uint32_t)LPB);
+  while (longm) {
+    const int src = __ffsll((long long)longm) - 1;
+    longm &= longm - 1;
+    const uint32_t st = (uint32_t)__builtin_amdgcn_readlane((int)st_v, src), y = (uint32_t)__builtin_amdgcn_readlane((int)n4_v, src);
+    const uint32_t ng = y & 0xffffu;
+    const unsigned char* blk = blob + ((uint64_t)st << 7);
+    const uint32_t d_head = lane < LPB ? reinterpret_cast<const uint32_t*>(blk + (uint64_t)ng * 4u)[lane] : 0u;   // deltas already applied
+    q8_walk<FMT>(acc, blk, ng, (uint32_t)LPB,
+                 (y >> 16) + (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_u32(d8_sum4(d_head)), 63), lane);
+  }
+}
+
+template <int FMT /* BE_F8_E4M3 / BE_F8_E5M2 */, int LPB /* 0: a wave per block; 8 / 16: lanes per block */, int FUSED = 0>
+__global__ void __launch_bounds__(1024) k_plan_accumulate_q8(const unsigned char* __restrict__ blob, const uint2* __restrict__ seg,
+                                                             const uint32_t* active,
+                                                             const uint32_t* __restrict__ n_active_p, int n_slices,
+                                                             int cap, int parts,
+                                                             unsigned long long* __restrict__ partial, int64_t active_stride,
+                                                             const void* __restrict__ fused_spikes, int64_t fused_m, int64_t fused_stride,
+                                                             uint32_t list_off, uint32_t lds_cap, uint32_t* __restrict__ glob_lists,
+                                                             int64_t glob_region) {
+  using acc_t = unsigned long long;
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  acc_t* acc = reinterpret_cast<acc_t*>(smem_raw);
+  const int S = cap;                     // even; >= slice width (no pad slot, as d8)
+  const PlanTask t(n_slices, parts);
+  if (t.idle()) return;
+  PlanRows<FUSED> rows(t, n_slices, parts, active, active_stride);
+  partial += t.slot() * S;
+  plan_zero_lds(smem_raw, (int)(((size_t)(S + 1) * sizeof(acc_t) + 15) / 16));
+  rows.list(seg, n_active_p, smem_raw, fused_spikes, fused_m, fused_stride, list_off, lds_cap, glob_lists, glob_region);
+  if (rows.any()) {
+    rows.start();
+    while (rows.more()) {
+      const int nvalid = rows.fetch();
+      const uint32_t st_v = rows.st_v, n4_v = rows.n4_v;
+      const int lane = rows.lane;
+      if constexpr (LPB > 0) {
+        constexpr int BPI = 64 / LPB;                       // blocks per load instruction
+        constexpr int NGRP = 64 / BPI;                      // groups of a 64-row batch, walked in straight-line code (see _d8)
+        constexpr int DEPTH = 4;
+        QGroupQ8 g[NGRP];
+#pragma unroll
+        for (int q = 0; q < DEPTH; ++q) q8q_issue<LPB>(g[q], q * BPI, nvalid, st_v, n4_v, lane, blob);
+#pragma unroll
+        for (int q = 0; q < NGRP; ++q) {
+          if (q + DEPTH < NGRP) q8q_issue<LPB>(g[q + DEPTH], (q + DEPTH) * BPI, nvalid, st_v, n4_v, lane, blob);
+          __builtin_amdgcn_sched_barrier(0);                  // issue before the wait: see k_plan_accumulate
+          q8q_consume<FMT, LPB>(g[q], acc, lane);
+        }
+        q8q_tails<FMT, LPB>(st_v, n4_v, nvalid, acc, lane, blob);
+      } else {
+        SegGroupQ8 gA, gB;
+        q8_issue(gA, 0, nvalid, st_v, n4_v, lane, blob);
+        for (int i = 0; i < nvalid; i += 8) {
+          q8_issue(gB, i + 4, nvalid, st_v, n4_v, lane, blob);
+          q8_consume<FMT>(gA, acc, lane, blob);
+          q8_issue(gA, i + 8, nvalid, st_v, n4_v, lane, blob);
+          q8_consume<FMT>(gB, acc, lane, blob);
+        }
+      }
+      rows.next();
+    }
+  }
+  __syncthreads();
+  store_partials<1>(smem_raw, partial, (int)((size_t)S * sizeof(acc_t) / 16));
+}
+
+// =================================================================================================
 // Small matrices: the whole planned step in ONE launch.  When the output is a single slice and one part is enough
 // (k <= 16384 weighted / 32768 counted accumulators, up to ~1M entries), one workgroup compacts the spikes itself (4096
 // at a time, into LDS), walks the active rows' blocks, and converts its accumulators straight into the output: no
@@ -1998,8 +2268,15 @@ static inline bool width_ok(int slice_shift, int slice_width, int layout = BE_PL
                               (layout == BE_PLAN_H8 && slice_width <= kH8MaxWidth));
 }
 // accumulators per task (= stride of a task's partial sums; a multiple of 16 bytes)
+// the q8 layout (FP8 codes) is not a code of the be_scatter_plan_* / be_binary_csrm*_t_plan entry points, which refuse it as
+// before: it is built and stepped through entry points of its own (be_scatter_plan_q8_*, be_binary_csrm*_t_plan_f8).  Its
+// accumulators are d8's: 64-bit, no pad slot, slices up to kD8MaxWidth columns.
+constexpr int kPlanQ8 = 3;
+static inline bool q8_width_ok(int slice_shift, int slice_width) {
+  return slice_width >= 0 && (slice_width <= (1 << slice_shift) || slice_width <= kD8MaxWidth);
+}
 static inline int64_t cap_of(int slice_shift, int slice_width, int layout, int homo) {
-  if (layout == BE_PLAN_D8) return (width_of(slice_shift, slice_width) + 1) & ~1ll;
+  if (layout == BE_PLAN_D8 || layout == kPlanQ8) return (width_of(slice_shift, slice_width) + 1) & ~1ll;
   if (layout == BE_PLAN_H8) return (width_of(slice_shift, slice_width) + 3) & ~3ll;
   const int64_t w = width_of(slice_shift, slice_width);      // u16: the slice's own columns (the LDS holds 2^shift + pad)
   return homo ? (w + 3) & ~3ll : (w + 1) & ~1ll;
@@ -2015,6 +2292,8 @@ struct PlanVariant { int lpb; bool nt; };
 static inline PlanVariant plan_variant_of(int layout, int homo, int block_hint) {
   const auto upto = [&](int max_block) { return block_hint > 0 && block_hint <= max_block; };
   if (layout == BE_PLAN_H8) return {0, false};
+  if (layout == kPlanQ8)       // d8's items per lane-group and per pass: d8's thresholds (no cache policy on its block loads)
+    return {upto(kD8EighthMaxBlock) ? 8 : upto(kD8QuarterMaxBlock) ? 16 : 0, false};
   if (layout == BE_PLAN_D8)
     return upto(kD8EighthMaxBlock) ? PlanVariant{8, false} : upto(kD8QuarterMaxBlock) ? PlanVariant{16, false}
                                                                                       : PlanVariant{0, block_hint >= kD8NtMinBlock};
@@ -2489,20 +2768,28 @@ int64_t be_binary_csrmv_t_plan_workspace_bytes(int64_t m, int64_t k, int slice_s
   return be_binary_csrmm_t_plan_workspace_bytes(m, k, 1, slice_shift, slice_width, parts, homo);
 }
 
+}  // extern "C"
+
+// The planned step of every layout.  be_binary_csrmm_t_plan (below) is this with q8_fmt < 0, which keeps the q8 layout out of
+// the public layout codes; be_binary_csrmm_t_plan_f8 calls it with layout = kPlanQ8 after its own checks (the function keeps the
+// entry point's name so that the messages of BE_REQUIRE / BE_HIP read as before).
+namespace plan_step {
 int be_binary_csrmm_t_plan(const void* weights, int homo, int wdtype, const void* blob, const void* seg,
                            const void* spikes, int spike_dtype, void* out, int64_t m, int64_t k, int64_t n_batch,
                            int slice_shift, int slice_width, int layout, int block_hint, int parts, int scale_exp,
-                           void* workspace, int64_t workspace_bytes, be_stream_t stream) {
+                           void* workspace, int64_t workspace_bytes, be_stream_t stream, int q8_fmt, double q8_scale) {
+  const bool q8 = layout == kPlanQ8 && q8_fmt >= 0;
   BE_REQUIRE(m > 0 && k > 0 && m <= 0xffffffffll && k <= 0xffffffffll, BE_ERR_INVALID, "bad shape");
-  BE_REQUIRE(layout == BE_PLAN_U16 || (layout == BE_PLAN_D8 && !homo) || (layout == BE_PLAN_H8 && homo), BE_ERR_INVALID,
-             "bad plan layout");
+  BE_REQUIRE(layout == BE_PLAN_U16 || (layout == BE_PLAN_D8 && !homo) || (layout == BE_PLAN_H8 && homo) || (q8 && !homo),
+             BE_ERR_INVALID, "bad plan layout");
   BE_REQUIRE(n_batch >= 1 && n_batch <= kMaxBatch, BE_ERR_INVALID, "n_batch out of range");
   BE_REQUIRE(slice_shift >= 4 && slice_shift <= 15, BE_ERR_INVALID, "slice_shift must be in [4, 15]");
-  BE_REQUIRE(width_ok(slice_shift, slice_width, layout), BE_ERR_INVALID, "slice_width out of range for this layout");
+  BE_REQUIRE(q8 ? q8_width_ok(slice_shift, slice_width) : width_ok(slice_shift, slice_width, layout), BE_ERR_INVALID,
+             "slice_width out of range for this layout");
   BE_REQUIRE(parts >= 1 && parts <= 64, BE_ERR_INVALID, "parts must be in [1, 64]");
   BE_REQUIRE(seg && spikes && out && blob, BE_ERR_INVALID, "null pointer");
   BE_REQUIRE(!homo || weights != nullptr, BE_ERR_INVALID, "missing weights");
-  BE_REQUIRE(homo || (scale_exp - 32 > -126 && scale_exp - 32 < 127), BE_ERR_INVALID, "scale_exp out of range");
+  BE_REQUIRE(homo || q8 || (scale_exp - 32 > -126 && scale_exp - 32 < 127), BE_ERR_INVALID, "scale_exp out of range");
   const int64_t S = cap_of(slice_shift, slice_width, layout, homo);                 // stride of a task's partial sums
   const int64_t slots = lds_slots_of(slice_shift, slice_width, layout, homo);
   const size_t lds = ((size_t)(slots + 1) * (homo ? 4 : 8) + 15) & ~(size_t)15;
@@ -2521,7 +2808,7 @@ int be_binary_csrmm_t_plan(const void* weights, int homo, int wdtype, const void
   const int64_t astride = plan_active_stride(m);
   void* partial = wsb + counts_bytes(n_batch) + n_batch * astride * 4;
   const int n_slices = n_slices_of(k, slice_shift, slice_width);
-  if (n_slices == 1 && parts == 1 && n_batch == 1 && wdtype != BE_F64 &&
+  if (!q8 && n_slices == 1 && parts == 1 && n_batch == 1 && wdtype != BE_F64 &&
       (spike_dtype == BE_SPIKE_BOOL || spike_dtype == BE_SPIKE_FLOAT) &&
       lds + kSingleChunk * 4 + 64 <= 160 * 1024) {
     // small matrix: compaction + accumulate + output conversion in one single-workgroup launch (k_plan_single)
@@ -2588,7 +2875,7 @@ int be_binary_csrmm_t_plan(const void* weights, int homo, int wdtype, const void
     seg_used = dense;
   }
   const float scale = ldexpf(1.0f, scale_exp - 32);   // see fixed_from_f32
-  const double inv_scale = ldexp(1.0, -scale_exp);
+  const double inv_scale = q8 ? ldexp((double)(float)q8_scale, q8_fmt == BE_F8_E4M3 ? -kF8ExpE4M3 : -kF8ExpE5M2) : ldexp(1.0, -scale_exp);
   const int n_tasks = n_slices * parts;
   const dim3 grid((unsigned)((n_tasks + 7) / 8 * 8), (unsigned)n_batch);
   const PlanVariant var = plan_variant_of(layout, homo, block_hint);
@@ -2601,6 +2888,13 @@ int be_binary_csrmm_t_plan(const void* weights, int homo, int wdtype, const void
                                     al.ids, al.count, own..., spikes, m, fused_stride, list_off, lds_cap, active, glob_region);
     };
     if (layout == BE_PLAN_H8) return launch(k_plan_accumulate_h8<FUSED>, n_slices, (int)S, parts, static_cast<uint32_t*>(partial), astride);
+    if (layout == kPlanQ8)
+      return be_dispatch_int<BE_F8_E4M3, BE_F8_E5M2>(q8_fmt, [&](auto f) {
+        return be_dispatch_int<0, 8, 16>(var.lpb, [&](auto l) {
+          return launch(k_plan_accumulate_q8<decltype(f)::value, decltype(l)::value, FUSED>, n_slices, (int)S, parts,
+                        static_cast<unsigned long long*>(partial), astride);
+        });
+      });
     if (layout == BE_PLAN_D8)
       return be_dispatch_int<0, 8, 16>(var.lpb, [&](auto l) {
         constexpr int LPB = decltype(l)::value;
@@ -2635,6 +2929,128 @@ int be_binary_csrmm_t_plan(const void* weights, int homo, int wdtype, const void
   if (rc != BE_OK) return rc;
   BE_LAUNCH_CHECK();
   return BE_OK;
+}
+}  // namespace plan_step
+
+extern "C" {
+
+int be_binary_csrmm_t_plan(const void* weights, int homo, int wdtype, const void* blob, const void* seg,
+                           const void* spikes, int spike_dtype, void* out, int64_t m, int64_t k, int64_t n_batch,
+                           int slice_shift, int slice_width, int layout, int block_hint, int parts, int scale_exp,
+                           void* workspace, int64_t workspace_bytes, be_stream_t stream) {
+  return plan_step::be_binary_csrmm_t_plan(weights, homo, wdtype, blob, seg, spikes, spike_dtype, out, m, k, n_batch, slice_shift,
+                                           slice_width, layout, block_hint, parts, scale_exp, workspace, workspace_bytes, stream, -1, 0.0);
+}
+
+// ---------------------------------------------------------------- q8: the plan of FP8 weights (layout and step: see k_plan_q8_fill)
+// the geometry checks the q8 entry points share; `who` = the entry point, which the message names
+static int q8_check_geometry(const char* who, int64_t m, int64_t k, int slice_shift, int slice_width, int* n_slices_out) {
+  const auto fail = [&](int code, const char* msg) { be_set_error(std::string(who) + ": " + msg); return code; };
+  if (m > 0xffffffffll || k > 0xffffffffll) return fail(BE_ERR_INVALID, "bad shape");
+  if (slice_shift < 4 || slice_shift > 15) return fail(BE_ERR_INVALID, "slice_shift must be in [4, 15]");
+  if (!q8_width_ok(slice_shift, slice_width)) return fail(BE_ERR_INVALID, "slice_width out of range for the q8 layout (at most 20000)");
+  if ((((cap_of(slice_shift, slice_width, kPlanQ8, 0) + 1) * 8 + 15) & ~15ll) > 160 * 1024)
+    return fail(BE_ERR_RANGE, "slice does not fit LDS (64-bit sums: slice_shift <= 14)");
+  const int64_t n_slices = (k + width_of(slice_shift, slice_width) - 1) / width_of(slice_shift, slice_width);
+  if (n_slices > kD8MaxSlices) return fail(BE_ERR_RANGE, "q8 layout: at most 1024 slices; use the direct route (be_binary_csrmm_t_f8)");
+  *n_slices_out = (int)n_slices;
+  return BE_OK;
+}
+
+int64_t be_scatter_plan_q8_scratch_bytes(int64_t m, int64_t k, int slice_shift, int slice_width) {
+  if (m < 0 || k < 0 || slice_shift < 4 || slice_shift > 15 || !q8_width_ok(slice_shift, slice_width)) return (int64_t)BE_ERR_INVALID;
+  return be_scatter_plan_scratch_bytes(m, k, slice_shift, slice_width);
+}
+
+int be_scatter_plan_q8_count(const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t row_len, int64_t m, int64_t k,
+                             int slice_shift, int slice_width, void* seg, void* scratch, int64_t scratch_bytes,
+                             int64_t* blob_bytes_host, uint16_t* order_out, be_stream_t stream) {
+  BE_REQUIRE(m >= 0 && k >= 0, BE_ERR_INVALID, "bad shape");
+  BE_REQUIRE(blob_bytes_host, BE_ERR_INVALID, "null pointer");
+  int n_slices = 0;
+  int rc = q8_check_geometry(__func__, m, k, slice_shift, slice_width, &n_slices);
+  if (rc != BE_OK) return rc;
+  *blob_bytes_host = 0;
+  if (m == 0 || k == 0) return BE_OK;
+  BE_REQUIRE(check_rows(indptr, row_len), BE_ERR_INVALID, "indptr is NULL and row_len < 0");
+  BE_REQUIRE(indptr != nullptr || row_len <= kD8MaxRow, BE_ERR_RANGE,
+             "q8 layout: rows of at most 16384 entries; use the direct route (be_binary_csrmm_t_f8)");
+  BE_REQUIRE(seg && scratch, BE_ERR_INVALID, "null pointer");
+  BE_REQUIRE(scratch_bytes >= be_scatter_plan_scratch_bytes(m, k, slice_shift, slice_width), BE_ERR_WORKSPACE, "scratch too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  BE_HIP(be_fill_async(plan_too_long(scratch, m, n_slices), 0, 8, st));
+  auto kern = k_plan_d8_count<false, true>;
+  BE_HIP(be_allow_lds(reinterpret_cast<const void*>(kern), kD8MaxRow * 8));
+  hipLaunchKernelGGL(kern, dim3(grid_for(m, 1, 256 * 8)), dim3(1024), kD8MaxRow * 8, st, indices, RowPtr{indptr, indptr_is_i64, row_len}, m,
+                     (uint32_t)width_of(slice_shift, slice_width), n_slices, static_cast<uint2*>(seg), plan_too_long(scratch, m, n_slices),
+                     order_out);
+  BE_LAUNCH_CHECK();
+  // (the scan reads the longest over-long row back and refuses the build: BE_ERR_RANGE)
+  rc = be_scatter_plan_scan(m, k, slice_shift, slice_width, seg, scratch, scratch_bytes, blob_bytes_host, stream);
+  if (rc == BE_ERR_RANGE) be_set_error(std::string(__func__) + ": a row of more than 16384 entries (or a plan above 512 GiB): the "
+                                       "q8 layout does not hold it; use the direct route (be_binary_csrmm_t_f8)");
+  return rc;
+}
+
+int be_scatter_plan_q8_fill(const void* codes, const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t row_len,
+                            int64_t m, int64_t k, int slice_shift, int slice_width, const void* seg, void* blob,
+                            const uint16_t* order, be_stream_t stream) {
+  BE_REQUIRE(m >= 0 && k >= 0, BE_ERR_INVALID, "bad shape");
+  int n_slices = 0;
+  const int rc = q8_check_geometry(__func__, m, k, slice_shift, slice_width, &n_slices);
+  if (rc != BE_OK) return rc;
+  if (m == 0 || k == 0) return BE_OK;
+  BE_REQUIRE(check_rows(indptr, row_len), BE_ERR_INVALID, "indptr is NULL and row_len < 0");
+  BE_REQUIRE(indptr != nullptr || row_len <= kD8MaxRow, BE_ERR_RANGE, "q8 layout: rows of at most 16384 entries");
+  BE_REQUIRE(seg && blob, BE_ERR_INVALID, "null pointer");      // (codes / indices may be NULL for a matrix without entries)
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto kern = k_plan_q8_fill;
+  BE_HIP(be_allow_lds(reinterpret_cast<const void*>(kern), kD8MaxRow * 8));
+  hipLaunchKernelGGL(kern, dim3(grid_for(m, 1, 256 * 8)), dim3(1024), kD8MaxRow * 8, st, static_cast<const uint8_t*>(codes), indices,
+                     RowPtr{indptr, indptr_is_i64, row_len}, m, (uint32_t)width_of(slice_shift, slice_width), n_slices,
+                     static_cast<const uint2*>(seg), static_cast<unsigned char*>(blob), order);
+  BE_LAUNCH_CHECK();
+  return BE_OK;
+}
+
+int64_t be_binary_csrmm_t_plan_f8_workspace_bytes(int64_t m, int64_t k, int64_t n_batch, int slice_shift, int slice_width, int parts,
+                                                  int block_hint) {
+  if (m < 0 || k < 0 || n_batch < 0 || slice_shift < 4 || slice_shift > 15 || !q8_width_ok(slice_shift, slice_width) || parts < 1 ||
+      parts > 64)
+    return (int64_t)BE_ERR_INVALID;
+  if (m == 0 || k == 0 || n_batch == 0) return 256;
+  return be_binary_csrmm_t_plan_workspace_bytes_for(m, k, n_batch, slice_shift, slice_width, parts, 0, block_hint);
+}
+int64_t be_binary_csrmv_t_plan_f8_workspace_bytes(int64_t m, int64_t k, int slice_shift, int slice_width, int parts, int block_hint) {
+  return be_binary_csrmm_t_plan_f8_workspace_bytes(m, k, 1, slice_shift, slice_width, parts, block_hint);
+}
+
+int be_binary_csrmm_t_plan_f8(const void* blob, const void* seg, int f8_format, double scale, const void* spikes_bm, int spike_dtype,
+                              void* out_bm, int64_t m, int64_t k, int64_t n_batch, int slice_shift, int slice_width, int block_hint,
+                              int parts, void* workspace, int64_t workspace_bytes, be_stream_t stream) {
+  BE_REQUIRE(f8_format == BE_F8_E4M3 || f8_format == BE_F8_E5M2, BE_ERR_INVALID, "f8_format must be BE_F8_E4M3 or BE_F8_E5M2");
+  BE_REQUIRE(m >= 0 && k >= 0 && n_batch >= 0 && n_batch <= kMaxBatch, BE_ERR_INVALID, "bad shape");
+  BE_REQUIRE(std::isfinite((float)scale), BE_ERR_INVALID, "scale must be a finite f32");
+  BE_REQUIRE(spike_dtype >= BE_SPIKE_BOOL && spike_dtype <= BE_SPIKE_IDS, BE_ERR_INVALID, "unknown spike dtype");
+  BE_REQUIRE(parts >= 1 && parts <= 64, BE_ERR_INVALID, "parts must be in [1, 64]");
+  int n_slices = 0;
+  const int rc = q8_check_geometry(__func__, m, k, slice_shift, slice_width, &n_slices);
+  if (rc != BE_OK) return rc;
+  if (m == 0 || k == 0 || n_batch == 0) return BE_OK;
+  BE_REQUIRE(spike_dtype != BE_SPIKE_IDS || n_batch == 1, BE_ERR_UNSUPPORTED, "BE_SPIKE_IDS takes a single event vector (n_batch = 1)");
+  BE_REQUIRE(seg && spikes_bm && out_bm && blob, BE_ERR_INVALID, "null pointer");
+  BE_REQUIRE(workspace != nullptr &&
+                 workspace_bytes >= be_binary_csrmm_t_plan_workspace_bytes(m, k, n_batch, slice_shift, slice_width, parts, 0),
+             BE_ERR_WORKSPACE, "workspace too small");
+  return plan_step::be_binary_csrmm_t_plan(nullptr, 0, BE_F32, blob, seg, spikes_bm, spike_dtype, out_bm, m, k, n_batch, slice_shift,
+                                           slice_width, kPlanQ8, block_hint, parts, 0, workspace, workspace_bytes, stream, f8_format, scale);
+}
+
+int be_binary_csrmv_t_plan_f8(const void* blob, const void* seg, int f8_format, double scale, const void* spikes, int spike_dtype,
+                              void* out, int64_t m, int64_t k, int slice_shift, int slice_width, int block_hint, int parts,
+                              void* workspace, int64_t workspace_bytes, be_stream_t stream) {
+  return be_binary_csrmm_t_plan_f8(blob, seg, f8_format, scale, spikes, spike_dtype, out, m, k, 1, slice_shift, slice_width, block_hint,
+                                   parts, workspace, workspace_bytes, stream);
 }
 
 int be_binary_csrmv_t_plan(const void* weights, int homo, int wdtype, const void* blob, const void* seg,

@@ -94,6 +94,20 @@ __device__ __forceinline__ void plan_count8(uint32_t* acc, uint32_t a, uint32_t 
   atomicAdd(&acc[d & 0xffffu], 1u); atomicAdd(&acc[d >> 16], 1u);
 }
 
+// ---------------------------------------------------------------- FP8 weights as exact integers (q8 plan and direct f8 route)
+// Q(c) = decode(c) * 2^E of a finite OCP FP8 code, E = 9 (e4m3) / 16 (e5m2), as a 64-bit two's-complement integer, decoded
+// with integer operations only: with MB mantissa bits the magnitude is m for a subnormal (exponent field 0) and
+// (2^MB + m) << (e - 1) otherwise — both formats' bias puts the subnormal step at 2^-E.  |Q| <= 229 376 / 3 758 096 384.
+// Non-finite codes are the caller's to keep out (include/brainevent_amd.h).
+constexpr int kF8ExpE4M3 = 9, kF8ExpE5M2 = 16;
+template <int FMT>
+__device__ __forceinline__ unsigned long long f8_fixed(uint32_t c) {
+  constexpr uint32_t MB = FMT == BE_F8_E4M3 ? 3u : 2u;
+  const uint32_t mant = c & ((1u << MB) - 1u), e = (c & 0x7fu) >> MB;
+  const uint32_t mag = e ? ((mant | (1u << MB)) << (e - 1u)) : mant;
+  return (c & 0x80u) ? 0ull - (unsigned long long)mag : (unsigned long long)mag;
+}
+
 typedef unsigned be_v2u __attribute__((ext_vector_type(2)));
 typedef unsigned be_v4u __attribute__((ext_vector_type(4)));
 constexpr int kBufFlags = 0x00020000;   // raw buffer, 32-bit data format (guide T8)

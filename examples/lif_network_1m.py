@@ -7,7 +7,10 @@ random f32 matrix with 1 % density (C2 of BASELINE.json: 1M x 1M, 10 000 synapse
 Excitatory (80 %) and inhibitory (20 %, 4x stronger) rows balance, so the recurrent input shapes the rate without
 taking it over.  This is a throughput demonstration, not a model from the literature.
 
-    python examples/lif_network_1m.py [n] [steps]
+    python examples/lif_network_1m.py [n] [steps] [--fp8[=e4m3|e5m2]]
+
+``--fp8`` runs the recurrence on one-byte synapses: the matrix quantised by ``csr.quantize_fp8`` (2 bytes per synapse in its
+plan instead of 5, exact integer sums); try it at a reduced size first, e.g. ``200000 200 --fp8``.
 """
 import os
 import sys
@@ -20,7 +23,7 @@ import brainevent_amd as be
 from bench import gen_csr_on_device
 
 
-def main(n=1_000_000, steps=500):
+def main(n=1_000_000, steps=500, fp8=None):
     dev = torch.device('cuda', 0)
     g = torch.Generator(device=dev); g.manual_seed(1)
     n_conn = max(1, n // 100)
@@ -30,10 +33,16 @@ def main(n=1_000_000, steps=500):
     scale = 0.2 / (n_conn * 0.01)                                            # ~0.2 of threshold arrives per step at 1 % firing
     w[: n_exc * n_conn] *= scale
     w[n_exc * n_conn:] *= -4.0 * scale
-    csr = be.CSR((w, idx, ptr), shape=(n, n), check_structure=False).prepare()
+    csr = be.CSR((w, idx, ptr), shape=(n, n), check_structure=False)
+    if fp8:
+        csr = csr.quantize_fp8(fp8).prepare()
+        route = f'{csr!r}, ' + (f'q8 plan of {csr._plan.nbytes() / 1e9:.2f} GB' if csr._plan is not None else 'direct route')
+        del w
+    else:
+        csr.prepare()
+        route = 'route ' + type(csr.buffers["scatter_plan"]).__name__
     torch.cuda.synchronize()
-    print(f'{n} neurons, {n * n_conn:.3g} synapses, route {type(csr.buffers["scatter_plan"]).__name__}, '
-          f'setup {time.perf_counter() - t0:.1f} s', flush=True)
+    print(f'{n} neurons, {n * n_conn:.3g} synapses, {route}, setup {time.perf_counter() - t0:.1f} s', flush=True)
 
     V = torch.rand(n, device=dev, generator=g)
     spk = torch.zeros(n, dtype=torch.bool, device=dev)
@@ -65,4 +74,7 @@ def main(n=1_000_000, steps=500):
 
 
 if __name__ == '__main__':
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000, int(sys.argv[2]) if len(sys.argv) > 2 else 500)
+    flags = [a for a in sys.argv[1:] if a.startswith('--fp8')]
+    pos = [a for a in sys.argv[1:] if not a.startswith('--')]
+    main(int(pos[0]) if len(pos) > 0 else 1_000_000, int(pos[1]) if len(pos) > 1 else 500,
+         (flags[0].partition('=')[2] or 'e4m3') if flags else None)

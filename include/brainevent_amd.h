@@ -998,6 +998,73 @@ int be_binary_densemm_f8(const void* weights, int f8_format, double scale, const
                          int64_t workspace_bytes, be_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * FP8 weights for the event-driven CSR products: `events @ W8`, the scatter over the active rows of a CSR matrix whose stored
+ * entries are OCP FP8 codes, one byte each (brainevent_amd/csrc/be_csr_f8.hip, the q8 layout of be_csr_plan.hip; no counterpart
+ * in the reference).  FP8 is not a wdtype: the format travels as f8_format (BE_F8_E4M3 / BE_F8_E5M2, never the fnuz forms).
+ *
+ * Semantics.  E = 9 for e4m3 and 16 for e5m2; Q(c) = decode(c) * 2^E is an exact integer for every finite code c
+ * (|Q| <= 229 376 for e4m3, <= 3 758 096 384 for e5m2).  For output column j of batch row b:
+ *     R_j    = sum over the active rows i of b, over the stored entries e of row i with indices[e] == j, of Q(codes[e])   (int64, exact)
+ *     out[j] = (float)((double)(long long)R_j * inv),      inv = ldexp((double)(float)scale, -E)
+ * "Active" is the rule of every scatter entry point: BE_SPIKE_BOOL != 0, BE_SPIKE_FLOAT > 0 (a negative or NaN value is
+ * inactive), a set bit of BE_SPIKE_BITS, a listed id of BE_SPIKE_IDS (single vector).  The output is always f32; there is one f32
+ * scale per matrix.  (double)R_j is exact while |R_j| < 2^53, and R_j itself cannot overflow while a column has fewer than 2^31
+ * stored entries (2^31 * 3 758 096 384 < 2^63).  The sums are integers at a fixed exponent: no per-matrix exponent, no accuracy gate,
+ * and the result is bit-identical whatever the route (plan or direct), the slice geometry, `parts` or the order of the adds.
+ * PRECONDITION: every code is finite (e4m3: (c & 0x7f) != 0x7f; e5m2: (c & 0x7c) != 0x7c); the kernels do not test it.
+ *
+ * Common contracts: explicit stream, caller-owned buffers, nothing allocated, no host read in a step (capturable); m, k or
+ * n_batch of zero: BE_OK and nothing else done, after the scalar arguments were checked.  BE_ERR_INVALID: an unknown f8_format or
+ * spike dtype, a non-finite scale, negative sizes, m or k above 2^32 - 1, n_batch above 65535, a NULL buffer, slice_shift outside
+ * [4, 15], slice_width negative or above max(2^slice_shift, 20000), parts outside [1, 64].  BE_ERR_WORKSPACE: a workspace or scratch
+ * that is NULL or too small.  BE_ERR_UNSUPPORTED: BE_SPIKE_IDS with n_batch > 1.
+ *
+ * Direct route: compaction, then a lane group per active row adds Q into int64[n_batch, k] with global 64-bit integer atomics,
+ * then one convert kernel.  No layout and no limits on rows or slices.  nnz = stored entries (sizes the lane group: a speed hint
+ * when indptr is given).  indptr == NULL: rows of row_len entries.
+ *   workspace >= be_binary_csrmm_t_f8_workspace_bytes(m, k, n_batch)
+ *
+ * Planned route, layout "q8": 2 bytes per entry.  For row r and slice s (slices as for the plans above) one 128-byte-aligned block
+ *     [ uint8 code x 4*ng ][ uint8 delta x 4*ng ],   seg = { block start in 128-B units, ng | (local column of the first entry << 16) }
+ * with the entries sorted by column and BE_PLAN_D8's delta rules: column = previous column + delta (first delta 0), a gap above
+ * 255 bridged by escape entries (code 0x00, delta 255), tail pads (code 0, delta 0).  Limits as d8: rows of at most 16384 entries
+ * (be_scatter_plan_q8_count checks every row on the device: BE_ERR_RANGE for a longer one), at most 1024 slices and a slice whose
+ * 64-bit sums fit LDS (BE_ERR_RANGE) — the direct route serves what the layout refuses.
+ *   be_scatter_plan_q8_count : fills seg (m * n_slices entries of 8 B), writes order_out (uint16[nnz], or NULL) as
+ *       be_scatter_plan_count_ordered does, returns the size of blob in *blob_bytes_host.  SYNCHRONOUS.  scratch >=
+ *       be_scatter_plan_q8_scratch_bytes(m, k, slice_shift, slice_width).
+ *   caller allocates blob (128-byte aligned, blob_bytes + 128).
+ *   be_scatter_plan_q8_fill  : fills blob from codes[nnz]; order = what the count wrote, or NULL (the rows are sorted again).
+ *   be_binary_csrm{v,m}_t_plan_f8 : the step.  block_hint, parts and the workspace contract (its first 4 * n_batch bytes ZERO on
+ *       entry, zero again after the call) as be_binary_csrmm_t_plan;
+ *       workspace >= be_binary_csrmm_t_plan_f8_workspace_bytes(m, k, n_batch, slice_shift, slice_width, parts, block_hint).
+ * ---------------------------------------------------------------------------------------------- */
+int64_t be_binary_csrmv_t_f8_workspace_bytes(int64_t m, int64_t k);
+int64_t be_binary_csrmm_t_f8_workspace_bytes(int64_t m, int64_t k, int64_t n_batch);
+int be_binary_csrmv_t_f8(const void* codes, int f8_format, double scale, const int32_t* indices, const void* indptr,
+                         int indptr_is_i64, int64_t row_len, int64_t nnz, const void* spikes, int spike_dtype, void* out_f32,
+                         int64_t m, int64_t k, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+int be_binary_csrmm_t_f8(const void* codes, int f8_format, double scale, const int32_t* indices, const void* indptr,
+                         int indptr_is_i64, int64_t row_len, int64_t nnz, const void* spikes_bm, int spike_dtype, void* out_f32_bm,
+                         int64_t m, int64_t k, int64_t n_batch, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+int64_t be_scatter_plan_q8_scratch_bytes(int64_t m, int64_t k, int slice_shift, int slice_width);
+int be_scatter_plan_q8_count(const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t row_len, int64_t m, int64_t k,
+                             int slice_shift, int slice_width, void* seg, void* scratch, int64_t scratch_bytes,
+                             int64_t* blob_bytes_host, uint16_t* order_out, be_stream_t stream);
+int be_scatter_plan_q8_fill(const void* codes, const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t row_len,
+                            int64_t m, int64_t k, int slice_shift, int slice_width, const void* seg, void* blob,
+                            const uint16_t* order, be_stream_t stream);
+int64_t be_binary_csrmv_t_plan_f8_workspace_bytes(int64_t m, int64_t k, int slice_shift, int slice_width, int parts, int block_hint);
+int64_t be_binary_csrmm_t_plan_f8_workspace_bytes(int64_t m, int64_t k, int64_t n_batch, int slice_shift, int slice_width, int parts,
+                                                  int block_hint);
+int be_binary_csrmv_t_plan_f8(const void* blob, const void* seg, int f8_format, double scale, const void* spikes, int spike_dtype,
+                              void* out_f32, int64_t m, int64_t k, int slice_shift, int slice_width, int block_hint, int parts,
+                              void* workspace, int64_t workspace_bytes, be_stream_t stream);
+int be_binary_csrmm_t_plan_f8(const void* blob, const void* seg, int f8_format, double scale, const void* spikes_bm, int spike_dtype,
+                              void* out_f32_bm, int64_t m, int64_t k, int64_t n_batch, int slice_shift, int slice_width,
+                              int block_hint, int parts, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * JIT-connectivity products (the matrix is regenerated on the fly, never stored)
  * replaces: jit_scalar_binary_jitsmv.{pack_bool,notrans_*,trans_*} (brainevent/_jit_scalar/binary_jitsmv.cu:107-321),
  *           jit_scalar_binary_jitsmm.{pack,notrans_*,trans_*} (brainevent/_jit_scalar/binary_jitsmm.cu),
