@@ -14,7 +14,8 @@ ordinary scatter per step (``_delay``).  Delayed synapses learn: ``DelayedCSR.up
 value of a synapse comes from a ``ValueRing``, read by age), and ``ring @ D`` is differentiable in the weights.
 The dense products also take OCP FP8 weights (``float8_e4m3fn`` / ``float8_e5m2`` tensors, ``Float8Dense``, ``quantize_fp8``;
 ``_dense_f8``): a byte per weight, f32 sums, f32 out.  So does the CSR scatter: ``Float8CSR`` / ``CSR.quantize_fp8`` (``_csr_f8``),
-two bytes per synapse in its plan, exact 64-bit integer sums, f32 out.
+two bytes per synapse in its plan, exact 64-bit integer sums, f32 out; ``W8.T`` / ``Float8CSC`` is the other view of the same
+arrays and gives the gather direction (a streaming kernel, or the mirror once ``build_mirror()`` was asked for), same bits.
 ``lif_step`` / ``lif_sequence`` are the spiking neuron between two products, with its surrogate gradient: one launch forwards and
 one backwards for a step or a whole input sequence (``_neuron_sg``); ``synaptic_lif_step`` / ``synaptic_lif_sequence`` are the same
 with a synaptic current in front of the membrane and an optional adaptive threshold, ``parametric_synaptic_lif_step`` /
@@ -39,7 +40,7 @@ from ._fcn import (FixedNumConn, FixedNumPerPre, FixedNumPerPost, binary_fcnmv, 
 from ._dense import (Dense, binary_densemv, binary_densemm, binary_densemv_p, binary_densemm_p, binary_densemv_p_call,
                      binary_densemm_p_call)
 from ._dense_f8 import Float8Dense, quantize_fp8
-from ._csr_f8 import Float8CSR, Q8Plan
+from ._csr_f8 import Float8CSR, Float8CSC, Q8Plan
 from ._convert import (csr_to_coo_index, coo_to_csc_index, coo2csr, csr_to_csc_index, csc_to_csr_index,
                        fixed_conn_num_csr_indptr, fixed_conn_num_csc_structure, fixed_conn_num_to_csc, CscBuilder)
 from ._float import (csrmv, csrmm, csrmv_p, csrmm_p, csrmv_p_call, csrmm_p_call, fcnmv, fcnmm, fcnmv_p, fcnmm_p, fcnmv_p_call,

@@ -58,6 +58,7 @@ _SIGNATURES = dict(
     be_binary_csrmv_nt='i:piippilpipllplp', be_binary_csrmm_nt='i:piippilpiplllplp',
     be_csr_to_csc_scratch_bytes='l:l', be_csr_to_csc_count='i:pllpp', be_csr_to_csc_indptr='i:plpiLplp',
     be_csr_to_csc_fill_block='i:ppilllllppppipipp', be_gather_by_perm='i:pipilpp',
+    be_csr_to_csc_fill_block_u8='i:ppilllllppppippp',
     be_csrmm_workspace_bytes='l:lllii', be_csrmm='i:piippilpplllliplp', be_csrmv='i:piippilppllliplp',
     be_dt2t='i:piipppilpllllip',
     be_slice_rows_tile_cols='i:i', be_slice_rows='i:piippilplplllp', be_slice_rows_grad_workspace_bytes='l:li',
@@ -70,6 +71,8 @@ _SIGNATURES = dict(
     be_binary_densemm_f8_workspace_bytes='l:lllii', be_binary_densemm_f8='i:pidpipllliplp',
     be_binary_csrmv_t_f8_workspace_bytes='l:ll', be_binary_csrmm_t_f8_workspace_bytes='l:lll',
     be_binary_csrmv_t_f8='i:pidppillpipllplp', be_binary_csrmm_t_f8='i:pidppillpiplllplp',
+    be_binary_csrmv_nt_f8_workspace_bytes='l:ll', be_binary_csrmm_nt_f8_workspace_bytes='l:lll',
+    be_binary_csrmv_nt_f8='i:pidppillpipllplp', be_binary_csrmm_nt_f8='i:pidppillpiplllplp',
     be_scatter_plan_q8_scratch_bytes='l:llii', be_scatter_plan_q8_count='i:ppillliipplLpp',
     be_scatter_plan_q8_fill='i:pppillliipppp', be_binary_csrmv_t_plan_f8_workspace_bytes='l:lliiii',
     be_binary_csrmm_t_plan_f8_workspace_bytes='l:llliiii', be_binary_csrmv_t_plan_f8='i:ppidpiplliiiiplp',

@@ -102,14 +102,15 @@ class CscBuilder:
 
     def block(self, c0: int, c1: int, data: Optional[torch.Tensor] = None, perm: bool = False):
         """``(rows, data_block, perm)`` of the columns ``[c0, c1)``: row ids (int32), the weights moved along (``None``
-        without per-entry ``data``) and the source positions (int32 until the entry count needs int64; ``None`` unless asked)."""
+        without per-entry ``data``; ``uint8`` data of one element per entry, the FP8 codes of a ``Float8CSR``, goes through
+        ``be_csr_to_csc_fill_block_u8``) and the source positions (int32 until the entry count needs int64; ``None`` unless asked)."""
         c0, c1 = int(c0), int(c1)
         assert 0 <= c0 <= c1 <= self.k
         dev, st = A.device(), A.stream_ptr()
         n = self.block_entries(c0, c1)
         rows = torch.empty(n, dtype=torch.int32, device=dev)
         w_out, wb = None, 0
-        if data is not None and data.numel() > 1:
+        if data is not None and (data.numel() > 1 or (data.dtype == torch.uint8 and data.numel() == self.nnz)):
             data = A.to_device(data).reshape(-1)
             assert data.numel() == self.nnz, "data must hold one weight per stored entry"
             wb = data.element_size()
@@ -121,6 +122,10 @@ class CscBuilder:
             return rows, w_out, p_out
         cursor = torch.empty(max(c1 - c0, 1), dtype=torch.int64, device=dev)
         is64 = int(self.indptr is not None and self.indptr.dtype == torch.int64)
+        if data is not None and data.dtype == torch.uint8 and wb == 1:
+            call('be_csr_to_csc_fill_block_u8', A.ptr(self.indices), A.ptr(self.indptr), is64, self.row_len, self.m, self.nnz, c0, c1,
+                 A.ptr(self.csc_indptr), A.ptr(cursor), A.ptr(rows), A.ptr(p_out), p64, A.ptr(data), A.ptr(w_out), st)
+            return rows, w_out, p_out
         call('be_csr_to_csc_fill_block', A.ptr(self.indices), A.ptr(self.indptr), is64, self.row_len, self.m, self.nnz, c0, c1,
              A.ptr(self.csc_indptr), A.ptr(cursor), A.ptr(rows), A.ptr(p_out), p64, A.ptr(data if wb else None), wb, A.ptr(w_out), st)
         return rows, w_out, p_out

@@ -2021,6 +2021,12 @@ class CSC(CompressedSparseData):
         return CSR._from_parts(rdata, ridx, rptr.to(self.indptr.dtype), shape=self.shape, backend=self.backend,
                                numpy_result=self._numpy_result)
 
+    def quantize_fp8(self, fmt: str = 'e4m3', scale: Optional[float] = None):
+        """This matrix with OCP FP8 weights: a read-only :class:`~brainevent_amd.Float8CSC` over the same ``indices`` / ``indptr``,
+        quantised by ``quantize_fp8``'s formula as :meth:`CSR.quantize_fp8` does."""
+        from ._csr_f8 import csc_quantize_fp8
+        return csc_quantize_fp8(self, fmt, scale)
+
     @property
     def T(self):
         return self.transpose()

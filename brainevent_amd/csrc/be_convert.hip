@@ -154,6 +154,7 @@ __global__ void __launch_bounds__(256) k_t_fill(const int32_t* __restrict__ indi
       const unsigned long long slot = atomicAdd(cursor + c, 1ull);
       rows_out[slot] = (int32_t)r;
       if (perm_out != nullptr) perm_out[slot] = (PT)j;
+      if (WB == 1) w_out[slot] = w_in[j];
       if (WB == 2) reinterpret_cast<uint16_t*>(w_out)[slot] = reinterpret_cast<const uint16_t*>(w_in)[j];
       if (WB == 4) reinterpret_cast<uint32_t*>(w_out)[slot] = reinterpret_cast<const uint32_t*>(w_in)[j];
       if (WB == 8) reinterpret_cast<unsigned long long*>(w_out)[slot] = reinterpret_cast<const unsigned long long*>(w_in)[j];
@@ -181,6 +182,7 @@ int launch_fill(int wbytes, const int32_t* indices, RowPtr rp, int64_t m, int64_
                      perm_out, wi, wo)
   switch (wbytes) {
     case 0: BE_T_FILL(0); break;
+    case 1: BE_T_FILL(1); break;      // (be_csr_to_csc_fill_block_u8 only: fill_block never passes a public 1 on)
     case 2: BE_T_FILL(2); break;
     case 4: BE_T_FILL(4); break;
     case 8: BE_T_FILL(8); break;
@@ -199,6 +201,41 @@ int fill_by_row_length(int64_t avg_row, int wbytes, const int32_t* indices, RowP
   if (avg_row <= 8) return launch_fill<4, PT>(wbytes, indices, rp, m, col_lo, col_hi, cursor, rows_out, perm_out, w_in, w_out, st);
   if (avg_row <= 48) return launch_fill<16, PT>(wbytes, indices, rp, m, col_lo, col_hi, cursor, rows_out, perm_out, w_in, w_out, st);
   return launch_fill<64, PT>(wbytes, indices, rp, m, col_lo, col_hi, cursor, rows_out, perm_out, w_in, w_out, st);
+}
+
+// The fill of one column block behind be_csr_to_csc_fill_block (`weight_bytes` 0, 2, 4 or 8) and be_csr_to_csc_fill_block_u8
+// (`one_byte`: weight_bytes is 1).  `who` names the entry point in the error text.  A public weight_bytes of 1 is refused where
+// every other unknown size is: by launch_fill's default case.
+inline int fb_fail(const char* who, int code, const char* msg) {
+  be_set_error(std::string(who) + ": " + msg);
+  return code;
+}
+int fill_block(const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t row_len, int64_t m, int64_t nnz,
+               int64_t col_lo, int64_t col_hi, const int64_t* csc_indptr, int64_t* cursor, int32_t* rows_out, void* perm_out,
+               int perm_is_i64, const void* weights, int weight_bytes, void* weights_out, bool one_byte, be_stream_t stream,
+               const char* who) {
+  if (!(m >= 0 && m <= 0x7fffffffll && nnz >= 0)) return fb_fail(who, BE_ERR_INVALID, "bad shape");
+  if (!(0 <= col_lo && col_lo <= col_hi && col_hi <= 0x7fffffffll)) return fb_fail(who, BE_ERR_INVALID, "bad column block");
+  if (!check_rows(indptr, row_len)) return fb_fail(who, BE_ERR_INVALID, "indptr is NULL and row_len < 0");
+  if (!(weight_bytes == 0 || (weights != nullptr && weights_out != nullptr)))
+    return fb_fail(who, BE_ERR_INVALID, "weights / weights_out is NULL");
+  if (col_hi == col_lo || m == 0 || nnz == 0) return BE_OK;
+  if (!(indices && csc_indptr && cursor && rows_out)) return fb_fail(who, BE_ERR_INVALID, "null pointer");
+  if (!(perm_out == nullptr || perm_is_i64 || nnz <= 0x7fffffffll))
+    return fb_fail(who, BE_ERR_RANGE, "an int32 perm holds at most 2^31 - 1 entries");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t nb = col_hi - col_lo;
+  unsigned long long* cur = reinterpret_cast<unsigned long long*>(cursor);
+  hipLaunchKernelGGL(k_t_cursor_init, dim3(grid_for(nb, 256, 2048)), dim3(256), 0, st, csc_indptr, col_lo, nb, cur);
+  BE_LAUNCH_CHECK();
+  RowPtr rp{indptr, indptr_is_i64, row_len};
+  const int64_t avg = nnz / m;
+  const int wsel = one_byte ? 1 : (weight_bytes == 1 ? -1 : weight_bytes);      // (-1: no case of launch_fill, as any unknown size)
+  if (perm_out != nullptr && !perm_is_i64)
+    return fill_by_row_length<int32_t>(avg, wsel, indices, rp, m, col_lo, col_hi, cur, rows_out,
+                                       static_cast<int32_t*>(perm_out), weights, weights_out, st);
+  return fill_by_row_length<int64_t>(avg, wsel, indices, rp, m, col_lo, col_hi, cur, rows_out,
+                                     static_cast<int64_t*>(perm_out), weights, weights_out, st);
 }
 
 }  // namespace
@@ -258,25 +295,17 @@ int be_csr_to_csc_fill_block(const int32_t* indices, const void* indptr, int ind
                              int64_t nnz, int64_t col_lo, int64_t col_hi, const int64_t* csc_indptr, int64_t* cursor,
                              int32_t* rows_out, void* perm_out, int perm_is_i64, const void* weights, int weight_bytes,
                              void* weights_out, be_stream_t stream) {
-  BE_REQUIRE(m >= 0 && m <= 0x7fffffffll && nnz >= 0, BE_ERR_INVALID, "bad shape");
-  BE_REQUIRE(0 <= col_lo && col_lo <= col_hi && col_hi <= 0x7fffffffll, BE_ERR_INVALID, "bad column block");
-  BE_REQUIRE(check_rows(indptr, row_len), BE_ERR_INVALID, "indptr is NULL and row_len < 0");
-  BE_REQUIRE(weight_bytes == 0 || (weights != nullptr && weights_out != nullptr), BE_ERR_INVALID, "weights / weights_out is NULL");
-  if (col_hi == col_lo || m == 0 || nnz == 0) return BE_OK;
-  BE_REQUIRE(indices && csc_indptr && cursor && rows_out, BE_ERR_INVALID, "null pointer");
-  BE_REQUIRE(perm_out == nullptr || perm_is_i64 || nnz <= 0x7fffffffll, BE_ERR_RANGE, "an int32 perm holds at most 2^31 - 1 entries");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t nb = col_hi - col_lo;
-  unsigned long long* cur = reinterpret_cast<unsigned long long*>(cursor);
-  hipLaunchKernelGGL(k_t_cursor_init, dim3(grid_for(nb, 256, 2048)), dim3(256), 0, st, csc_indptr, col_lo, nb, cur);
-  BE_LAUNCH_CHECK();
-  RowPtr rp{indptr, indptr_is_i64, row_len};
-  const int64_t avg = nnz / m;
-  if (perm_out != nullptr && !perm_is_i64)
-    return fill_by_row_length<int32_t>(avg, weight_bytes, indices, rp, m, col_lo, col_hi, cur, rows_out,
-                                       static_cast<int32_t*>(perm_out), weights, weights_out, st);
-  return fill_by_row_length<int64_t>(avg, weight_bytes, indices, rp, m, col_lo, col_hi, cur, rows_out,
-                                     static_cast<int64_t*>(perm_out), weights, weights_out, st);
+  return fill_block(indices, indptr, indptr_is_i64, row_len, m, nnz, col_lo, col_hi, csc_indptr, cursor, rows_out, perm_out,
+                    perm_is_i64, weights, weight_bytes, weights_out, false, stream, __func__);
+}
+
+int be_csr_to_csc_fill_block_u8(const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t row_len, int64_t m,
+                                int64_t nnz, int64_t col_lo, int64_t col_hi, const int64_t* csc_indptr, int64_t* cursor,
+                                int32_t* rows_out, void* perm_out, int perm_is_i64, const void* bytes, void* bytes_out,
+                                be_stream_t stream) {
+  BE_REQUIRE(bytes != nullptr && bytes_out != nullptr, BE_ERR_INVALID, "bytes / bytes_out is NULL");
+  return fill_block(indices, indptr, indptr_is_i64, row_len, m, nnz, col_lo, col_hi, csc_indptr, cursor, rows_out, perm_out,
+                    perm_is_i64, bytes, 1, bytes_out, true, stream, __func__);
 }
 
 int be_gather_by_perm(const void* src, int elem_bytes, const void* perm, int perm_is_i64, int64_t n, void* out,

@@ -834,6 +834,9 @@ int be_binary_csrmm_nt(const void* weights, int homo, int wdtype, const int32_t*
  *   The order of the entries INSIDE a column is unspecified (slots are drawn from per-column cursors with atomics), exactly as
  *   in the reference's kernel (csr_to_csc.cu:26-27); every product over the result is insensitive to it.
  *   be_gather_by_perm: out[i] = src[perm[i]] for 2 / 4 / 8-byte elements — how a mirror that kept perm follows a weight update.
+ *   be_csr_to_csc_fill_block_u8: step 3 with a ONE-byte payload per entry (bytes[nnz] -> bytes_out, both non-NULL): how the FP8
+ *        codes of a Float8CSR move into its mirror.  Everything else as be_csr_to_csc_fill_block, which keeps refusing a
+ *        weight_bytes of 1.
  * ---------------------------------------------------------------------------------------------- */
 int64_t be_csr_to_csc_scratch_bytes(int64_t n_cols);
 int be_csr_to_csc_count(const int32_t* indices, int64_t nnz, int64_t n_cols, int64_t* counts, be_stream_t stream);
@@ -843,6 +846,10 @@ int be_csr_to_csc_fill_block(const int32_t* indices, const void* indptr, int ind
                              int64_t nnz, int64_t col_lo, int64_t col_hi, const int64_t* csc_indptr, int64_t* cursor,
                              int32_t* rows_out, void* perm_out, int perm_is_i64, const void* weights, int weight_bytes,
                              void* weights_out, be_stream_t stream);
+int be_csr_to_csc_fill_block_u8(const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t row_len, int64_t m,
+                                int64_t nnz, int64_t col_lo, int64_t col_hi, const int64_t* csc_indptr, int64_t* cursor,
+                                int32_t* rows_out, void* perm_out, int perm_is_i64, const void* bytes, void* bytes_out,
+                                be_stream_t stream);
 int be_gather_by_perm(const void* src, int elem_bytes, const void* perm, int perm_is_i64, int64_t n, void* out,
                       be_stream_t stream);
 
@@ -1038,6 +1045,20 @@ int be_binary_densemm_f8(const void* weights, int f8_format, double scale, const
  *   be_binary_csrm{v,m}_t_plan_f8 : the step.  block_hint, parts and the workspace contract (its first 4 * n_batch bytes ZERO on
  *       entry, zero again after the call) as be_binary_csrmm_t_plan;
  *       workspace >= be_binary_csrmm_t_plan_f8_workspace_bytes(m, k, n_batch, slice_shift, slice_width, parts, block_hint).
+ *
+ * Gather direction (brainevent_amd/csrc/be_csr_f8_gather.hip): `W8 @ events` over the stored rows, which is `events @ W8.T` of a
+ * Float8CSR and `events @ Float8CSC`.  E, Q(c), inv, the "active" rule and the finite-code precondition are those above.  For a
+ * matrix of m stored rows over k columns and the spike vector s[k] of batch row b:
+ *     R_i       = sum over the stored entries e of row i with s[indices[e]] active, of Q(codes[e])        (int64, exact)
+ *     out[b, i] = (float)((double)(long long)R_i * inv)
+ * — the finish of the scatter direction, so the gather over a matrix and the scatter over its transpose (the mirror, planned or
+ * direct) give the same bits, whatever the lanes-per-row instance.  Spikes: BE_SPIKE_BOOL / FLOAT [n_batch, k], or BE_SPIKE_BITS
+ * ([n_batch, ceil(k / 32)] words, read in place); BE_SPIKE_IDS: BE_ERR_UNSUPPORTED.  The workspace holds the packed bitmaps only
+ * (be_pack_spikes_batched's layout): no atomics, no accumulators, no convert launch; every out[b, i] is written once.  nnz = the
+ * length of codes / indices (no load reaches past it; with an indptr also the lanes-per-row hint); indptr == NULL: rows of
+ * row_len entries, and nnz >= m * row_len (BE_ERR_INVALID otherwise).  No alignment is asked of codes or indices beyond their types'.
+ * Contracts and the other error conditions as above.
+ *   workspace >= be_binary_csrmm_nt_f8_workspace_bytes(m, k, n_batch)
  * ---------------------------------------------------------------------------------------------- */
 int64_t be_binary_csrmv_t_f8_workspace_bytes(int64_t m, int64_t k);
 int64_t be_binary_csrmm_t_f8_workspace_bytes(int64_t m, int64_t k, int64_t n_batch);
@@ -1047,6 +1068,14 @@ int be_binary_csrmv_t_f8(const void* codes, int f8_format, double scale, const i
 int be_binary_csrmm_t_f8(const void* codes, int f8_format, double scale, const int32_t* indices, const void* indptr,
                          int indptr_is_i64, int64_t row_len, int64_t nnz, const void* spikes_bm, int spike_dtype, void* out_f32_bm,
                          int64_t m, int64_t k, int64_t n_batch, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+int64_t be_binary_csrmv_nt_f8_workspace_bytes(int64_t m, int64_t k);
+int64_t be_binary_csrmm_nt_f8_workspace_bytes(int64_t m, int64_t k, int64_t n_batch);
+int be_binary_csrmv_nt_f8(const void* codes, int f8_format, double scale, const int32_t* indices, const void* indptr,
+                          int indptr_is_i64, int64_t row_len, int64_t nnz, const void* spikes, int spike_dtype, void* out_f32,
+                          int64_t m, int64_t k, void* workspace, int64_t workspace_bytes, be_stream_t stream);
+int be_binary_csrmm_nt_f8(const void* codes, int f8_format, double scale, const int32_t* indices, const void* indptr,
+                          int indptr_is_i64, int64_t row_len, int64_t nnz, const void* spikes_bm, int spike_dtype, void* out_f32_bm,
+                          int64_t m, int64_t k, int64_t n_batch, void* workspace, int64_t workspace_bytes, be_stream_t stream);
 int64_t be_scatter_plan_q8_scratch_bytes(int64_t m, int64_t k, int slice_shift, int slice_width);
 int be_scatter_plan_q8_count(const int32_t* indices, const void* indptr, int indptr_is_i64, int64_t row_len, int64_t m, int64_t k,
                              int slice_shift, int slice_width, void* seg, void* scratch, int64_t scratch_bytes,
