@@ -28,7 +28,14 @@ the kernels keep a sample's last ``depth`` spike vectors on the chip and walk th
 neuron ``i``'s synapses of delay ``d``); ``s0`` may hold up to ``depth`` past steps, and the leaf of the weight gradient is
 ``rec.stacked.data``, as for ``ring @ D``.  Delay 0 everywhere is the layer without delays.
 
-Not built: CSC / fixed-number / dense / JITC recurrences, one shared (homogeneous) weight, learnable ``v_reset`` / ``alpha``,
+A DENSE RECURRENCE (``be_lif_rec_dense_sg_forward`` / ``be_lif_rec_dense_sg_backward``,
+``csrc/be_neuron_sg_rec_dense.hip``): ``rec`` may be a :class:`~brainevent_amd.Dense` ``[N, N]`` (f32, rows = presynaptic neurons).
+The function is the one above on the CSR that stores all ``N * N`` entries — the same fixed-point sums, so the same forward bits —
+but the kernels walk the matrix itself: forwards the active rows are streamed into register sums from a spike mask in LDS,
+backwards the gather is a row-times-vector product.  The leaf of the weight gradient is ``rec.data`` (``be_grad_dense``).
+
+Not built: CSC / fixed-number / JITC recurrences, a Dense recurrence with delays or tensor parameters, one shared (homogeneous)
+weight, learnable ``v_reset`` / ``alpha``,
 per-sample (``[B, N]``) parameters, learnable delays, learnable neuron parameters together with delays, more than 8192 neurons (one
 sample's sums and spike ids live in one workgroup's LDS; with delays also its spike history: see :func:`delay_fits`), a sample split
 over several workgroups.  A cached scatter plan or mirror of ``rec`` is neither used nor needed: the kernels read the raw CSR arrays.
@@ -268,21 +275,126 @@ class DelayedRecurrentLifSequence(torch.autograd.Function):
         return (g_x if need[0] else None), g_c0, g_v0, g_a0, g_s0, g_w, None, None, None, None, None
 
 
+class _DenseRec:
+    """The weights of a :class:`~brainevent_amd.Dense` as the dense kernels take them: contiguous ``[N, N]`` (no neuron: one unused
+    element, no NULL pointer)."""
+    __slots__ = ('w',)
+
+    def __init__(self, w):
+        self.w = w.contiguous() if w.numel() else torch.zeros(1, dtype=torch.float32, device=w.device)
+
+
+def _forward_dense(x, r: _DenseRec, s0, c0, v0, a0, T: int, B: int, N: int, p: _Params, e: int, want_v: bool, want_h: bool):
+    """``be_lif_rec_dense_sg_forward``: :func:`_forward` with the matrix itself."""
+    new = lambda: torch.empty((B, N), dtype=x.dtype, device=x.device)
+    s = torch.empty_like(x)
+    v_seq = torch.empty_like(x) if want_v else None
+    h = torch.empty_like(x) if want_h else None
+    th = torch.empty_like(x) if want_h and p.adaptive else None
+    c_last, v_last, a_last = new(), new(), (new() if p.adaptive else None)
+    if T == 0:                                # no step: the state passes through
+        for out, start in ((c_last, c0), (v_last, v0), (a_last, a0)):
+            if out is not None:
+                out.zero_() if start is None else out.copy_(start)
+    else:
+        call('be_lif_rec_dense_sg_forward', A.ptr(x), A.ptr(r.w), A.ptr(s0), A.ptr(c0), A.ptr(v0), A.ptr(a0), A.ptr(s), A.ptr(v_seq),
+             A.ptr(h), A.ptr(th), A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho,
+             p.kappa, p.reset, p.adaptive, e, A.stream_ptr())
+    return s, v_seq, h, th, c_last, v_last, a_last
+
+
+def _backward_dense(h, th, r: _DenseRec, g_s, g_vseq, g_last, T: int, B: int, N: int, p: _Params, want):
+    """``be_lif_rec_dense_sg_backward``: ``(g_x, g_c0, g_v0, g_a0, g_s0)``; None as in :func:`_backward`."""
+    g_x = torch.empty_like(h)
+    g_state = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in want]
+    if T == 0:
+        for out, g in zip(g_state[:3], g_last):
+            if out is not None:
+                out.zero_() if g is None else out.copy_(g)
+        if g_state[3] is not None:
+            g_state[3].zero_()
+    else:
+        call('be_lif_rec_dense_sg_backward', A.ptr(h), A.ptr(th), A.ptr(r.w), A.ptr(g_s), A.ptr(g_vseq), A.ptr(g_last[0]),
+             A.ptr(g_last[1]), A.ptr(g_last[2]), A.ptr(g_x), A.ptr(g_state[0]), A.ptr(g_state[1]), A.ptr(g_state[2]), A.ptr(g_state[3]),
+             T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.surrogate, p.alpha, p.adaptive,
+             p.detach_reset, A.stream_ptr())
+    return (g_x,) + tuple(g_state)
+
+
+def _weight_grad_dense(w, s, s0, g_x, T: int, B: int, N: int) -> torch.Tensor:
+    """``g_W[i, :] = sum over (t, b) with sp[t][b][i] of g_x[t][b][:]``, ``sp = cat(s0, s[:-1])``: ``be_grad_dense`` (the
+    ``transpose=True`` side) over ``T * B`` batch rows — ``(T - 1) * B`` without ``s0``."""
+    if s0 is None:
+        sp, g = s[:max(T - 1, 0)], g_x[1:]
+    else:
+        sp, g = torch.cat(((s0 != 0).to(s.dtype)[None], s[:max(T - 1, 0)])), g_x
+    nb = int(sp.shape[0]) * B
+    if T == 0 or N == 0 or nb == 0:
+        return torch.zeros_like(w)
+    mask, _ = _autograd.activity(sp.reshape(nb, N), 'bm')
+    return _autograd.dense_weight_grad(w, True, mask, nb, g.reshape(nb, N).T)
+
+
+class DenseRecurrentLifSequence(torch.autograd.Function):
+    """:class:`RecurrentLifSequence` over a :class:`~brainevent_amd.Dense`: ``w`` is ``rec.data`` ``[N, N]``.  Saved: ``h``, ``th``
+    when adaptive, ``s``, the weights and ``s0``; a None gradient goes in as NULL; the weight gradient is computed only if the
+    weights need one."""
+
+    @staticmethod
+    def forward(ctx, x, c0, v0, a0, s0, w, r: _DenseRec, dims, p: _Params, e: int, return_v: bool):
+        ctx.set_materialize_grads(False)
+        T, B, N = dims
+        s, v_seq, h, th, c_last, v_last, a_last = _forward_dense(x, r, s0, c0, v0, a0, T, B, N, p, e, return_v, True)
+        ctx.save_for_backward(h, th, s, w, s0)
+        ctx.meta = (dims, p, return_v)
+        return tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_s, *rest):
+        (T, B, N), p, return_v = ctx.meta
+        g_vseq = rest[0] if return_v else None
+        g_last = list(rest[1:] if return_v else rest) + [None] * (3 - p.entries)
+        if g_s is None and g_vseq is None and all(g is None for g in g_last):
+            return (None,) * 11
+        h, th, s, w, s0 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = [need[1], need[2], bool(p.adaptive) and need[3], need[4]]
+        r = _DenseRec(w.detach())             # the weights as they were at the forward call (autograd checks their version)
+        g_x, g_c0, g_v0, g_a0, g_s0 = _backward_dense(h, th, r, _grad_in(g_s), _grad_in(g_vseq), [_grad_in(g) for g in g_last], T, B,
+                                                      N, p, want)
+        g_w = _weight_grad_dense(w, s, s0, g_x, T, B, N) if need[5] else None
+        return (g_x if need[0] else None), g_c0, g_v0, g_a0, g_s0, g_w, None, None, None, None, None
+
+
 def _is_delayed(rec) -> bool:
     from ._delay import DelayedCSR
     return isinstance(rec, DelayedCSR)
 
 
+def _is_dense(rec) -> bool:
+    from ._dense import Dense
+    return isinstance(rec, Dense)
+
+
 def _check_rec(who, rec, n: int):
     from ._csr import CSR
-    delayed = _is_delayed(rec)
-    if not delayed and not isinstance(rec, CSR):
-        raise TypeError(f"{who}: rec must be a CSR matrix (rows = presynaptic neurons) or a DelayedCSR, not {type(rec).__name__}; "
-                        f"CSC, fixed-number, dense, JITC and planned matrices are not built.")
+    delayed, dense = _is_delayed(rec), _is_dense(rec)
+    if not delayed and not dense and not isinstance(rec, CSR):
+        raise TypeError(f"{who}: rec must be a CSR matrix (rows = presynaptic neurons), a DelayedCSR or a Dense, not "
+                        f"{type(rec).__name__}; CSC, fixed-number, JITC and planned matrices are not built.")
     if rec.shape[0] != rec.shape[1]:
         raise ValueError(f"{who}: rec {tuple(rec.shape)} must be square (a recurrent projection).")
     if rec.shape[0] != n:
         raise ValueError(f"{who}: rec {tuple(rec.shape)} must have the size of x's last axis, {n}.")
+    if dense:                                 # one [N, N] array, nothing else to check
+        if rec.data.dtype != torch.float32:
+            raise TypeError(f"{who}: the weights of rec must be float32, not {rec.data.dtype} (f16 / bf16 dense weights are not built).")
+        if rec.data.ndim != 2:
+            raise ValueError(f"{who}: the data of a Dense rec must be two-dimensional, not {rec.data.ndim}-dimensional.")
+        if n > MAX_N:
+            raise ValueError(f"{who}: {n} neurons; the limit is {MAX_N} (one workgroup holds a sample's neurons).")
+        return
     m = rec.stacked if delayed else rec       # with delays the kernels read the stacked arrays
     if m.data.dtype != torch.float32:
         raise TypeError(f"{who}: the weights of rec must be float32, not {m.data.dtype}.")
@@ -303,6 +415,12 @@ def _check_rec(who, rec, n: int):
 
 
 def _scale_exp(who, scale_exp, rec, n: int) -> int:
+    if scale_exp is None and _is_dense(rec):  # the exponent of the CSR that stores all N * N entries
+        if n == 0:
+            return 0
+        from ._csr import fixed_point_exponent
+        cols = torch.arange(n, dtype=torch.int32, device=rec.data.device).repeat(n)
+        return fixed_point_exponent(rec.data.detach().reshape(-1), cols, n)
     if scale_exp is None:
         m = rec.stacked if _is_delayed(rec) else rec      # (the stacked matrix has the same columns: every stacked row active)
         if m.indices.numel() == 0 or n == 0:
@@ -356,8 +474,16 @@ def recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Sequence[Optio
     gradient to the order the synapses were given in.  The limit is ``N <= 8192`` with ``8 * N + 8 * depth * ceil(N / 64) + 16384 <=
     162816`` (every ``N <= 8192`` at ``depth <= 16``, every ``N <= 2048`` at ``depth <= 256``).
 
-    Not built: CSC / fixed-number / dense / JITC recurrences, one shared weight, learnable delays, ``N > 8192``, a sample split over
-    several workgroups (only ``B`` of the chip's compute units work)."""
+    **A dense recurrence.**  ``rec`` may be a :class:`Dense` ``[N, N]`` (f32, rows = presynaptic neurons; ``rec.data`` may be a
+    ``torch.nn.Parameter``): the same function as on the :class:`CSR` that stores all ``N * N`` entries of the matrix at the same
+    exponent — the forward outputs are equal bit for bit, a zero entry adds the integer 0 — through kernels that walk the matrix
+    itself (``be_lif_rec_dense_sg_forward`` / ``_backward``), still one launch each way.  ``scale_exp=None`` asks for the exponent of
+    that fully stored CSR (one host synchronisation).  Differentiable in ``x``, the state, ``s0`` and ``rec.data``; the backward
+    row products are f32 sums in an order ``N`` alone fixes (not the CSR kernel's).  ``N <= 8192``.
+
+    Not built: CSC / fixed-number / JITC recurrences, a Dense recurrence with delays or tensor parameters, f16 / bf16 dense weights,
+    one shared weight, learnable delays, ``N > 8192``, a sample split over several workgroups (only ``B`` of the chip's compute units
+    work)."""
     who = 'recurrent_lif_sequence'
     p = _Params(who, syn_decay, beta, v_th, v_reset, reset, surrogate, alpha, detach_reset, adapt)
     (T, B, N), slots, x3, (c0, v0, a0, sp), e = _prepare(who, x, rec, state0, s0, p, scale_exp)
@@ -366,6 +492,10 @@ def recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Sequence[Optio
         w = rec.stacked.data
         r = _DelayedRec(w.detach(), rec)
         function, forward = DelayedRecurrentLifSequence, _forward_delay
+    elif _is_dense(rec):                      # the matrix itself
+        w = rec.data
+        r = _DenseRec(w.detach())
+        function, forward = DenseRecurrentLifSequence, _forward_dense
     else:
         w = rec.data
         r = _Rec(w.detach(), rec.indices, rec.indptr)
@@ -527,8 +657,8 @@ def parametric_recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Seq
     the bit-for-bit forward contract are :func:`recurrent_lif_sequence`'s (``be_lif_rec_sg_forward_params``); differentiable, once,
     in ``x``, the state entries, ``s0``, ``rec.data`` and the five parameters.
 
-    A :class:`DelayedCSR` is taken with all-number parameters only (that is :func:`recurrent_lif_sequence`); with a tensor parameter
-    it raises ``NotImplementedError``.
+    A :class:`DelayedCSR` or a :class:`Dense` is taken with all-number parameters only (that is :func:`recurrent_lif_sequence`); with
+    a tensor parameter it raises ``NotImplementedError``.
 
     Not built: learnable ``v_reset`` / ``alpha``, ``[B, N]`` parameters, tensor parameters with synaptic delays, and what
     :func:`recurrent_lif_sequence` does not build."""
@@ -538,6 +668,9 @@ def parametric_recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Seq
         return recurrent_lif_sequence(x, rec, state0, s0, syn_decay=syn_decay, beta=beta, v_th=v_th, v_reset=v_reset, reset=reset,
                                       surrogate=surrogate, alpha=alpha, detach_reset=detach_reset, adapt=adapt, return_v=return_v,
                                       scale_exp=scale_exp)
+    if _is_dense(rec):
+        raise NotImplementedError(f"{who}: learnable (tensor) neuron parameters together with a Dense recurrence are not built: a "
+                                  f"Dense rec takes syn_decay, beta, v_th and adapt as Python numbers (recurrent_lif_sequence).")
     if _is_delayed(rec):
         raise NotImplementedError(f"{who}: learnable (tensor) neuron parameters together with synaptic delays are not built: a "
                                   f"DelayedCSR takes syn_decay, beta, v_th and adapt as Python numbers (recurrent_lif_sequence).")

@@ -420,6 +420,32 @@ int be_lif_rec_delay_sg_backward(const float* h_save, const float* th_save, cons
                                  float* g_a0, float* g_s_hist, int hist_ages, int64_t T, int64_t B, int64_t N, double syn_decay,
                                  double beta, double v_th, double v_reset, double rho, double kappa, int reset_mode, int surrogate,
                                  double alpha, int adaptive, int detach_reset, be_stream_t stream);
+/* The recurrent layer with a DENSE recurrence (brainevent_amd/csrc/be_neuron_sg_rec_dense.hip): be_lif_rec_sg_forward / _backward with
+ * (w, indices, indptr) replaced by w, f32 [N, N] row-major, rows = presynaptic neurons — step t's input is x[t] + s[t-1] @ W.  The
+ * function is be_lif_rec_sg_forward's on the CSR that stores all N * N entries of W (indices = 0 .. N-1 in every row) at the same
+ * scale_exp: R[j] = sum over the rows i with sp[i] != 0 of fixed(W[i][j]), a 64-bit wrapping integer sum (a zero entry adds the
+ * integer 0), r[j] = (float)((double)(int64)R[j] * inv), then the step above — so every forward output equals that call's, bit
+ * for bit.  be_fixed_point_exponent on that fully stored CSR gives the exponent.
+ *   backward: the loop of be_lif_rec_sg_backward with  g_rec[i] = sum_j W[i][j] * G[j]  (G = g_x[t+1][b]) and, after it,
+ *     g_s0[b][i] = sum_j W[i][j] * g_x[0][b][j]:  each product rounded, then summed in f32 in an order N alone fixes — L lanes per
+ *     row, L the power of two with 2 * L >= ceil(N / 4) up to 64; lane l takes the groups of four columns l, l + L, ... in ascending
+ *     order, then a butterfly over the L partial sums.  Two calls give the same bits; it is NOT be_lif_rec_sg_backward's order.
+ *     16-byte loads of W when N % 4 == 0 and w is 16-byte aligned, 4-byte loads otherwise; the results do not depend on which.
+ *   The weight gradient is be_grad_dense (transpose = 1) over the T * B batch rows sp[t][b] / g_x[t][b], with g_sn = 1, g_sb = N.
+ * NULL conventions and error codes are be_lif_rec_sg_forward / _backward's: T == 0, B == 0 or N == 0: BE_OK, nothing launched;
+ * BE_ERR_RANGE: N > 8192; BE_ERR_INVALID: the codes above, B < 0, w NULL, scale_exp outside -90 .. 150 — the sizes, the modes and
+ * the exponent are checked before any pointer is looked at.  No workspace, no allocation, no global atomics; never synchronises
+ * the host. */
+int be_lif_rec_dense_sg_forward(const float* x, const float* w, const float* s0, const float* c0, const float* v0, const float* a0,
+                                float* s_out, float* v_seq, float* h_save, float* th_save, float* c_last, float* v_last,
+                                float* a_last, int64_t T, int64_t B, int64_t N, double syn_decay, double beta, double v_th,
+                                double v_reset, double rho, double kappa, int reset_mode, int adaptive, int scale_exp,
+                                be_stream_t stream);
+int be_lif_rec_dense_sg_backward(const float* h_save, const float* th_save, const float* w, const float* g_s, const float* g_vseq,
+                                 const float* g_clast, const float* g_vlast, const float* g_alast, float* g_x, float* g_c0,
+                                 float* g_v0, float* g_a0, float* g_s0, int64_t T, int64_t B, int64_t N, double syn_decay,
+                                 double beta, double v_th, double v_reset, double rho, double kappa, int reset_mode, int surrogate,
+                                 double alpha, int adaptive, int detach_reset, be_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * event vector helpers (replace: brainevent/_jit_scalar/binary_jitsmv.cu:107-125 `_pack_bool_kern`
