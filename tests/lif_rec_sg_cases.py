@@ -131,16 +131,23 @@ def recurrent_input(m, fixed, active, e):
 def forward(x, m, s0, c0, v0, a0, p, e):
     """``x [T, B, N]``; ``s0`` / ``c0`` / ``v0`` / ``a0 [B, N]`` or None -> :class:`Forward` (``r [T, B, N]``: the recurrent input
     of every step, for the tests' own assertions)."""
-    assert x.dtype == F and x.ndim == 3 and x.shape[2] == m.n
-    T, B, N = x.shape
+    assert x.ndim == 3 and x.shape[2] == m.n
     fixed = fixed_from_f32(m.w, e)
+    return forward_with(x, lambda active: recurrent_input(m, fixed, active, e), s0, c0, v0, a0, p)
+
+
+def forward_with(x, recurrent, s0, c0, v0, a0, p):
+    """:func:`forward` with the recurrent input as a function: ``recurrent(active [N] bool) -> r [N] f32`` of one sample.  The
+    neuron's step is stated here once, for every way of summing the rows (tests/lif_rec_dense_cases.py is the other)."""
+    assert x.dtype == F and x.ndim == 3
+    T, B, N = x.shape
     flat = lambda a: None if a is None else a.reshape(-1)
     c, v, a = flat(c0), flat(v0), flat(a0) if p.adaptive else None
     sp = np.zeros((B, N), bool) if s0 is None else (s0 != 0)
     outs = [np.empty_like(x) for _ in range(5)]
     s_out, v_seq, h_save, th_save, r_all = outs
     for t in range(T):
-        r = np.stack([recurrent_input(m, fixed, sp[b], e) for b in range(B)]) if B else np.zeros((0, N), F)
+        r = np.stack([recurrent(sp[b]) for b in range(B)]) if B else np.zeros((0, N), F)
         xin = x[t] + r
         assert xin.dtype == F
         f = S.forward(xin.reshape(1, -1), c, v, a, p)

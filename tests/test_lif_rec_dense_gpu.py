@@ -11,6 +11,7 @@ import torch
 
 import lif_rec_sg_cases as C
 import lif_syn_sg_cases as S
+from lif_rec_dense_cases import stored                     # the CSR that stores every entry of W, as the restatement takes it
 from lif_rec_sg_cases import F, Params, same_bits
 from test_lif_rec_sg_gpu import dev, host, within          # device copy, host copy, |got - want| <= bound with NaN for NaN
 
@@ -24,12 +25,6 @@ INVALID, RANGE = -1, -4
 N_SIZES = (1, 63, 64, 65, 129, 260, 513, 1032)
 FWD = ('s_out', 'v_seq', 'h_save', 'th_save', 'c_last', 'v_last', 'a_last')
 BWD = ('g_x', 'g_c0', 'g_v0', 'g_a0', 'g_s0')
-
-
-def stored(W):
-    """The CSR that stores every entry of ``W``, as the restatement takes it."""
-    N = W.shape[0]
-    return C.Matrix(W.reshape(-1), np.tile(np.arange(N, dtype=np.int32), N), (np.arange(N + 1) * N).astype(np.int32), N)
 
 
 @functools.lru_cache(maxsize=None)
