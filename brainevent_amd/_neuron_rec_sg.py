@@ -33,6 +33,10 @@ A DENSE RECURRENCE (``be_lif_rec_dense_sg_forward`` / ``be_lif
 The function is the one above on the CSR that stores all ``N * N`` entries — the same fixed-point sums, so the same forward bits —
 but the kernels walk the matrix itself: forwards the active rows are streamed into register sums from a spike mask in LDS,
 backwards the gather is a row-times-vector product.  The leaf of the weight gradient is ``rec.data`` (``be_grad_dense``).
+``rec.data`` may also be f16 or bf16 (``be_lif_rec_dense_half_sg_forward`` / ``_backward``,
+``csrc/be_neuron_sg_rec_dense_half.hip``): the layer is then the f32 layer on ``rec.data.float()`` — the up-conversion is exact, the
+forward outputs equal the f32 call's bit for bit — through kernels that load two weights in 4 bytes forwards and eight in 16 bytes
+backwards; the weight gradient is summed in f32 and rounded to the weights' dtype once.
 
 Not built: CSC / fixed-number / JITC recurrences, a Dense recurrence with delays or tensor parameters, one shared (homogeneous)
 weight, learnable ``v_reset`` / ``alpha``,
@@ -281,11 +285,21 @@ class _DenseRec:
     __slots__ = ('w',)
 
     def __init__(self, w):
-        self.w = w.contiguous() if w.numel() else torch.zeros(1, dtype=torch.float32, device=w.device)
+        self.w = w.contiguous() if w.numel() else torch.zeros(1, dtype=w.dtype, device=w.device)
+
+    @property
+    def half(self) -> bool:
+        return self.w.dtype != torch.float32
+
+    @property
+    def args(self):
+        """The arguments that stand for the matrix: ``w``, and for two-byte weights (the ``_half_`` entry points) the dtype code."""
+        return (A.ptr(self.w), A.wcode(self.w)) if self.half else (A.ptr(self.w),)
 
 
 def _forward_dense(x, r: _DenseRec, s0, c0, v0, a0, T: int, B: int, N: int, p: _Params, e: int, want_v: bool, want_h: bool):
-    """``be_lif_rec_dense_sg_forward``: :func:`_forward` with the matrix itself."""
+    """``be_lif_rec_dense_sg_forward`` (f16 / bf16 weights: ``be_lif_rec_dense_half_sg_forward``): :func:`_forward` with the matrix
+    itself."""
     new = lambda: torch.empty((B, N), dtype=x.dtype, device=x.device)
     s = torch.empty_like(x)
     v_seq = torch.empty_like(x) if want_v else None
@@ -297,14 +311,16 @@ def _forward_dense(x, r: _DenseRec, s0, c0, v0, a0, T: int, B: int, N: int, p: _
             if out is not None:
                 out.zero_() if start is None else out.copy_(start)
     else:
-        call('be_lif_rec_dense_sg_forward', A.ptr(x), A.ptr(r.w), A.ptr(s0), A.ptr(c0), A.ptr(v0), A.ptr(a0), A.ptr(s), A.ptr(v_seq),
-             A.ptr(h), A.ptr(th), A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho,
-             p.kappa, p.reset, p.adaptive, e, A.stream_ptr())
+        name = 'be_lif_rec_dense_half_sg_forward' if r.half else 'be_lif_rec_dense_sg_forward'
+        call(name, A.ptr(x), *r.args, A.ptr(s0), A.ptr(c0), A.ptr(v0), A.ptr(a0), A.ptr(s), A.ptr(v_seq), A.ptr(h), A.ptr(th),
+             A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa, p.reset,
+             p.adaptive, e, A.stream_ptr())
     return s, v_seq, h, th, c_last, v_last, a_last
 
 
 def _backward_dense(h, th, r: _DenseRec, g_s, g_vseq, g_last, T: int, B: int, N: int, p: _Params, want):
-    """``be_lif_rec_dense_sg_backward``: ``(g_x, g_c0, g_v0, g_a0, g_s0)``; None as in :func:`_backward`."""
+    """``be_lif_rec_dense_sg_backward`` (f16 / bf16 weights: ``be_lif_rec_dense_half_sg_backward``): ``(g_x, g_c0, g_v0, g_a0,
+    g_s0)``; None as in :func:`_backward`."""
     g_x = torch.empty_like(h)
     g_state = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in want]
     if T == 0:
@@ -314,16 +330,18 @@ def _backward_dense(h, th, r: _DenseRec, g_s, g_vseq, g_last, T: int, B: int, N:
         if g_state[3] is not None:
             g_state[3].zero_()
     else:
-        call('be_lif_rec_dense_sg_backward', A.ptr(h), A.ptr(th), A.ptr(r.w), A.ptr(g_s), A.ptr(g_vseq), A.ptr(g_last[0]),
-             A.ptr(g_last[1]), A.ptr(g_last[2]), A.ptr(g_x), A.ptr(g_state[0]), A.ptr(g_state[1]), A.ptr(g_state[2]), A.ptr(g_state[3]),
-             T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.surrogate, p.alpha, p.adaptive,
-             p.detach_reset, A.stream_ptr())
+        name = 'be_lif_rec_dense_half_sg_backward' if r.half else 'be_lif_rec_dense_sg_backward'
+        call(name, A.ptr(h), A.ptr(th), *r.args, A.ptr(g_s), A.ptr(g_vseq), A.ptr(g_last[0]), A.ptr(g_last[1]), A.ptr(g_last[2]),
+             A.ptr(g_x), A.ptr(g_state[0]), A.ptr(g_state[1]), A.ptr(g_state[2]), A.ptr(g_state[3]), T, B, N, p.syn_decay, p.beta,
+             p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.surrogate, p.alpha, p.adaptive, p.detach_reset, A.stream_ptr())
     return (g_x,) + tuple(g_state)
 
 
 def _weight_grad_dense(w, s, s0, g_x, T: int, B: int, N: int) -> torch.Tensor:
     """``g_W[i, :] = sum over (t, b) with sp[t][b][i] of g_x[t][b][:]``, ``sp = cat(s0, s[:-1])``: ``be_grad_dense`` (the
-    ``transpose=True`` side) over ``T * B`` batch rows — ``(T - 1) * B`` without ``s0``."""
+    ``transpose=True`` side) over ``T * B`` batch rows — ``(T - 1) * B`` without ``s0``.  For f16 / bf16 weights the sum is the same
+    f32 sum of the f32 ``g_x`` into an f32 ``[N, N]`` temporary, rounded to ``w.dtype`` ONCE: the gradient has the leaf's dtype, as
+    torch requires, and carries one rounding, not ``T * B`` of them."""
     if s0 is None:
         sp, g = s[:max(T - 1, 0)], g_x[1:]
     else:
@@ -332,6 +350,8 @@ def _weight_grad_dense(w, s, s0, g_x, T: int, B: int, N: int) -> torch.Tensor:
     if T == 0 or N == 0 or nb == 0:
         return torch.zeros_like(w)
     mask, _ = _autograd.activity(sp.reshape(nb, N), 'bm')
+    if w.dtype != torch.float32:
+        return _autograd.dense_weight_grad(((N, N), torch.float32), True, mask, nb, g.reshape(nb, N).T).to(w.dtype)
     return _autograd.dense_weight_grad(w, True, mask, nb, g.reshape(nb, N).T)
 
 
@@ -388,8 +408,8 @@ def _check_rec(who, rec, n: int):
     if rec.shape[0] != n:
         raise ValueError(f"{who}: rec {tuple(rec.shape)} must have the size of x's last axis, {n}.")
     if dense:                                 # one [N, N] array, nothing else to check
-        if rec.data.dtype != torch.float32:
-            raise TypeError(f"{who}: the weights of rec must be float32, not {rec.data.dtype} (f16 / bf16 dense weights are not built).")
+        if rec.data.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"{who}: the weights of rec must be float32, float16 or bfloat16, not {rec.data.dtype}.")
         if rec.data.ndim != 2:
             raise ValueError(f"{who}: the data of a Dense rec must be two-dimensional, not {rec.data.ndim}-dimensional.")
         if n > MAX_N:
@@ -420,7 +440,7 @@ def _scale_exp(who, scale_exp, rec, n: int) -> int:
             return 0
         from ._csr import fixed_point_exponent
         cols = torch.arange(n, dtype=torch.int32, device=rec.data.device).repeat(n)
-        return fixed_point_exponent(rec.data.detach().reshape(-1), cols, n)
+        return fixed_point_exponent(rec.data.detach().float().reshape(-1), cols, n)     # (f16 / bf16: the up-converted matrix)
     if scale_exp is None:
         m = rec.stacked if _is_delayed(rec) else rec      # (the stacked matrix has the same columns: every stacked row active)
         if m.indices.numel() == 0 or n == 0:
@@ -474,14 +494,23 @@ def recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Sequence[Optio
     gradient to the order the synapses were given in.  The limit is ``N <= 8192`` with ``8 * N + 8 * depth * ceil(N / 64) + 16384 <=
     162816`` (every ``N <= 8192`` at ``depth <= 16``, every ``N <= 2048`` at ``depth <= 256``).
 
-    **A dense recurrence.**  ``rec`` may be a :class:`Dense` ``[N, N]`` (f32, rows = presynaptic neurons; ``rec.data`` may be a
+    **A dense recurrence.**  ``rec`` may be a :class:`Dense` ``[N, N]`` (f32 — or f16 / bf16, below —, rows = presynaptic neurons; ``rec.data`` may be a
     ``torch.nn.Parameter``): the same function as on the :class:`CSR` that stores all ``N * N`` entries of the matrix at the same
     exponent — the forward outputs are equal bit for bit, a zero entry adds the integer 0 — through kernels that walk the matrix
     itself (``be_lif_rec_dense_sg_forward`` / ``_backward``), still one launch each way.  ``scale_exp=None`` asks for the exponent of
     that fully stored CSR (one host synchronisation).  Differentiable in ``x``, the state, ``s0`` and ``rec.data``; the backward
     row products are f32 sums in an order ``N`` alone fixes (not the CSR kernel's).  ``N <= 8192``.
 
-    Not built: CSC / fixed-number / JITC recurrences, a Dense recurrence with delays or tensor parameters, f16 / bf16 dense weights,
+    **f16 / bf16 dense weights.**  ``rec.data`` of a :class:`Dense` may be ``torch.float16`` or ``torch.bfloat16`` (row-major, possibly
+    a ``Parameter``): the layer is the f32 layer on ``rec.data.float()``.  The up-conversion is exact and the recurrent sums are the
+    same 64-bit integers, so every forward output equals the f32 call's on ``rec.data.float()`` at the same exponent, bit for bit
+    (``be_lif_rec_dense_half_sg_forward`` / ``_backward``: kernels of their own, one launch each way, no f32 copy of the matrix).
+    ``scale_exp=None`` asks for the exponent of the up-converted matrix: one host synchronisation AND an f32 ``[N, N]`` temporary
+    per call; an ``int`` is used as given and runs under ``capture_step``.  The backward row products up-convert in registers, round
+    every product and add in f32 in an order ``N`` alone fixes (the half kernel's own).  The gradient of ``rec.data`` has its dtype:
+    it is summed in f32 from the f32 ``g_x`` (``be_grad_dense`` into an f32 ``[N, N]`` temporary) and rounded to the dtype once.
+
+    Not built: CSC / fixed-number / JITC recurrences, a Dense recurrence with delays or tensor parameters,
     one shared weight, learnable delays, ``N > 8192``, a sample split over several workgroups (only ``B`` of the chip's compute units
     work)."""
     who = 'recurrent_lif_sequence'
@@ -657,8 +686,8 @@ def parametric_recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Seq
     the bit-for-bit forward contract are :func:`recurrent_lif_sequence`'s (``be_lif_rec_sg_forward_params``); differentiable, once,
     in ``x``, the state entries, ``s0``, ``rec.data`` and the five parameters.
 
-    A :class:`DelayedCSR` or a :class:`Dense` is taken with all-number parameters only (that is :func:`recurrent_lif_sequence`); with
-    a tensor parameter it raises ``NotImplementedError``.
+    A :class:`DelayedCSR` or a :class:`Dense` (f32, f16 or bf16 weights) is taken with all-number parameters only (that is
+    :func:`recurrent_lif_sequence`); with a tensor parameter it raises ``NotImplementedError``.
 
     Not built: learnable ``v_reset`` / ``alpha``, ``[B, N]`` parameters, tensor parameters with synaptic delays, and what
     :func:`recurrent_lif_sequence` does not build."""

@@ -446,6 +446,31 @@ int be_lif_rec_dense_sg_backward(const float* h_save, const float* th_save, cons
                                  float* g_v0, float* g_a0, float* g_s0, int64_t T, int64_t B, int64_t N, double syn_decay,
                                  double beta, double v_th, double v_reset, double rho, double kappa, int reset_mode, int surrogate,
                                  double alpha, int adaptive, int detach_reset, be_stream_t stream);
+/* The dense recurrence in TWO-BYTE weights (brainevent_amd/csrc/be_neuron_sg_rec_dense_half.hip): be_lif_rec_dense_sg_forward /
+ * _backward with w as const void*, [N, N] row-major of wdtype = BE_F16 or BE_BF16 (any other code: BE_ERR_INVALID), 2-byte
+ * aligned.  The layer is the f32 layer on float(W): every weight is up-converted exactly, R[j] = sum over the active rows i of
+ * fixed((float)W[i][j]) at scale_exp, so every forward output equals be_lif_rec_dense_sg_forward's on the up-converted matrix,
+ * bit for bit.  4-byte loads of adjacent column pairs when N is even and w 4-byte aligned, 2-byte loads otherwise; the results do
+ * not depend on which.
+ *   backward: g_rec[i] = sum_j (float)W[i][j] * G[j], each product rounded, then summed in f32 in an order N alone fixes — L lanes
+ *     per row, L the power of two with 2 * L >= ceil(N / 8) up to 64; lane l takes the groups of eight columns l, l + L, ... in
+ *     ascending order, then a butterfly over the L partial sums.  Two calls give the same bits; it is neither
+ *     be_lif_rec_sg_backward's order nor be_lif_rec_dense_sg_backward's.  16-byte loads of W when N % 8 == 0 and w is 16-byte
+ *     aligned, 2-byte loads otherwise; the results do not depend on which.
+ *   The weight gradient is be_grad_dense (transpose = 1) in f32 from the f32 g_x, rounded to the weights' type once by the caller.
+ * NULL conventions and error codes are be_lif_rec_dense_sg_forward / _backward's; the sizes, the modes, wdtype and the exponent are
+ * checked before any pointer is looked at.  No workspace, no allocation, no global atomics; never synchronises the host. */
+int be_lif_rec_dense_half_sg_forward(const float* x, const void* w, int wdtype, const float* s0, const float* c0, const float* v0,
+                                     const float* a0, float* s_out, float* v_seq, float* h_save, float* th_save, float* c_last,
+                                     float* v_last, float* a_last, int64_t T, int64_t B, int64_t N, double syn_decay, double beta,
+                                     double v_th, double v_reset, double rho, double kappa, int reset_mode, int adaptive,
+                                     int scale_exp, be_stream_t stream);
+int be_lif_rec_dense_half_sg_backward(const float* h_save, const float* th_save, const void* w, int wdtype, const float* g_s,
+                                      const float* g_vseq, const float* g_clast, const float* g_vlast, const float* g_alast,
+                                      float* g_x, float* g_c0, float* g_v0, float* g_a0, float* g_s0, int64_t T, int64_t B, int64_t N,
+                                      double syn_decay, double beta, double v_th, double v_reset, double rho, double kappa,
+                                      int reset_mode, int surrogate, double alpha, int adaptive, int detach_reset,
+                                      be_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * event vector helpers (replace: brainevent/_jit_scalar/binary_jitsmv.cu:107-125 `_pack_bool_kern`
