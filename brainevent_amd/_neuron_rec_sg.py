@@ -38,8 +38,15 @@ backwards the gather is a row-times-vector product.  The leaf of the weight grad
 forward outputs equal the f32 call's bit for bit — through kernels that load two weights in 4 bytes forwards and eight in 16 bytes
 backwards; the weight gradient is summed in f32 and rounded to the weights' dtype once.
 
-Not built: CSC / fixed-number / JITC recurrences, a Dense recurrence with delays or tensor parameters, one shared (homogeneous)
-weight, learnable ``v_reset`` / ``alpha``,
+FP8 WEIGHTS (``be_lif_rec_dense_f8_sg_forward`` / ``_backward``, ``csrc/be_neuron_sg_rec_dense_f8.hip``): ``rec`` may be
+a :class:`~brainevent_amd.Float8Dense` ``[N, N]`` (e4m3 or e5m2 codes, one f32 scale, rows = presynaptic neurons).  Every finite
+FP8 value is a multiple of 2^-9 / 2^-16, so the recurrent sum of the decoded weights is an exact integer in that unit, rounded to
+f32 once and multiplied by the scale in f32 — ``Float8Dense``'s product contract with an exact sum; there is no exponent and no
+host synchronisation.  The weights are read-only and get no gradient; ``x``, the state and ``s0`` do.
+
+Not built: CSC / fixed-number / JITC recurrences, a Dense or Float8Dense recurrence with delays or tensor parameters, FP8 weights
+for the CSR / delayed recurrence, a (straight-through) gradient of FP8 weights, per-row or per-block FP8 scales, one shared
+(homogeneous) weight, learnable ``v_reset`` / ``alpha``,
 per-sample (``[B, N]``) parameters, learnable delays, learnable neuron parameters together with delays, more than 8192 neurons (one
 sample's sums and spike ids live in one workgroup's LDS; with delays also its spike history: see :func:`delay_fits`), a sample split
 over several workgroups.  A cached scatter plan or mirror of ``rec`` is neither used nor needed: the kernels read the raw CSR arrays.
@@ -387,6 +394,90 @@ class DenseRecurrentLifSequence(torch.autograd.Function):
         return (g_x if need[0] else None), g_c0, g_v0, g_a0, g_s0, g_w, None, None, None, None, None
 
 
+class _Float8Rec:
+    """The codes of a :class:`~brainevent_amd.Float8Dense` as the FP8 kernels take them: contiguous ``[N, N]`` bytes on the device (no
+    neuron: one unused byte, no NULL pointer), the format's code and the scale."""
+    __slots__ = ('codes', 'fmt_code', 'scale')
+
+    def __init__(self, rec):
+        from ._dense_f8 import _CODE_OF_FMT
+        c = rec._device_codes()
+        self.codes = c.contiguous() if c.numel() else torch.zeros(1, dtype=torch.uint8, device=c.device)
+        self.fmt_code, self.scale = _CODE_OF_FMT[rec.fmt], float(rec.scale)
+
+    @property
+    def args(self):
+        return A.ptr(self.codes), self.fmt_code, self.scale
+
+
+def _forward_dense_f8(x, r: _Float8Rec, s0, c0, v0, a0, T: int, B: int, N: int, p: _Params, e, want_v: bool, want_h: bool):
+    """``be_lif_rec_dense_f8_sg_forward``: :func:`_forward_dense` with the codes, the format and the scale; ``e`` is unused (the
+    sums are exact integers in the format's own unit: the call has no exponent)."""
+    new = lambda: torch.empty((B, N), dtype=x.dtype, device=x.device)
+    s = torch.empty_like(x)
+    v_seq = torch.empty_like(x) if want_v else None
+    h = torch.empty_like(x) if want_h else None
+    th = torch.empty_like(x) if want_h and p.adaptive else None
+    c_last, v_last, a_last = new(), new(), (new() if p.adaptive else None)
+    if T == 0:                                # no step: the state passes through
+        for out, start in ((c_last, c0), (v_last, v0), (a_last, a0)):
+            if out is not None:
+                out.zero_() if start is None else out.copy_(start)
+    else:
+        call('be_lif_rec_dense_f8_sg_forward', A.ptr(x), *r.args, A.ptr(s0), A.ptr(c0), A.ptr(v0), A.ptr(a0), A.ptr(s), A.ptr(v_seq),
+             A.ptr(h), A.ptr(th), A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho,
+             p.kappa, p.reset, p.adaptive, A.stream_ptr())
+    return s, v_seq, h, th, c_last, v_last, a_last
+
+
+def _backward_dense_f8(h, th, r: _Float8Rec, g_s, g_vseq, g_last, T: int, B: int, N: int, p: _Params, want):
+    """``be_lif_rec_dense_f8_sg_backward``: ``(g_x, g_c0, g_v0, g_a0, g_s0)``; None as in :func:`_backward`."""
+    g_x = torch.empty_like(h)
+    g_state = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in want]
+    if T == 0:
+        for out, g in zip(g_state[:3], g_last):
+            if out is not None:
+                out.zero_() if g is None else out.copy_(g)
+        if g_state[3] is not None:
+            g_state[3].zero_()
+    else:
+        call('be_lif_rec_dense_f8_sg_backward', A.ptr(h), A.ptr(th), *r.args, A.ptr(g_s), A.ptr(g_vseq), A.ptr(g_last[0]),
+             A.ptr(g_last[1]), A.ptr(g_last[2]), A.ptr(g_x), A.ptr(g_state[0]), A.ptr(g_state[1]), A.ptr(g_state[2]), A.ptr(g_state[3]),
+             T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.surrogate, p.alpha, p.adaptive,
+             p.detach_reset, A.stream_ptr())
+    return (g_x,) + tuple(g_state)
+
+
+class Float8RecurrentLifSequence(torch.autograd.Function):
+    """:class:`DenseRecurrentLifSequence` over a :class:`~brainevent_amd.Float8Dense`: the weights are read-only, so they are neither
+    a differentiable input nor saved — ``r`` holds the codes (a Float8Dense's codes are not written in place).  Saved: ``h`` and
+    ``th`` when adaptive; a None gradient goes in as NULL."""
+
+    @staticmethod
+    def forward(ctx, x, c0, v0, a0, s0, r: _Float8Rec, dims, p: _Params, return_v: bool):
+        ctx.set_materialize_grads(False)
+        T, B, N = dims
+        s, v_seq, h, th, c_last, v_last, a_last = _forward_dense_f8(x, r, s0, c0, v0, a0, T, B, N, p, None, return_v, True)
+        ctx.save_for_backward(h, th)
+        ctx.meta = (r, dims, p, return_v)
+        return tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_s, *rest):
+        r, (T, B, N), p, return_v = ctx.meta
+        g_vseq = rest[0] if return_v else None
+        g_last = list(rest[1:] if return_v else rest) + [None] * (3 - p.entries)
+        if g_s is None and g_vseq is None and all(g is None for g in g_last):
+            return (None,) * 9
+        h, th = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = [need[1], need[2], bool(p.adaptive) and need[3], need[4]]
+        g_x, g_c0, g_v0, g_a0, g_s0 = _backward_dense_f8(h, th, r, _grad_in(g_s), _grad_in(g_vseq), [_grad_in(g) for g in g_last], T,
+                                                         B, N, p, want)
+        return (g_x if need[0] else None), g_c0, g_v0, g_a0, g_s0, None, None, None, None
+
+
 def _is_delayed(rec) -> bool:
     from ._delay import DelayedCSR
     return isinstance(rec, DelayedCSR)
@@ -397,9 +488,25 @@ def _is_dense(rec) -> bool:
     return isinstance(rec, Dense)
 
 
-def _check_rec(who, rec, n: int):
+def _is_float8(rec) -> bool:
+    from ._dense_f8 import Float8Dense
+    return isinstance(rec, Float8Dense)
+
+
+def _check_rec(who, rec, n: int, like=None):
     from ._csr import CSR
     delayed, dense = _is_delayed(rec), _is_dense(rec)
+    if _is_float8(rec):                       # codes [N, N] and one scale; the constructor has refused non-finite codes
+        if rec.shape[0] != rec.shape[1]:
+            raise ValueError(f"{who}: rec {tuple(rec.shape)} must be square (a recurrent projection).")
+        if rec.shape[0] != n:
+            raise ValueError(f"{who}: rec {tuple(rec.shape)} must have the size of x's last axis, {n}.")
+        if n > MAX_N:
+            raise ValueError(f"{who}: {n} neurons; the limit is {MAX_N} (one workgroup holds a sample's neurons).")
+        codes = rec._device_codes()
+        if like is not None and codes.device != like.device:
+            raise ValueError(f"{who}: the codes of rec are on {codes.device}, x is on {like.device}: they must share a device.")
+        return
     if not delayed and not dense and not isinstance(rec, CSR):
         raise TypeError(f"{who}: rec must be a CSR matrix (rows = presynaptic neurons), a DelayedCSR or a Dense, not "
                         f"{type(rec).__name__}; CSC, fixed-number, JITC and planned matrices are not built.")
@@ -435,6 +542,11 @@ def _check_rec(who, rec, n: int):
 
 
 def _scale_exp(who, scale_exp, rec, n: int) -> int:
+    if _is_float8(rec):                       # exact integer sums in the format's own unit: nothing to ask for, nothing to give
+        if scale_exp is not None:
+            raise ValueError(f"{who}: scale_exp must be None with a Float8Dense rec: its recurrent sums are exact integers in the "
+                             f"format's own unit (2^-9 for e4m3, 2^-16 for e5m2) and take no exponent.")
+        return 0
     if scale_exp is None and _is_dense(rec):  # the exponent of the CSR that stores all N * N entries
         if n == 0:
             return 0
@@ -510,13 +622,34 @@ def recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Sequence[Optio
     every product and add in f32 in an order ``N`` alone fixes (the half kernel's own).  The gradient of ``rec.data`` has its dtype:
     it is summed in f32 from the f32 ``g_x`` (``be_grad_dense`` into an f32 ``[N, N]`` temporary) and rounded to the dtype once.
 
-    Not built: CSC / fixed-number / JITC recurrences, a Dense recurrence with delays or tensor parameters,
+    **FP8 dense weights.**  ``rec`` may be a :class:`Float8Dense` ``[N, N]`` (``quantize_fp8(W, fmt)``: e4m3 or e5m2 codes and one f32
+    ``scale``; rows = presynaptic neurons): ``xin[t][j] = x[t][j] + fl32(fl32(sum of decode(codes[i, j]) over the spiking i) * scale)``.
+    Every finite e4m3 / e5m2 value is a multiple of 2^-9 / 2^-16, so the inner sum is an exact integer in that unit — rounded to f32
+    once, then multiplied by ``scale`` in f32: ``Float8Dense``'s own product contract with the sum exact, equal to the per-step loop
+    ``x[t] + BinaryArray(s) @ rec`` wherever that loop's f32 sums are exact, and a function of the inputs bit for bit
+    (``be_lif_rec_dense_f8_sg_forward`` / ``_backward``, one launch each way, ``N <= 8192``).  ``scale_exp`` must stay ``None`` (an
+    int raises ``ValueError``: there is no exponent); the call never synchronises the host and always runs under ``capture_step``.
+    The weights are read-only and get no gradient.  Unlike the ``events @ Float8Dense`` products, which refuse an operand that
+    requires grad, this layer ACCEPTS a grad-requiring ``x`` / state / ``s0`` and differentiates them, once — a frozen, quantised
+    recurrence inside a trained network passes ``g_x`` to the layers below; backwards ``g_rec[i] = fl32((sum_j decode(codes[i, j]) *
+    G[j]) * scale)``, f32 products and sums in an order ``N`` alone fixes, the scale applied once per row.
+
+    Not built: CSC / fixed-number / JITC recurrences, a Dense or Float8Dense recurrence with delays or tensor parameters, FP8 weights
+    for a CSR / DelayedCSR recurrence, a (straight-through) gradient of FP8 weights, per-row or per-block FP8 scales,
     one shared weight, learnable delays, ``N > 8192``, a sample split over several workgroups (only ``B`` of the chip's compute units
     work)."""
     who = 'recurrent_lif_sequence'
     p = _Params(who, syn_decay, beta, v_th, v_reset, reset, surrogate, alpha, detach_reset, adapt)
     (T, B, N), slots, x3, (c0, v0, a0, sp), e = _prepare(who, x, rec, state0, s0, p, scale_exp)
     return_v = bool(return_v)
+    if _is_float8(rec):                       # read-only codes: no weights among the differentiable inputs
+        r = _Float8Rec(rec)
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x3, c0, v0, a0, sp)):
+            outs = Float8RecurrentLifSequence.apply(x3, c0, v0, a0, sp, r, (T, B, N), p, return_v)
+        else:                                 # no backward pass: h / th are not kept
+            s, v_seq, _, _, c_last, v_last, a_last = _forward_dense_f8(x3, r, sp, c0, v0, a0, T, B, N, p, None, return_v, False)
+            outs = tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
+        return _shaped(outs, x, slots, return_v)
     if _is_delayed(rec):                      # the stacked matrix, a history [A, B, N]
         w = rec.stacked.data
         r = _DelayedRec(w.detach(), rec)
@@ -546,7 +679,7 @@ def _prepare(who, x, rec, state0, s0, p: _Params, scale_exp):
     slots = tuple(x.shape[1:])
     T, N = int(x.shape[0]), int(x.shape[-1])
     B = int(x.shape[1]) if x.ndim == 3 else 1
-    _check_rec(who, rec, N)
+    _check_rec(who, rec, N, x)
     state = _check_state(who, 'state0', state0, p, slots, allow_none=True)
     ages = None                               # with delays: the past steps s0 holds
     if s0 is not None:
@@ -686,10 +819,11 @@ def parametric_recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Seq
     the bit-for-bit forward contract are :func:`recurrent_lif_sequence`'s (``be_lif_rec_sg_forward_params``); differentiable, once,
     in ``x``, the state entries, ``s0``, ``rec.data`` and the five parameters.
 
-    A :class:`DelayedCSR` or a :class:`Dense` (f32, f16 or bf16 weights) is taken with all-number parameters only (that is
+    A :class:`DelayedCSR`, a :class:`Dense` (f32, f16 or bf16 weights) or a :class:`Float8Dense` is taken with all-number parameters only (that is
     :func:`recurrent_lif_sequence`); with a tensor parameter it raises ``NotImplementedError``.
 
-    Not built: learnable ``v_reset`` / ``alpha``, ``[B, N]`` parameters, tensor parameters with synaptic delays, and what
+    Not built: learnable ``v_reset`` / ``alpha``, ``[B, N]`` parameters, tensor parameters with synaptic delays or a dense (Dense,
+    Float8Dense) recurrence, and what
     :func:`recurrent_lif_sequence` does not build."""
     who = 'parametric_recurrent_lif_sequence'
     given, stand_in, any_tensor = _split_params(who, syn_decay, beta, v_th, adapt)
@@ -700,6 +834,10 @@ def parametric_recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Seq
     if _is_dense(rec):
         raise NotImplementedError(f"{who}: learnable (tensor) neuron parameters together with a Dense recurrence are not built: a "
                                   f"Dense rec takes syn_decay, beta, v_th and adapt as Python numbers (recurrent_lif_sequence).")
+    if _is_float8(rec):
+        raise NotImplementedError(f"{who}: learnable (tensor) neuron parameters together with a Float8Dense recurrence are not "
+                                  f"built: a Float8Dense rec takes syn_decay, beta, v_th and adapt as Python numbers "
+                                  f"(recurrent_lif_sequence).")
     if _is_delayed(rec):
         raise NotImplementedError(f"{who}: learnable (tensor) neuron parameters together with synaptic delays are not built: a "
                                   f"DelayedCSR takes syn_decay, beta, v_th and adapt as Python numbers (recurrent_lif_sequence).")

@@ -471,6 +471,33 @@ int be_lif_rec_dense_half_sg_backward(const float* h_save, const float* th_save,
                                       double syn_decay, double beta, double v_th, double v_reset, double rho, double kappa,
                                       int reset_mode, int surrogate, double alpha, int adaptive, int detach_reset,
                                       be_stream_t stream);
+/* The dense recurrence in OCP FP8 CODES (brainevent_amd/csrc/be_neuron_sg_rec_dense_f8.hip): the _half_ calls with (w, wdtype) replaced
+ * by (codes, fmt_code, w_scale) — codes [N, N] bytes row-major, rows = presynaptic neurons, any alignment; fmt_code = BE_F8_E4M3 or
+ * BE_F8_E5M2 (0 / 1, defined with be_binary_densemm_f8 below; any other code: BE_ERR_INVALID); w_scale one finite f32 (a value that
+ * is not finite as a float: BE_ERR_INVALID) — and WITHOUT scale_exp in the forward call.  The caller guarantees finite codes.
+ *   forward: xin[t][j] = x[t][j] + fl32( fl32( sum over the rows i with sp[i] != 0 of decode(codes[i][j]) ) * w_scale ).  The inner sum
+ *     is EXACT: every finite e4m3 / e5m2 value is a multiple of 2^-9 / 2^-16, so the sum is an integer in that unit (32 bits for
+ *     e4m3: 8192 * 448 * 512 < 2^31; 64 bits for e5m2), rounded to f32 once and then multiplied by w_scale in f32 — Float8Dense's
+ *     product contract with an exact sum.  The forward pass is a function of its inputs bit for bit, and no exponent exists.
+ *     4-byte loads of adjacent column quads when N % 4 == 0 and codes is 4-byte aligned, byte loads otherwise: the same bits.
+ *   backward: g_rec[i] = fl32( (sum_j decode(codes[i][j]) * G[j]) * w_scale ), each product rounded, summed in f32 in an order N alone
+ *     fixes — L lanes per row, L the power of two with L >= ceil(N / 16) up to 64; lane l takes the groups of sixteen columns l,
+ *     l + L, ... in ascending order, then a butterfly over the L partial sums, then the scale, once per row.  Two calls give the
+ *     same bits.  16-byte loads when N % 16 == 0 and codes is 16-byte aligned, byte loads otherwise; the results do not depend on
+ *     which.  The codes get no gradient.
+ * NULL conventions and error codes are be_lif_rec_dense_half_sg_forward / _backward's; the sizes, the modes, fmt_code and w_scale are
+ * checked before any pointer is looked at.  No workspace, no allocation, no global atomics; never synchronises the host. */
+int be_lif_rec_dense_f8_sg_forward(const float* x, const void* codes, int fmt_code, double w_scale, const float* s0, const float* c0,
+                                   const float* v0, const float* a0, float* s_out, float* v_seq, float* h_save, float* th_save,
+                                   float* c_last, float* v_last, float* a_last, int64_t T, int64_t B, int64_t N, double syn_decay,
+                                   double beta, double v_th, double v_reset, double rho, double kappa, int reset_mode, int adaptive,
+                                   be_stream_t stream);
+int be_lif_rec_dense_f8_sg_backward(const float* h_save, const float* th_save, const void* codes, int fmt_code, double w_scale,
+                                    const float* g_s, const float* g_vseq, const float* g_clast, const float* g_vlast,
+                                    const float* g_alast, float* g_x, float* g_c0, float* g_v0, float* g_a0, float* g_s0, int64_t T,
+                                    int64_t B, int64_t N, double syn_decay, double beta, double v_th, double v_reset, double rho,
+                                    double kappa, int reset_mode, int surrogate, double alpha, int adaptive, int detach_reset,
+                                    be_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * event vector helpers (replace: brainevent/_jit_scalar/binary_jitsmv.cu:107-125 `_pack_bool_kern`
