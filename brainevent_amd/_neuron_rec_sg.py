@@ -61,7 +61,7 @@ from . import _array as A
 from . import _autograd
 from ._lib import call, fn
 from ._neuron_sg import _check_device, _check_tensor, _grad_in, _reduce_slots
-from ._neuron_syn_sg import FIVE_TENSORS, _Params, _check_state, _device_params, _split_params
+from ._neuron_syn_sg import FIVE_TENSORS, _Params, _check_state, _device_params, _new_grads, _new_outputs, _split_params
 
 __all__ = ['recurrent_lif_sequence', 'parametric_recurrent_lif_sequence']
 
@@ -82,489 +82,294 @@ def delay_fits(n: int, depth: int) -> bool:
     return n <= MAX_N and 1 <= depth <= MAX_DEPTH and 8 * n + 8 * depth * ((n + 63) // 64) + 4 * DELAY_MIN_IDS <= DELAY_LDS_BYTES
 
 
+def _limit(who, n: int, why: str):
+    if n > MAX_N:
+        raise ValueError(f"{who}: {n} neurons; the limit is {MAX_N} ({why}).")
+
+
 class _Rec:
-    """The CSR arrays as the kernels take them (a matrix without entries hands over one unused element: no NULL pointer)."""
-    __slots__ = ('w', 'indices', 'indptr', 'nse')
+    """A :class:`~brainevent_amd.CSR` recurrence as the host path takes it — and the shape of every family's adapter (DESIGN.md
+    §2.32): the family's checks (the constructor), its entry points, the arguments that stand for the matrix in the C calls, how
+    ``s0`` goes in, the exponent, the leaf of the weight gradient and that gradient.  A matrix without entries hands over one unused
+    element: no NULL pointer."""
+    forward = 'be_lif_rec_sg_forward'
+    backward = 'be_lif_rec_sg_backward'
+    takes_exp = True                          # the C calls take scale_exp
+    no_tensors = None                         # or: why parametric_recurrent_lif_sequence refuses the family tensor parameters
+    ages = None                               # with delays: the past steps s0 holds
 
-    def __init__(self, w, indices, indptr):
-        self.nse = int(indices.numel())
-        self.w = w.reshape(-1) if self.nse else torch.zeros(1, dtype=torch.float32, device=indptr.device)
-        self.indices = indices if self.nse else torch.zeros(1, dtype=torch.int32, device=indptr.device)
-        self.indptr = indptr
+    def __init__(self, who, m, n: int, like=None, int64_hint='.'):
+        if m.data.dtype != torch.float32:
+            raise TypeError(f"{who}: the weights of rec must be float32, not {m.data.dtype}.")
+        self.nse = int(m.indices.numel())
+        if m.data.numel() != self.nse:
+            raise ValueError(f"{who}: rec must hold one weight per stored entry ({self.nse}), not {m.data.numel()} (one shared weight "
+                             f"is not built).")
+        if m.indptr.dtype != torch.int32:
+            raise TypeError(f"{who}: the indptr of rec must be int32, not {m.indptr.dtype}" + int64_hint)
+        _limit(who, n, "one sample's sums and spike ids live in one workgroup's LDS")
+        self.m, self.leaf = m, m.data
+        self.w = m.data.detach().reshape(-1) if self.nse else torch.zeros(1, dtype=torch.float32, device=m.indptr.device)
+        self.indices = m.indices if self.nse else torch.zeros(1, dtype=torch.int32, device=m.indptr.device)
+        self.indptr = m.indptr
+        self.matrix = (A.ptr(self.w), A.ptr(self.indices), A.ptr(self.indptr))
 
+    def check_s0(self, who, s0, slots):
+        if tuple(s0.shape) != slots:
+            raise ValueError(f"{who}: s0 {tuple(s0.shape)} must have the shape of a step of x, {slots}.")
 
-def _forward(x, r: _Rec, s0, c0, v0, a0, T: int, B: int, N: int, p: _Params, e: int, want_v: bool, want_h: bool):
-    """``be_lif_rec_sg_forward`` on contiguous ``x [T, B, N]``: ``(s, v_seq, h, th, c_last, v_last, a_last)``; what was not asked
-    for (and, without adaptation, ``th`` / ``a_last``) is None and neither allocated nor written."""
-    new = lambda: torch.empty((B, N), dtype=x.dtype, device=x.device)
-    s = torch.empty_like(x)
-    v_seq = torch.empty_like(x) if want_v else None
-    h = torch.empty_like(x) if want_h else None
-    th = torch.empty_like(x) if want_h and p.adaptive else None
-    c_last, v_last, a_last = new(), new(), (new() if p.adaptive else None)
-    if T == 0:                                # no step: the state passes through
-        for out, start in ((c_last, c0), (v_last, v0), (a_last, a0)):
-            if out is not None:
-                out.zero_() if start is None else out.copy_(start)
-    else:
-        call('be_lif_rec_sg_forward', A.ptr(x), A.ptr(r.w), A.ptr(r.indices), A.ptr(r.indptr), A.ptr(s0), A.ptr(c0), A.ptr(v0),
-             A.ptr(a0), A.ptr(s), A.ptr(v_seq), A.ptr(h), A.ptr(th), A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N,
-             p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.adaptive, e, A.stream_ptr())
-    return s, v_seq, h, th, c_last, v_last, a_last
+    def s0_shape(self, B: int, N: int):
+        """``s0`` — and its gradient — as the kernels take it."""
+        return (B, N) if self.ages is None else (self.ages, B, N)
 
+    def s0_args(self, t):
+        """Forwards ``s0``, backwards its gradient: a pointer, with delays a pointer and the ages."""
+        return (A.ptr(t),) if self.ages is None else (A.ptr(t), self.ages)
 
-def _backward(h, th, r: _Rec, g_s, g_vseq, g_last, T: int, B: int, N: int, p: _Params, want):
-    """``be_lif_rec_sg_backward``: ``(g_x, g_c0, g_v0, g_a0, g_s0)``.  A gradient that is None goes in as NULL; a state or ``s0``
-    gradient is None unless ``want`` asks for it."""
-    g_x = torch.empty_like(h)
-    g_state = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in want]
-    if T == 0:
-        for out, g in zip(g_state[:3], g_last):
-            if out is not None:
-                out.zero_() if g is None else out.copy_(g)
-        if g_state[3] is not None:
-            g_state[3].zero_()
-    else:
-        call('be_lif_rec_sg_backward', A.ptr(h), A.ptr(th), A.ptr(r.w), A.ptr(r.indices), A.ptr(r.indptr), A.ptr(g_s), A.ptr(g_vseq),
-             A.ptr(g_last[0]), A.ptr(g_last[1]), A.ptr(g_last[2]), A.ptr(g_x), A.ptr(g_state[0]), A.ptr(g_state[1]), A.ptr(g_state[2]),
-             A.ptr(g_state[3]), T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.surrogate, p.alpha,
-             p.adaptive, p.detach_reset, A.stream_ptr())
-    return (g_x,) + tuple(g_state)
+    def exponent(self, who, scale_exp, n: int) -> int:
+        if scale_exp is None:
+            return self.own_exponent(n)
+        if isinstance(scale_exp, bool) or not isinstance(scale_exp, numbers.Integral):
+            raise TypeError(f"{who}: scale_exp must be None or an int, not {type(scale_exp).__name__}.")
+        if not SCALE_EXP_RANGE[0] <= scale_exp <= SCALE_EXP_RANGE[1]:
+            raise ValueError(f"{who}: scale_exp {scale_exp} is outside {SCALE_EXP_RANGE[0]} .. {SCALE_EXP_RANGE[1]}, the exponents "
+                             f"fixed_point_exponent returns.")
+        return int(scale_exp)
 
+    def own_exponent(self, n: int) -> int:    # (a stacked matrix has the same columns: every stacked row active)
+        if self.nse == 0 or n == 0:
+            return 0
+        from ._csr import fixed_point_exponent
+        return fixed_point_exponent(self.m.data.detach(), self.m.indices, n)
 
-def _weight_grad(w, r: _Rec, s, s0, g_x, T: int, B: int, N: int) -> torch.Tensor:
-    """``g_w[k] = sum over t, b of sp[t][b][row k] * g_x[t][b][col k]`` with ``sp = cat(s0, s[:-1])``: ``be_grad_rows`` (the
-    ``transpose=True`` side) over ``T * B`` batch rows — ``(T - 1) * B`` without ``s0`` — in ascending order; ``g_x`` is read
-    batch-major through the stride arguments, nothing is transposed."""
-    if T == 0 or r.nse == 0:
-        return torch.zeros_like(w)
-    if s0 is None:
-        sp, g = s[:T - 1], g_x[1:]
-    else:
-        sp, g = torch.cat(((s0 != 0).to(s.dtype)[None], s[:T - 1])), g_x
-    nb = int(sp.shape[0]) * B
-    if nb == 0:
-        return torch.zeros_like(w)
-    mask, _ = _autograd.activity(sp.reshape(nb, N), 'bm')
-    dw = torch.empty(r.nse, dtype=w.dtype, device=w.device)
-    g = g.contiguous()
-    call('be_grad_rows', 1, A.ptr(dw), 0, A.wcode(dw), A.ptr(r.indices), A.ptr(r.indptr), 0, -1, N, r.nse, A.ptr(mask), nb, A.ptr(g),
-         1, N, A.ptr(None), 0, A.stream_ptr())
-    return dw.reshape(w.shape)
-
-
-class RecurrentLifSequence(torch.autograd.Function):
-    """Outputs ``s, [v_seq,] c_last, v_last [, a_last]``.  Saved: ``h``, ``th`` when adaptive, ``s`` (the weight gradient's
-    activity), the weights and ``s0``.  The gradient of an output nobody used arrives as None (``set_materialize_grads(False)``)
-    and goes in as NULL."""
-
-    @staticmethod
-    def forward(ctx, x, c0, v0, a0, s0, w, r: _Rec, dims, p: _Params, e: int, return_v: bool):
-        ctx.set_materialize_grads(False)
-        T, B, N = dims
-        s, v_seq, h, th, c_last, v_last, a_last = _forward(x, r, s0, c0, v0, a0, T, B, N, p, e, return_v, True)
-        ctx.save_for_backward(h, th, s, w, s0)
-        ctx.meta = (r, dims, p, return_v)
-        return tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_s, *rest):
-        r, (T, B, N), p, return_v = ctx.meta
-        g_vseq = rest[0] if return_v else None
-        g_last = list(rest[1:] if return_v else rest) + [None] * (3 - p.entries)
-        if g_s is None and g_vseq is None and all(g is None for g in g_last):
-            return (None,) * 11
-        h, th, s, w, s0 = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        want = [need[1], need[2], bool(p.adaptive) and need[3], need[4]]
-        g_x, g_c0, g_v0, g_a0, g_s0 = _backward(h, th, r, _grad_in(g_s), _grad_in(g_vseq), [_grad_in(g) for g in g_last], T, B, N, p,
-                                                want)
-        g_w = _weight_grad(w, r, s, s0, g_x, T, B, N) if need[5] else None
-        return (g_x if need[0] else None), g_c0, g_v0, g_a0, g_s0, g_w, None, None, None, None, None
+    def weight_grad(self, s, w, s0, g_x, T: int, B: int, N: int) -> torch.Tensor:
+        """``g_w[k] = sum over t, b of sp[t][b][row k] * g_x[t][b][col k]`` with ``sp = cat(s0, s[:-1])``: ``be_grad_rows`` (the
+        ``transpose=True`` side) over ``T * B`` batch rows — ``(T - 1) * B`` without ``s0`` — in ascending order; ``g_x`` is read
+        batch-major through the stride arguments, nothing is transposed."""
+        if T == 0 or self.nse == 0:
+            return torch.zeros_like(w)
+        if s0 is None:
+            sp, g = s[:T - 1], g_x[1:]
+        else:
+            sp, g = torch.cat(((s0 != 0).to(s.dtype)[None], s[:T - 1])), g_x
+        nb = int(sp.shape[0]) * B
+        if nb == 0:
+            return torch.zeros_like(w)
+        mask, _ = _autograd.activity(sp.reshape(nb, N), 'bm')
+        dw = torch.empty(self.nse, dtype=w.dtype, device=w.device)
+        g = g.contiguous()
+        call('be_grad_rows', 1, A.ptr(dw), 0, A.wcode(dw), A.ptr(self.indices), A.ptr(self.indptr), 0, -1, N, self.nse, A.ptr(mask),
+             nb, A.ptr(g), 1, N, A.ptr(None), 0, A.stream_ptr())
+        return dw.reshape(w.shape)
 
 
-class _DelayedRec:
-    """The stacked arrays of a :class:`~brainevent_amd.DelayedCSR` as the delayed kernels take them (as :class:`_Rec`: a matrix
-    without entries hands over one unused element)."""
-    __slots__ = ('w', 'indices', 'indptr', 'row_mask', 'depth', 'nse')
+class _DelayedRec(_Rec):
+    """A :class:`~brainevent_amd.DelayedCSR`: the stacked arrays, the row mask and the depth; ``s0`` is a history ``[ages, B, N]``
+    and the leaf ``rec.stacked.data``."""
+    forward = 'be_lif_rec_delay_sg_forward'
+    backward = 'be_lif_rec_delay_sg_backward'
+    no_tensors = ('synaptic delays', 'DelayedCSR')
 
-    def __init__(self, w, rec):
-        st = rec.stacked
-        self.nse = int(st.indices.numel())
-        self.w = w.reshape(-1) if self.nse else torch.zeros(1, dtype=torch.float32, device=st.indptr.device)
-        self.indices = st.indices if self.nse else torch.zeros(1, dtype=torch.int32, device=st.indptr.device)
-        self.indptr, self.row_mask, self.depth = st.indptr, rec.row_mask, int(rec.depth)
+    def __init__(self, who, rec, n: int, like=None):
+        super().__init__(who, rec.stacked, n, like,  # with delays the kernels read the stacked arrays
+                         " (a DelayedCSR built from an int64 indptr, or with 2^31 entries or more, is not built).")
+        self.row_mask, self.depth, self.ages = rec.row_mask, int(rec.depth), 0
+        self.matrix += (A.ptr(self.row_mask), self.depth)
+        if not delay_fits(n, self.depth):
+            raise ValueError(f"{who}: {n} neurons at depth {self.depth} do not fit: with delays 8 * N + 8 * depth * ceil(N / 64) + "
+                             f"{4 * DELAY_MIN_IDS} must stay within {DELAY_LDS_BYTES} bytes (one sample's sums, its spike history and a "
+                             f"list of active rows live in one workgroup's LDS; every N <= 8192 fits at depth <= 16, every N <= 2048 at "
+                             f"depth <= {MAX_DEPTH}); a sample split over several workgroups is not built.")
 
+    def check_s0(self, who, s0, slots):
+        if tuple(s0.shape) == slots:
+            self.ages = 1
+        elif s0.ndim == len(slots) + 1 and tuple(s0.shape[1:]) == slots and 1 <= s0.shape[0] <= self.depth:
+            self.ages = int(s0.shape[0])
+        else:
+            raise ValueError(f"{who}: s0 {tuple(s0.shape)} must have the shape of a step of x, {slots}, or hold A past steps, "
+                             f"(A,) + {slots} with 1 <= A <= depth = {self.depth} (s0[a]: the spikes a + 1 steps before step 0).")
 
-def _forward_delay(x, r: _DelayedRec, s_hist, c0, v0, a0, T: int, B: int, N: int, p: _Params, e: int, want_v: bool, want_h: bool):
-    """``be_lif_rec_delay_sg_forward``: :func:`_forward` with the stacked arrays and ``s_hist [A, B, N]`` (or None: ``A = 0``)."""
-    new = lambda: torch.empty((B, N), dtype=x.dtype, device=x.device)
-    s = torch.empty_like(x)
-    v_seq = torch.empty_like(x) if want_v else None
-    h = torch.empty_like(x) if want_h else None
-    th = torch.empty_like(x) if want_h and p.adaptive else None
-    c_last, v_last, a_last = new(), new(), (new() if p.adaptive else None)
-    if T == 0:                                # no step: the state passes through
-        for out, start in ((c_last, c0), (v_last, v0), (a_last, a0)):
-            if out is not None:
-                out.zero_() if start is None else out.copy_(start)
-    else:
-        call('be_lif_rec_delay_sg_forward', A.ptr(x), A.ptr(r.w), A.ptr(r.indices), A.ptr(r.indptr), A.ptr(r.row_mask), r.depth,
-             A.ptr(s_hist), 0 if s_hist is None else int(s_hist.shape[0]), A.ptr(c0), A.ptr(v0), A.ptr(a0), A.ptr(s), A.ptr(v_seq),
-             A.ptr(h), A.ptr(th), A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho,
-             p.kappa, p.reset, p.adaptive, e, A.stream_ptr())
-    return s, v_seq, h, th, c_last, v_last, a_last
-
-
-def _backward_delay(h, th, r: _DelayedRec, g_s, g_vseq, g_last, ages: int, T: int, B: int, N: int, p: _Params, want):
-    """``be_lif_rec_delay_sg_backward``: ``(g_x, g_c0, g_v0, g_a0, g_s_hist)``, the last ``[ages, B, N]``; None as in
-    :func:`_backward`."""
-    g_x = torch.empty_like(h)
-    g_state = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in want[:3]]
-    g_hist = torch.empty((ages, B, N), dtype=h.dtype, device=h.device) if want[3] else None
-    if T == 0:
-        for out, g in zip(g_state, g_last):
-            if out is not None:
-                out.zero_() if g is None else out.copy_(g)
-        if g_hist is not None:
-            g_hist.zero_()
-    else:
-        call('be_lif_rec_delay_sg_backward', A.ptr(h), A.ptr(th), A.ptr(r.w), A.ptr(r.indices), A.ptr(r.indptr), A.ptr(r.row_mask),
-             r.depth, A.ptr(g_s), A.ptr(g_vseq), A.ptr(g_last[0]), A.ptr(g_last[1]), A.ptr(g_last[2]), A.ptr(g_x), A.ptr(g_state[0]),
-             A.ptr(g_state[1]), A.ptr(g_state[2]), A.ptr(g_hist), ages, T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa,
-             p.reset, p.surrogate, p.alpha, p.adaptive, p.detach_reset, A.stream_ptr())
-    return (g_x,) + tuple(g_state) + (g_hist,)
+    def weight_grad(self, s, w, s_hist, g_x, T: int, B: int, N: int) -> torch.Tensor:
+        """``g_w[k] = sum over t, b of sp(t - 1 - d)[b][i] * g_x[t][b][col k]`` for ``k`` in stacked row ``d * N + i``: one launch packs
+        the aged activity of all ``depth * N`` stacked rows over the ``T * B`` batch rows (``be_grad_pack_activity_aged``), then
+        ``be_grad_rows`` (``transpose=True``) over the stacked matrix, in ascending ``(t, b)``."""
+        nb = T * B
+        if nb == 0 or N == 0 or self.nse == 0:
+            return torch.zeros_like(w)
+        rows = self.depth * N
+        mask = torch.empty(max(fn('be_grad_mask_bytes')(rows, nb), 4) // 4, dtype=torch.int32, device=w.device)
+        call('be_grad_pack_activity_aged', A.ptr(s), A.ptr(s_hist), N, B, T, self.depth, 0 if s_hist is None else int(s_hist.shape[0]),
+             A.ptr(mask), A.stream_ptr())
+        dw = torch.empty(self.nse, dtype=w.dtype, device=w.device)
+        call('be_grad_rows', 1, A.ptr(dw), 0, A.wcode(dw), A.ptr(self.indices), A.ptr(self.indptr), 0, -1, rows, self.nse,
+             A.ptr(mask), nb, A.ptr(g_x), 1, N, A.ptr(None), 0, A.stream_ptr())
+        return dw.reshape(w.shape)
 
 
-def _weight_grad_delay(w, r: _DelayedRec, s, s_hist, g_x, T: int, B: int, N: int) -> torch.Tensor:
-    """``g_w[k] = sum over t, b of sp(t - 1 - d)[b][i] * g_x[t][b][col k]`` for ``k`` in stacked row ``d * N + i``: one launch packs the
-    aged activity of all ``depth * N`` stacked rows over the ``T * B`` batch rows (``be_grad_pack_activity_aged``), then
-    ``be_grad_rows`` (``transpose=True``) over the stacked matrix, in ascending ``(t, b)``."""
-    nb = T * B
-    if nb == 0 or N == 0 or r.nse == 0:
-        return torch.zeros_like(w)
-    rows = r.depth * N
-    mask = torch.empty(max(fn('be_grad_mask_bytes')(rows, nb), 4) // 4, dtype=torch.int32, device=w.device)
-    call('be_grad_pack_activity_aged', A.ptr(s), A.ptr(s_hist), N, B, T, r.depth, 0 if s_hist is None else int(s_hist.shape[0]),
-         A.ptr(mask), A.stream_ptr())
-    dw = torch.empty(r.nse, dtype=w.dtype, device=w.device)
-    call('be_grad_rows', 1, A.ptr(dw), 0, A.wcode(dw), A.ptr(r.indices), A.ptr(r.indptr), 0, -1, rows, r.nse, A.ptr(mask), nb,
-         A.ptr(g_x), 1, N, A.ptr(None), 0, A.stream_ptr())
-    return dw.reshape(w.shape)
+class _DenseRec(_Rec):
+    """A :class:`~brainevent_amd.Dense`: the matrix itself, contiguous ``[N, N]`` (no neuron: one unused element), and for two-byte
+    weights — the ``_half_`` entry points — its dtype code; the leaf is ``rec.data``."""
+    no_tensors = ('a Dense recurrence', 'Dense rec')
+
+    def __init__(self, who, rec, n: int, like=None):
+        w = rec.data
+        if w.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"{who}: the weights of rec must be float32, float16 or bfloat16, not {w.dtype}.")
+        if w.ndim != 2:
+            raise ValueError(f"{who}: the data of a Dense rec must be two-dimensional, not {w.ndim}-dimensional.")
+        _limit(who, n, "one workgroup holds a sample's neurons")
+        self.leaf = w
+        self.w = w.detach().contiguous() if w.numel() else torch.zeros(1, dtype=w.dtype, device=w.device)
+        self.half = w.dtype != torch.float32
+        self.forward = 'be_lif_rec_dense_half_sg_forward' if self.half else 'be_lif_rec_dense_sg_forward'
+        self.backward = 'be_lif_rec_dense_half_sg_backward' if self.half else 'be_lif_rec_dense_sg_backward'
+        self.matrix = (A.ptr(self.w), A.wcode(self.w)) if self.half else (A.ptr(self.w),)
+
+    def own_exponent(self, n: int) -> int:    # the exponent of the CSR that stores all N * N entries
+        if n == 0:
+            return 0
+        from ._csr import fixed_point_exponent
+        cols = torch.arange(n, dtype=torch.int32, device=self.leaf.device).repeat(n)
+        return fixed_point_exponent(self.leaf.detach().float().reshape(-1), cols, n)    # (f16 / bf16: the up-converted matrix)
+
+    def weight_grad(self, s, w, s0, g_x, T: int, B: int, N: int) -> torch.Tensor:
+        """``g_W[i, :] = sum over (t, b) with sp[t][b][i] of g_x[t][b][:]``, ``sp = cat(s0, s[:-1])``: ``be_grad_dense`` (the
+        ``transpose=True`` side) over ``T * B`` batch rows — ``(T - 1) * B`` without ``s0``.  For f16 / bf16 weights the sum is the
+        same f32 sum of the f32 ``g_x`` into an f32 ``[N, N]`` temporary, rounded to ``w.dtype`` ONCE: the gradient has the leaf's
+        dtype, as torch requires, and carries one rounding, not ``T * B`` of them."""
+        if s0 is None:
+            sp, g = s[:max(T - 1, 0)], g_x[1:]
+        else:
+            sp, g = torch.cat(((s0 != 0).to(s.dtype)[None], s[:max(T - 1, 0)])), g_x
+        nb = int(sp.shape[0]) * B
+        if T == 0 or N == 0 or nb == 0:
+            return torch.zeros_like(w)
+        mask, _ = _autograd.activity(sp.reshape(nb, N), 'bm')
+        if w.dtype != torch.float32:
+            return _autograd.dense_weight_grad(((N, N), torch.float32), True, mask, nb, g.reshape(nb, N).T).to(w.dtype)
+        return _autograd.dense_weight_grad(w, True, mask, nb, g.reshape(nb, N).T)
 
 
-class DelayedRecurrentLifSequence(torch.autograd.Function):
-    """:class:`RecurrentLifSequence` over a :class:`~brainevent_amd.DelayedCSR`: ``w`` is ``rec.stacked.data`` and ``s0`` the
-    history ``[A, B, N]`` (or None).  Saved: ``h``, ``th`` when adaptive, ``s``, the weights and ``s0``; a None gradient goes in as
-    NULL; the weight gradient is computed only if the weights need one."""
+class _Float8Rec(_Rec):
+    """A :class:`~brainevent_amd.Float8Dense`: the codes, contiguous ``[N, N]`` bytes on the device (no neuron: one unused byte), the
+    format's code and the scale.  The sums are exact integers in the format's own unit, so there is no exponent; the weights are
+    read-only, so there is no leaf (a Float8Dense's codes are not written in place) and no weight gradient."""
+    forward = 'be_lif_rec_dense_f8_sg_forward'
+    backward = 'be_lif_rec_dense_f8_sg_backward'
+    takes_exp, leaf = False, None
+    no_tensors = ('a Float8Dense recurrence', 'Float8Dense rec')
 
-    @staticmethod
-    def forward(ctx, x, c0, v0, a0, s0, w, r: _DelayedRec, dims, p: _Params, e: int, return_v: bool):
-        ctx.set_materialize_grads(False)
-        T, B, N = dims
-        s, v_seq, h, th, c_last, v_last, a_last = _forward_delay(x, r, s0, c0, v0, a0, T, B, N, p, e, return_v, True)
-        ctx.save_for_backward(h, th, s, w, s0)
-        ctx.meta = (r, dims, p, return_v)
-        return tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_s, *rest):
-        r, (T, B, N), p, return_v = ctx.meta
-        g_vseq = rest[0] if return_v else None
-        g_last = list(rest[1:] if return_v else rest) + [None] * (3 - p.entries)
-        if g_s is None and g_vseq is None and all(g is None for g in g_last):
-            return (None,) * 11
-        h, th, s, w, s0 = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        want = [need[1], need[2], bool(p.adaptive) and need[3], need[4]]
-        ages = 0 if s0 is None else int(s0.shape[0])
-        g_x, g_c0, g_v0, g_a0, g_s0 = _backward_delay(h, th, r, _grad_in(g_s), _grad_in(g_vseq), [_grad_in(g) for g in g_last], ages,
-                                                      T, B, N, p, want)
-        g_w = _weight_grad_delay(w, r, s, s0, g_x, T, B, N) if need[5] else None
-        return (g_x if need[0] else None), g_c0, g_v0, g_a0, g_s0, g_w, None, None, None, None, None
-
-
-class _DenseRec:
-    """The weights of a :class:`~brainevent_amd.Dense` as the dense kernels take them: contiguous ``[N, N]`` (no neuron: one unused
-    element, no NULL pointer)."""
-    __slots__ = ('w',)
-
-    def __init__(self, w):
-        self.w = w.contiguous() if w.numel() else torch.zeros(1, dtype=w.dtype, device=w.device)
-
-    @property
-    def half(self) -> bool:
-        return self.w.dtype != torch.float32
-
-    @property
-    def args(self):
-        """The arguments that stand for the matrix: ``w``, and for two-byte weights (the ``_half_`` entry points) the dtype code."""
-        return (A.ptr(self.w), A.wcode(self.w)) if self.half else (A.ptr(self.w),)
-
-
-def _forward_dense(x, r: _DenseRec, s0, c0, v0, a0, T: int, B: int, N: int, p: _Params, e: int, want_v: bool, want_h: bool):
-    """``be_lif_rec_dense_sg_forward`` (f16 / bf16 weights: ``be_lif_rec_dense_half_sg_forward``): :func:`_forward` with the matrix
-    itself."""
-    new = lambda: torch.empty((B, N), dtype=x.dtype, device=x.device)
-    s = torch.empty_like(x)
-    v_seq = torch.empty_like(x) if want_v else None
-    h = torch.empty_like(x) if want_h else None
-    th = torch.empty_like(x) if want_h and p.adaptive else None
-    c_last, v_last, a_last = new(), new(), (new() if p.adaptive else None)
-    if T == 0:                                # no step: the state passes through
-        for out, start in ((c_last, c0), (v_last, v0), (a_last, a0)):
-            if out is not None:
-                out.zero_() if start is None else out.copy_(start)
-    else:
-        name = 'be_lif_rec_dense_half_sg_forward' if r.half else 'be_lif_rec_dense_sg_forward'
-        call(name, A.ptr(x), *r.args, A.ptr(s0), A.ptr(c0), A.ptr(v0), A.ptr(a0), A.ptr(s), A.ptr(v_seq), A.ptr(h), A.ptr(th),
-             A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa, p.reset,
-             p.adaptive, e, A.stream_ptr())
-    return s, v_seq, h, th, c_last, v_last, a_last
-
-
-def _backward_dense(h, th, r: _DenseRec, g_s, g_vseq, g_last, T: int, B: int, N: int, p: _Params, want):
-    """``be_lif_rec_dense_sg_backward`` (f16 / bf16 weights: ``be_lif_rec_dense_half_sg_backward``): ``(g_x, g_c0, g_v0, g_a0,
-    g_s0)``; None as in :func:`_backward`."""
-    g_x = torch.empty_like(h)
-    g_state = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in want]
-    if T == 0:
-        for out, g in zip(g_state[:3], g_last):
-            if out is not None:
-                out.zero_() if g is None else out.copy_(g)
-        if g_state[3] is not None:
-            g_state[3].zero_()
-    else:
-        name = 'be_lif_rec_dense_half_sg_backward' if r.half else 'be_lif_rec_dense_sg_backward'
-        call(name, A.ptr(h), A.ptr(th), *r.args, A.ptr(g_s), A.ptr(g_vseq), A.ptr(g_last[0]), A.ptr(g_last[1]), A.ptr(g_last[2]),
-             A.ptr(g_x), A.ptr(g_state[0]), A.ptr(g_state[1]), A.ptr(g_state[2]), A.ptr(g_state[3]), T, B, N, p.syn_decay, p.beta,
-             p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.surrogate, p.alpha, p.adaptive, p.detach_reset, A.stream_ptr())
-    return (g_x,) + tuple(g_state)
-
-
-def _weight_grad_dense(w, s, s0, g_x, T: int, B: int, N: int) -> torch.Tensor:
-    """``g_W[i, :] = sum over (t, b) with sp[t][b][i] of g_x[t][b][:]``, ``sp = cat(s0, s[:-1])``: ``be_grad_dense`` (the
-    ``transpose=True`` side) over ``T * B`` batch rows — ``(T - 1) * B`` without ``s0``.  For f16 / bf16 weights the sum is the same
-    f32 sum of the f32 ``g_x`` into an f32 ``[N, N]`` temporary, rounded to ``w.dtype`` ONCE: the gradient has the leaf's dtype, as
-    torch requires, and carries one rounding, not ``T * B`` of them."""
-    if s0 is None:
-        sp, g = s[:max(T - 1, 0)], g_x[1:]
-    else:
-        sp, g = torch.cat(((s0 != 0).to(s.dtype)[None], s[:max(T - 1, 0)])), g_x
-    nb = int(sp.shape[0]) * B
-    if T == 0 or N == 0 or nb == 0:
-        return torch.zeros_like(w)
-    mask, _ = _autograd.activity(sp.reshape(nb, N), 'bm')
-    if w.dtype != torch.float32:
-        return _autograd.dense_weight_grad(((N, N), torch.float32), True, mask, nb, g.reshape(nb, N).T).to(w.dtype)
-    return _autograd.dense_weight_grad(w, True, mask, nb, g.reshape(nb, N).T)
-
-
-class DenseRecurrentLifSequence(torch.autograd.Function):
-    """:class:`RecurrentLifSequence` over a :class:`~brainevent_amd.Dense`: ``w`` is ``rec.data`` ``[N, N]``.  Saved: ``h``, ``th``
-    when adaptive, ``s``, the weights and ``s0``; a None gradient goes in as NULL; the weight gradient is computed only if the
-    weights need one."""
-
-    @staticmethod
-    def forward(ctx, x, c0, v0, a0, s0, w, r: _DenseRec, dims, p: _Params, e: int, return_v: bool):
-        ctx.set_materialize_grads(False)
-        T, B, N = dims
-        s, v_seq, h, th, c_last, v_last, a_last = _forward_dense(x, r, s0, c0, v0, a0, T, B, N, p, e, return_v, True)
-        ctx.save_for_backward(h, th, s, w, s0)
-        ctx.meta = (dims, p, return_v)
-        return tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_s, *rest):
-        (T, B, N), p, return_v = ctx.meta
-        g_vseq = rest[0] if return_v else None
-        g_last = list(rest[1:] if return_v else rest) + [None] * (3 - p.entries)
-        if g_s is None and g_vseq is None and all(g is None for g in g_last):
-            return (None,) * 11
-        h, th, s, w, s0 = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        want = [need[1], need[2], bool(p.adaptive) and need[3], need[4]]
-        r = _DenseRec(w.detach())             # the weights as they were at the forward call (autograd checks their version)
-        g_x, g_c0, g_v0, g_a0, g_s0 = _backward_dense(h, th, r, _grad_in(g_s), _grad_in(g_vseq), [_grad_in(g) for g in g_last], T, B,
-                                                      N, p, want)
-        g_w = _weight_grad_dense(w, s, s0, g_x, T, B, N) if need[5] else None
-        return (g_x if need[0] else None), g_c0, g_v0, g_a0, g_s0, g_w, None, None, None, None, None
-
-
-class _Float8Rec:
-    """The codes of a :class:`~brainevent_amd.Float8Dense` as the FP8 kernels take them: contiguous ``[N, N]`` bytes on the device (no
-    neuron: one unused byte, no NULL pointer), the format's code and the scale."""
-    __slots__ = ('codes', 'fmt_code', 'scale')
-
-    def __init__(self, rec):
+    def __init__(self, who, rec, n: int, like=None):      # codes [N, N] and one scale; the constructor has refused non-finite codes
         from ._dense_f8 import _CODE_OF_FMT
+        _limit(who, n, "one workgroup holds a sample's neurons")
         c = rec._device_codes()
+        if like is not None and c.device != like.device:
+            raise ValueError(f"{who}: the codes of rec are on {c.device}, x is on {like.device}: they must share a device.")
         self.codes = c.contiguous() if c.numel() else torch.zeros(1, dtype=torch.uint8, device=c.device)
-        self.fmt_code, self.scale = _CODE_OF_FMT[rec.fmt], float(rec.scale)
+        self.matrix = (A.ptr(self.codes), _CODE_OF_FMT[rec.fmt], float(rec.scale))
 
-    @property
-    def args(self):
-        return A.ptr(self.codes), self.fmt_code, self.scale
-
-
-def _forward_dense_f8(x, r: _Float8Rec, s0, c0, v0, a0, T: int, B: int, N: int, p: _Params, e, want_v: bool, want_h: bool):
-    """``be_lif_rec_dense_f8_sg_forward``: :func:`_forward_dense` with the codes, the format and the scale; ``e`` is unused (the
-    sums are exact integers in the format's own unit: the call has no exponent)."""
-    new = lambda: torch.empty((B, N), dtype=x.dtype, device=x.device)
-    s = torch.empty_like(x)
-    v_seq = torch.empty_like(x) if want_v else None
-    h = torch.empty_like(x) if want_h else None
-    th = torch.empty_like(x) if want_h and p.adaptive else None
-    c_last, v_last, a_last = new(), new(), (new() if p.adaptive else None)
-    if T == 0:                                # no step: the state passes through
-        for out, start in ((c_last, c0), (v_last, v0), (a_last, a0)):
-            if out is not None:
-                out.zero_() if start is None else out.copy_(start)
-    else:
-        call('be_lif_rec_dense_f8_sg_forward', A.ptr(x), *r.args, A.ptr(s0), A.ptr(c0), A.ptr(v0), A.ptr(a0), A.ptr(s), A.ptr(v_seq),
-             A.ptr(h), A.ptr(th), A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho,
-             p.kappa, p.reset, p.adaptive, A.stream_ptr())
-    return s, v_seq, h, th, c_last, v_last, a_last
+    def exponent(self, who, scale_exp, n: int) -> int:    # nothing to ask for, nothing to give
+        if scale_exp is not None:
+            raise ValueError(f"{who}: scale_exp must be None with a Float8Dense rec: its recurrent sums are exact integers in the "
+                             f"format's own unit (2^-9 for e4m3, 2^-16 for e5m2) and take no exponent.")
+        return 0
 
 
-def _backward_dense_f8(h, th, r: _Float8Rec, g_s, g_vseq, g_last, T: int, B: int, N: int, p: _Params, want):
-    """``be_lif_rec_dense_f8_sg_backward``: ``(g_x, g_c0, g_v0, g_a0, g_s0)``; None as in :func:`_backward`."""
-    g_x = torch.empty_like(h)
-    g_state = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in want]
-    if T == 0:
-        for out, g in zip(g_state[:3], g_last):
-            if out is not None:
-                out.zero_() if g is None else out.copy_(g)
-        if g_state[3] is not None:
-            g_state[3].zero_()
-    else:
-        call('be_lif_rec_dense_f8_sg_backward', A.ptr(h), A.ptr(th), *r.args, A.ptr(g_s), A.ptr(g_vseq), A.ptr(g_last[0]),
-             A.ptr(g_last[1]), A.ptr(g_last[2]), A.ptr(g_x), A.ptr(g_state[0]), A.ptr(g_state[1]), A.ptr(g_state[2]), A.ptr(g_state[3]),
-             T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.surrogate, p.alpha, p.adaptive,
-             p.detach_reset, A.stream_ptr())
-    return (g_x,) + tuple(g_state)
-
-
-class Float8RecurrentLifSequence(torch.autograd.Function):
-    """:class:`DenseRecurrentLifSequence` over a :class:`~brainevent_amd.Float8Dense`: the weights are read-only, so they are neither
-    a differentiable input nor saved — ``r`` holds the codes (a Float8Dense's codes are not written in place).  Saved: ``h`` and
-    ``th`` when adaptive; a None gradient goes in as NULL."""
-
-    @staticmethod
-    def forward(ctx, x, c0, v0, a0, s0, r: _Float8Rec, dims, p: _Params, return_v: bool):
-        ctx.set_materialize_grads(False)
-        T, B, N = dims
-        s, v_seq, h, th, c_last, v_last, a_last = _forward_dense_f8(x, r, s0, c0, v0, a0, T, B, N, p, None, return_v, True)
-        ctx.save_for_backward(h, th)
-        ctx.meta = (r, dims, p, return_v)
-        return tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_s, *rest):
-        r, (T, B, N), p, return_v = ctx.meta
-        g_vseq = rest[0] if return_v else None
-        g_last = list(rest[1:] if return_v else rest) + [None] * (3 - p.entries)
-        if g_s is None and g_vseq is None and all(g is None for g in g_last):
-            return (None,) * 9
-        h, th = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        want = [need[1], need[2], bool(p.adaptive) and need[3], need[4]]
-        g_x, g_c0, g_v0, g_a0, g_s0 = _backward_dense_f8(h, th, r, _grad_in(g_s), _grad_in(g_vseq), [_grad_in(g) for g in g_last], T,
-                                                         B, N, p, want)
-        return (g_x if need[0] else None), g_c0, g_v0, g_a0, g_s0, None, None, None, None
-
-
-def _is_delayed(rec) -> bool:
-    from ._delay import DelayedCSR
-    return isinstance(rec, DelayedCSR)
-
-
-def _is_dense(rec) -> bool:
-    from ._dense import Dense
-    return isinstance(rec, Dense)
-
-
-def _is_float8(rec) -> bool:
-    from ._dense_f8 import Float8Dense
-    return isinstance(rec, Float8Dense)
-
-
-def _check_rec(who, rec, n: int, like=None):
+def _family(rec):
+    """The adapter class of ``rec``'s family, or None."""
     from ._csr import CSR
-    delayed, dense = _is_delayed(rec), _is_dense(rec)
-    if _is_float8(rec):                       # codes [N, N] and one scale; the constructor has refused non-finite codes
-        if rec.shape[0] != rec.shape[1]:
-            raise ValueError(f"{who}: rec {tuple(rec.shape)} must be square (a recurrent projection).")
-        if rec.shape[0] != n:
-            raise ValueError(f"{who}: rec {tuple(rec.shape)} must have the size of x's last axis, {n}.")
-        if n > MAX_N:
-            raise ValueError(f"{who}: {n} neurons; the limit is {MAX_N} (one workgroup holds a sample's neurons).")
-        codes = rec._device_codes()
-        if like is not None and codes.device != like.device:
-            raise ValueError(f"{who}: the codes of rec are on {codes.device}, x is on {like.device}: they must share a device.")
-        return
-    if not delayed and not dense and not isinstance(rec, CSR):
+    from ._delay import DelayedCSR
+    from ._dense import Dense
+    from ._dense_f8 import Float8Dense
+    for container, adapter in ((Float8Dense, _Float8Rec), (DelayedCSR, _DelayedRec), (Dense, _DenseRec), (CSR, _Rec)):
+        if isinstance(rec, container):
+            return adapter
+    return None
+
+
+def _recurrence(who, rec, n: int, like=None) -> _Rec:
+    """``rec`` classified, once, and checked: its family's adapter."""
+    adapter = _family(rec)
+    if adapter is None:
         raise TypeError(f"{who}: rec must be a CSR matrix (rows = presynaptic neurons), a DelayedCSR or a Dense, not "
                         f"{type(rec).__name__}; CSC, fixed-number, JITC and planned matrices are not built.")
     if rec.shape[0] != rec.shape[1]:
         raise ValueError(f"{who}: rec {tuple(rec.shape)} must be square (a recurrent projection).")
     if rec.shape[0] != n:
         raise ValueError(f"{who}: rec {tuple(rec.shape)} must have the size of x's last axis, {n}.")
-    if dense:                                 # one [N, N] array, nothing else to check
-        if rec.data.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise TypeError(f"{who}: the weights of rec must be float32, float16 or bfloat16, not {rec.data.dtype}.")
-        if rec.data.ndim != 2:
-            raise ValueError(f"{who}: the data of a Dense rec must be two-dimensional, not {rec.data.ndim}-dimensional.")
-        if n > MAX_N:
-            raise ValueError(f"{who}: {n} neurons; the limit is {MAX_N} (one workgroup holds a sample's neurons).")
-        return
-    m = rec.stacked if delayed else rec       # with delays the kernels read the stacked arrays
-    if m.data.dtype != torch.float32:
-        raise TypeError(f"{who}: the weights of rec must be float32, not {m.data.dtype}.")
-    nse = int(m.indices.numel())
-    if m.data.numel() != nse:
-        raise ValueError(f"{who}: rec must hold one weight per stored entry ({nse}), not {m.data.numel()} (one shared weight is not "
-                         f"built).")
-    if m.indptr.dtype != torch.int32:
-        raise TypeError(f"{who}: the indptr of rec must be int32, not {m.indptr.dtype}" +
-                        (" (a DelayedCSR built from an int64 indptr, or with 2^31 entries or more, is not built)." if delayed else "."))
-    if n > MAX_N:
-        raise ValueError(f"{who}: {n} neurons; the limit is {MAX_N} (one sample's sums and spike ids live in one workgroup's LDS).")
-    if delayed and not delay_fits(n, int(rec.depth)):
-        raise ValueError(f"{who}: {n} neurons at depth {int(rec.depth)} do not fit: with delays 8 * N + 8 * depth * ceil(N / 64) + "
-                         f"{4 * DELAY_MIN_IDS} must stay within {DELAY_LDS_BYTES} bytes (one sample's sums, its spike history and a "
-                         f"list of active rows live in one workgroup's LDS; every N <= 8192 fits at depth <= 16, every N <= 2048 at "
-                         f"depth <= {MAX_DEPTH}); a sample split over several workgroups is not built.")
+    return adapter(who, rec, n, like)
 
 
 def _scale_exp(who, scale_exp, rec, n: int) -> int:
-    if _is_float8(rec):                       # exact integer sums in the format's own unit: nothing to ask for, nothing to give
-        if scale_exp is not None:
-            raise ValueError(f"{who}: scale_exp must be None with a Float8Dense rec: its recurrent sums are exact integers in the "
-                             f"format's own unit (2^-9 for e4m3, 2^-16 for e5m2) and take no exponent.")
-        return 0
-    if scale_exp is None and _is_dense(rec):  # the exponent of the CSR that stores all N * N entries
-        if n == 0:
-            return 0
-        from ._csr import fixed_point_exponent
-        cols = torch.arange(n, dtype=torch.int32, device=rec.data.device).repeat(n)
-        return fixed_point_exponent(rec.data.detach().float().reshape(-1), cols, n)     # (f16 / bf16: the up-converted matrix)
-    if scale_exp is None:
-        m = rec.stacked if _is_delayed(rec) else rec      # (the stacked matrix has the same columns: every stacked row active)
-        if m.indices.numel() == 0 or n == 0:
-            return 0
-        from ._csr import fixed_point_exponent
-        return fixed_point_exponent(m.data.detach(), m.indices, n)
-    if isinstance(scale_exp, bool) or not isinstance(scale_exp, numbers.Integral):
-        raise TypeError(f"{who}: scale_exp must be None or an int, not {type(scale_exp).__name__}.")
-    if not SCALE_EXP_RANGE[0] <= scale_exp <= SCALE_EXP_RANGE[1]:
-        raise ValueError(f"{who}: scale_exp {scale_exp} is outside {SCALE_EXP_RANGE[0]} .. {SCALE_EXP_RANGE[1]}, the exponents "
-                         f"fixed_point_exponent returns.")
-    return int(scale_exp)
+    """The exponent the calls on ``rec`` take: ``scale_exp`` checked, or for None the family's own."""
+    return _recurrence(who, rec, n).exponent(who, scale_exp, n)
+
+
+def _forward(x, r: _Rec, s0, c0, v0, a0, T: int, B: int, N: int, p: _Params, e: int, want_v: bool, want_h: bool):
+    """The family's forward entry point on contiguous ``x [T, B, N]``: ``(s, v_seq, h, th, c_last, v_last, a_last)``; what was not
+    asked for (and, without adaptation, ``th`` / ``a_last``) is None and neither allocated nor written.  ``s0`` is ``[B, N]``, with
+    delays ``[ages, B, N]``, or None."""
+    outs = _new_outputs(x, (B, N), (c0, v0, a0), T, p, (want_v, want_h, want_h and p.adaptive))
+    if T != 0:
+        s, v_seq, h, th, c_last, v_last, a_last = outs
+        call(r.forward, A.ptr(x), *r.matrix, *r.s0_args(s0), A.ptr(c0), A.ptr(v0), A.ptr(a0), A.ptr(s), A.ptr(v_seq), A.ptr(h),
+             A.ptr(th), A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N, p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa,
+             p.reset, p.adaptive, *((e,) if r.takes_exp else ()), A.stream_ptr())
+    return outs
+
+
+def _backward(h, th, r: _Rec, g_s, g_vseq, g_last, T: int, B: int, N: int, p: _Params, want):
+    """The family's backward entry point: ``(g_x, g_c0, g_v0, g_a0, g_s0)``, the last in ``s0``'s shape.  A gradient that is None
+    goes in as NULL; a state or ``s0`` gradient is None unless ``want`` asks for it."""
+    shapes = [(B, N) if k else None for k in want[:3]] + [r.s0_shape(B, N) if want[3] else None]
+    g_x, g_c0, g_v0, g_a0, g_s0 = grads = _new_grads(h, shapes, g_last, T == 0)
+    if T != 0:
+        call(r.backward, A.ptr(h), A.ptr(th), *r.matrix, A.ptr(g_s), A.ptr(g_vseq), A.ptr(g_last[0]), A.ptr(g_last[1]),
+             A.ptr(g_last[2]), A.ptr(g_x), A.ptr(g_c0), A.ptr(g_v0), A.ptr(g_a0), *r.s0_args(g_s0), T, B, N, p.syn_decay, p.beta,
+             p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.surrogate, p.alpha, p.adaptive, p.detach_reset, A.stream_ptr())
+    return grads
+
+
+def _grads_in(ctx, g_s, rest):
+    """The prologue both Functions' ``backward`` share: None if no output's gradient arrived; else what was saved, ``needs_input_grad``,
+    which state and ``s0`` gradients are wanted, and the arrived gradients contiguous — ``g_s``, ``g_vseq``, ``g_last`` (three entries)."""
+    p, return_v = ctx.meta[2:]
+    g_vseq = rest[0] if return_v else None
+    g_last = list(rest[1:] if return_v else rest) + [None] * (3 - p.entries)
+    if g_s is None and g_vseq is None and all(g is None for g in g_last):
+        return None
+    saved, need = ctx.saved_tensors, ctx.needs_input_grad
+    want = [need[1], need[2], bool(p.adaptive) and need[3], need[4]]
+    return saved, need, want, _grad_in(g_s), _grad_in(g_vseq), [_grad_in(g) for g in g_last]
+
+
+class RecurrentLifSequence(torch.autograd.Function):
+    """Every family's Function.  Outputs ``s, [v_seq,] c_last, v_last [, a_last]``; ``w`` is the adapter's leaf and ``s0`` as the
+    kernels take it.  Saved: ``h``, ``th`` when adaptive and, where there is a leaf (all but FP8 weights), ``s`` (the weight
+    gradient's activity), the weights and ``s0``.  The gradient of an output nobody used arrives as None
+    (``set_materialize_grads(False)``) and goes in as NULL; the weight gradient is computed only if the weights need one."""
+
+    @staticmethod
+    def forward(ctx, x, c0, v0, a0, s0, w, r: _Rec, dims, p: _Params, e: int, return_v: bool):
+        ctx.set_materialize_grads(False)
+        T, B, N = dims
+        s, v_seq, h, th, c_last, v_last, a_last = _forward(x, r, s0, c0, v0, a0, T, B, N, p, e, return_v, True)
+        ctx.save_for_backward(*((h, th) if w is None else (h, th, s, w, s0)))
+        ctx.meta = (r, dims, p, return_v)
+        return tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_s, *rest):
+        grads = _grads_in(ctx, g_s, rest)
+        if grads is None:
+            return (None,) * 11
+        (h, th, *kept), need, want, g_s, g_vseq, g_last = grads
+        r, (T, B, N), p, _ = ctx.meta
+        g_x, g_c0, g_v0, g_a0, g_s0 = _backward(h, th, r, g_s, g_vseq, g_last, T, B, N, p, want)
+        g_w = r.weight_grad(*kept, g_x, T, B, N) if need[5] else None
+        return (g_x if need[0] else None), g_c0, g_v0, g_a0, g_s0, g_w, None, None, None, None, None
 
 
 def recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Sequence[Optional[torch.Tensor]]] = None,
@@ -640,68 +445,38 @@ def recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Sequence[Optio
     work)."""
     who = 'recurrent_lif_sequence'
     p = _Params(who, syn_decay, beta, v_th, v_reset, reset, surrogate, alpha, detach_reset, adapt)
-    (T, B, N), slots, x3, (c0, v0, a0, sp), e = _prepare(who, x, rec, state0, s0, p, scale_exp)
+    r, (T, B, N), slots, x3, (c0, v0, a0, sp), e = _prepare(who, x, rec, state0, s0, p, scale_exp)
     return_v = bool(return_v)
-    if _is_float8(rec):                       # read-only codes: no weights among the differentiable inputs
-        r = _Float8Rec(rec)
-        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x3, c0, v0, a0, sp)):
-            outs = Float8RecurrentLifSequence.apply(x3, c0, v0, a0, sp, r, (T, B, N), p, return_v)
-        else:                                 # no backward pass: h / th are not kept
-            s, v_seq, _, _, c_last, v_last, a_last = _forward_dense_f8(x3, r, sp, c0, v0, a0, T, B, N, p, None, return_v, False)
-            outs = tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
-        return _shaped(outs, x, slots, return_v)
-    if _is_delayed(rec):                      # the stacked matrix, a history [A, B, N]
-        w = rec.stacked.data
-        r = _DelayedRec(w.detach(), rec)
-        function, forward = DelayedRecurrentLifSequence, _forward_delay
-    elif _is_dense(rec):                      # the matrix itself
-        w = rec.data
-        r = _DenseRec(w.detach())
-        function, forward = DenseRecurrentLifSequence, _forward_dense
-    else:
-        w = rec.data
-        r = _Rec(w.detach(), rec.indices, rec.indptr)
-        function, forward = RecurrentLifSequence, _forward
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x3, c0, v0, a0, sp, w)):
-        outs = function.apply(x3, c0, v0, a0, sp, w, r, (T, B, N), p, e, return_v)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x3, c0, v0, a0, sp, r.leaf)):
+        outs = RecurrentLifSequence.apply(x3, c0, v0, a0, sp, r.leaf, r, (T, B, N), p, e, return_v)
     else:                                     # no backward pass: h / th are not kept
-        s, v_seq, _, _, c_last, v_last, a_last = forward(x3, r, sp, c0, v0, a0, T, B, N, p, e, return_v, False)
+        s, v_seq, _, _, c_last, v_last, a_last = _forward(x3, r, sp, c0, v0, a0, T, B, N, p, e, return_v, False)
         outs = tuple(o for o in (s, v_seq, c_last, v_last, a_last) if o is not None)
     return _shaped(outs, x, slots, return_v)
 
 
 def _prepare(who, x, rec, state0, s0, p: _Params, scale_exp):
-    """The checks and layouts both functions share: ``(T, B, N)``, the shape of a step, contiguous ``x [T, B, N]``, the state entries
-    and ``s0`` as ``[B, N]`` (or None), and the exponent."""
+    """The checks and layouts both functions share: the adapter of ``rec``, ``(T, B, N)``, the shape of a step, contiguous
+    ``x [T, B, N]``, the state entries and ``s0`` as the kernels take them (``[B, N]``, with delays ``[ages, B, N]``; or None), and the
+    exponent."""
     _check_tensor(who, 'x', x)
     if x.ndim not in (2, 3):
         raise ValueError(f"{who}: x must be [T, B, N] or [T, N], not {x.ndim}-dimensional.")
     slots = tuple(x.shape[1:])
     T, N = int(x.shape[0]), int(x.shape[-1])
     B = int(x.shape[1]) if x.ndim == 3 else 1
-    _check_rec(who, rec, N, x)
+    r = _recurrence(who, rec, N, x)
     state = _check_state(who, 'state0', state0, p, slots, allow_none=True)
-    ages = None                               # with delays: the past steps s0 holds
     if s0 is not None:
         _check_tensor(who, 's0', s0)
-        if _is_delayed(rec):
-            depth = int(rec.depth)
-            if tuple(s0.shape) == slots:
-                ages = 1
-            elif s0.ndim == len(slots) + 1 and tuple(s0.shape[1:]) == slots and 1 <= s0.shape[0] <= depth:
-                ages = int(s0.shape[0])
-            else:
-                raise ValueError(f"{who}: s0 {tuple(s0.shape)} must have the shape of a step of x, {slots}, or hold A past steps, "
-                                 f"(A,) + {slots} with 1 <= A <= depth = {depth} (s0[a]: the spikes a + 1 steps before step 0).")
-        elif tuple(s0.shape) != slots:
-            raise ValueError(f"{who}: s0 {tuple(s0.shape)} must have the shape of a step of x, {slots}.")
+        r.check_s0(who, s0, slots)
     _check_device(who, x=x, s0=s0, **{f'state0 entry {k}': t for k, t in zip('cva', state)})
-    e = _scale_exp(who, scale_exp, rec, N)
+    e = r.exponent(who, scale_exp, N)
     x3 = x.contiguous().reshape(T, B, N)
     start = tuple(None if t is None else t.contiguous().reshape(B, N) for t in state)
     if s0 is not None:
-        s0 = s0.contiguous().reshape((B, N) if ages is None else (ages, B, N))
-    return (T, B, N), slots, x3, start + (s0,), e
+        s0 = s0.contiguous().reshape(r.s0_shape(B, N))
+    return r, (T, B, N), slots, x3, start + (s0,), e
 
 
 def _shaped(outs, x, slots, return_v: bool):
@@ -715,30 +490,21 @@ def _forward_params(x, r: _Rec, s0, c0, v0, a0, params, T: int, B: int, N: int, 
     """``be_lif_rec_sg_forward_params``: :func:`_forward` with the five parameters contiguous f32 device tensors (``rho`` / ``kappa``
     None without adaptation; a period is the element count): ``(s, v_seq, h, c_save, a_save, c_last, v_last, a_last)``.  ``a_save`` —
     the trace every step started from — is kept beside ``h`` when adaptive, ``c_save`` only when asked for."""
-    new = lambda: torch.empty((B, N), dtype=x.dtype, device=x.device)
-    s = torch.empty_like(x)
-    v_seq = torch.empty_like(x) if want_v else None
-    h = torch.empty_like(x) if want_h else None
-    c_save = torch.empty_like(x) if want_c else None
-    a_save = torch.empty_like(x) if want_h and p.adaptive else None
-    c_last, v_last, a_last = new(), new(), (new() if p.adaptive else None)
-    if T == 0:                                # no step: the state passes through
-        for out, start in ((c_last, c0), (v_last, v0), (a_last, a0)):
-            if out is not None:
-                out.zero_() if start is None else out.copy_(start)
-    elif B * N > 0:
-        call('be_lif_rec_sg_forward_params', A.ptr(x), A.ptr(r.w), A.ptr(r.indices), A.ptr(r.indptr), A.ptr(s0), A.ptr(c0), A.ptr(v0),
-             A.ptr(a0), *(v for t in params for v in (A.ptr(t), 1 if t is None else t.numel())), A.ptr(s), A.ptr(v_seq), A.ptr(h),
+    outs = _new_outputs(x, (B, N), (c0, v0, a0), T, p, (want_v, want_h, want_c, want_h and p.adaptive))
+    if T != 0 and B * N > 0:
+        s, v_seq, h, c_save, a_save, c_last, v_last, a_last = outs
+        call('be_lif_rec_sg_forward_params', A.ptr(x), *r.matrix, A.ptr(s0), A.ptr(c0), A.ptr(v0), A.ptr(a0),
+             *(v for t in params for v in (A.ptr(t), 1 if t is None else t.numel())), A.ptr(s), A.ptr(v_seq), A.ptr(h),
              A.ptr(c_save), A.ptr(a_save), A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, B, N, p.v_reset, p.reset, p.adaptive, e,
              A.stream_ptr())
-    return s, v_seq, h, c_save, a_save, c_last, v_last, a_last
+    return outs
 
 
 class RecurrentLifSequenceParams(torch.autograd.Function):
-    """:class:`RecurrentLifSequence` with the five parameters as device tensors that may require grad.  Saved: ``h``, ``a_save``
-    in ``th``'s place when adaptive, ``s``, the weights, ``s0``, the parameters, ``c_save`` only if ``syn_decay`` needs a gradient,
-    and ``c0`` / ``v0`` only for the gradient of ``syn_decay`` / ``beta`` (what the first step started from).  A parameter that does
-    not need a gradient has its ``[B, N]`` accumulator go in as NULL."""
+    """:class:`RecurrentLifSequence` over a CSR with the five parameters as device tensors that may require grad.  Saved: ``h``,
+    ``a_save`` in ``th``'s place when adaptive, ``s``, the weights, ``s0``, the parameters, ``c_save`` only if ``syn_decay`` needs a
+    gradient, and ``c0`` / ``v0`` only for the gradient of ``syn_decay`` / ``beta`` (what the first step started from).  A parameter
+    that does not need a gradient has its ``[B, N]`` accumulator go in as NULL."""
 
     @staticmethod
     def forward(ctx, x, c0, v0, a0, s0, w, syn_decay, beta, v_th, rho, kappa, r: _Rec, dims, p: _Params, e: int, return_v: bool):
@@ -755,34 +521,25 @@ class RecurrentLifSequenceParams(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_s, *rest):
-        r, (T, B, N), p, return_v = ctx.meta
-        g_vseq = rest[0] if return_v else None
-        g_last = list(rest[1:] if return_v else rest) + [None] * (3 - p.entries)
-        if g_s is None and g_vseq is None and all(g is None for g in g_last):
+        grads = _grads_in(ctx, g_s, rest)
+        if grads is None:
             return (None,) * 16
-        h, a_save, s, w, s0, c_save, *params, c0, v0 = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        want = [need[1], need[2], bool(p.adaptive) and need[3], need[4]]
+        (h, a_save, s, w, s0, c_save, *params, c0, v0), need, want, g_s, g_vseq, g_last = grads
+        r, (T, B, N), p, _ = ctx.meta
         need_p = [need[6 + k] and params[k] is not None for k in range(5)]
-        g_s, g_vseq, g_last = _grad_in(g_s), _grad_in(g_vseq), [_grad_in(g) for g in g_last]
-        g_x = torch.empty_like(h)
-        g_state = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in want]
-        if T == 0 or B * N == 0:              # no step: the state's gradient passes through, the parameters were not used
-            for out, g in zip(g_state[:3], g_last):
-                if out is not None:
-                    out.zero_() if g is None else out.copy_(g)
-            if g_state[3] is not None:
-                g_state[3].zero_()
+        no_step = T == 0 or B * N == 0        # the state's gradient passes through, the parameters were not used
+        g_x, *g_state = _new_grads(h, [(B, N) if k else None for k in want], g_last, no_step)
+        if no_step:
             g_params = [torch.zeros_like(t) if k else None for t, k in zip(params, need_p)]
         else:
             slot = [torch.empty((B, N), dtype=h.dtype, device=h.device) if k else None for k in need_p]
-            call('be_lif_rec_sg_backward_params', A.ptr(h), A.ptr(c_save), A.ptr(a_save), A.ptr(c0), A.ptr(v0), A.ptr(r.w),
-                 A.ptr(r.indices), A.ptr(r.indptr), A.ptr(g_s), A.ptr(g_vseq), A.ptr(g_last[0]), A.ptr(g_last[1]), A.ptr(g_last[2]),
-                 *(v for t in params for v in (A.ptr(t), 1 if t is None else t.numel())), A.ptr(g_x), A.ptr(g_state[0]),
-                 A.ptr(g_state[1]), A.ptr(g_state[2]), A.ptr(g_state[3]), *(A.ptr(t) for t in slot), T, B, N, p.v_reset, p.reset,
-                 p.surrogate, p.alpha, p.adaptive, p.detach_reset, A.stream_ptr())
+            call('be_lif_rec_sg_backward_params', A.ptr(h), A.ptr(c_save), A.ptr(a_save), A.ptr(c0), A.ptr(v0), *r.matrix, A.ptr(g_s),
+                 A.ptr(g_vseq), A.ptr(g_last[0]), A.ptr(g_last[1]), A.ptr(g_last[2]),
+                 *(v for t in params for v in (A.ptr(t), 1 if t is None else t.numel())), A.ptr(g_x), *(A.ptr(g) for g in g_state),
+                 *(A.ptr(t) for t in slot), T, B, N, p.v_reset, p.reset, p.surrogate, p.alpha, p.adaptive, p.detach_reset,
+                 A.stream_ptr())
             g_params = [_reduce_slots(sl.reshape(-1), t) if k else None for sl, t, k in zip(slot, params, need_p)]
-        g_w = _weight_grad(w, r, s, s0, g_x, T, B, N) if need[5] else None
+        g_w = r.weight_grad(s, w, s0, g_x, T, B, N) if need[5] else None
         return ((g_x if need[0] else None), *g_state, g_w, *g_params, None, None, None, None, None)
 
 
@@ -831,25 +588,18 @@ def parametric_recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Seq
         return recurrent_lif_sequence(x, rec, state0, s0, syn_decay=syn_decay, beta=beta, v_th=v_th, v_reset=v_reset, reset=reset,
                                       surrogate=surrogate, alpha=alpha, detach_reset=detach_reset, adapt=adapt, return_v=return_v,
                                       scale_exp=scale_exp)
-    if _is_dense(rec):
-        raise NotImplementedError(f"{who}: learnable (tensor) neuron parameters together with a Dense recurrence are not built: a "
-                                  f"Dense rec takes syn_decay, beta, v_th and adapt as Python numbers (recurrent_lif_sequence).")
-    if _is_float8(rec):
-        raise NotImplementedError(f"{who}: learnable (tensor) neuron parameters together with a Float8Dense recurrence are not "
-                                  f"built: a Float8Dense rec takes syn_decay, beta, v_th and adapt as Python numbers "
-                                  f"(recurrent_lif_sequence).")
-    if _is_delayed(rec):
-        raise NotImplementedError(f"{who}: learnable (tensor) neuron parameters together with synaptic delays are not built: a "
-                                  f"DelayedCSR takes syn_decay, beta, v_th and adapt as Python numbers (recurrent_lif_sequence).")
+    adapter = _family(rec)
+    if adapter is not None and adapter.no_tensors is not None:
+        what, which = adapter.no_tensors
+        raise NotImplementedError(f"{who}: learnable (tensor) neuron parameters together with {what} are not built: a {which} "
+                                  f"takes syn_decay, beta, v_th and adapt as Python numbers (recurrent_lif_sequence).")
     p = _Params(who, stand_in[0], stand_in[1], stand_in[2], v_reset, reset, surrogate, alpha, detach_reset,
                 None if adapt is None else (stand_in[3], stand_in[4]), FIVE_TENSORS)
-    (T, B, N), slots, x3, (c0, v0, a0, sp), e = _prepare(who, x, rec, state0, s0, p, scale_exp)
+    r, (T, B, N), slots, x3, (c0, v0, a0, sp), e = _prepare(who, x, rec, state0, s0, p, scale_exp)
     params = _layer_params(who, given, x, N, p.adaptive)
-    w = rec.data
-    r = _Rec(w.detach(), rec.indices, rec.indptr)
     return_v = bool(return_v)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x3, c0, v0, a0, sp, w, *params)):
-        outs = RecurrentLifSequenceParams.apply(x3, c0, v0, a0, sp, w, *params, r, (T, B, N), p, e, return_v)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x3, c0, v0, a0, sp, r.leaf, *params)):
+        outs = RecurrentLifSequenceParams.apply(x3, c0, v0, a0, sp, r.leaf, *params, r, (T, B, N), p, e, return_v)
     else:                                     # no backward pass: nothing is kept
         s, v_seq, _, _, _, c_last, v_last, a_last = _forward_params(x3, r, sp, c0, v0, a0, params, T, B, N, p, e, return_v, False,
                                                                     False)

@@ -79,37 +79,50 @@ class _Params:
         return 3 if self.adaptive else 2
 
 
+def _new_outputs(x, slots, start, T: int, p: _Params, want):
+    """The outputs of a forward launch on ``x``, in the order they are allocated: ``s``, one ``empty_like(x)`` per true entry of
+    ``want`` (None for a false one), and ``c_last, v_last, a_last`` (``slots``; ``a_last`` None without adaptation).  ``T == 0``, no
+    step: the state ``start = (c0, v0, a0)`` passes through (a None entry: zeros) and nothing is left for a launch to write."""
+    seq = [torch.empty_like(x)] + [torch.empty_like(x) if k else None for k in want]
+    last = [torch.empty(slots, dtype=x.dtype, device=x.device) if k else None for k in (True, True, p.adaptive)]
+    if T == 0:
+        for out, given in zip(last, start):
+            if out is not None:
+                out.zero_() if given is None else out.copy_(given)
+    return (*seq, *last)
+
+
+def _new_grads(h, shapes, g_last, no_step: bool):
+    """The outputs of a backward launch: ``g_x`` and one gradient per entry of ``shapes`` (None: not wanted, no tensor) — the state's,
+    then whatever else the step started from (the recurrent layer's ``s0``).  ``no_step``: a state entry's gradient is the one that
+    arrived for it in ``g_last`` (None: zeros), any later entry's is zero, and nothing is left for a launch to write."""
+    g_x = torch.empty_like(h)
+    g_in = [None if shape is None else torch.empty(shape, dtype=h.dtype, device=h.device) for shape in shapes]
+    if no_step:
+        for out, g in zip(g_in, list(g_last) + [None] * (len(g_in) - len(g_last))):
+            if out is not None:
+                out.zero_() if g is None else out.copy_(g)
+    return [g_x] + g_in
+
+
 def _forward(x, c0, v0, a0, T: int, slots: Tuple[int, ...], p: _Params, want_v: bool, want_h: bool):
     """``be_lif_syn_sg_forward`` on contiguous ``x`` (``T`` rows of ``slots``) and a state whose entries are ``slots`` or None:
     ``(s, v_seq, h, th, c_last, v_last, a_last)``; what was not asked for (and, without adaptation, ``th`` / ``a_last``) is None
     and neither allocated nor written."""
-    new = lambda: torch.empty(slots, dtype=x.dtype, device=x.device)
-    s = torch.empty_like(x)
-    v_seq = torch.empty_like(x) if want_v else None
-    h = torch.empty_like(x) if want_h else None
-    th = torch.empty_like(x) if want_h and p.adaptive else None
-    c_last, v_last, a_last = new(), new(), (new() if p.adaptive else None)
-    if T == 0:                                # no step: the state passes through
-        for out, start in ((c_last, c0), (v_last, v0), (a_last, a0)):
-            if out is not None:
-                out.zero_() if start is None else out.copy_(start)
-    else:
+    outs = _new_outputs(x, slots, (c0, v0, a0), T, p, (want_v, want_h, want_h and p.adaptive))
+    if T != 0:
+        s, v_seq, h, th, c_last, v_last, a_last = outs
         call('be_lif_syn_sg_forward', A.ptr(x), A.ptr(c0), A.ptr(v0), A.ptr(a0), A.ptr(s), A.ptr(v_seq), A.ptr(h), A.ptr(th),
              A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, _numel(slots), p.syn_decay, p.beta, p.v_th, p.v_reset, p.rho, p.kappa,
              p.reset, p.adaptive, A.stream_ptr())
-    return s, v_seq, h, th, c_last, v_last, a_last
+    return outs
 
 
 def _backward(h, th, g_s, g_vseq, g_last, T: int, slots: Tuple[int, ...], p: _Params, want):
     """``be_lif_syn_sg_backward``: ``(g_x, g_c0, g_v0, g_a0)``.  A gradient that is None goes in as NULL; a state gradient is None
     unless ``want`` asks for it."""
-    g_x = torch.empty_like(h)
-    g_state = [torch.empty(slots, dtype=h.dtype, device=h.device) if w else None for w in want]
-    if T == 0:
-        for out, g in zip(g_state, g_last):
-            if out is not None:
-                out.zero_() if g is None else out.copy_(g)
-    else:
+    g_x, *g_state = _new_grads(h, [slots if w else None for w in want], g_last, T == 0)
+    if T != 0:
         call('be_lif_syn_sg_backward', A.ptr(h), A.ptr(th), A.ptr(g_s), A.ptr(g_vseq), A.ptr(g_last[0]), A.ptr(g_last[1]),
              A.ptr(g_last[2]), A.ptr(g_x), A.ptr(g_state[0]), A.ptr(g_state[1]), A.ptr(g_state[2]), T, _numel(slots), p.syn_decay,
              p.beta, p.v_th, p.v_reset, p.rho, p.kappa, p.reset, p.surrogate, p.alpha, p.adaptive, p.detach_reset, A.stream_ptr())
@@ -229,24 +242,15 @@ def _forward_params(x, c0, v0, a0, params, T: int, slots, p: _Params, want_v: bo
     """``be_lif_syn_sg_forward_params``: :func:`_forward` with the five parameters contiguous f32 device tensors (``rho`` / ``kappa``
     None without adaptation; a period is the element count): ``(s, v_seq, h, c_save, a_save, c_last, v_last, a_last)``.  ``a_save`` —
     the trace every step started from — is kept beside ``h`` when adaptive, ``c_save`` only when asked for."""
-    new = lambda: torch.empty(slots, dtype=x.dtype, device=x.device)
-    s = torch.empty_like(x)
-    v_seq = torch.empty_like(x) if want_v else None
-    h = torch.empty_like(x) if want_h else None
-    c_save = torch.empty_like(x) if want_c else None
-    a_save = torch.empty_like(x) if want_h and p.adaptive else None
-    c_last, v_last, a_last = new(), new(), (new() if p.adaptive else None)
+    outs = _new_outputs(x, slots, (c0, v0, a0), T, p, (want_v, want_h, want_c, want_h and p.adaptive))
     n = _numel(slots)
-    if T == 0:
-        for out, start in ((c_last, c0), (v_last, v0), (a_last, a0)):
-            if out is not None:
-                out.zero_() if start is None else out.copy_(start)
-    elif n > 0:
+    if T != 0 and n > 0:
+        s, v_seq, h, c_save, a_save, c_last, v_last, a_last = outs
         call('be_lif_syn_sg_forward_params', A.ptr(x), A.ptr(c0), A.ptr(v0), A.ptr(a0),
              *(v for t in params for v in (A.ptr(t), 1 if t is None else t.numel())), A.ptr(s), A.ptr(v_seq), A.ptr(h),
              A.ptr(c_save), A.ptr(a_save),
              A.ptr(c_last), A.ptr(v_last), A.ptr(a_last), T, n, p.v_reset, p.reset, p.adaptive, A.stream_ptr())
-    return s, v_seq, h, c_save, a_save, c_last, v_last, a_last
+    return outs
 
 
 class SynapticLifSequenceParams(torch.autograd.Function):
@@ -279,12 +283,8 @@ class SynapticLifSequenceParams(torch.autograd.Function):
         need_p = [need[4 + k] and params[k] is not None for k in range(5)]
         g_s, g_vseq, g_last = _grad_in(g_s), _grad_in(g_vseq), [_grad_in(g) for g in g_last]
         n = _numel(slots)
-        g_x = torch.empty_like(h)
-        g_state = [torch.empty(slots, dtype=h.dtype, device=h.device) if w else None for w in want]
+        g_x, *g_state = _new_grads(h, [slots if w else None for w in want], g_last, T == 0 or n == 0)
         if T == 0 or n == 0:                  # no step: the state's gradient passes through, the parameters were not used
-            for out, g in zip(g_state, g_last):
-                if out is not None:
-                    out.zero_() if g is None else out.copy_(g)
             g_params = [torch.zeros_like(t) if w else None for t, w in zip(params, need_p)]
             return ((g_x if need[0] else None), *g_state, *g_params, None, None, None, None)
         slot = [torch.empty(n, dtype=h.dtype, device=h.device) if w else None for w in need_p]

@@ -120,13 +120,16 @@ _ANY = '(' + '|'.join(sorted({v for f in FAMILIES for v in f}, key=len, reverse=
 
 def _symbol_names(node, assigned):
     """The symbol names an expression at a call site can stand for: literals as they are, an f-string as the table's names it
-    matches (checked to be a full product of families), a conditional as both arms, a local variable as what it was assigned."""
+    matches (checked to be a full product of families), a conditional as both arms, a local variable as what it was assigned, an
+    attribute (``r.forward``) as everything the module's classes assign to that name (under the key ``.forward``)."""
     if isinstance(node, ast.Constant) and isinstance(node.value, str):
         return [node.value]
     if isinstance(node, ast.IfExp):
         return _symbol_names(node.body, assigned) + _symbol_names(node.orelse, assigned)
     if isinstance(node, ast.Name) and node.id in assigned:
         return [n for v in assigned[node.id] for n in _symbol_names(v, assigned)]
+    if isinstance(node, ast.Attribute) and '.' + node.attr in assigned:
+        return [n for v in assigned['.' + node.attr] for n in _symbol_names(v, assigned)]
     if isinstance(node, ast.JoinedStr):
         pattern = ''.join(re.escape(p.value) if isinstance(p, ast.Constant) else _ANY for p in node.values)
         found = {m.groups() for m in (re.fullmatch(pattern, n) for n in _abi.PROTOTYPES) if m}
@@ -157,11 +160,20 @@ def _call_sites():
         tree = ast.parse(open(os.path.join(PKG, fname)).read())
         imported = {a.asname or a.name for n in ast.walk(tree) if isinstance(n, ast.ImportFrom) and n.module == '_lib'
                     for a in n.names} & {'fn', 'call'}
+        members = {}                                                   # `name = ...` in a class body, `self.name = ...` anywhere
+        for n in ast.walk(tree):
+            if isinstance(n, ast.ClassDef):
+                for a in n.body:
+                    if isinstance(a, ast.Assign) and len(a.targets) == 1 and isinstance(a.targets[0], ast.Name):
+                        members.setdefault('.' + a.targets[0].id, []).append(a.value)
+            elif (isinstance(n, ast.Assign) and len(n.targets) == 1 and isinstance(n.targets[0], ast.Attribute)
+                  and ast.unparse(n.targets[0].value) == 'self'):
+                members.setdefault('.' + n.targets[0].attr, []).append(n.value)
         for scope in ast.walk(tree):
             if not isinstance(scope, (ast.Module, ast.FunctionDef)):
                 continue
             nodes = list(_own_nodes(scope))
-            assigned = {}
+            assigned = dict(members)
             for n in nodes:
                 if isinstance(n, ast.Assign) and len(n.targets) == 1 and isinstance(n.targets[0], ast.Name):
                     assigned.setdefault(n.targets[0].id, []).append(n.value)

@@ -13,7 +13,7 @@ distribution and inputs.  For each ``N`` (default 256, 1024 and 4096) three side
 Each side has the weights its dtype can hold, so the spikes of the three differ (their rates are printed); before any time is
 printed the script asserts that each half side's spikes equal the f32 layer's on its up-converted matrix and that its gradients agree
 with that call's within 1e-4 of the gradient's scale (``x``; two summation orders) and one rounding of the dtype (the weights).  A
-second loop times the forward launch and the backward launch of each side alone (``_forward_dense`` / ``_backward_dense``: no
+second loop times the forward launch and the backward launch of each side alone (``_forward`` / ``_backward`` on the Dense adapter: no
 weight gradient, no autograd).  HIP-event medians and quartiles of ``--reps`` turns, the order shuffled (seeded) for every turn.
 Prints one JSON line and, with ``--out``, writes it.
 
@@ -98,17 +98,17 @@ def main():
 
         # the two launches alone
         xd, saved = x.detach(), {}
-        recs = {nm: R._DenseRec(ws[nm].detach()) for nm in names}
+        recs = {nm: R._recurrence('exp', be.Dense(ws[nm].detach()), n) for nm in names}
 
         def forward(nm):
             def run():
-                saved[nm] = R._forward_dense(xd, recs[nm], None, None, None, None, T, B, n, p, e, False, True)[2:4]
+                saved[nm] = R._forward(xd, recs[nm], None, None, None, None, T, B, n, p, e, False, True)[2:4]
             return run
 
         def backward(nm):
             def run():
                 h, th = saved[nm]
-                R._backward_dense(h, th, recs[nm], g_s, None, [None] * 3, T, B, n, p, [False] * 4)
+                R._backward(h, th, recs[nm], g_s, None, [None] * 3, T, B, n, p, [False] * 4)
             return run
 
         for nm in names:
