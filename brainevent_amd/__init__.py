@@ -23,7 +23,9 @@ with a synaptic current in front of the membrane and an optional adaptive thresh
 runs that neuron with a sparse recurrent projection inside the time loop, a whole sequence per launch, and
 ``parametric_recurrent_lif_sequence`` that layer with learnable, per-neuron parameters (``_neuron_rec_sg``); given a ``DelayedCSR``
 as the recurrence, ``recurrent_lif_sequence`` runs the layer with a conduction delay per synapse — a sample's spike history stays on
-the chip —, still one launch each way and differentiable through the spikes, the history and ``stacked.data``.
+the chip —, still one launch each way and differentiable through the spikes, the history and ``stacked.data``.  Given a ``Float8CSR``
+it runs the layer on the quantised sparse recurrence as it is stored — a byte per weight, ``Float8CSR``'s exact sums, no exponent and
+no host synchronisation; read-only weights, gradients for ``x``, the state and ``s0``.
 """
 from ._version import __version__
 __version_info__ = tuple(int(p) for p in __version__.split('.')[:3] if p.isdigit())

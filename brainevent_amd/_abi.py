@@ -36,6 +36,7 @@ _SIGNATURES = dict(
     be_lif_rec_dense_half_sg_backward='i:pppipppppppppplllddddddiidiip',
     be_lif_rec_dense_f8_sg_forward='i:ppidppppppppppplllddddddiip',
     be_lif_rec_dense_f8_sg_backward='i:pppidpppppppppplllddddddiidiip',
+    be_lif_rec_f8_sg_forward='i:ppidpplppppppppppplllddddddiip', be_lif_rec_f8_sg_backward='i:pppidpplpppppppppplllddddddiidiip',
     be_pack_spikes='i:pilpp', be_pack_spikes_batched='i:pillpp', be_unpack_spikes='i:plpp', be_compact_spikes='i:pilppp',
     be_compact_spikes_batched='i:pillplpp',
     be_exchange_unique_id_bytes='i:', be_exchange_get_unique_id='i:p', be_exchange_init='i:piilP', be_exchange_slice='i:piLL',

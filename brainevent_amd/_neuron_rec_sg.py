@@ -44,8 +44,15 @@ FP8 value is a multiple of 2^-9 / 2^-16, so the recurrent sum of the decoded wei
 f32 once and multiplied by the scale in f32 — ``Float8Dense``'s product contract with an exact sum; there is no exponent and no
 host synchronisation.  The weights are read-only and get no gradient; ``x``, the state and ``s0`` do.
 
-Not built: CSC / fixed-number / JITC recurrences, a Dense or Float8Dense recurrence with delays or tensor parameters, FP8 weights
-for the CSR / delayed recurrence, a (straight-through) gradient of FP8 weights, per-row or per-block FP8 scales, one shared
+FP8 WEIGHTS FOR THE SPARSE RECURRENCE (``be_lif_rec_f8_sg_forward`` / ``_backward``, ``csrc/be_neuron_sg_rec_f8.hip``):
+``rec`` may be a :class:`~brainevent_amd.Float8CSR` ``[N, N]`` (one e4m3 or e5m2 code per stored entry, one f32 scale, an int32
+``indptr``).  The recurrent sums are ``Float8CSR``'s own — exact 64-bit integers in the format's unit, finished as ``events @ W8``
+finishes them — so the layer equals the per-step loop ``x[t] + BinaryArray(s) @ W8`` bit for bit, with no exponent and no host
+synchronisation.  The kernels are the CSR layer's split of work with a row walk made for one byte per weight: forwards four codes
+in one 4-byte load and their columns in one 16-byte load, decoded in the integer ALU.  Read-only weights, as ``Float8Dense``'s.
+
+Not built: CSC / fixed-number / JITC recurrences, a Dense, Float8Dense or Float8CSR recurrence with tensor parameters, a Dense or
+FP8 recurrence with delays (FP8 weights for a DelayedCSR), a (straight-through) gradient of FP8 weights, per-row or per-block FP8 scales, one shared
 (homogeneous) weight, learnable ``v_reset`` / ``alpha``,
 per-sample (``[B, N]``) parameters, learnable delays, learnable neuron parameters together with delays, more than 8192 neurons (one
 sample's sums and spike ids live in one workgroup's LDS; with delays also its spike history: see :func:`delay_fits`), a sample split
@@ -259,6 +266,7 @@ class _Float8Rec(_Rec):
     backward = 'be_lif_rec_dense_f8_sg_backward'
     takes_exp, leaf = False, None
     no_tensors = ('a Float8Dense recurrence', 'Float8Dense rec')
+    kind = 'Float8Dense'
 
     def __init__(self, who, rec, n: int, like=None):      # codes [N, N] and one scale; the constructor has refused non-finite codes
         from ._dense_f8 import _CODE_OF_FMT
@@ -271,18 +279,45 @@ class _Float8Rec(_Rec):
 
     def exponent(self, who, scale_exp, n: int) -> int:    # nothing to ask for, nothing to give
         if scale_exp is not None:
-            raise ValueError(f"{who}: scale_exp must be None with a Float8Dense rec: its recurrent sums are exact integers in the "
+            raise ValueError(f"{who}: scale_exp must be None with a {self.kind} rec: its recurrent sums are exact integers in the "
                              f"format's own unit (2^-9 for e4m3, 2^-16 for e5m2) and take no exponent.")
         return 0
+
+
+class _Float8CSRRec(_Float8Rec):
+    """A :class:`~brainevent_amd.Float8CSR`: the device arrays of its stored rows — one code per entry, the columns, an int32
+    ``indptr`` — as they are (no plan, no mirror, no repacking), the format's code, the scale and the entry count.  The sums are
+    ``Float8CSR``'s own exact 64-bit integers, so there is no exponent; the weights are read-only: no leaf, no weight gradient."""
+    forward = 'be_lif_rec_f8_sg_forward'
+    backward = 'be_lif_rec_f8_sg_backward'
+    no_tensors = ('a Float8CSR recurrence', 'Float8CSR rec')
+    kind = 'Float8CSR'
+
+    def __init__(self, who, rec, n: int, like=None):      # the constructor has checked the structure and refused non-finite codes
+        from ._dense_f8 import _CODE_OF_FMT
+        codes, indices, indptr = rec._rows.device_arrays()
+        if indptr.dtype != torch.int32:
+            raise TypeError(f"{who}: the indptr of rec must be int32, not {indptr.dtype} (a Float8CSR built from an int64 indptr, or "
+                            f"with 2^31 entries or more, is not built).")
+        _limit(who, n, "one sample's sums and spike ids live in one workgroup's LDS")
+        if like is not None and codes.device != like.device:
+            raise ValueError(f"{who}: the codes of rec are on {codes.device}, x is on {like.device}: they must share a device.")
+        self.nse = int(indices.numel())
+        self.codes = codes.view(torch.uint8).reshape(-1) if self.nse else torch.zeros(1, dtype=torch.uint8, device=indptr.device)
+        self.indices = indices if self.nse else torch.zeros(1, dtype=torch.int32, device=indptr.device)
+        self.indptr = indptr
+        self.matrix = (A.ptr(self.codes), _CODE_OF_FMT[rec.fmt], float(rec.scale), A.ptr(self.indices), A.ptr(self.indptr), self.nse)
 
 
 def _family(rec):
     """The adapter class of ``rec``'s family, or None."""
     from ._csr import CSR
+    from ._csr_f8 import Float8CSR
     from ._delay import DelayedCSR
     from ._dense import Dense
     from ._dense_f8 import Float8Dense
-    for container, adapter in ((Float8Dense, _Float8Rec), (DelayedCSR, _DelayedRec), (Dense, _DenseRec), (CSR, _Rec)):
+    for container, adapter in ((Float8Dense, _Float8Rec), (Float8CSR, _Float8CSRRec), (DelayedCSR, _DelayedRec), (Dense, _DenseRec),
+                               (CSR, _Rec)):
         if isinstance(rec, container):
             return adapter
     return None
@@ -292,8 +327,9 @@ def _recurrence(who, rec, n: int, like=None) -> _Rec:
     """``rec`` classified, once, and checked: its family's adapter."""
     adapter = _family(rec)
     if adapter is None:
-        raise TypeError(f"{who}: rec must be a CSR matrix (rows = presynaptic neurons), a DelayedCSR or a Dense, not "
-                        f"{type(rec).__name__}; CSC, fixed-number, JITC and planned matrices are not built.")
+        raise TypeError(f"{who}: rec must be a CSR matrix (rows = presynaptic neurons), a DelayedCSR, a Dense, a Float8Dense or a "
+                        f"Float8CSR, not {type(rec).__name__}; CSC (Float8CSC), fixed-number, JITC and planned matrices are not "
+                        f"built.")
     if rec.shape[0] != rec.shape[1]:
         raise ValueError(f"{who}: rec {tuple(rec.shape)} must be square (a recurrent projection).")
     if rec.shape[0] != n:
@@ -346,7 +382,7 @@ def _grads_in(ctx, g_s, rest):
 
 class RecurrentLifSequence(torch.autograd.Function):
     """Every family's Function.  Outputs ``s, [v_seq,] c_last, v_last [, a_last]``; ``w`` is the adapter's leaf and ``s0`` as the
-    kernels take it.  Saved: ``h``, ``th`` when adaptive and, where there is a leaf (all but FP8 weights), ``s`` (the weight
+    kernels take it.  Saved: ``h``, ``th`` when adaptive and, where there is a leaf (all but FP8 weights, dense or sparse), ``s`` (the weight
     gradient's activity), the weights and ``s0``.  The gradient of an output nobody used arrives as None
     (``set_materialize_grads(False)``) and goes in as NULL; the weight gradient is computed only if the weights need one."""
 
@@ -439,8 +475,21 @@ def recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Sequence[Optio
     recurrence inside a trained network passes ``g_x`` to the layers below; backwards ``g_rec[i] = fl32((sum_j decode(codes[i, j]) *
     G[j]) * scale)``, f32 products and sums in an order ``N`` alone fixes, the scale applied once per row.
 
-    Not built: CSC / fixed-number / JITC recurrences, a Dense or Float8Dense recurrence with delays or tensor parameters, FP8 weights
-    for a CSR / DelayedCSR recurrence, a (straight-through) gradient of FP8 weights, per-row or per-block FP8 scales,
+    **FP8 sparse weights.**  ``rec`` may be a :class:`Float8CSR` ``[N, N]`` (``csr.quantize_fp8(fmt)``: one e4m3 or e5m2 code per stored
+    entry and one f32 ``scale``; rows = presynaptic neurons, an int32 ``indptr``; duplicate columns, self-loops and empty rows are
+    allowed): ``xin[t][j] = x[t][j] + f32(f64(R[j]) * ldexp(f64(scale), -E))`` with ``R[j]`` the sum of ``decode(code) * 2^E`` (``E`` = 9 /
+    16: an integer for every finite code) over the entries of column ``j`` in the rows that spiked — an exact 64-bit integer whatever
+    the order, finished as ``events @ W8`` finishes it.  So the layer equals the per-step loop ``x[t] + BinaryArray(s) @ rec`` bit for
+    bit, unconditionally, and is a function of its inputs bit for bit (``be_lif_rec_f8_sg_forward`` / ``_backward``, one launch each
+    way, ``N <= 8192``; the kernels read the container's arrays as they are: no plan, no mirror, no repacking).  ``scale_exp`` must
+    stay ``None`` (an int raises ``ValueError``: there is no exponent); the call never synchronises the host and always runs under
+    ``capture_step``.  The weights are read-only and get no gradient.  Unlike the ``events @ Float8CSR`` products, which refuse an
+    operand that requires grad, this layer ACCEPTS a grad-requiring ``x`` / state / ``s0`` and differentiates them, once, as with a
+    :class:`Float8Dense`: backwards ``g_rec[i] = fl32((sum over row i of decode(code_k) * G[col_k]) * scale)``, f32 products and sums
+    in an order the row's length alone fixes, the scale applied once per row.  A :class:`Float8CSC` (``W8.T``) is refused.
+
+    Not built: CSC / fixed-number / JITC recurrences, a Dense, Float8Dense or Float8CSR recurrence with tensor parameters, a Dense or
+    FP8 recurrence with delays (FP8 weights for a DelayedCSR), a (straight-through) gradient of FP8 weights, per-row or per-block FP8 scales,
     one shared weight, learnable delays, ``N > 8192``, a sample split over several workgroups (only ``B`` of the chip's compute units
     work)."""
     who = 'recurrent_lif_sequence'
@@ -576,11 +625,11 @@ def parametric_recurrent_lif_sequence(x: torch.Tensor, rec, state0: Optional[Seq
     the bit-for-bit forward contract are :func:`recurrent_lif_sequence`'s (``be_lif_rec_sg_forward_params``); differentiable, once,
     in ``x``, the state entries, ``s0``, ``rec.data`` and the five parameters.
 
-    A :class:`DelayedCSR`, a :class:`Dense` (f32, f16 or bf16 weights) or a :class:`Float8Dense` is taken with all-number parameters only (that is
-    :func:`recurrent_lif_sequence`); with a tensor parameter it raises ``NotImplementedError``.
+    A :class:`DelayedCSR`, a :class:`Dense` (f32, f16 or bf16 weights), a :class:`Float8Dense` or a :class:`Float8CSR` is taken with
+    all-number parameters only (that is :func:`recurrent_lif_sequence`); with a tensor parameter it raises ``NotImplementedError``.
 
-    Not built: learnable ``v_reset`` / ``alpha``, ``[B, N]`` parameters, tensor parameters with synaptic delays or a dense (Dense,
-    Float8Dense) recurrence, and what
+    Not built: learnable ``v_reset`` / ``alpha``, ``[B, N]`` parameters, tensor parameters with synaptic delays, a dense (Dense,
+    Float8Dense) or an FP8 (Float8Dense, Float8CSR) recurrence, and what
     :func:`recurrent_lif_sequence` does not build."""
     who = 'parametric_recurrent_lif_sequence'
     given, stand_in, any_tensor = _split_params(who, syn_decay, beta, v_th, adapt)

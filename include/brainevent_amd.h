@@ -498,6 +498,38 @@ int be_lif_rec_dense_f8_sg_backward(const float* h_save, const float* th_save, c
                                     int64_t B, int64_t N, double syn_decay, double beta, double v_th, double v_reset, double rho,
                                     double kappa, int reset_mode, int surrogate, double alpha, int adaptive, int detach_reset,
                                     be_stream_t stream);
+/* The SPARSE recurrence in OCP FP8 CODES (brainevent_amd/csrc/be_neuron_sg_rec_f8.hip): be_lif_rec_sg_forward / _backward with
+ * (w, indices, indptr) replaced by (codes, fmt_code, w_scale, indices, indptr, nse) — a Float8CSR's arrays as they are: codes one
+ * byte per stored entry, any alignment; fmt_code = BE_F8_E4M3 or BE_F8_E5M2 (any other code: BE_ERR_INVALID); w_scale one finite
+ * f32 (a value that is not finite as a float: BE_ERR_INVALID); indices [nse] int32 columns in [0, N), indptr [N + 1] int32,
+ * non-decreasing within [0, nse]; 0 <= nse < 2^31 (else BE_ERR_INVALID; nse = 0 is the layer without recurrence) — and WITHOUT
+ * scale_exp in the forward call.  Duplicate columns, self-loops and empty rows are allowed.  The caller guarantees finite codes.
+ *   forward: with E = 9 / 16 and Q(c) = decode(c) * 2^E (an integer for every finite code, |Q| < 2^32; both zeros are 0),
+ *       R[j]      = sum of Q(codes[k]) over the entries k of the rows i with sp[i] != 0 that have indices[k] == j   (int64, exact)
+ *       xin[t][j] = x[t][j] + (float)( (double)R[j] * ldexp((double)(float)w_scale, -E) )
+ *     — the finish of be_binary_csrmm_t_f8 ("FP8 weights for the event-driven CSR products" below), so the pass equals the per-step
+ *     loop of that product bit for bit, and is a function of its inputs bit for bit whatever the order of the additions.  No
+ *     overflow is possible and no exponent exists.  Entries are read as aligned quads (four codes in 4 bytes, four columns in 16)
+ *     when codes is 4-byte and indices 16-byte aligned, one by one otherwise, and so is the quad that reaches past nse: the same
+ *     bits, and nothing outside [0, nse) is read.
+ *   backward: g_rec[b][i] = fl32( (sum over row i of fl32(decode(codes[k])) * G[b][indices[k]]) * fl32(w_scale) ), each product rounded,
+ *     summed in f32 in an order the row's length alone fixes — lane l of the row's 8 takes the entries 4 * (l + 8 * m) .. + 3 of
+ *     the row, m = 0, 1, ..., in ascending order, then a butterfly over the 8 partial sums, then the scale, once per row.  Two calls
+ *     give the same bits; it is not be_lif_rec_sg_backward's order.  g_s0 is the same gather from g_x[0].  The codes get no gradient.
+ * NULL conventions and error codes are be_lif_rec_sg_forward / _backward's (codes, indices and indptr are required, also with
+ * nse = 0); the sizes, the modes, fmt_code, w_scale and nse are checked before any pointer is looked at.  N <= 8192 (BE_ERR_RANGE).
+ * No workspace, no allocation, no global atomics; never synchronises the host. */
+int be_lif_rec_f8_sg_forward(const float* x, const void* codes, int fmt_code, double w_scale, const int32_t* indices,
+                             const int32_t* indptr, int64_t nse, const float* s0, const float* c0, const float* v0, const float* a0,
+                             float* s_out, float* v_seq, float* h_save, float* th_save, float* c_last, float* v_last, float* a_last,
+                             int64_t T, int64_t B, int64_t N, double syn_decay, double beta, double v_th, double v_reset, double rho,
+                             double kappa, int reset_mode, int adaptive, be_stream_t stream);
+int be_lif_rec_f8_sg_backward(const float* h_save, const float* th_save, const void* codes, int fmt_code, double w_scale,
+                              const int32_t* indices, const int32_t* indptr, int64_t nse, const float* g_s, const float* g_vseq,
+                              const float* g_clast, const float* g_vlast, const float* g_alast, float* g_x, float* g_c0, float* g_v0,
+                              float* g_a0, float* g_s0, int64_t T, int64_t B, int64_t N, double syn_decay, double beta, double v_th,
+                              double v_reset, double rho, double kappa, int reset_mode, int surrogate, double alpha, int adaptive,
+                              int detach_reset, be_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * event vector helpers (replace: brainevent/_jit_scalar/binary_jitsmv.cu:107-125 `_pack_bool_kern`
